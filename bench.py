@@ -21,6 +21,12 @@ The JSON line also carries
   parity_max_abs: max |GPU - C oracle| over the accelerations of the timed step (same x0, same settings);
   cpu_baseline : the CPU oracle (oracle/scp_oracle_c.c, single-threaded C restatement of the same algorithm =
                  "port") timed on rank 0's host on one complete step from the same input state (~30 s).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0): DIR/accelerations.npy (N, K, D)
+and DIR/rel_step.npy (1,), both float64; beyond 64 MB the accelerations of a fixed, seeded sample of agents are
+written instead, with their ids in DIR/accelerations_agents.npy (float64 like the rest: exact integers, cast with
+.astype(np.int64) before indexing).  The inputs depend on the arguments only, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -32,6 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "ba-path-planning_amd"))
 
+DUMP_MAX_BYTES = 64 << 20
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 
 
@@ -78,6 +85,21 @@ def cpu_baseline(N, K, D, h, T, R, space, p0, pf, margin, step_info, x0, x_gpu):
     }
 
 
+def dump_outputs(out_dir, acc, rel_step):
+    """The last timed step's result as .npy files (float64), at most DUMP_MAX_BYTES in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    acc = np.ascontiguousarray(acc, dtype=np.float64)
+    if acc.nbytes > DUMP_MAX_BYTES - 4096:  # a fixed sample of whole agents, the same for every build
+        keep = (DUMP_MAX_BYTES - 4096) // (acc.nbytes // acc.shape[0] + 8)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one agent's accelerations alone exceed {DUMP_MAX_BYTES} bytes")
+        agents = np.sort(np.random.default_rng(0).choice(acc.shape[0], size=keep, replace=False))
+        np.save(os.path.join(out_dir, "accelerations_agents.npy"), agents.astype(np.float64))
+        acc = acc[agents]
+    np.save(os.path.join(out_dir, "accelerations.npy"), acc)
+    np.save(os.path.join(out_dir, "rel_step.npy"), np.array([rel_step], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -89,7 +111,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL) on a multi-GPU node; gloo for one-GPU rehearsals")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     import numpy as np
     import torch
@@ -151,7 +177,8 @@ def main():
     comm0 = (solver.shard.comm_seconds, solver.shard.comm_calls)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, rel, lms, vms = step()
+        # a fresh output tensor per call (_hip.py step / shard_end): the untimed steps below leave last_acc untouched
+        last_acc, rel, lms, vms = step()
         lin_ms.append(lms)
         viol_ms.append(vms)
         infos.append(dict(solver._last_qp_info, rel_step=rel))
@@ -282,6 +309,8 @@ def main():
         out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     else:
         out["cpu_baseline"] = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_acc.cpu().numpy(), infos[-1]["rel_step"])
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
