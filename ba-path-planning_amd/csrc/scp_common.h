@@ -50,6 +50,10 @@ struct scp_ctx {
   int timing;                     // HIP events around the pairwise kernels and the QP solves (scp_ctx_set_option; default on)
   int small_pass;                 // one-launch pairwise passes for small problems (scp_ctx_set_option; default on)
   unsigned long long rel_seq;     // of the latest scp_rel_step (completion word: h_scratch[64]; partials: h_scratch[0..64))
+  void* gen_ws;                   // device workspace of scp_generate_grid_swap (grown on demand)
+  size_t gen_ws_bytes;
+  int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
+  int* d_gen_flag;
 };
 
 static inline int scp_fail(scp_ctx* ctx, int code, const char* fmt, ...) {

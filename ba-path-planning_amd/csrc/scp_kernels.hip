@@ -80,6 +80,8 @@ extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
   if (ctx->cmp_map) (void)hipFree(ctx->cmp_map);
   if (ctx->cmp_tot) (void)hipFree(ctx->cmp_tot);
   if (ctx->tm_scratch) (void)hipFree(ctx->tm_scratch);
+  if (ctx->gen_ws) (void)hipFree(ctx->gen_ws);
+  if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
   (void)hipHostFree(ctx->h_scratch);
   (void)hipHostFree(ctx->h_mirror);
   (void)hipEventDestroy(ctx->ev0);

@@ -118,7 +118,29 @@ class QpInfo(C.Structure):
         return d
 
 
-ABI_VERSION = 5  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
+class GenParams(C.Structure):
+    """struct scp_gen_params"""
+
+    _fields_ = [
+        ("pitch", C.c_double), ("jitter", C.c_double), ("layer_gap", C.c_double), ("min_sep", C.c_double),
+        ("block", C.c_int32), ("max_tries", C.c_int32), ("sweeps", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class GenStats(C.Structure):
+    """struct scp_gen_stats (one per scenario; a DEVICE array of them is what scp_generate_grid_swap writes)"""
+
+    _fields_ = [
+        ("sweeps", C.c_int32), ("unmet_blocks", C.c_int32), ("conflicts", C.c_int64), ("min_approach", C.c_double),
+        ("ok", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+GEN_STATS_DTYPE = np.dtype([("sweeps", np.int32), ("unmet_blocks", np.int32), ("conflicts", np.int64),
+                            ("min_approach", np.float64), ("ok", np.int32), ("reserved", np.int32)])
+
+
+ABI_VERSION = 6  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
 
 EXPORTS = [
     "scp_set_host_wait", "scp_abi_version", "scp_ctx_create", "scp_ctx_destroy", "scp_last_error", "scp_ctx_synchronize",
@@ -130,7 +152,7 @@ EXPORTS = [
     "scp_qp_get_duals", "scp_gemm_f64", "scp_qp_peek", "scp_qp_debug_set",
     "scp_solve_default_options", "scp_solver_create", "scp_solver_destroy", "scp_solver_update_settings", "scp_solver_solve",
     "scp_solver_step", "scp_solver_shard_begin", "scp_solver_shard_rows", "scp_solver_shard_qp", "scp_solver_shard_violations",
-    "scp_solver_shard_round_done", "scp_solver_shard_end",
+    "scp_solver_shard_round_done", "scp_solver_shard_end", "scp_gen_default_params", "scp_generate_grid_swap",
 ]
 
 
@@ -215,8 +237,22 @@ def load_library():
     lib.scp_solver_shard_violations.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(C.c_double)]
     lib.scp_solver_shard_round_done.argtypes = [vp, i64, f64, C.POINTER(QpRecord), C.POINTER(i32)]
     lib.scp_solver_shard_end.argtypes = [vp, vp, C.POINTER(QpRecord)]
+    lib.scp_gen_default_params.argtypes = [C.POINTER(GenParams)]
+    lib.scp_gen_default_params.restype = None
+    lib.scp_generate_grid_swap.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_uint64), C.POINTER(GenParams), vp, vp, vp, vp]
     _LIB, _LIB_PATH = lib, path
     return lib
+
+
+def gen_params(**overrides) -> GenParams:
+    """scp_gen_default_params with the given fields replaced (pitch, jitter, block, layer_gap, min_sep, max_tries, sweeps)"""
+    p = GenParams()
+    load_library().scp_gen_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if k == "reserved" or not hasattr(p, k):
+            raise TypeError(f"unknown grid-swap parameter {k!r}")
+        setattr(p, k, v)
+    return p
 
 
 def default_settings(**overrides) -> QpSettings:
@@ -337,6 +373,24 @@ class Context:
         out = (C.c_double * 3)()
         self.check(self.lib.scp_rel_step(self.h, a_new.numel(), a_new.data_ptr(), a_prev.data_ptr(), out))
         return float(out[0]), float(out[1]), float(out[2])
+
+    def generate_grid_swap(self, N, D, seeds, params: GenParams | None = None):
+        """scp_generate_grid_swap: B = len(seeds) scenarios of the grid-swap-device family in one call.
+        Returns device tensors init (B, N, D), goal (B, N, D), space (B, 2D) and the stats as a numpy structured array
+        (GEN_STATS_DTYPE) of B entries.  Synchronises."""
+        torch = _torch()
+        sd = np.array([int(v) & UINT64_MAX for v in np.asarray(seeds).reshape(-1)], dtype=np.uint64)
+        B = int(sd.size)
+        p = params if params is not None else gen_params()
+        init = self.empty(max(B, 1), max(N, 1), D)
+        goal = self.empty(max(B, 1), max(N, 1), D)
+        space = self.empty(max(B, 1), 2 * D)
+        stats = torch.empty(max(B, 1) * GEN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_generate_grid_swap(self.h, B, int(N), int(D), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   C.byref(p), init.data_ptr(), goal.data_ptr(), space.data_ptr(),
+                                                   stats.data_ptr()))
+        st = stats.cpu().numpy().view(GEN_STATS_DTYPE)
+        return init, goal, space, st
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

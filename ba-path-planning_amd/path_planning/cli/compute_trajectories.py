@@ -9,6 +9,7 @@ import time
 
 import numpy as np
 
+from ..scenarios.grid_swap_device import generate_grid_swap_device
 from ..scenarios.position_generator import generate_grid_swap, generate_positions
 from ..solvers.scp import SCP
 
@@ -20,7 +21,7 @@ def build_parser():
     p.add_argument("--time-step", type=float, default=0.2)
     p.add_argument("--min-distance", type=float, default=0.8)
     p.add_argument("--space", type=float, nargs="+", default=None, help="[min..., max...]; default 0 0 200 200")
-    p.add_argument("--scenario", choices=["reference", "grid-swap"], default="reference")
+    p.add_argument("--scenario", choices=["reference", "grid-swap", "grid-swap-device"], default="reference")
     p.add_argument("--dim", type=int, choices=[2, 3], default=2)
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--max-iterations", type=int, default=15)
@@ -42,9 +43,9 @@ def main(argv=None):
     time_horizon = args.time_horizon
     time_step = args.time_step
     min_distance = args.min_distance
-    if args.scenario == "grid-swap":
-        initial_positions, final_positions, space_dims = generate_grid_swap(
-            n_vehicles, seed=args.seed or 0, dim=args.dim)
+    if args.scenario in ("grid-swap", "grid-swap-device"):
+        gen = generate_grid_swap if args.scenario == "grid-swap" else generate_grid_swap_device
+        initial_positions, final_positions, space_dims = gen(n_vehicles, seed=args.seed or 0, dim=args.dim)
         if args.space is not None:
             space_dims = args.space
     else:

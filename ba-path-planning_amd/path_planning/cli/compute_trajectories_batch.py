@@ -18,6 +18,7 @@ from pathlib import Path
 
 import numpy as np
 
+from ..scenarios.grid_swap_device import generate_grid_swap_batch, generate_grid_swap_device
 from ..scenarios.position_generator import generate_grid_swap, generate_positions
 from ..solvers.scp import SCP
 
@@ -33,7 +34,8 @@ CONFIG = {
     "rng_seed": None,
     "results_dir": "data/trial_xxx",
     # additions
-    "scenario": "reference",  # or "grid-swap" (needed for N >= 60)
+    "scenario": "reference",  # or "grid-swap" (needed for N >= 60), or "grid-swap-device" (the same
+    # geometry generated in batches on the GPU)
     "dim": 2,
 }
 
@@ -49,6 +51,8 @@ def make_scenario(N, cfg, seed=None):
     """Start / goal positions and the space box of one trial (compute_trajectories_batch.py:36-41)."""
     if cfg.get("scenario", "reference") == "grid-swap":
         return generate_grid_swap(N, seed=seed or 0, dim=cfg.get("dim", 2))
+    if cfg["scenario"] == "grid-swap-device":
+        return generate_grid_swap_device(N, seed=seed or 0, dim=cfg.get("dim", 2), device=cfg.get("device", 0))
     init_pos, final_pos = generate_positions(N, cfg["min_distance"], seed=seed)
     return init_pos, final_pos, cfg["space_dims"]
 
@@ -182,7 +186,7 @@ def build_parser():
     p = argparse.ArgumentParser(prog="compute-trajectories-batch", description=__doc__.split("\n\n")[0])
     p.add_argument("--Ns", type=int, nargs="+", default=None)
     p.add_argument("--trials", type=int, default=None)
-    p.add_argument("--scenario", choices=["reference", "grid-swap"], default=None)
+    p.add_argument("--scenario", choices=["reference", "grid-swap", "grid-swap-device"], default=None)
     p.add_argument("--dim", type=int, choices=[2, 3], default=None)
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--results-dir", default=None)
@@ -280,11 +284,24 @@ def main(argv=None):
     # N = 128) would otherwise be what the scenarios/s figure measures
     t_gen = time.perf_counter()
     scenarios = {}
-    for N, trial in jobs:
-        seed = trial_seed(cfg, N, trial)
-        if seed is not None:
-            np.random.seed(seed)
-        scenarios[(N, trial)] = make_scenario(N, cfg, seed)
+    scenario_ok = {}
+    if cfg["scenario"] == "grid-swap-device":
+        # all of this rank's jobs of one N in one batched call on the GPU (seeds as make_scenario: seed or 0); a scenario
+        # whose separation guarantee failed is still solved, its record says so (scenario_ok)
+        for N in dict.fromkeys(n for n, _ in jobs):
+            mine = [t for n, t in jobs if n == N]
+            seeds = [trial_seed(cfg, N, t) or 0 for t in mine]
+            init, goal, space, stats = generate_grid_swap_batch(N, seeds, dim=cfg.get("dim", 2), device=local_rank)
+            init, goal, space = init.cpu().numpy(), goal.cpu().numpy(), space.cpu().numpy()
+            for b, t in enumerate(mine):
+                scenarios[(N, t)] = (init[b], goal[b], [float(v) for v in space[b]])
+                scenario_ok[(N, t)] = bool(stats["ok"][b])
+    else:
+        for N, trial in jobs:
+            seed = trial_seed(cfg, N, trial)
+            if seed is not None:
+                np.random.seed(seed)
+            scenarios[(N, trial)] = make_scenario(N, cfg, seed)
     t_gen = time.perf_counter() - t_gen
 
     import threading
@@ -300,6 +317,8 @@ def main(argv=None):
         res = run_single_trial(N, cfg, rng=np.random, seed=seed, device=local_rank, scenario=scenarios[job], save_path=save,
                                pool=None if args.fresh_solvers else pools.solvers)
         res["trial_index"] = trial
+        if job in scenario_ok:
+            res["scenario_ok"] = scenario_ok[job]
         status_str = "OK" if res["status"] == "success" else f"ERR ({res['error']})"
         print(f"  [rank {rank}] N={N} trial {trial+1:02d}/{cfg['trials_per_N']}  time = {res['time_sec']:.3f}s  [{status_str}]")
         return res

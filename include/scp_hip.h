@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SCP_ABI_VERSION 5
+#define SCP_ABI_VERSION 6
 
 typedef enum scp_status {
   SCP_OK = 0,
@@ -357,6 +357,73 @@ int scp_solver_shard_violations(scp_solver* s, int64_t* rows_out, int64_t rows_c
                                 double* max_violation);
 int scp_solver_shard_round_done(scp_solver* s, int64_t n_all, double max_violation_all, scp_qp_record* rec, int* more);
 int scp_solver_shard_end(scp_solver* s, double* acc_out, scp_qp_record* rec);
+
+/* ---- scenario family "grid-swap-device": B grid-swap scenarios per call ------------------------------------------------
+ * Same geometry and acceptance rules as the host generator generate_grid_swap (path_planning/scenarios/
+ * position_generator.py); the random draws come from a counter-based hash, so this is a family of its own (not the host's
+ * numpy stream).  Scenario b depends on seeds[b] and the parameters only, never on B or on b.
+ *
+ * Layout.  layers = 1 (2-D) or the smallest L with L^3 >= N (3-D); per = ceil(N / layers); side = the smallest s with
+ * s^2 >= per.  Agent k lies in layer L = k / per at in-layer index c = k - L per, cell (cx, cy) = (c / side, c % side); a
+ * layer holds min(per, remaining) agents.  Block key = (cx / block) (side / block + 1) + cy / block; a block's local id
+ * ("owner") is the rank of its key among the distinct keys of its layer, its members are its agents in ascending order
+ * (m <= block^2 of them).  In 3-D every agent's z (start and goal) is L * layer_gap.
+ *
+ * Random numbers.  mix(z) = SplitMix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31 (uint64 arithmetic).  The number of a key (tag, layer, block, sweep,
+ * round, cand, lane) is h = mix(mix(mix(mix(mix(mix(mix(mix(seed) ^ tag) ^ layer) ^ block) ^ sweep) ^ round) ^ cand) ^ lane).
+ * u = (h >> 11) * 2^-53; a jitter is (2u - 1) * jitter; a coordinate is (double)cell * pitch + jitter, each product rounded.
+ *   start of agent c of layer L, coordinate d (0 = x, 1 = y):  tag 1, (L, 0, 0, 0, 0, 2c + d)
+ *   Fisher-Yates of candidate t in round r of block o at sweep s: tag 2, (L, o, s, r, t, i) for i = m-1 .. 1:
+ *     j = ((h >> 32) (i + 1)) >> 32, swap(perm[i], perm[j]), perm starting as the identity
+ *   goal jitter of that candidate's slot i, coordinate d: tag 3, (L, o, s, r, t, 2i + d)
+ * Candidate t's goal of member i is cell(member perm[i]) * pitch + its jitter.
+ *
+ * Block draw (sweep s).  Rounds r = 0 .. max(1, max_tries / 256) - 1 of T = 256 candidates.  A candidate's score is the
+ * smallest d^2 over the pairs i < j of the block (+inf for m = 1), d^2 the squared closest approach of
+ * straight_line_min_distance without the sqrt: r0 = a_i - a_j, dr = (g_i - g_j) - r0, den = dr.dr,
+ * s = clip(-(r0.dr) / (den > 0 ? den : 1), 0, 1), c = r0 + s dr, d^2 = c.c -- x terms before y terms, every product
+ * rounded (no contraction).  A round picks its lowest-index candidate with d^2 >= min_sep^2, else the largest d^2 (lowest
+ * index on ties); the block keeps the best pick over its rounds (a later round replaces it only with a strictly larger
+ * d^2) and stops after the first round that has an acceptable candidate.
+ *
+ * Sweeps.  Sweep 0 draws every block.  Sweep s = 1 .. sweeps: every pair of a layer whose agents lie in different blocks
+ * and have d^2 < min_sep^2 flags the block with the larger owner id; no flag ends the scenario's sweeps, otherwise the
+ * flagged blocks are redrawn with sweep index s (a draw reads its own block's agents only, so redrawing them together is
+ * the host's sequential redraw).
+ *
+ * Statistics per scenario (scp_gen_stats, DEVICE array of B): sweeps = redraw sweeps done; unmet_blocks = blocks whose
+ * draw has no acceptable candidate; conflicts = cross-block pairs of a layer left with d^2 < min_sep^2; min_approach =
+ * sqrt(min d^2 over all pairs of the scenario, z included; +inf for N = 1); ok = min_approach >= min_sep.
+ * space[b] = [lo_0 .. lo_{D-1}, hi_0 .. hi_{D-1}], lo = min(init, goal) - 2, hi = max(init, goal) + 2 per coordinate.
+ *
+ * Supported: 1 <= N <= 65536, B >= 1, D in {2, 3}, 2 <= block <= 8 (m <= 64), finite pitch / layer_gap / min_sep >= 0,
+ * jitter >= 0, 0 <= sweeps <= 1000; anything else returns SCP_ERR_INVALID.  init / goal [B][N][D], space [B][2D] and stats
+ * are DEVICE pointers, seeds [host].  Enqueued on the ctx's stream; one 4-byte host read per sweep; synchronises. */
+typedef struct scp_gen_params {
+  double pitch;      /* 2.0: grid pitch (m) */
+  double jitter;     /* 0.2: start / goal jitter, uniform in [-jitter, jitter) per coordinate */
+  double layer_gap;  /* 2.0: z distance of the layers (3-D) */
+  double min_sep;    /* 0.3: closest straight-line approach a draw aims at */
+  int32_t block;     /* 4: goals are permuted inside block x block cells */
+  int32_t max_tries; /* 8192: candidates per block draw (256 per round) */
+  int32_t sweeps;    /* 20: cross-block sweeps at most */
+  int32_t reserved;  /* 0 */
+} scp_gen_params;
+
+typedef struct scp_gen_stats {
+  int32_t sweeps;        /* redraw sweeps this scenario needed */
+  int32_t unmet_blocks;  /* blocks without an acceptable candidate */
+  int64_t conflicts;     /* cross-block pairs left closer than min_sep */
+  double min_approach;   /* closest straight-line approach over all pairs */
+  int32_t ok;            /* min_approach >= min_sep */
+  int32_t reserved;
+} scp_gen_stats;
+
+void scp_gen_default_params(scp_gen_params* p);
+int scp_generate_grid_swap(scp_ctx* ctx, int B, int N, int D, const uint64_t* seeds /* [host] B */, const scp_gen_params* p,
+                           double* init /* [B][N][D] */, double* goal /* [B][N][D] */, double* space /* [B][2D] */,
+                           scp_gen_stats* stats /* [B] */);
 
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
