@@ -248,13 +248,18 @@ def working_rows(prob, rows):
 
 
 def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, st: Settings | None = None,
-                    rows0=None, trace=None):
+                    rows0=None, trace=None, snapshots=None, snap_out=None):
     """Joint QP  min ||x||^2  s.t. fixed rows and ALL collision rows (eta, l_col; None -> QP#0).
 
     Exact constraint generation: ADMM runs on the fixed rows plus a working set W of collision rows;
     after it terminates every row outside W is checked at the solution and violated rows join W
     (duals start at 0), until none is violated.  The final point satisfies the KKT conditions of the
     FULL joint QP (rows outside W are feasible with zero multiplier) to the solver tolerances.
+
+    snapshots (a set of ADMM step counts m, counted over all rounds) + snap_out (a dict): snap_out[m] receives the
+    state after exactly m steps -- the state a solve with max_iter = m ends in: "x" (N, K, D); "zf" / "yf", the four
+    fixed-row blocks (jerk, acc, vel, pos) as in `y` below; "rows", "zc", "yc" of the working collision rows (sorted row
+    ids); "rho" (after that step's adaptive-rho test) and "round" (1-based).  Results are unchanged by it.
     """
     st = st or Settings()
     N, K, D, h = prob.N, prob.K, prob.D, prob.h
@@ -388,6 +393,12 @@ def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, 
                 tc = col_apply(xt, wk, wi, wj_, we)
                 zc, yc = upd(tc, zc, yc, rho_c, wl, np.inf)
             x = x_new
+            if snapshots is not None and total_it in snapshots:
+                snap_out[total_it] = {
+                    "x": x.copy(), "zf": tuple(a.copy() for a in (zj, za, zv, zp)),
+                    "yf": tuple(a.copy() for a in (yj, ya, yv, yp)), "rows": W.copy(),
+                    "zc": zc.copy() if W.size else np.zeros(0), "yc": yc.copy() if W.size else np.zeros(0),
+                    "rho": rho, "round": rnd + 1}
 
             check = (it % cad == 0) or total_it >= st.max_iter
             if check:
@@ -453,6 +464,8 @@ def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, 
                         rho = new
                         rvv, rpp, M, Hf = build(rho)
                         info["rho_updates"] += 1
+                        if snapshots is not None and total_it in snapshots:
+                            snap_out[total_it]["rho"] = rho
                         if fine:  # (the residuals usually fall below the tolerances within a few steps of a new rho)
                             cad = fine
         # constraint generation: check every collision row outside W at the ADMM solution
