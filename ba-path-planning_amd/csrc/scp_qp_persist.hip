@@ -765,7 +765,7 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   {
     const int nb = nblk + 1;  // (+1: the fault-injection hook below may announce one more workgroup)
     const size_t fixed = lean ? scp_persist16_lds_bytes(K, 0, nb, D, apb) : persist_lds_bytes(K, D, 0, nb);
-    const size_t per_entry = (size_t)(4 * D + 4) * sizeof(double) + (lean ? 1 : 3) * sizeof(int);
+    const size_t per_entry = lean ? scp_persist16_entry_bytes(D) : (size_t)(4 * D + 4) * sizeof(double) + 3 * sizeof(int);
     const size_t budget_lds = 160 * 1024 - (lean ? 2048 : 1024);  // minus the static __shared__ of the kernel (580 B / 1.2 KB)
     if (fixed + 64 * per_entry > budget_lds) return SCP_OK;
     qp->persist_cap = (int)((budget_lds - fixed) / per_entry / 64 * 64);

@@ -17,13 +17,18 @@
 //     bounds are per row;
 //   * H_f^{-1} (packed MFMA operands, 26 KB at K = 50) lives in LDS and is streamed into the matrix cores, not held in 32
 //     registers per lane; eight waves run the 4 row tiles x 2 column tiles of p = H_f^{-1} r; S0 p comes from two more
-//     prefix scans (no T = S0 H_f^{-1} tiles: the matrix pipes are the busiest unit with four waves per SIMD);
+//     prefix scans (no T = S0 H_f^{-1} tiles: the matrix pipes are the busiest unit with four waves per SIMD).  <2, 8>
+//     instead forms S0 p = T r on the four waves its single column tile leaves idle and publishes the cells from the
+//     accumulators, so the hand-off starts before any scan (t_on_mfma);
+//   * a collision row carries its value at x, c . (S0 x_own - S0 x_partner), instead of both S0 x cells: z~ and the next
+//     row value are fma(a, s, ax), fma(alpha a, s, ax) with s the row value of p the row loop forms anyway, and the
+//     check refreshes it exactly;
 //   * delta-y of a batch's last step (primal infeasibility certificate) is reduced on the spot -- |dy|, the support value and
 //     |A^T dy| per lane -- instead of being kept in 16 registers until the check;
 //   * y / rho and (.) / h are multiplications by reciprocals (fp64 division is ~14 VALU instructions a piece, eight of them
 //     per lane and step).
-// Entry tables: 100 B per incident row in the LDS that is left (~900 rows around a block of 16 agents at K = 50; more ->
-// EXIT_OVERFLOW -> three-launch pipeline for that working set, as before).
+// Entry tables: 68 B per incident row in 2-D (76 B in 3-D) in the LDS that is left (1280 rows around a block of 16 agents
+// at 4096 x 50, 1088 around one of 8 at 1024 x 50; more -> EXIT_OVERFLOW -> three-launch pipeline for that working set).
 #include "scp_qp_persist_device.h"
 
 namespace {
@@ -52,11 +57,19 @@ __device__ unsigned long long scp_persist16_clk[16];
 constexpr int nct_of(int D, int APB) { return (D * APB + 15) / 16; }  // 16-column MFMA tiles of a workgroup
 constexpr int AB_STRIDE = 32;  // per-agent bound table: 8 groups of 4 doubles
 
+// <2, 8> has four of its eight waves idle in the MFMA phase (one column tile): they form S0 p = T r (T = S0 H_f^{-1}, packed
+// like H_f^{-1}) next to p = H_f^{-1} r and publish the cells straight from the accumulators, before any prefix scan.  (<2, 16>
+// would have the waves too, but not the registers or the LDS; <3, 8> has none.)
+constexpr bool t_on_mfma(int D, int APB) { return 4 * nct_of(D, APB) < APB && APB <= 8; }
+// entry tables, doubles per incident row: signed eta [D], l, z, y, g, c . (S0 x_own - S0 x_partner), c . (S0 p_own - S0 p_partner)
+constexpr int ent_doubles(int D) { return D + 6; }
+
 struct Lds16 {  // carve-up shared by the kernel and the host's size computation (doubles, then ints)
   int RSK, tK, nks;
-  size_t rt, pt, ml, gp, ab, gchk, ent, n_dbl;
+  size_t rt, pt, qt, ml, tl, gp, ab, gchk, ent, n_dbl;
   __host__ __device__ Lds16(int K, int cap, int nblk, int D, int APB) {
     const int NC16 = 16 * nct_of(D, APB), APB16 = APB;
+    const bool tq = t_on_mfma(D, APB);
     RSK = pad_col(K);
     tK = (K + 15) >> 4;
     nks = (K + 3) >> 2;
@@ -64,12 +77,18 @@ struct Lds16 {  // carve-up shared by the kernel and the host's size computation
     rt = o; o += (size_t)NC16 * RSK;
     pt = o; o += (size_t)NC16 * RSK;
     ml = o; o += (size_t)tK * nks * 64;
+    qt = pt;  // (scan path: S0 p overwrites p in place)
+    tl = ml;
+    if (tq) {
+      qt = o; o += (size_t)NC16 * RSK;
+      tl = o; o += (size_t)tK * nks * 64;
+    }
     gp = o; o += (size_t)2 * nblk;
     ab = o; o += (size_t)APB16 * AB_STRIDE;
-    // the nine-value all-gather of a termination check reuses the two tiles when they are large enough
+    // the nine-value all-gather of a termination check reuses the r / p tiles when they are large enough
     if ((size_t)2 * NC16 * RSK >= (size_t)NCHK * nblk) gchk = rt;
     else { gchk = o; o += (size_t)NCHK * nblk; }
-    ent = o; o += (size_t)cap * (4 * D + 4);
+    ent = o; o += (size_t)cap * ent_doubles(D);
     n_dbl = o;
   }
 };
@@ -79,6 +98,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   constexpr int NT16 = 64 * APB16;             // threads: one wave per agent
   constexpr int NCT = nct_of(D, APB16);        // column tiles of the MFMA phase
   constexpr int NC16 = 16 * NCT;               // tile columns (D APB16 of them in use)
+  constexpr bool TQ = t_on_mfma(D, APB16);     // S0 p = T r on the matrix waves the column tiles leave idle
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ double red[NCHK][APB16];
   __shared__ double cert_s[3][APB16];  // per wave: |dy|, support value, |A^T dy| of the batch's last step (fixed rows)
@@ -98,8 +118,10 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   const Lds16 L(K, cap, nblk, D, APB16);
   const int RSK = L.RSK, tK = L.tK, nks = L.nks;
   double* Rt = lds + L.rt;            // [32][RSK] r, MFMA B operand
-  double* Pt = lds + L.pt;            // [32][RSK] p, overwritten in place by the lane's S0 p cell (what the row loops read)
+  double* Pt = lds + L.pt;            // [32][RSK] p (scan path: overwritten in place by the lane's S0 p cell)
+  double* Qt = lds + L.qt;            // [32][RSK] the S0 p cells the row loop reads (TQ: T r; else = Pt)
   double* Ml = lds + L.ml;            // [tK][nks][64] packed H_f^{-1}
+  double* Tl = lds + L.tl;            // [tK][nks][64] packed T = S0 H_f^{-1} (TQ only)
   double* gp = lds + L.gp;            // [nblk][2] all-gathered line-search partials
   double* ab = lds + L.ab;            // [APB][8 groups of 4] per agent, per axis: l_vel, u_vel, vf - v0, pos_min, pos_max, pf, -1e300, +1e300
   double* gck = lds + L.gchk;         // [nblk][9] all-gathered check results
@@ -108,9 +130,8 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   double* e_z = e_l + cap;
   double* e_y = e_z + cap;
   double* e_g = e_y + cap;            // row value of the next right-hand side
-  double* e_qo = e_g + cap;           // [cap][2] S0 x cell of the own agent
-  double* e_qp = e_qo + (size_t)cap * D;  // [cap][2] ... of the partner agent
-  double* e_pp = e_qp + (size_t)cap * D;  // [cap][2] S0 p cell of the partner (this step); [e][0]: delta-y parked for the check
+  double* e_ax = e_g + cap;           // row value at x: c . (S0 x_own - S0 x_partner), exact after a check, carried in between
+  double* e_s = e_ax + cap;           // row value of this step's p: c . (S0 p_own - S0 p_partner); then delta-y parked for the check
   int* e_code = (int*)(lds + L.n_dbl);    // [cap] k | local agent << 6 | side << 10 | partner agent << 11
   int* cptr = e_code + cap;               // [16 K + 1] cell offsets relative to this workgroup's first entry
 
@@ -153,20 +174,25 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
     const int own = side ? wj : wi, par = side ? wi : wj;
     e_code[e] = wk | ((own - a0) << 6) | (side << 10) | (par << 11);
     const int64_t bo = (int64_t)wk * C + (int64_t)own * D, bp = (int64_t)wk * C + (int64_t)par * D;
+    double ax = 0.0;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const double eta = A.w_eta[(size_t)n * D + d];
-      e_c[(size_t)e * D + d] = side ? -eta : eta;
-      e_qo[(size_t)e * D + d] = A.Qx[bo + d];
-      e_qp[(size_t)e * D + d] = A.Qx[bp + d];
+      const double c = side ? -eta : eta;
+      e_c[(size_t)e * D + d] = c;
+      ax += c * (A.Qx[bo + d] - A.Qx[bp + d]);
     }
+    e_ax[e] = ax;
     e_l[e] = A.w_l[n];
     e_z[e] = A.zc[n];
     e_y[e] = A.yc[n];
     e_g[e] = A.gval[ebase + e];
   }
   for (int i = threadIdx.x; i < NC16 * RSK; i += NT16) Rt[i] = 0.0;  // columns beyond the block stay zero
-  for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) Ml[i] = A.pMinv[i];
+  for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) {
+    Ml[i] = A.pMinv[i];
+    if constexpr (TQ) Tl[i] = A.pT[i];
+  }
 
   // ---- column state: lane k of the agent's wave holds the rows of time step k --------------------------------------
   // row types t = 0 jerk (k < K - 1), 1 acc, 2 vel, 3 pos;  slab row of (t, k): t = 0: k, else t K - 1 + k
@@ -298,11 +324,13 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
     }
     __syncthreads();
     PSTAMP(1);
-    // ---- p = H_f^{-1} r on the matrix cores: eight waves = 4 row tiles x 2 column tiles, operands streamed from LDS ----
-    if (wave < 4 * NCT && (wave & 3) < tK) {
+    // ---- p = H_f^{-1} r on the matrix cores: 4 row tiles x NCT column tiles, operands streamed from LDS; TQ: the next
+    //      four waves form S0 p = T r from the same r tile and publish the cells (those with rows) from the accumulators ----
+    if ((wave < 4 * NCT || (TQ && wave < 4 * NCT + 4)) && (wave & 3) < tK) {
+      const bool tw = TQ && wave >= 4 * NCT;
       const int li = lane & 15, lk = lane >> 4;
-      const int tile = wave & 3, ct = wave >> 2;
-      const double* Mt = Ml + (size_t)tile * nks * 64 + lane;
+      const int tile = wave & 3, ct = tw ? 0 : wave >> 2;
+      const double* Mt = (tw ? Tl : Ml) + (size_t)tile * nks * 64 + lane;
       const double* Bt = Rt + (size_t)(ct * 16 + li) * RSK;
       double4_t acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
@@ -311,16 +339,32 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         const double b = kk < K ? Bt[kk] : 0.0;
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Mt[(size_t)s * 64], b, acc, 0, 0, 0);
       }
-      double* Ot = Pt + (size_t)(ct * 16 + li) * RSK;
+      if (TQ && tw) {
+        // column li = (local agent al, axis d); row = time step.  The row loop reads the very bits that are published.
+        const int al = li / D, d = li % D;
+        const bool col_ok = li < D * APB16 && a0 + al < N;
+        double* Ot = Qt + (size_t)li * RSK;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row = tile * 16 + lk + 4 * q;
-        if (row < K) Ot[row] = acc[q];
+        for (int q = 0; q < 4; ++q) {
+          const int row = tile * 16 + lk + 4 * q;
+          if (row < K) {
+            Ot[row] = acc[q];
+            if (col_ok && cptr[al * K + row + 1] > cptr[al * K + row])  // cells with rows only
+              st_granules(A.cells + ((size_t)((int64_t)row * N + a0 + al) * D + d) * 2, tag, acc[q]);
+          }
+        }
+      } else {
+        double* Ot = Pt + (size_t)(ct * 16 + li) * RSK;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = tile * 16 + lk + 4 * q;
+          if (row < K) Ot[row] = acc[q];
+        }
       }
     }
     __syncthreads();
     PSTAMP(2);
-    // ---- prefix sums of p, S0 p (published where the cell has rows), r.p ------------------------------------------------
+    // ---- prefix sums of p, r.p; scan path: S0 p from them, published where the cell has rows ----------------------------
     double p[D], s1p[D], s2p[D];
     {
       double rz = 0.0;
@@ -330,18 +374,20 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         rz += (live ? my_rt[d * RSK] : 0.0) * p[d];  // r of this lane, re-read from its tile
         const double cs1 = wave_incl_sum(p[d]);
         const double cs2 = lane_below(wave_incl_sum(cs1));
-        const double qp = hh * (cs2 - 0.5 * lane_below(cs1));
         s1p[d] = live ? cs1 : 0.0;
         s2p[d] = live ? cs2 : 0.0;
-        if (has_rows) {
-          st_granules(my_cell + 2 * d, tag, qp);
-          my_pt[d * RSK] = qp;  // the row loops read the own agent's S0 p cell here
+        if constexpr (!TQ) {
+          const double qp = hh * (cs2 - 0.5 * lane_below(cs1));
+          if (has_rows) {
+            st_granules(my_cell + 2 * d, tag, qp);
+            my_pt[d * RSK] = qp;  // the row loops read the own agent's S0 p cell here
+          }
         }
       }
       rz = wave_incl_sum(rz);
-      if (lane == 63) red[0][wave] = rz;
+      if (lane == 63) red[0][wave] = rz;  // (read after the row loop's barrier)
     }
-    __syncthreads();
+    if constexpr (!TQ) __syncthreads();  // the own S0 p cells in Pt (TQ: in Qt since the MFMA barrier)
     PSTAMP(3);
     // ---- working rows: partner cells (polled until they carry this step's tag), eta . d(S0 p) ---------------------------
     {
@@ -369,11 +415,8 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         if (bad) break;
         double s = 0.0;
 #pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const double pp = pair_value(w[d]);
-          e_pp[(size_t)e * D + d] = pp;
-          s += e_c[(size_t)e * D + d] * (Pt[(size_t)(al * D + d) * RSK + ek] - pp);
-        }
+        for (int d = 0; d < D; ++d) s += e_c[(size_t)e * D + d] * (Qt[(size_t)(al * D + d) * RSK + ek] - pair_value(w[d]));
+        e_s[e] = s;              // (both copies of a row: the same bits, c and the difference change sign together)
         if (!side) sq += s * s;  // every row once
       }
       if (bad) {
@@ -395,6 +438,21 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
 #pragma unroll
       for (int w = 0; w < APB16; ++w) t += red[threadIdx.x][w];
       st_granules(gpart + (size_t)blockIdx.x * 4 + 2 * threadIdx.x, tag, t);
+    }
+    // what the fixed-row update needs and a does not change, formed while the partials are in flight: z = Pi(v)
+    double zcl[D][4];
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      double lo[2], hi[2];
+      bounds(d, lo, hi);
+      zcl[d][0] = fmin(fmax(v[d][0], jlo), jhi);
+      zcl[d][1] = fmin(fmax(v[d][1], alo), ahi);
+      zcl[d][2] = fmin(fmax(v[d][2], lo[0]), hi[0]);
+      zcl[d][3] = fmin(fmax(v[d][3], lo[1]), hi[1]);
+      if (first) {  // z of a reset is A x0 itself (y = 0, v = z)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) zcl[d][t] = v[d][t];
+      }
     }
     {
       unsigned spins = 0;
@@ -440,20 +498,10 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
     {
       const double irc = 1.0 / rho_c;
       for (int e = threadIdx.x; e < ne; e += NT16) {
-        const int code = e_code[e];
-        const int ek = code & 63, al = (code >> 6) & 15;
-        double tc = 0.0, ax = 0.0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const double c = e_c[(size_t)e * D + d];
-          const double po = Pt[(size_t)(al * D + d) * RSK + ek], pp = e_pp[(size_t)e * D + d];
-          const double qo = e_qo[(size_t)e * D + d], qq = e_qp[(size_t)e * D + d];
-          tc += c * (fma(a, po, qo) - fma(a, pp, qq));
-          const double qon = fma(aa, po, qo), qqn = fma(aa, pp, qq);
-          ax += c * (qon - qqn);
-          e_qo[(size_t)e * D + d] = qon;
-          e_qp[(size_t)e * D + d] = qqn;
-        }
+        // row values at x + a p (z~) and x + alpha a p (the next x): c . (S0 x_own - S0 x_partner) + a c . (S0 p_own - ...)
+        const double s = e_s[e], ax0 = e_ax[e];
+        const double tc = fma(a, s, ax0), ax = fma(aa, s, ax0);
+        e_ax[e] = ax;
         const double zo = e_z[e], yo = e_y[e];
         const double zh = alpha * tc + (1.0 - alpha) * zo;
         const double zn = fmax(zh + yo * irc, e_l[e]);
@@ -461,8 +509,8 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         e_z[e] = zn;
         e_y[e] = yn;
         e_g[e] = (rho_c * zn - yn) - rho_c * ax;
-        if (last && with_dy) e_pp[(size_t)e * D] = fmin(yn - yo, 0.0);  // delta-y of the batch's last step (u = +inf: polar of
-                                                                        // the recession cone), parked until the check
+        if (last && with_dy) e_s[e] = fmin(yn - yo, 0.0);  // delta-y of the batch's last step (u = +inf: polar of the
+                                                          // recession cone), parked until the check
       }
     }
     const bool cert = last && with_dy;
@@ -475,12 +523,8 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         const double xt = fma(a, p[d], x[d]);
         const double t1 = fma(a, s1p[d], c1[d]), t2 = fma(a, s2p[d], c2[d]);
         const double xtn = lane_above(xt);
-        double lo[2], hi[2];
-        bounds(d, lo, hi);
         // v' = v + alpha (F x~ - Pi(v)); the new z, y are Pi(v'), rho (v' - Pi(v'))
-        double cj = fmin(fmax(v[d][0], jlo), jhi), ca = fmin(fmax(v[d][1], alo), ahi);
-        double cv = fmin(fmax(v[d][2], lo[0]), hi[0]), cp = fmin(fmax(v[d][3], lo[1]), hi[1]);
-        if (first) { cj = v[d][0]; ca = v[d][1]; cv = v[d][2]; cp = v[d][3]; }
+        const double cj = zcl[d][0], ca = zcl[d][1], cv = zcl[d][2], cp = zcl[d][3];
         const double nj = jok ? fma(alpha, (xtn - xt) * ih - cj, v[d][0]) : v[d][0];
         const double na = fma(alpha, xt - ca, v[d][1]);
         const double nv = fma(alpha, h * t1 - cv, v[d][2]);
@@ -488,6 +532,8 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         if (cert) {
           // OSQP's certificate on delta-y = rho [(v' - Pi(v')) - (v - Pi(v))] of this step: |dy|, the support value
           // u.dy+ + l.dy-, and A^T dy by the r chain
+          double lo[2], hi[2];
+          bounds(d, lo, hi);
           const double dyj = rho * ((nj - fmin(fmax(nj, jlo), jhi)) - (v[d][0] - cj));
           const double dya = rho * ((na - fmin(fmax(na, alo), ahi)) - (v[d][1] - ca));
           const double dyv = rv * ((nv - fmin(fmax(nv, lo[0]), hi[0])) - (v[d][2] - cv));
@@ -496,7 +542,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
           m_supp += (jhi * fmax(dyj, 0.0) + jlo * fmin(dyj, 0.0)) + (ahi * fmax(dya, 0.0) + alo * fmin(dya, 0.0)) +
                     (hi[0] * fmax(dyv, 0.0) + lo[0] * fmin(dyv, 0.0)) + (hi[1] * fmax(dyp, 0.0) + lo[1] * fmin(dyp, 0.0));
           double gd = 0.0;
-          for (int e = c0; e < c1e; ++e) gd += e_c[(size_t)e * D + d] * e_pp[(size_t)e * D];
+          for (int e = c0; e < c1e; ++e) gd += e_c[(size_t)e * D + d] * e_s[e];
           const double u1 = h * dyv + 0.5 * hh * (dyp - gd);
           const double u2 = dyp + gd;
           const double d1 = wave_incl_rsum(u1);
@@ -587,7 +633,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
       }
     }
     __syncthreads();
-    {  // collision rows: exact S0 x cells of both agents (the carried copies are refreshed), residuals, delta-y
+    {  // collision rows: exact S0 x cells of both agents (the carried row values are refreshed), residuals, delta-y
       unsigned spins = 0;
       bool bad = false;
       for (int e = threadIdx.x; e < ne; e += NT16) {
@@ -614,17 +660,16 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         for (int d = 0; d < D; ++d) {
           const double qq = pair_value(w[d]);
           const double qo = Pt[(size_t)(al * D + d) * RSK + ek];
-          e_qo[(size_t)e * D + d] = qo;
-          e_qp[(size_t)e * D + d] = qq;
           ax += e_c[(size_t)e * D + d] * (qo - qq);
         }
+        e_ax[e] = ax;
         if (!side) {
           const double zc_ = e_z[e];
           m[CK_RP] = fmax(m[CK_RP], fabs(ax - zc_));
           m[CK_NAX] = fmax(m[CK_NAX], fabs(ax));
           m[CK_NZ] = fmax(m[CK_NZ], fabs(zc_));
           if (with_dy) {
-            const double dd = e_pp[(size_t)e * D];
+            const double dd = e_s[e];
             m[CK_NDY] = fmax(m[CK_NDY], fabs(dd));
             m[CK_SUPP] += e_l[e] * dd;
           }
@@ -736,13 +781,12 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
           }
           rho = nrs;
           rho_c = rho * A.rho_col_scale;
-          for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) Ml[i] = A.tab[slot].pMinv[i];
-          for (int e = threadIdx.x; e < ne; e += NT16) {  // row values of the next right-hand side from the exact S0 x cells
-            double ax = 0.0;
-#pragma unroll
-            for (int d = 0; d < D; ++d) ax += e_c[(size_t)e * D + d] * (e_qo[(size_t)e * D + d] - e_qp[(size_t)e * D + d]);
-            e_g[e] = (rho_c * e_z[e] - e_y[e]) - rho_c * ax;
+          for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) {
+            Ml[i] = A.tab[slot].pMinv[i];
+            if constexpr (TQ) Tl[i] = A.tab[slot].pT[i];
           }
+          for (int e = threadIdx.x; e < ne; e += NT16)  // row values of the next right-hand side from the exact S0 x cells
+            e_g[e] = (rho_c * e_z[e] - e_y[e]) - rho_c * e_ax[e];
           ++n_rho;
           if (A.check_fine > 0) cad = A.check_fine;
         }
@@ -826,6 +870,8 @@ extern "C" int scp_debug_persist16_clocks(unsigned long long* out, int n) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_persist16_clk), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
 }
 #endif
+
+size_t scp_persist16_entry_bytes(int D) { return (size_t)ent_doubles(D) * sizeof(double) + sizeof(int); }
 
 size_t scp_persist16_lds_bytes(int K, int cap, int nblk, int D, int apb) {
   const Lds16 L(K, cap, nblk, D, apb);

@@ -46,8 +46,8 @@ def main():
             print(f"  {name:44s} {v if i in (0, 8) else v / steps:8.2f} us{' (total)' if i in (0, 8) else ''}")
         print(f"  {'sum':44s} {sum(pb) * 0.01:8.2f} us per launch")
     if hasattr(lib, "scp_debug_persist16_clocks") and lib.scp_debug_persist16_clocks(pb, 16) == 0 and sum(pb):
-        names = ["state load (once per launch)", "gather G, W', r: suffix scans", "p = Minv r (MFMA, operands from LDS)",
-                 "prefix sums of p, S0 p, publish cells", "rows: poll partner cells, eta . dS0p", "all-gather of the partials",
+        names = ["state load (once per launch)", "gather G, W', r: suffix scans", "p = Minv r (MFMA; <2,8>: + S0 p = T r, publish)",
+                 "prefix sums of p (+ S0 p, publish cells), r.p", "rows: poll partner cells, eta . dS0p", "all-gather of the partials (+ z = Pi(v))",
                  "step length", "updates (entries, then registers)", "state write-back (once per launch)", "termination checks (total)"]
         steps = max(int(pb[15]), 1)
         pb[15] = 0
@@ -55,8 +55,8 @@ def main():
         for i, name in enumerate(names):
             v = pb[i] * 0.01
             once = i in (0, 8, 9)
-            print(f"  {name:44s} {v if once else v / steps:8.2f} us{' (total)' if once else ''}")
-        print(f"  {'sum':44s} {sum(pb) * 0.01:8.2f} us per launch")
+            print(f"  {name:50s} {v if once else v / steps:8.2f} us{' (total)' if once else ''}")
+        print(f"  {'sum':50s} {sum(pb) * 0.01:8.2f} us per launch")
         return
     buf = (C.c_ulonglong * 64)()
     assert lib.scp_debug_phase_clocks(buf, 64) == 0
