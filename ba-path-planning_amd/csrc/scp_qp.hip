@@ -435,9 +435,9 @@ struct Carver {
   }
 };
 
-size_t kkt_slot_doubles(int K) {  // Hf, HS, Minv, T + packed HS, Minv, T, each 256-byte aligned
+size_t kkt_slot_doubles(int K) {  // Hf, HS, Minv, T + packed Minv, T, each 256-byte aligned
   auto al = [](size_t n) { return (n + 31) / 32 * 32; };
-  return al((size_t)K * K) * 3 + al((size_t)2 * K * K) + al(scp_packed_count(2 * K, K)) + 2 * al(scp_packed_count(K, K));
+  return al((size_t)K * K) * 3 + al((size_t)2 * K * K) + 2 * al(scp_packed_count(K, K));
 }
 
 // Adaptive rho moves on a geometric grid (steps of 2^(1/4)), so a solver object that is reused from scenario to scenario
@@ -460,11 +460,7 @@ size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
   d.gj_tmp = c.take<double>((size_t)3 * K);
   d.wrow = c.take<double>((size_t)Rf);
   d.G0 = c.take<double>((size_t)K * K);
-  d.pF = c.take<double>(scp_packed_count(Rf, K));
-  d.pFt = c.take<double>(scp_packed_count(K, Rf));
-  d.pS0 = c.take<double>(scp_packed_count(K, K));
-  d.pS0t = c.take<double>(scp_packed_count(K, K));
-  d.pHS = d.pMinv = d.T = d.pT = nullptr;
+  d.pMinv = d.T = d.pT = nullptr;
   d.kkt_pool = c.take<double>((size_t)kkt_slots(K) * kkt_slot_doubles(K));
   const size_t nf = (size_t)Rf * C, nx = (size_t)K * C;
   d.lf = c.take<double>(nf);
@@ -492,7 +488,7 @@ size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
   d.yc = c.take<double>((size_t)cap);
   d.scal = c.take<double>(SL_COUNT + SCP_RESID_CAP);
   d.part = c.take<double>(2 * SCP_PART_CAP);
-  d.hpf = c.take<double>(nx);
+  d.s0p = c.take<double>(nx);
   d.fx = c.take<double>(nf);
   d.dyf = c.take<double>(nf);
   d.dyc = c.take<double>((size_t)cap);
@@ -537,7 +533,7 @@ int gemm(scp_qp* qp, int R, int M, double alpha, const double* A, const double* 
 template <int MODE>
 int row_scatter(scp_qp* qp, const double* Q, const double* vec = nullptr) {
   if (!qp->csr_valid) QP_CHECK(scp_qp_csr_build(qp));
-  if (MODE == ROW_HMUL) return scp_qp_rows_gather(qp, false, Q);
+  if (MODE == ROW_HMUL) return scp_qp_rows_gather(qp, Q);
   return scp_qp_csr_scatter(qp, MODE == ROW_RHS ? 0 : (MODE == ROW_Y ? 1 : 2), vec);
 }
 
@@ -564,10 +560,6 @@ int build_kkt(scp_qp* qp) {
   QpDev& d = qp->d;
   const int K = qp->K;
   hipStream_t s = qp->ctx->stream;
-  if (!qp->consts_packed) {
-    QP_CHECK(scp_qp_pack_operands(qp, true));
-    qp->consts_packed = true;
-  }
   // cache lookup: the blocks of this (rho, sigma) may still be resident
   scp_qp::KktSlot* slot = nullptr;
   for (int i = 0; i < qp->n_kkt; ++i)
@@ -580,7 +572,7 @@ int build_kkt(scp_qp* qp) {
   }
   slot->used = ++qp->kkt_clock;
   d.Hf = slot->Hf; d.HS = slot->HS; d.Minv = slot->Minv; d.T = slot->T;
-  d.pHS = slot->pHS; d.pMinv = slot->pMinv; d.pT = slot->pT;
+  d.pMinv = slot->pMinv; d.pT = slot->pT;
   if (hit) return SCP_OK;
   slot->rho = qp->rho;
   slot->sigma = qp->st.sigma;
@@ -604,7 +596,7 @@ int build_kkt(scp_qp* qp) {
   QP_LAUNCHED(qp);
   // T = S0 H_f^{-1}: the persistent kernel forms S0 p = T r on spare matrix-core waves next to p = H_f^{-1} r
   QP_CHECK(scp_launch_gemm(qp->ctx, 1, K, K, K, 1.0, d.S0, d.Minv, 0.0, d.T));
-  return scp_qp_pack_operands(qp, false);
+  return scp_qp_pack_operands(qp);
 }
 
 int admm_iteration(scp_qp* qp, int* cg_count) {
@@ -811,13 +803,11 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
       k.Minv = q; q += al((size_t)K * K);
       k.T = q; q += al((size_t)K * K);
       k.HS = q; q += al((size_t)2 * K * K);
-      k.pHS = q; q += al(scp_packed_count(2 * K, K));
       k.pMinv = q; q += al(scp_packed_count(K, K));
       k.pT = q;
       base += kkt_slot_doubles(K);
     }
     qp->kkt_clock = 0;
-    qp->consts_packed = false;
   }
   qp->check_seq = 0;
   qp->persist_off = false;
@@ -1060,13 +1050,36 @@ int scp_qp_add_rows_from_pass(scp_qp* qp, int64_t n, const int64_t* rows, const 
   return add_rows_impl(qp, n, rows, eta, l_col, scp_eta_stride(qp->K, q_end - q_begin), q_begin, q_end - q_begin);
 }
 
+// The ADMM pipeline of a solve.  Its inputs (settings, K, C, nW) do not change within a scp_qp_solve call.
+enum class QpPipe {
+  QP0,       // fixed rows only (everything is column-local): every iteration up to the next check in ONE launch
+  CG1,       // single PCG step with collision rows: the persistent kernel where it runs, else the three launches
+  CG1_BIGK,  // the same three launches with cg1_colK_kernel as the column kernel (K in 121..1024, e.g. the reference's
+             // demo K = 500); its termination check is the generic one (snapshot of the duals)
+  GENERIC    // one product per launch: cg_iters > 1, use_mfma 0 / 2, and shapes beyond the column kernels
+};
+
+static QpPipe choose_pipeline(const scp_qp* qp) {
+  const scp_qp_settings& st = qp->st;
+  if (st.use_mfma != 1) return QpPipe::GENERIC;
+  const bool cols_fit = qp->K <= SCP_FUSED_MAX_K && (qp->C + 15) / 16 <= SCP_PART_CAP / 2;  // 16-column workgroups
+  if (qp->nW == 0) return cols_fit ? QpPipe::QP0 : QpPipe::GENERIC;
+  if (st.cg_iters != 1) return QpPipe::GENERIC;
+  if (cols_fit) return QpPipe::CG1;
+  if (qp->K > SCP_FUSED_MAX_K && qp->K <= SCP_BIGK_MAX_K && qp->C <= SCP_PART_CAP / 2) return QpPipe::CG1_BIGK;
+  return QpPipe::GENERIC;
+}
+
 extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
   if (!qp) return SCP_ERR_INVALID;
   scp_ctx* ctx = qp->ctx;
   if (!qp->reset_done) return scp_fail(ctx, SCP_ERR_STATE, "qp_solve: call scp_qp_reset first");
   SCP_REQUIRE(ctx, info, "qp_solve: null info");
-  const bool fused = qp->st.use_mfma == 1 && qp->K <= SCP_FUSED_MAX_K && (qp->C + 15) / 16 <= SCP_PART_CAP / 2;
   const scp_qp_settings& st = qp->st;
+  const QpPipe pipe = choose_pipeline(qp);
+  // QP0 and CG1 run their own termination check (scp_qp_fused_residuals), which also forms delta-y and |A^T dy|
+  const bool own_check = pipe == QpPipe::QP0 || pipe == QpPipe::CG1;
+  static constexpr int persist_pipe[] = {SCP_PIPE_PERSIST, SCP_PIPE_PERSIST16, SCP_PIPE_PERSIST8L};  // by persist_variant
   memset(info, 0, sizeof(*info));
   info->status_val = -2;  // OSQP_MAX_ITER_REACHED
   qp->cg1_ready = false;  // settings may have changed between calls
@@ -1077,26 +1090,12 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
   int pipes = 0;
   double rp = INFINITY, rd = INFINITY;
   int cad = st.check_termination;  // steps between two checks (settings.check_fine: shorter once the residuals are close)
-  // (the fine cadence applies when it divides the coarse one; otherwise the cadence is fixed)
-  // and to QPs with collision rows: QP#0 keeps the fixed cadence (its 20 surplus steps are cheap, and a better converged
-  // starting point saves the first joint QP of large problems far more: 250 instead of 400 steps at 1024 x 50)
-  // ... and up to SCP_FINE_MAX_COLUMNS columns: beyond, it measured slower (4096 x 50: 195 instead of 200 steps, but 0.27 ms
-  // more in every repetition; profiles/r03_check_cadence.txt, r03_check_cost.txt)
-  constexpr int64_t SCP_FINE_MAX_COLUMNS = 4096;
-  const int fine = (st.check_fine > 0 && st.check_fine < st.check_termination && st.check_termination % st.check_fine == 0 && qp->nW > 0 &&
-                    qp->C <= SCP_FINE_MAX_COLUMNS) ? st.check_fine : 0;
+  const int fine = scp_qp_fine_cadence(qp);
   while (it < st.max_iter) {
-    // fixed rows only (everything is column-local): every iteration up to the next termination check goes into ONE
-    // launch; the persistent single-step kernel goes further and runs the checks itself, returning only when the host has
-    // something to decide (solved, infeasible, iteration limit, a rho update)
-    const bool qp0_it = fused && qp->nW == 0;
-    // long horizons (K in 121..1024, e.g. the reference's demo K = 500): the same single-step pipeline with
-    // cg1_colK_kernel as its column kernel; its termination check is the generic one (snapshot of the duals)
-    const bool bigk = st.use_mfma == 1 && qp->K > SCP_FUSED_MAX_K && qp->K <= SCP_BIGK_MAX_K && qp->C <= SCP_PART_CAP / 2;
-    const bool cg1_big = bigk && st.cg_iters == 1 && qp->nW > 0;
-    const bool cg1_it = fused && st.cg_iters == 1 && qp->nW > 0;  // its update kernel emits delta-y itself
+    // the persistent single-step kernel runs the checks itself, returning only when the host has something to decide
+    // (solved, infeasible, iteration limit, a rho update)
     bool persist_done = false;
-    if (cg1_it && !qp->persist_skip_solve && scp_qp_persist_eligible(qp)) {
+    if (pipe == QpPipe::CG1 && !qp->persist_skip_solve && scp_qp_persist_eligible(qp)) {
       int ran = 0, code = 0, it_done = it;
       QP_CHECK(scp_qp_cg1_persist(qp, it, cad, &ran, &code, &it_done));
       if (ran && code == SCP_PERSIST_GAVE_UP) {
@@ -1109,7 +1108,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
       } else if (ran) {
         ++info->persist_launches;
         info->rho_switches_in_kernel += qp->persist_rho_switches;
-        pipes |= 1 << (qp->persist_variant == 1 ? SCP_PIPE_PERSIST16 : (qp->persist_variant == 2 ? SCP_PIPE_PERSIST8L : SCP_PIPE_PERSIST));
+        pipes |= 1 << persist_pipe[qp->persist_variant];
         cg_total += it_done - it;
         qp->steps_since_reset += it_done - it;
         it = it_done;
@@ -1125,7 +1124,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
       }
     }
     int n_it = 1;
-    if (!persist_done && qp0_it) {
+    if (!persist_done && pipe == QpPipe::QP0) {
       n_it = cad - it % cad;
       if (it + n_it > st.max_iter) n_it = st.max_iter - it;
     }
@@ -1136,28 +1135,29 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
     const bool will_check = persist_done || it % cad == 0 || it >= st.max_iter;
     const bool with_dy = will_check && st.eps_prim_inf > 0.0;
     if (!persist_done) {
-      if (with_dy && !cg1_it && !qp0_it) {  // snapshot of the duals: delta-y of this iteration feeds the certificate
+      if (with_dy && !own_check) {  // snapshot of the duals: delta-y of this iteration feeds the certificate
         SCP_HIP_CHECK(ctx, hipMemcpyAsync(qp->d.dyf, qp->d.yf, (size_t)qp->Rf * qp->C * sizeof(double),
                                           hipMemcpyDeviceToDevice, ctx->stream));
         if (qp->nW > 0)
           SCP_HIP_CHECK(ctx, hipMemcpyAsync(qp->d.dyc, qp->d.yc, (size_t)qp->nW * sizeof(double),
                                             hipMemcpyDeviceToDevice, ctx->stream));
       }
-      if (cg1_it) { QP_CHECK(scp_qp_cg1_iteration(qp, &cg_total, with_dy)); pipes |= 1 << SCP_PIPE_CG1; }
-      else if (cg1_big) { QP_CHECK(scp_qp_cg1_iteration(qp, &cg_total, false)); pipes |= 1 << SCP_PIPE_CG1_BIGK; }
-      else if (qp0_it) { QP_CHECK(scp_qp_qp0_iterations(qp, n_it, with_dy ? qp->d.dyf : nullptr)); pipes |= 1 << SCP_PIPE_QP0; }
-      else if (fused) { QP_CHECK(scp_qp_fused_iteration(qp, &cg_total)); pipes |= 1 << SCP_PIPE_FUSED; }
-      else { QP_CHECK(admm_iteration(qp, &cg_total)); pipes |= 1 << SCP_PIPE_GENERIC; }
+      switch (pipe) {  // (CG1's update kernel emits delta-y itself)
+        case QpPipe::QP0: QP_CHECK(scp_qp_qp0_iterations(qp, n_it, with_dy ? qp->d.dyf : nullptr)); pipes |= 1 << SCP_PIPE_QP0; break;
+        case QpPipe::CG1: QP_CHECK(scp_qp_cg1_iteration(qp, &cg_total, with_dy)); pipes |= 1 << SCP_PIPE_CG1; break;
+        case QpPipe::CG1_BIGK: QP_CHECK(scp_qp_cg1_iteration(qp, &cg_total, false)); pipes |= 1 << SCP_PIPE_CG1_BIGK; break;
+        case QpPipe::GENERIC: QP_CHECK(admm_iteration(qp, &cg_total)); pipes |= 1 << SCP_PIPE_GENERIC; break;
+      }
     }
     if (will_check) {
       if (persist_done) {
         // (the kernel left the nine check results in h_scal)
-      } else if (cg1_it || qp0_it) {
+      } else if (own_check) {
         QP_CHECK(scp_qp_fused_residuals(qp, with_dy));
       } else {
         QP_CHECK(residuals(qp, with_dy));
       }
-      if (!cg1_it) { qp->cg1_ready = false; qp->gval_valid = false; qp->qx_fresh = false; }  // residuals() used G and the Q slabs as scratch (the fused check keeps
+      if (pipe != QpPipe::CG1) { qp->cg1_ready = false; qp->gval_valid = false; qp->qx_fresh = false; }  // residuals() used G and the Q slabs as scratch (the fused check keeps
                                            // the pipeline's carried state and refreshes S0 x, F x exactly)
       const double* hs = qp->h_scal;
       rp = hs[SL_RP];
@@ -1178,7 +1178,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
       if (with_dy) {  // OSQP's is_primal_infeasible on the unscaled problem
         const double ndy = hs[SL_NDY], supp = hs[SL_SUPP];
         if (ndy > st.eps_prim_inf && supp < -st.eps_prim_inf * ndy) {
-          if (!cg1_it && !qp0_it) QP_CHECK(certificate_atdy(qp));  // the fused check has |A^T dy| already
+          if (!own_check) QP_CHECK(certificate_atdy(qp));  // the fused check has |A^T dy| already
           if (qp->h_scal[SL_NATDY] < st.eps_prim_inf * ndy) {
             info->status_val = -3;
             break;
@@ -1316,7 +1316,7 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
   else if (!strcmp(name, "w_eta")) { src = d.w_eta; n = qp->nW * qp->D; }
   else if (!strcmp(name, "w_l")) { src = d.w_l; n = qp->nW; }
   else if (!strcmp(name, "p")) { src = d.p; n = nx; }
-  else if (!strcmp(name, "qp")) { src = d.hpf; n = nx; }
+  else if (!strcmp(name, "qp")) { src = d.s0p; n = nx; }
   else return scp_fail(ctx, SCP_ERR_INVALID, "qp_peek: unknown array %s", name);
   *n_out = n;
   if (n > cap) return scp_fail(ctx, SCP_ERR_CAPACITY, "qp_peek: %lld doubles needed", (long long)n);

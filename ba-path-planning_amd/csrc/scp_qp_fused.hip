@@ -1,14 +1,13 @@
-// Column-block kernels of the joint QP (fused path, K <= SCP_FUSED_MAX_K).
+// Column-block kernels of the joint QP (use_mfma = 1: the single-step pipeline, K <= SCP_FUSED_MAX_K with 16 columns
+// per workgroup, K <= SCP_BIGK_MAX_K with one workgroup per column; QP#0's column-local kernel; the termination check).
 //
 // Every operation of an ADMM step except the working-row gather/scatter is local to a column c = (agent, axis):
 // the fixed rows, the K x K KKT block and the Toeplitz block S0 act along the time index only.
-// One workgroup (16 waves) therefore owns 16 columns, keeps their K-vectors as [rows][16] tiles in LDS and chains
-// whole sequences of products  tile_out = A . tile_in  (A one of F^T, [H_f; S0], S0^T, H_f^{-1}, F) on the fp64
-// matrix cores -- v_mfma_f64_16x16x4_f64, one 16 x 16 output tile per wave and step, the A operand preloaded from
-// L2 in chunks of 16 k-steps so that a chain costs one memory latency, not one per step.  Kernel boundaries remain
-// only where the algorithm needs the whole grid: the two PCG inner products and the row gather/scatter.
-// An ADMM step with n PCG steps is 4n + 3 launches, 7 at the default n = 1 (15n + ... on the generic path of scp_qp.hip, which stays as the fallback
-// for K > 128 and as the use_mfma = 0/2 reference); the arithmetic is the same, statement by statement.
+// One workgroup (16 waves) therefore owns 16 columns and keeps their K-vectors in LDS: F, F^T, S0 and S0^T are
+// jerk stencils and cumulative sums (wave-wide scans), and the only dense product left, H_f^{-1}, runs on the fp64
+// matrix cores (v_mfma_f64_16x16x4_f64, operand pre-packed in lane order: scp_qp_pack_operands).  Kernel boundaries
+// remain only where the algorithm needs the whole grid: the inner products and the row gather/scatter.
+// cg_iters > 1 and use_mfma = 0 / 2 run on the generic pipeline of scp_qp.hip (one product per launch).
 #include "scp_qp_device.h"
 #include "scp_pair_device.h"
 #include "scp_reset_device.h"
@@ -30,387 +29,6 @@ __device__ unsigned long long scp_phase_clk[64];
 #else
 #define PHASE_MARK(slot) ((void)0)
 #endif
-
-// O[R][16] = (ACC ? O : 0) + A[R][M] . V[M][16];  A: global, PACKED in operand order (QpDev::pF ...: [row tile][k step]
-// [lane], zero padded);  V, O: distinct LDS tiles.  The waves [w0, w0+nw) of the workgroup share the row tiles; other
-// waves return at once, so independent products run side by side on disjoint wave sets.  One operand load is 512
-// contiguous bytes per wave (row-major A cost 16 cache lines per load and kept the L1 busy for most of a phase).  The
-// operands of the NEXT chunk of 16 k-steps are loaded while the MFMAs of the current chunk issue.
-// Operand maps of v_mfma_f64_16x16x4_f64 as in scp_gemm.hip.  Caller synchronises before reading O.
-template <bool ACC>
-__device__ inline void wg_mm_range(const double* __restrict__ P, int R, int M, int kb, int ke, const double* V, double* O,
-                                   int w0, int nw) {
-  // O[R][16] (+)= A[R][kb:ke] . V[kb:ke][16]   (kb a multiple of 4; V is indexed by the absolute k)
-  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6) - w0;
-  if (wave < 0 || wave >= nw) return;
-  const int li = lane & 15, lk = lane >> 4;
-  const int tiles = (R + 15) >> 4, nks = (M + 3) >> 2;
-  const int ks0 = kb >> 2, ks1 = (ke + 3) >> 2;
-  for (int t = wave; t < tiles; t += nw) {
-    const int r0 = t * 16;
-    const double* Ap = P + (size_t)t * nks * 64 + lane;
-    double4_t acc = {0.0, 0.0, 0.0, 0.0};
-    if (ACC) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = r0 + lk + 4 * r;
-        acc[r] = row < R ? O[row * CB + li] : 0.0;
-      }
-    }
-    double a[16], an[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) a[s] = Ap[(size_t)min(ks0 + s, ks1 - 1) * 64];  // clamped: straight-line loads
-    for (int kc = ks0; kc < ks1; kc += 16) {
-      const bool more = kc + 16 < ks1;  // wave-uniform
-      if (more) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) an[s] = Ap[(size_t)min(kc + 16 + s, ks1 - 1) * 64];
-      }
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        if (kc + s < ks1) {  // wave-uniform
-          const int kk = 4 * (kc + s) + lk;
-          const double b = kk < ke ? V[kk * CB + li] : 0.0;
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], b, acc, 0, 0, 0);
-        }
-      }
-      if (more) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) a[s] = an[s];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = r0 + lk + 4 * r;
-      if (row < R) O[row * CB + li] = acc[r];
-    }
-  }
-}
-
-template <bool ACC>
-__device__ inline void wg_mm(const double* __restrict__ A, int R, int M, const double* V, double* O, int w0, int nw) {
-  wg_mm_range<ACC>(A, R, M, 0, M, V, O, w0, nw);
-}
-
-// tile <-> global ([rows][C] slab, columns c0 .. c0+15); out-of-range columns read as 0 and are not written
-__device__ inline void tile_load(double* T, const double* __restrict__ g, int rows, int64_t C, int64_t c0) {
-  for (int e = threadIdx.x; e < rows * CB; e += FT) {
-    const int r = e >> 4, c = e & 15;
-    T[e] = (c0 + c < C) ? g[(int64_t)r * C + c0 + c] : 0.0;
-  }
-}
-__device__ inline void tile_store(const double* T, double* __restrict__ g, int rows, int64_t C, int64_t c0) {
-  for (int e = threadIdx.x; e < rows * CB; e += FT) {
-    const int r = e >> 4, c = e & 15;
-    if (c0 + c < C) g[(int64_t)r * C + c0 + c] = T[e];
-  }
-}
-__device__ inline void tile_zero_global(double* __restrict__ g, int rows, int64_t C, int64_t c0) {
-  for (int e = threadIdx.x; e < rows * CB; e += FT) {
-    const int r = e >> 4, c = e & 15;
-    if (c0 + c < C) g[(int64_t)r * C + c0 + c] = 0.0;
-  }
-}
-
-// deterministic workgroup sum (fixed tree); result valid in every thread
-__device__ inline double wg_sum(double v) {
-  __shared__ double s[FT / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NWV; ++w) t += s[w];
-  __syncthreads();
-  return t;
-}
-
-// sum of the per-workgroup partials of an inner product, same order in every workgroup
-__device__ inline double sum_parts(const double* __restrict__ part, int n) {
-  double v = 0.0;
-  for (int b = threadIdx.x; b < n; b += FT) v += part[b];
-  return wg_sum(v);
-}
-
-// ---- K_A: rhs and the fixed part of the PCG start ------------------------------------------------------
-// W = rho w_r z_f - y_f ; rhsF = sigma x + F^T W ; [Hx ; Qx] = [H_f ; S0] x
-// has_rows: r0 = rhsF - Hx -> rhs, Qx -> Q, xt = x, G = 0        (PCG follows)
-// else    : xt = H_f^{-1} rhsF                                    (the x-update is exact)
-__global__ __launch_bounds__(FT) void fused_pre_kernel(int K, int Rf, int64_t C, double rho, double sigma, int has_rows,
-                                                        const double* __restrict__ Ft, const double* __restrict__ HS,
-                                                        const double* __restrict__ Minv,
-                                                        const double* __restrict__ wrow, const double* __restrict__ x,
-                                                        const double* __restrict__ zf, const double* __restrict__ yf,
-                                                        double* __restrict__ rhs, double* __restrict__ Q,
-                                                        double* __restrict__ xt, double* __restrict__ G) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* X = lds;                  // [K][16]
-  double* W = X + K * CB;           // [Rf][16]
-  double* T1 = W + Rf * CB;         // [K][16]
-  double* T2 = T1 + K * CB;         // [2K][16]
-  const int64_t c0 = (int64_t)blockIdx.x * CB;
-  tile_load(X, x, K, C, c0);
-  for (int e = threadIdx.x; e < Rf * CB; e += FT) {
-    const int r = e >> 4, c = e & 15;
-    const int64_t g = (int64_t)r * C + c0 + c;
-    W[e] = (c0 + c < C) ? rho * wrow[r] * zf[g] - yf[g] : 0.0;
-  }
-  __syncthreads();
-  if (has_rows) {  // two independent products side by side
-    wg_mm<false>(Ft, K, Rf, W, T1, 0, 8);
-    wg_mm<false>(HS, 2 * K, K, X, T2, 8, NWV - 8);
-  } else {
-    wg_mm<false>(Ft, K, Rf, W, T1, 0, NWV);
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < K * CB; e += FT) T1[e] += sigma * X[e];  // rhsF
-  __syncthreads();
-  if (has_rows) {
-    for (int e = threadIdx.x; e < K * CB; e += FT) {
-      const int r = e >> 4, c = e & 15;
-      if (c0 + c < C) {
-        const int64_t g = (int64_t)r * C + c0 + c;
-        rhs[g] = T1[e] - T2[e];
-        Q[g] = T2[K * CB + e];
-        xt[g] = X[e];
-        G[g] = 0.0;
-      }
-    }
-  } else {
-    wg_mm<false>(Minv, K, K, T1, T2, 0, NWV);
-    __syncthreads();
-    tile_store(T2, xt, K, C, c0);
-  }
-}
-
-// ---- K_B / K_D: working rows, G = A_W^T g: rows_value_kernel + csr_gather_kernel (scp_qp_rows_gather below) -- a gather
-// over the sorted incidence lists, so the sums have a fixed order (the round-1 version scattered with atomics)
-// ---- K_C: PCG start ---------------------------------------------------------------------------------------
-// r = r0 + S0^T G ; zz = Minv r ; p = zz ; part[b] = r.zz ; [HpF ; Qp] = [H_f ; S0] p ; G = 0
-__global__ __launch_bounds__(FT) void fused_cg_init_kernel(int K, int64_t C, const double* __restrict__ S0t,
-                                                            const double* __restrict__ Minv,
-                                                            const double* __restrict__ HS, const double* __restrict__ r0,
-                                                            double* __restrict__ G, double* __restrict__ r,
-                                                            double* __restrict__ p, double* __restrict__ hpf,
-                                                            double* __restrict__ Q, double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* Gt = lds;                 // [K][16]
-  double* R = Gt + K * CB;          // [K][16]
-  double* Z = R + K * CB;           // [K][16]
-  double* T2 = Z + K * CB;          // [2K][16]
-  const int64_t c0 = (int64_t)blockIdx.x * CB;
-  tile_load(Gt, G, K, C, c0);
-  tile_load(R, r0, K, C, c0);
-  __syncthreads();
-  tile_zero_global(G, K, C, c0);
-  wg_mm<true>(S0t, K, K, Gt, R, 0, NWV);
-  __syncthreads();
-  wg_mm<false>(Minv, K, K, R, Z, 0, NWV);
-  __syncthreads();
-  wg_mm<false>(HS, 2 * K, K, Z, T2, 0, NWV);
-  double dot = 0.0;
-  for (int e = threadIdx.x; e < K * CB; e += FT) dot += R[e] * Z[e];
-  dot = wg_sum(dot);  // (barrier inside: T2 complete afterwards)
-  if (threadIdx.x == 0) part[blockIdx.x] = dot;
-  for (int e = threadIdx.x; e < K * CB; e += FT) {
-    const int rr = e >> 4, c = e & 15;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)rr * C + c0 + c;
-      r[g] = R[e];
-      p[g] = Z[e];
-      hpf[g] = T2[e];
-      Q[g] = T2[K * CB + e];
-    }
-  }
-}
-
-// ---- K_E: Hp = HpF + S0^T G ; part[b] = p.Hp ; G = 0 -----------------------------------------------------
-__global__ __launch_bounds__(FT) void fused_cg_hp_kernel(int K, int64_t C, const double* __restrict__ S0t,
-                                                          double* __restrict__ G, const double* __restrict__ hpf,
-                                                          const double* __restrict__ p, double* __restrict__ Hp,
-                                                          double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* Gt = lds;                 // [K][16]
-  double* H = Gt + K * CB;          // [K][16]
-  const int64_t c0 = (int64_t)blockIdx.x * CB;
-  tile_load(Gt, G, K, C, c0);
-  tile_load(H, hpf, K, C, c0);
-  __syncthreads();
-  tile_zero_global(G, K, C, c0);
-  wg_mm<true>(S0t, K, K, Gt, H, 0, NWV);
-  __syncthreads();
-  double dot = 0.0;
-  for (int e = threadIdx.x; e < K * CB; e += FT) {
-    const int rr = e >> 4, c = e & 15;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)rr * C + c0 + c;
-      Hp[g] = H[e];
-      dot += p[g] * H[e];
-    }
-  }
-  dot = wg_sum(dot);
-  if (threadIdx.x == 0) part[blockIdx.x] = dot;
-}
-
-// ---- K_F: alpha = rz / pHp ; xt += alpha p ; r -= alpha Hp ; zz = Minv r ; part[b] = r.zz -------------------
-// rz: first = 1 -> sum(part_rz) (the PCG start wrote partials), else scal[slot]
-__global__ __launch_bounds__(FT) void fused_cg_step_kernel(int K, int64_t C, int nblk, int first, int slot,
-                                                            const double* __restrict__ Minv, double* __restrict__ scal,
-                                                            const double* __restrict__ part_rz,
-                                                            const double* __restrict__ part_php,
-                                                            const double* __restrict__ p, const double* __restrict__ Hp,
-                                                            double* __restrict__ xt, double* __restrict__ r,
-                                                            double* __restrict__ zz, double* __restrict__ part_new) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* R = lds;                  // [K][16]
-  double* Z = R + K * CB;           // [K][16]
-  const int64_t c0 = (int64_t)blockIdx.x * CB;
-  const double rz = first ? sum_parts(part_rz, nblk) : scal[slot];
-  const double pHp = sum_parts(part_php, nblk);
-  const double alpha = (pHp > 0.0 && rz != 0.0) ? rz / pHp : 0.0;
-  if (first && blockIdx.x == 0 && threadIdx.x == 0) scal[slot] = rz;
-  for (int e = threadIdx.x; e < K * CB; e += FT) {
-    const int rr = e >> 4, c = e & 15;
-    double v = 0.0;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)rr * C + c0 + c;
-      xt[g] += alpha * p[g];
-      v = r[g] - alpha * Hp[g];
-      r[g] = v;
-    }
-    R[e] = v;
-  }
-  __syncthreads();
-  wg_mm<false>(Minv, K, K, R, Z, 0, NWV);
-  __syncthreads();
-  double dot = 0.0;
-  for (int e = threadIdx.x; e < K * CB; e += FT) dot += R[e] * Z[e];
-  dot = wg_sum(dot);
-  if (threadIdx.x == 0) part_new[blockIdx.x] = dot;
-  tile_store(Z, zz, K, C, c0);
-}
-
-// ---- K_G: beta = rz_new / rz ; p = zz + beta p ; [HpF ; Qp] = [H_f ; S0] p ; scal[slot^1] = rz_new ------------
-__global__ __launch_bounds__(FT) void fused_cg_dir_kernel(int K, int64_t C, int nblk, int slot,
-                                                           const double* __restrict__ HS, double* __restrict__ scal,
-                                                           const double* __restrict__ part_new,
-                                                           const double* __restrict__ zz, double* __restrict__ p,
-                                                           double* __restrict__ hpf, double* __restrict__ Q) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* P = lds;                  // [K][16]
-  double* T2 = P + K * CB;          // [2K][16]
-  const int64_t c0 = (int64_t)blockIdx.x * CB;
-  const double rz = scal[slot];
-  const double rz_new = sum_parts(part_new, nblk);
-  const double beta = rz != 0.0 ? rz_new / rz : 0.0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) scal[slot ^ 1] = rz_new;
-  for (int e = threadIdx.x; e < K * CB; e += FT) {
-    const int rr = e >> 4, c = e & 15;
-    double v = 0.0;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)rr * C + c0 + c;
-      v = zz[g] + beta * p[g];
-      p[g] = v;
-    }
-    P[e] = v;
-  }
-  __syncthreads();
-  wg_mm<false>(HS, 2 * K, K, P, T2, 0, NWV);
-  __syncthreads();
-  for (int e = threadIdx.x; e < K * CB; e += FT) {
-    const int rr = e >> 4, c = e & 15;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)rr * C + c0 + c;
-      hpf[g] = T2[e];
-      Q[g] = T2[K * CB + e];
-    }
-  }
-}
-
-// ---- K_U: z~ = F x~ ; relaxation, projection, duals of the fixed rows ; x = alpha x~ + (1-alpha) x ; Q = S0 x~ ---
-// fold = 1: the LAST PCG step is applied here, x~ = xt + a p with a = rz / pHp (its residual update and the
-// preconditioner product would be dead work), saving one launch per ADMM step.
-__global__ __launch_bounds__(FT) void fused_post_kernel(int K, int Rf, int64_t C, double rho, double alpha, int has_rows,
-                                                         int fold, int nblk, int first, int slot,
-                                                         const double* __restrict__ scal,
-                                                         const double* __restrict__ part_rz,
-                                                         const double* __restrict__ part_php,
-                                                         const double* __restrict__ pdir,
-                                                         const double* __restrict__ F, const double* __restrict__ S0,
-                                                         const double* __restrict__ wrow, const double* __restrict__ xt,
-                                                         const double* __restrict__ lf, const double* __restrict__ uf,
-                                                         double* __restrict__ zf, double* __restrict__ yf,
-                                                         double* __restrict__ x, double* __restrict__ Q) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* X = lds;                  // [K][16]
-  double* T = X + K * CB;           // [Rf][16]
-  double* Qt = T + Rf * CB;         // [K][16]
-  const int64_t c0 = (int64_t)blockIdx.x * CB;
-  if (fold) {
-    const double rz = first ? sum_parts(part_rz, nblk) : scal[slot];
-    const double pHp = sum_parts(part_php, nblk);
-    const double a = (pHp > 0.0 && rz != 0.0) ? rz / pHp : 0.0;
-    for (int e = threadIdx.x; e < K * CB; e += FT) {
-      const int r = e >> 4, c = e & 15;
-      const int64_t g = (int64_t)r * C + c0 + c;
-      X[e] = (c0 + c < C) ? xt[g] + a * pdir[g] : 0.0;
-    }
-  } else {
-    tile_load(X, xt, K, C, c0);
-  }
-  __syncthreads();
-  if (has_rows) {
-    wg_mm<false>(F, Rf, K, X, T, 0, NWV - 3);
-    wg_mm<false>(S0, K, K, X, Qt, NWV - 3, 3);
-  } else {
-    wg_mm<false>(F, Rf, K, X, T, 0, NWV);
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < Rf * CB; e += FT) {
-    const int r = e >> 4, c = e & 15;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)r * C + c0 + c;
-      const double rr = rho * wrow[r];
-      const double zh = alpha * T[e] + (1.0 - alpha) * zf[g];
-      const double y = yf[g];
-      const double zn = fmin(fmax(zh + y / rr, lf[g]), uf[g]);
-      yf[g] = y + rr * (zh - zn);
-      zf[g] = zn;
-    }
-  }
-  for (int e = threadIdx.x; e < K * CB; e += FT) {
-    const int r = e >> 4, c = e & 15;
-    if (c0 + c < C) {
-      const int64_t g = (int64_t)r * C + c0 + c;
-      x[g] = alpha * X[e] + (1.0 - alpha) * x[g];
-      if (has_rows) Q[g] = Qt[e];
-    }
-  }
-}
-
-// ---- K_V: collision rows: relaxation, projection (u = +inf), duals ------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void fused_row_update_kernel(int64_t nW, int64_t C, double rho, double alpha,
-                                                                const int* __restrict__ wk, const int* __restrict__ wi,
-                                                                const int* __restrict__ wj,
-                                                                const double* __restrict__ weta,
-                                                                const double* __restrict__ wl,
-                                                                const double* __restrict__ Q, double* __restrict__ zc,
-                                                                double* __restrict__ yc) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nW) return;
-  const int64_t bi = (int64_t)wk[n] * C + (int64_t)wi[n] * D;
-  const int64_t bj = (int64_t)wk[n] * C + (int64_t)wj[n] * D;
-  double tc = 0.0;
-#pragma unroll
-  for (int d = 0; d < D; ++d) tc += weta[n * D + d] * (Q[bi + d] - Q[bj + d]);
-  const double zh = alpha * tc + (1.0 - alpha) * zc[n];
-  const double y = yc[n];
-  const double zn = fmax(zh + y / rho, wl[n]);
-  yc[n] = y + rho * (zh - zn);
-  zc[n] = zn;
-}
 
 // =====================================================================================================
 // Single-PCG-step pipeline (settings.cg_iters == 1, the default): 3 launches per ADMM step.
@@ -1100,88 +718,6 @@ int allow_lds(scp_qp* qp, Kern kernel, size_t bytes) {
 
 }  // namespace
 
-int scp_qp_fused_iteration(scp_qp* qp, int* cg_count) {
-  const QpDev& d = qp->d;
-  hipStream_t s = qp->ctx->stream;
-  const int K = qp->K, Rf = qp->Rf;
-  const int64_t C = qp->C, nx = (int64_t)K * C;
-  const int nblk = (int)((C + CB - 1) / CB);
-  const int has_rows = qp->nW > 0 ? 1 : 0;
-  const double rho_c = qp->rho * qp->st.rho_col_scale;
-  const dim3 cgrid(nblk), cblock(FT);
-  const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
-  const size_t tile = (size_t)CB * sizeof(double);
-  double* Q = d.HQ + nx;   // S0 v slab
-  double* Hp = d.HQ;       // H p slab
-  double* part_rz = d.part;
-  double* part_php = d.part + SCP_PART_CAP;
-  int fold = 0, fold_first = 0, fold_slot = SL_RZ0;
-  const double* fold_part = part_rz;
-
-  {
-    int rc = allow_lds(qp, fused_pre_kernel, (size_t)(4 * K + Rf) * tile);
-    if (!rc) rc = allow_lds(qp, fused_cg_init_kernel, (size_t)(5 * K) * tile);
-    if (!rc) rc = allow_lds(qp, fused_post_kernel, (size_t)(2 * K + Rf) * tile);
-    if (rc) return rc;
-  }
-  hipLaunchKernelGGL(fused_pre_kernel, cgrid, cblock, (size_t)(4 * K + Rf) * tile, s, K, Rf, C, qp->rho, qp->st.sigma,
-                     has_rows, d.pFt, d.pHS, d.pMinv, d.wrow, d.x, d.zf, d.yf, d.rhs, Q, d.xt, d.G);
-  FUSED_LAUNCHED(qp);
-  if (has_rows) {
-    {
-      int rc = scp_qp_rows_gather(qp, true, Q);
-      if (rc) return rc;
-    }
-    hipLaunchKernelGGL(fused_cg_init_kernel, cgrid, cblock, (size_t)(5 * K) * tile, s, K, C, d.pS0t, d.pMinv, d.pHS, d.rhs,
-                       d.G, d.r, d.p, d.hpf, Q, part_rz);
-    FUSED_LAUNCHED(qp);
-    int slot = SL_RZ0;
-    const int ncg = qp->st.cg_iters;
-    for (int it = 0; it < ncg; ++it) {
-      {
-        int rc = scp_qp_rows_gather(qp, false, Q);
-        if (rc) return rc;
-      }
-      hipLaunchKernelGGL(fused_cg_hp_kernel, cgrid, cblock, (size_t)(2 * K) * tile, s, K, C, d.pS0t, d.G, d.hpf, d.p, Hp,
-                         part_php);
-      FUSED_LAUNCHED(qp);
-      ++*cg_count;
-      if (it + 1 == ncg) {  // the last step is folded into the post kernel
-        fold = 1;
-        fold_first = it == 0 ? 1 : 0;
-        fold_slot = slot;
-        fold_part = (it & 1) ? part_rz + SCP_PART_CAP / 2 : part_rz;
-        break;
-      }
-      // the step kernel reads part_rz (first step) or scal[slot], writes the new partials to the OTHER half of
-      // the rz array so that workgroups still summing the old partials are not disturbed
-      double* part_new = (it & 1) ? part_rz : part_rz + SCP_PART_CAP / 2;
-      double* part_old = (it & 1) ? part_rz + SCP_PART_CAP / 2 : part_rz;
-      hipLaunchKernelGGL(fused_cg_step_kernel, cgrid, cblock, (size_t)(2 * K) * tile, s, K, C, nblk, it == 0 ? 1 : 0, slot,
-                         d.pMinv, d.scal, part_old, part_php, d.p, Hp, d.xt, d.r, d.zz, part_new);
-      FUSED_LAUNCHED(qp);
-      hipLaunchKernelGGL(fused_cg_dir_kernel, cgrid, cblock, (size_t)(3 * K) * tile, s, K, C, nblk, slot, d.pHS, d.scal,
-                         part_new, d.zz, d.p, d.hpf, Q);
-      FUSED_LAUNCHED(qp);
-      slot ^= 1;
-    }
-  }
-  hipLaunchKernelGGL(fused_post_kernel, cgrid, cblock, (size_t)(2 * K + Rf) * tile, s, K, Rf, C, qp->rho, qp->st.alpha,
-                     has_rows, fold, nblk, fold_first, fold_slot, d.scal, fold_part, part_php, d.p, d.pF, d.pS0, d.wrow, d.xt,
-                     d.lf, d.uf, d.zf, d.yf, d.x, Q);
-  FUSED_LAUNCHED(qp);
-  if (has_rows) {
-    if (qp->D == 2)
-      hipLaunchKernelGGL(fused_row_update_kernel<2>, rgrid, rblock, 0, s, qp->nW, C, rho_c, qp->st.alpha, d.w_k, d.w_i,
-                         d.w_j, d.w_eta, d.w_l, Q, d.zc, d.yc);
-    else
-      hipLaunchKernelGGL(fused_row_update_kernel<3>, rgrid, rblock, 0, s, qp->nW, C, rho_c, qp->st.alpha, d.w_k, d.w_i,
-                         d.w_j, d.w_eta, d.w_l, Q, d.zc, d.yc);
-    FUSED_LAUNCHED(qp);
-  }
-  return SCP_OK;
-}
-
 // `nit` ADMM iterations on the fixed rows alone in one launch (qp->nW == 0); dy_out: where to leave delta-y of the last
 // iteration for scp_qp_fused_residuals (NULL: not needed)
 int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out) {
@@ -1305,7 +841,7 @@ int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy) {
   const int K = qp->K, Rf = qp->Rf;
   const int64_t C = qp->C, nx = (int64_t)K * C;
   const int nblk = (int)((C + CB - 1) / CB);
-  double* Qp = d.hpf;  // S0 p
+  double* Qp = d.s0p;  // S0 p
   double* Fp = d.tf;   // F p
   double* part_rz = d.part;
   double* part_sq = d.part + SCP_PART_CAP / 2;
@@ -1709,8 +1245,8 @@ int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec) {
   return SCP_OK;
 }
 
-// G = A_W^T g with g = (rho zc - yc) - rho A_W v (init) or rho A_W v, Q = S0 v: row values, then the per-cell gather
-int scp_qp_rows_gather(scp_qp* qp, bool init, const double* Q) {
+// G = A_W^T g with g = rho A_W v, Q = S0 v: row values, then the per-cell gather
+int scp_qp_rows_gather(scp_qp* qp, const double* Q) {
   const QpDev& d = qp->d;
   hipStream_t s = qp->ctx->stream;
   if (!qp->csr_valid) {
@@ -1720,17 +1256,12 @@ int scp_qp_rows_gather(scp_qp* qp, bool init, const double* Q) {
   const int64_t C = qp->C, nx = (int64_t)qp->K * C;
   const double rho_c = qp->rho * qp->st.rho_col_scale;
   const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
-#define SCP_ROWS_VALUE(DD, INIT)                                                                                        \
-  hipLaunchKernelGGL((rows_value_kernel<DD, INIT>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Q, \
-                     d.zc, d.yc, d.pos_i, d.pos_j, d.gval)
-  if (qp->D == 2) {
-    if (init) SCP_ROWS_VALUE(2, true);
-    else SCP_ROWS_VALUE(2, false);
-  } else {
-    if (init) SCP_ROWS_VALUE(3, true);
-    else SCP_ROWS_VALUE(3, false);
-  }
-#undef SCP_ROWS_VALUE
+  if (qp->D == 2)
+    hipLaunchKernelGGL((rows_value_kernel<2, false>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Q,
+                       d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
+  else
+    hipLaunchKernelGGL((rows_value_kernel<3, false>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Q,
+                       d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
   hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, qp->K, qp->N, qp->D,
                      d.cell_ptr, d.coef, d.gval, d.G);
   FUSED_LAUNCHED(qp);
@@ -1739,7 +1270,7 @@ int scp_qp_rows_gather(scp_qp* qp, bool init, const double* Q) {
 }
 
 // =====================================================================================================
-// Operand packing of the constant blocks (see QpDev::pF ...)
+// Operand packing of the active KKT slot's H_f^{-1} and T (see QpDev::pMinv)
 // =====================================================================================================
 namespace {
 struct PackDesc {
@@ -1748,7 +1279,7 @@ struct PackDesc {
   int R, M;
 };
 struct PackArgs {
-  PackDesc m[7];
+  PackDesc m[2];
 };
 __global__ __launch_bounds__(256) void pack_operands_kernel(PackArgs a) {
   const PackDesc d = a.m[blockIdx.y];
@@ -1764,22 +1295,13 @@ __global__ __launch_bounds__(256) void pack_operands_kernel(PackArgs a) {
 }
 }  // namespace
 
-int scp_qp_pack_operands(scp_qp* qp, bool constants) {
+int scp_qp_pack_operands(scp_qp* qp) {
   const QpDev& d = qp->d;
-  const int K = qp->K, Rf = qp->Rf;
+  const int K = qp->K;
   PackArgs a;
-  int n = 0;
-  if (constants) {
-    a.m[n++] = {d.F, d.pF, Rf, K};
-    a.m[n++] = {d.Ft, d.pFt, K, Rf};
-    a.m[n++] = {d.S0, d.pS0, K, K};
-    a.m[n++] = {d.S0t, d.pS0t, K, K};
-  } else {
-    a.m[n++] = {d.HS, d.pHS, 2 * K, K};
-    a.m[n++] = {d.Minv, d.pMinv, K, K};
-    a.m[n++] = {d.T, d.pT, K, K};
-  }
-  hipLaunchKernelGGL(pack_operands_kernel, dim3(16, n), dim3(256), 0, qp->ctx->stream, a);
+  a.m[0] = {d.Minv, d.pMinv, K, K};
+  a.m[1] = {d.T, d.pT, K, K};
+  hipLaunchKernelGGL(pack_operands_kernel, dim3(16, 2), dim3(256), 0, qp->ctx->stream, a);
   FUSED_LAUNCHED(qp);
   return SCP_OK;
 }
@@ -1790,23 +1312,6 @@ int scp_qp_pack_operands(scp_qp* qp, bool constants) {
 // (collision rows' residuals and delta-y).  14 launches on the generic path.
 // =====================================================================================================
 namespace {
-
-__device__ inline double wg_max(double v) {
-  __shared__ double s[NWV];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NWV; ++w) t = fmax(t, s[w]);
-  __syncthreads();
-  return t;
-}
-
-__device__ inline void atomic_max_nn(double* addr, double v) {
-  atomicMax((unsigned long long*)addr, (unsigned long long)__double_as_longlong(v));
-}
 
 // per-workgroup partial results of a check: [rp, |Ax|, |z|, rd, |Px|, |A^T y|, |dy|, supp, |A^T dy|] (maxima / a sum),
 // reduced on the host -- 7 same-address atomics per workgroup cost more than the rest of the kernel

@@ -1,4 +1,5 @@
-// Declarations shared by scp_qp.hip (ADMM driver, generic kernels) and scp_qp_fused.hip (column-block kernels).
+// Declarations shared by scp_qp.hip (ADMM driver, generic kernels), scp_qp_fused.hip (column-block kernels) and the
+// persistent kernels (scp_qp_persist.hip, scp_qp_persist16.hip).
 #pragma once
 #include "scp_common.h"
 
@@ -19,10 +20,10 @@ struct QpDev {
   double *F, *Ft, *S0, *S0t, *HS, *Hf, *Minv, *aug, *wrow;
   double* gj_tmp;  // [3K]: pivot row and column of the per-pivot Gauss-Jordan launches (K > SCP_INV_LDS_MAX_K)
   double* G0;  // [K][K]: F^T w F (constant; H_f = (2 + sigma) I + rho G0)
-  // the same blocks in MFMA A-operand order for the column-block kernels (scp_qp_pack_operands):
+  // H_f^{-1} in MFMA A-operand order for the column kernels (scp_qp_pack_operands):
   // [row tile][k step][lane] = A[16 tile + (lane & 15)][4 step + (lane >> 4)], zero beyond the matrix, so that one
   // wave-wide operand load is 512 contiguous bytes
-  double *pF, *pFt, *pS0, *pS0t, *pHS, *pMinv;
+  double* pMinv;
   double *T, *pT;  // T = S0 H_f^{-1} (K x K, rebuilt with H_f^{-1}) and its packed form: S0 p = T r without waiting for p
   // fixed rows
   double *lf, *uf, *zf, *yf, *wf, *tf;
@@ -37,7 +38,7 @@ struct QpDev {
   // scalars
   double* scal;   // SL_COUNT, followed by SCP_RESID_CAP partial results of a termination check
   double* part;   // 2 * SCP_PART_CAP
-  double* hpf;    // [K][C]: H_f p of the fused PCG
+  double* s0p;    // [K][C]: S0 p of the single-step pipeline (scp_qp_peek "qp")
   double* fx;     // [Rf][C]: F x carried by the single-step pipeline (F p goes to tf)
   double* dyf;    // [Rf][C]: snapshot of y_f, then delta-y (primal infeasibility certificate)
   double* dyc;    // [cap]  : same for the working rows
@@ -74,17 +75,16 @@ struct scp_qp {
   int qx_sel;      // which half of HQ holds S0 x (the single-step pipeline ping-pongs: 0 -> rows [K, 2K), 1 -> [0, K))
   double rho;
   QpDev d;
-  // rho-dependent blocks (H_f, [H_f; S0], H_f^{-1}, T and their packed forms) are cached per rho: adaptive rho is snapped
-  // to a geometric grid and every solve starts from settings.rho, so the same few values recur from QP to QP and the
-  // 48 us single-workgroup inverse is paid once per value.  d.Hf / HS / Minv / T / pHS / pMinv / pT point into the active slot.
+  // rho-dependent blocks (H_f, [H_f; S0], H_f^{-1}, T and the packed H_f^{-1}, T) are cached per rho: adaptive rho is
+  // snapped to a geometric grid and every solve starts from settings.rho, so the same few values recur from QP to QP and
+  // the 48 us single-workgroup inverse is paid once per value.  d.Hf / HS / Minv / T / pMinv / pT point into the active slot.
   struct KktSlot {
     double rho, sigma;
     unsigned long long used;  // LRU stamp, 0 = empty
-    double *Hf, *HS, *Minv, *T, *pHS, *pMinv, *pT;
+    double *Hf, *HS, *Minv, *T, *pMinv, *pT;
   } kkt[SCP_KKT_SLOTS_MAX];
   int n_kkt;  // slots in use for this K (scp_kkt_slots)
   unsigned long long kkt_clock;
-  bool consts_packed;  // F, F^T, S0, S0^T are packed once
   double* h_scal;  // pinned, SL_COUNT + SCP_RESID_CAP doubles + the completion flag of a fused check
   double* h_scal_dev;  // the same memory as the device sees it: the check kernels write their partials straight to it
   unsigned long long check_seq;  // value the flag takes when the current check has finished
@@ -111,16 +111,27 @@ struct scp_qp {
   unsigned* h_persist_dev;
 };
 
+// Steps between two termination checks once the residuals are close to the tolerances (settings.check_fine), or 0: the
+// cadence stays fixed.  The fine cadence applies when it divides the coarse one, to QPs with collision rows (QP#0 keeps the
+// fixed cadence: its 20 surplus steps are cheap, and a better converged starting point saves the first joint QP of large
+// problems far more: 250 instead of 400 steps at 1024 x 50), and up to SCP_FINE_MAX_COLUMNS columns: beyond, it measured
+// slower (4096 x 50: 195 instead of 200 steps, but 0.27 ms more in every repetition; profiles/r03_check_cadence.txt,
+// r03_check_cost.txt).  The host loop of scp_qp_solve and the persistent kernels both follow this rule.
+constexpr int64_t SCP_FINE_MAX_COLUMNS = 4096;
+inline int scp_qp_fine_cadence(const scp_qp* qp) {
+  const scp_qp_settings& st = qp->st;
+  const bool fine = st.check_fine > 0 && st.check_fine < st.check_termination && st.check_termination % st.check_fine == 0 &&
+                    qp->nW > 0 && qp->C <= SCP_FINE_MAX_COLUMNS;
+  return fine ? st.check_fine : 0;
+}
 
-// scp_qp_fused.hip: one ADMM iteration with the column-local chains fused into column-block kernels
-// (K <= SCP_FUSED_MAX_K).  Same arithmetic as admm_iteration() in scp_qp.hip.
+// scp_qp_fused.hip: the column kernels of the single-step pipeline, QP#0 and the termination check (use_mfma = 1)
 constexpr int SCP_RESID_STRIDE = 12;  // doubles per workgroup in the partial results of a fused termination check
 constexpr int SCP_RESID_CAP = (4096 / 2 + 128) * SCP_RESID_STRIDE;  // (SCP_PART_CAP / 2 column blocks + row blocks)
 constexpr int SCP_INV_LDS_MAX_K = 96;  // [H_f | I] (K x 2K doubles) resident in LDS for the Gauss-Jordan inverse
 constexpr int SCP_BIGK_MAX_K = 1024;  // single-step pipeline with one workgroup per column and one thread per time step
-constexpr int SCP_FUSED_MAX_K = 120;  // (6K + 4K-1) * 128 B of LDS tiles <= 160 KiB (limit raised above 64 KiB)
-constexpr int SCP_PART_CAP = 4096;  // capacity of each partial-sum array (column blocks of the fused path)
-int scp_qp_fused_iteration(scp_qp* qp, int* cg_count);
+constexpr int SCP_FUSED_MAX_K = 120;  // the 16-column workgroups of scp_qp_fused.hip (wave scans of up to 128 time steps)
+constexpr int SCP_PART_CAP = 4096;  // capacity of each partial-sum array (column blocks of the single-step pipeline)
 // single-PCG-step pipeline (cg_iters == 1 and a non-empty working set): 3 launches per ADMM step
 int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy);
 // nW == 0: `nit` complete ADMM iterations in one launch (everything is column-local)
@@ -129,8 +140,8 @@ int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out);
 // 2: g = vec[n].  Two launches, no atomics.
 int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec);
 int scp_qp_csr_build(scp_qp* qp);
-// G = A_W^T g, g = (rho zc - yc) - rho A_W v (init) or rho A_W v with Q = S0 v: deterministic (gather over the incidence lists)
-int scp_qp_rows_gather(scp_qp* qp, bool init, const double* Q);
+// G = A_W^T g, g = rho A_W v with Q = S0 v: deterministic (gather over the incidence lists)
+int scp_qp_rows_gather(scp_qp* qp, const double* Q);
 int scp_qp_cg1_prepare(scp_qp* qp);
 // small problems: working rows [nW, nW + n) recomputed from the linearisation point (scp_qp_add_rows_at) AND the incidence
 // lists + row values of all nW + n rows in ONE launch; *done = false: not eligible, nothing was launched
@@ -155,8 +166,8 @@ bool scp_persist_claim(int device, int n_cu_total, int n_wg, int wait_ms);
 void scp_persist_release(int device, int n_wg);
 constexpr int SCP_PERSIST_GAVE_UP = 2;  // exit code of the persistent kernel: a spin timed out, nothing was written back
 int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* it_done);  // cad0: steps to the next check
-// (re)pack F, Ft, S0, S0t, HS, Minv into the MFMA operand order; called at the end of build_kkt
-int scp_qp_pack_operands(scp_qp* qp, bool constants);  // constants: F, F^T, S0, S0^T; else the active slot's HS, Minv, T
+// pack the active slot's H_f^{-1} and T into the MFMA operand order; called at the end of build_kkt
+int scp_qp_pack_operands(scp_qp* qp);
 static inline size_t scp_packed_count(int R, int M) { return (size_t)((R + 15) / 16) * ((M + 3) / 4) * 64; }
 // Termination-check quantities of the single-step pipeline in 3 launches (row values, column blocks, rows):
 // fills qp->h_scal[SL_RP .. SL_SUPP] like residuals() in scp_qp.hip and leaves S0 x and F x in their slabs.  Synchronises.

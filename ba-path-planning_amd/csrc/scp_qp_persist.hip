@@ -795,8 +795,7 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   a.K = K; a.N = qp->N; a.nblk = nblk_expected; a.ent_cap = qp->persist_cap;
   a.it0 = it0; a.max_iter = st.max_iter; a.check_every = st.check_termination;
   a.cad0 = cad0 > 0 ? cad0 : st.check_termination; a.fine_ratio = st.check_fine_ratio;
-  a.check_fine = (st.check_fine > 0 && st.check_fine < st.check_termination && st.check_termination % st.check_fine == 0 && C <= 4096)
-                     ? st.check_fine : 0;  // (the rule of scp_qp_solve; a persistent launch always has collision rows)
+  a.check_fine = scp_qp_fine_cadence(qp);
   a.rho_interval = st.adaptive_rho_interval > 0 ? st.adaptive_rho_interval : 1;
   a.C = C;
   a.rho = qp->rho; a.rho_c = qp->rho * st.rho_col_scale; a.rho_eq = st.rho_eq_scale; a.alpha = st.alpha; a.h = qp->h;

@@ -21,7 +21,7 @@ UINT64_MAX = (1 << 64) - 1
 STATUS_TEXT = {1: "solved", 2: "solved inaccurate", -2: "maximum iterations reached", -3: "primal infeasible"}
 
 
-# enum scp_qp_pipeline: bit numbers of scp_qp_info.pipeline
+# enum scp_qp_pipeline: bit numbers of scp_qp_info.pipeline ("fused", bit 5, is retired and never set)
 PIPELINES = ("qp0", "persistent", "persistent16", "three-launch", "three-launch-bigK", "fused", "generic", "persistent8-lean")
 
 

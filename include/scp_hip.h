@@ -67,8 +67,9 @@ typedef struct scp_qp_settings {
                                     50 is the measured choice of profiles/r03_rho_interval_sweep.txt) */
   double adaptive_rho_tolerance; /* 5 */
   int32_t cg_iters;              /* 1: PCG steps per ADMM step (fixed count >= 1, warm started at x) */
-  int32_t use_mfma;              /* 1: fused column-block kernels, every K-dimension product on
-                                    v_mfma_f64_16x16x4_f64 (K <= 120; larger K falls back to 2);
+  int32_t use_mfma;              /* 1: column kernels, H_f^{-1} on v_mfma_f64_16x16x4_f64: the single-step pipeline
+                                    (cg_iters == 1, K <= 1024) and QP#0's column-local kernel (K <= 120, any cg_iters);
+                                    everything else, cg_iters > 1 with collision rows among it, runs as with 2;
                                     2: one MFMA product per launch (generic path); 0: VALU products */
   double rho_col_scale;          /* 10: rho of the collision rows = rho * rho_col_scale (like OSQP's per-row rho,
                                     which the reference gets x 1e3 on equality rows only).  Measured at 1024 x 50:
@@ -119,7 +120,7 @@ typedef enum scp_qp_pipeline {
   SCP_PIPE_PERSIST16 = 2,  /* its lean form: 16 agents per workgroup (2-D, 2048 < N <= 4096) */
   SCP_PIPE_CG1 = 3,        /* single-step pipeline, three launches per ADMM step */
   SCP_PIPE_CG1_BIGK = 4,   /* the same with one workgroup per column (K > 120) */
-  SCP_PIPE_FUSED = 5,      /* cg_iters > 1: fused column-block chains */
+  SCP_PIPE_FUSED = 5,      /* retired, never set (cg_iters > 1 runs SCP_PIPE_GENERIC); kept so that no other bit moves */
   SCP_PIPE_GENERIC = 6,    /* one product per launch */
   SCP_PIPE_PERSIST8L = 7   /* the lean kernel's state diet with 8 agents per workgroup (3-D, 1024 < N <= 2048) */
 } scp_qp_pipeline;

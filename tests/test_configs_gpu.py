@@ -154,7 +154,7 @@ def test_scp_128_agents_vs_c_oracle(cg, tol):
 @pytest.mark.parametrize("n,persistent", [(128, 1), (128, 0), (128, 4), (128, 2), (40, 1)])
 def test_adaptive_check_cadence(n, persistent):
     """settings.check_fine = 5 (after a check that finds the residuals within 4 x their tolerances, or that changes rho, the
-    next check comes after 5 steps instead of 25).  Two PCG steps: the host loop (QP#0 kernel, fused path) follows the C
+    next check comes after 5 steps instead of 25).  Two PCG steps: the host loop (QP#0 kernel, generic pipeline) follows the C
     oracle's cadence iterate for iterate.  One PCG step: every persistent kernel (default lean 8-agent, lean 16-agent,
     round 2's) takes the same decisions inside the kernel as the host loop of the three-launch pipeline does -- the same
     counts up to the summation-order effect the fixed cadence has too (here: a few fine intervals)."""

@@ -76,8 +76,8 @@ def test_qp0_matches_oracle(ctx, n, seed, T, h, use_mfma):
 
 @pytest.mark.parametrize("cg,use_mfma", [(1, 1), (2, 1), (3, 2), (3, 0)])
 def test_collision_qp_paths_and_pcg_steps(ctx, cg, use_mfma):
-    """Default fused path with 1 and 2 PCG steps per ADMM step, and the generic MFMA / VALU paths: all follow
-    the oracle iterate for iterate."""
+    """One PCG step per ADMM step on the default single-step pipeline, 2 and 3 on the generic pipeline (MFMA products with
+    use_mfma 1 and 2, VALU with 0): all follow the oracle iterate for iterate."""
     import torch
 
     prob = ref_problem(10, 7, 10.0, 0.2)
@@ -93,6 +93,8 @@ def test_collision_qp_paths_and_pcg_steps(ctx, cg, use_mfma):
     info = qp.solve()
     assert info["status_val"] == io["status_val"] == 1 and info["iter"] == io["iter"]
     assert info["cg_iters_total"] == cg * info["iter"]
+    if cg > 1:
+        assert info["pipeline"] == "generic", info["pipeline"]
     np.testing.assert_allclose(qp.solution().cpu().numpy(), xo, rtol=0, atol=1e-8)
     qp.close()
 
@@ -100,8 +102,8 @@ def test_collision_qp_paths_and_pcg_steps(ctx, cg, use_mfma):
 @pytest.mark.parametrize("cg,use_mfma", [(1, 1), (2, 1), (3, 2), (3, 0)])
 def test_every_qp_path_is_deterministic(ctx, cg, use_mfma):
     """No atomics on floating-point data anywhere in the iteration: A_W^T g is a gather over sorted incidence lists on every
-    path (single-step, multi-step fused, generic MFMA / VALU), so two solves of the same QP agree bit for bit -- primal
-    and duals.  (Round 1 scattered with atomics on the cg_iters >= 2 and generic paths.)"""
+    path (single-step, generic MFMA / VALU), so two solves of the same QP agree bit for bit -- primal and duals.
+    (Round 1 scattered with atomics on the cg_iters >= 2 and generic paths.)"""
     import torch
 
     prob = ref_problem(24, 5, 10.0, 0.2)

@@ -389,7 +389,7 @@ def test_edge_sizes(n, T, h, dim):
 def test_large_K_paths(T, K):
     """K = 64: the persistent kernel's limit (one time step per lane); K = 65: two time steps per lane in the wave scans of
     the three-launch column kernels (and 8 slab rows per thread in the QP#0 kernel); K = 70, 120: more than 64 KiB of LDS
-    tiles, 120 the largest fused size; K = 130, 250, 500: the long-horizon column kernel (one workgroup per column, block
+    tiles, 120 the largest 16-column size; K = 130, 250, 500: the long-horizon column kernel (one workgroup per column, block
     scans; the reference's compute-trajectories demo runs K = 500) with the generic QP#0 and check.  Same oracle, same
     tolerance."""
     from path_planning.scenarios.position_generator import generate_positions
