@@ -22,7 +22,8 @@
 //     S0 p cells only after it has every partial of the previous step, which every workgroup publishes after reading
 //     its partners' cells; the partials alternate between two buffers.
 // Every spin is bounded: a workgroup that times out raises a give-up word, every workgroup then leaves WITHOUT writing
-// state back, and the host repeats the iterations on the three-launch pipeline.
+// state back, and the host repeats the iterations on the three-launch pipeline.  The protocol -- polls, all-gathers,
+// give-up, the decision after a check, the exit words -- is shared with the lean kernel (scp_qp_persist_device.h).
 #include "scp_qp_persist_device.h"
 
 #include <algorithm>
@@ -100,22 +101,7 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
   const int a1 = min(a0 + APB, N);
   const int ebase = A.cell_ptr[cell_of(0, a0, K)];
   const int ne = A.cell_ptr[cell_of(0, a1, K)] - ebase;
-  // More incident rows around some block of agents than the LDS tables hold: EVERY workgroup finds that out by itself
-  // (the largest block's count, a few loads) and leaves before anything is published -- nobody spins on anybody.
-  {
-    int worst = 0;
-    for (int b = threadIdx.x; b < (N + APB - 1) / APB; b += NT) {
-      const int b0 = b * APB, b1 = min(b0 + APB, N);
-      worst = max(worst, A.cell_ptr[cell_of(0, b1, K)] - A.cell_ptr[cell_of(0, b0, K)]);
-    }
-    if (__syncthreads_or(worst > cap)) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(A.host_status, (unsigned)EXIT_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      return;
-    }
-  }
+  if (entries_overflow<APB>(A)) return;
   if (threadIdx.x == 0) fail_s = 0;
   for (int i = threadIdx.x; i <= (a1 - a0) * K; i += NT) cptr[i] = A.cell_ptr[cell_of(0, a0, K) + i] - ebase;
   for (int e = threadIdx.x; e < ne; e += NT) {
@@ -292,20 +278,10 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
         const int ek = code & 0xFF, al = (code >> 8) & 0xFF, side = (code >> 16) & 1;
         const u64* pc = A.cells + e_pad[e];
         u32x4 w[D];
-        for (;;) {
-          ld_cell<D>(pc, w);
-          bool valid = true;
-#pragma unroll
-          for (int d = 0; d < D; ++d) valid = valid && pair_ok(w[d], tag);
-          if (valid) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
+        if (!wait_cell<D>(A, pc, tag, spins, w)) {
+          bad = true;
+          break;
         }
-        if (bad) break;
         double s = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) {
@@ -315,10 +291,7 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
         }
         if (!side) sq += s * s;  // every row once
       }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
+      if (bad) raise_give_up(A, fail_s);
       sq = wave_incl_sum(sq);
       if (lane == 63) red[1][wave] = sq;
     }
@@ -326,50 +299,12 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
     if (fail_s) { ok = false; break; }
     PSTAMP(4);
     // ---- all-gather of the two partials of every workgroup -----------------------------------------------------------------
-    if (threadIdx.x < 2) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < APB; ++w) t += red[threadIdx.x][w];
-      st_granules(gpart + (size_t)blockIdx.x * 4 + 2 * threadIdx.x, tag, t);
-    }
-    {
-      unsigned spins = 0;
-      bool bad = false;
-      for (int q = threadIdx.x; q < 2 * nblk; q += NT) {  // one double (two granules) per thread and pass
-        u32x4 w;
-        for (;;) {
-          w = ld_pair(gpart + 2 * q);
-          if (pair_ok(w, tag)) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
-        }
-        if (bad) break;
-        gp[q] = pair_value(w);
-      }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
-    }
+    publish_partials(red, 2, 3u, gpart + (size_t)blockIdx.x * 4, tag);
+    gather_pairs<NT>(A, gpart, 2 * nblk, tag, gp, fail_s);
     __syncthreads();
     if (fail_s) { ok = false; break; }
     PSTAMP(5);
-    double a;
-    {  // every wave sums the partials in the same order: the same bits everywhere, no further barrier
-      double vr = 0.0, vs = 0.0;
-      for (int b = lane; b < nblk; b += 64) {
-        vr += gp[2 * b];
-        vs += gp[2 * b + 1];
-      }
-      const double rzt = read_lane(wave_incl_sum(vr), 63);
-      const double sqt = read_lane(wave_incl_sum(vs), 63);
-      const double pHp = rzt + rho_c * sqt;
-      a = (pHp > 0.0 && rzt != 0.0) ? rzt / pHp : 0.0;
-    }
+    const double a = step_length(gp, nblk, rho_c);
     const double aa = alpha * a;
     PSTAMP(6);
     // ---- everything after the step length is elementwise -------------------------------------------------------------------
@@ -505,20 +440,10 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
         const int ek = code & 0xFF, al = (code >> 8) & 0xFF, side = (code >> 16) & 1;
         const u64* pc = A.cells + e_pad[e];
         u32x4 w[D];
-        for (;;) {
-          ld_cell<D>(pc, w);
-          bool valid = true;
-#pragma unroll
-          for (int d = 0; d < D; ++d) valid = valid && pair_ok(w[d], ctag);
-          if (valid) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
+        if (!wait_cell<D>(A, pc, ctag, spins, w)) {
+          bad = true;
+          break;
         }
-        if (bad) break;
         double ax = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) {
@@ -540,10 +465,7 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
           }
         }
       }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
+      if (bad) raise_give_up(A, fail_s);
     }
 #pragma unroll
     for (int j = 0; j < NCHK; ++j) {
@@ -552,102 +474,36 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
     }
     __syncthreads();
     if (fail_s) { ok = false; break; }
-    if (threadIdx.x < NCHK) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < APB; ++w) t = threadIdx.x == CK_SUPP ? t + red[threadIdx.x][w] : fmax(t, red[threadIdx.x][w]);
-      st_granules(A.gcheck + ((size_t)blockIdx.x * NCHK + threadIdx.x) * 2, ctag, t);
-    }
-    {
-      unsigned spins = 0;
-      bool bad = false;
-      for (int q = threadIdx.x; q < NCHK * nblk; q += NT) {
-        u32x4 w;
-        for (;;) {
-          w = ld_pair(A.gcheck + 2 * q);
-          if (pair_ok(w, ctag)) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
-        }
-        if (bad) break;
-        gp[q] = pair_value(w);
-      }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
-    }
+    publish_partials(red, NCHK, 1u << CK_SUPP, A.gcheck + (size_t)blockIdx.x * NCHK * 2, ctag);
+    gather_pairs<NT>(A, A.gcheck, NCHK * nblk, ctag, gp, fail_s);
     __syncthreads();
     if (fail_s) { ok = false; break; }
-#pragma unroll
-    for (int j = 0; j < NCHK; ++j) {  // the same reduction order in every wave of every workgroup: identical decisions
-      double v = 0.0;
-      for (int b = lane; b < nblk; b += 64) v = j == CK_SUPP ? v + gp[b * NCHK + j] : fmax(v, gp[b * NCHK + j]);
-      chk[j] = read_lane(j == CK_SUPP ? wave_incl_sum(v) : wave_max_nn(v), 63);
-    }
+    reduce_checks(gp, nblk, chk);
     __syncthreads();  // gp is reused by the next step's all-gather
-    // ---- decide (the host repeats these tests on the same nine numbers, scp_qp_solve) ------------------------------------
-    const double np_ = fmax(chk[CK_NAX], chk[CK_NZ]), nd_ = fmax(chk[CK_NPX], chk[CK_NATY]);
-    const double tol_p = A.eps_abs + A.eps_rel * np_, tol_d = A.eps_abs + A.eps_rel * nd_;
-    if (chk[CK_RP] <= tol_p && chk[CK_RD] <= tol_d) { exit_code = EXIT_SOLVED; break; }
-    if (A.check_fine > 0)  // (the same decision as scp_qp_solve's, from the same nine numbers)
-      cad = (chk[CK_RP] < A.fine_ratio * tol_p && chk[CK_RD] < A.fine_ratio * tol_d) ? A.check_fine : A.check_every;
-    if (it_done >= A.max_iter) { exit_code = EXIT_MAX_ITER; break; }
-    if (with_dy && chk[CK_NDY] > A.eps_prim_inf && chk[CK_SUPP] < -A.eps_prim_inf * chk[CK_NDY] &&
-        chk[CK_NATDY] < A.eps_prim_inf * chk[CK_NDY]) { exit_code = EXIT_INFEASIBLE; break; }
-    if (A.rho_tol > 0.0 && it_done % A.rho_interval == 0) {
-      // OSQP's rho estimate, snapped to the 2^(1/4) grid as the host does it (scp_qp_solve).  Device log2 / exp2 may differ
-      // from the host's in the last bit, so the candidate only SELECTS: the value that counts is the host-computed double
-      // in the table of cached rho, and the threshold test is repeated on it exactly as the host would.
-      const double prim = chk[CK_RP] / fmax(np_, 1e-10), dual = chk[CK_RD] / fmax(nd_, 1e-10);
-      const double nr = fmin(fmax(rho * sqrt(prim / fmax(dual, 1e-10)), 1e-6), 1e6);
-      const double cand = exp2(round(4.0 * log2(nr)) * 0.25);
-      if (cand > rho * A.rho_tol * (1.0 - 1e-9) || cand < rho / A.rho_tol * (1.0 + 1e-9)) {  // (else: clearly no update)
-        int slot = -1;
-        for (int i = 0; i < A.n_tab; ++i)
-          if (fabs(A.tab[i].rho - cand) <= 1e-12 * cand) slot = i;
-        if (slot < 0) { exit_code = EXIT_RHO; break; }  // not cached yet: the host builds the blocks and relaunches
-        const double nrs = A.tab[slot].rho;
-        if (nrs > rho * A.rho_tol || nrs < rho / A.rho_tol) {
-          // ---- switch rho in place (what the host does between two launches: build_kkt hit + rows_value_kernel) -------------
-          rho = nrs;
-          rho_c = rho * A.rho_col_scale;
+    int slot;
+    exit_code = check_decision(A, chk, it_done, rho, with_dy, cad, slot);
+    if (exit_code) break;
+    if (slot >= 0) {
+      // ---- switch rho in place (what the host does between two launches: build_kkt hit + rows_value_kernel) -----------------
+      rho = A.tab[slot].rho;
+      rho_c = rho * A.rho_col_scale;
 #pragma unroll
-          for (int t = 0; t < 4; ++t) rr[t] = (t >= 2 && k == K - 1) ? rho * A.rho_eq : rho;
-          tile_prefetch<CHB>(use_T && wave >= tK ? A.tab[slot].pT : A.tab[slot].pMinv, nks,
-                             wave < tK ? wave : (use_T && wave < 2 * tK ? wave - tK : 0), 0, nks, aM);
-          for (int e = threadIdx.x; e < ne; e += NT) {  // row values of the next right-hand side from the exact S0 x cells
-            double ax = 0.0;
+      for (int t = 0; t < 4; ++t) rr[t] = (t >= 2 && k == K - 1) ? rho * A.rho_eq : rho;
+      tile_prefetch<CHB>(use_T && wave >= tK ? A.tab[slot].pT : A.tab[slot].pMinv, nks,
+                         wave < tK ? wave : (use_T && wave < 2 * tK ? wave - tK : 0), 0, nks, aM);
+      for (int e = threadIdx.x; e < ne; e += NT) {  // row values of the next right-hand side from the exact S0 x cells
+        double ax = 0.0;
 #pragma unroll
-            for (int d = 0; d < D; ++d) ax += e_c[(size_t)e * D + d] * (e_qo[(size_t)e * D + d] - e_qp[(size_t)e * D + d]);
-            e_g[e] = (rho_c * e_z[e] - e_y[e]) - rho_c * ax;
-          }
-          __syncthreads();
-          ++n_rho;
-          if (A.check_fine > 0) cad = A.check_fine;
-        }
+        for (int d = 0; d < D; ++d) ax += e_c[(size_t)e * D + d] * (e_qo[(size_t)e * D + d] - e_qp[(size_t)e * D + d]);
+        e_g[e] = (rho_c * e_z[e] - e_y[e]) - rho_c * ax;
       }
+      __syncthreads();
+      ++n_rho;
     }
   }
   }  // batches
 
-  // The exit decision is collective: a workgroup that timed out has raised the give-up word BEFORE the cell or partial it
-  // was waiting for appeared, so every workgroup that got past that exchange afterwards sees the word here and leaves
-  // without writing back as well (the host additionally drops its carried-state flags on a give-up).
-  if (ok && __syncthreads_or(threadIdx.x == 0 &&
-                             __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u))
-    ok = false;
-  if (!ok) {
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(A.host_status, (unsigned)EXIT_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return;  // nothing was written back: the state in global memory is the state before this launch
-  }
+  if (leave_if_gave_up(A, ok)) return;
   // ---- write the state back ---------------------------------------------------------------------------------------------------
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -685,22 +541,10 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
   if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0)
     for (int i = 0; i < 16; ++i) scp_persist_clk[i] = i == 15 ? (unsigned long long)steps : pacc[i];
 #endif
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // the nine check results in the slots the host reads (scp_qp::h_scal), then the exit code and the completion word
-    const int slot[NCHK] = {SL_RP, SL_NAX, SL_NZ, SL_RD, SL_NPX, SL_NATY, SL_NDY, SL_SUPP, SL_NATDY};
-#pragma unroll
-    for (int j = 0; j < NCHK; ++j)
-      __hip_atomic_store((u64*)(A.host_scal + slot[j]), (u64)__double_as_longlong(chk[j]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_status + 1, (unsigned)it_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_status + 2, n_rho, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store((u64*)A.host_rho, (u64)__double_as_longlong(rho), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_status, exit_code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  publish_exit(A, chk, it_done, n_rho, rho, exit_code);
 }
 
-size_t persist_lds_bytes(int K, int D, int cap, int nblk) {
-  const int apb = persist_apb(D);
+size_t persist_lds_bytes(int K, int cap, int nblk, int D, int apb) {
   size_t dbl = (size_t)3 * CB * pad_col(K) + (size_t)apb * 64 * D + (size_t)NCHK * nblk + (size_t)cap * (4 * D + 4);
   size_t ints = (size_t)3 * cap + (size_t)apb * K + 1;
   return dbl * sizeof(double) + ((ints + 1) / 2 * 2) * sizeof(int);
@@ -727,7 +571,22 @@ static int persist_variant_for(const scp_qp* qp) {
   if (qp->D == 2) return fits8 ? 2 : (fits16 ? 1 : -1);
   return fits_old ? 0 : (fits8 ? 2 : -1);  // 3-D: the 4-agent kernel is the faster one up to 1024 agents
 }
-static int variant_apb(int variant, int D) { return variant == 1 ? 16 : (variant == 2 ? 8 : persist_apb(D)); }
+
+// What the host needs to know about the kernel of a variant of persist_variant_for.
+struct PersistKernel {
+  int apb;                                                        // agents = waves per workgroup
+  size_t (*lds_bytes)(int K, int cap, int nblk, int D, int apb);  // dynamic LDS of a launch
+  size_t entry_bytes;                                             // LDS per incident row (entry tables + its code)
+  size_t static_lds;  // reserve for the kernel's static __shared__ (at most 848 B / 1.9 KB)
+  KernelFn kernel;     // null: no instantiation
+};
+static PersistKernel persist_kernel(int variant, int D) {
+  if (variant == 0)
+    return {persist_apb(D), persist_lds_bytes, (size_t)(4 * D + 4) * sizeof(double) + 3 * sizeof(int), 1024,
+            D == 2 ? cg1_persist_kernel<2> : cg1_persist_kernel<3>};
+  const int apb = variant == 1 ? 16 : 8;
+  return {apb, scp_persist16_lds_bytes, scp_persist16_entry_bytes(D), 2048, scp_persist16_kernel(D, apb)};
+}
 
 bool scp_qp_persist_eligible(const scp_qp* qp) {
   if (!qp->st.persistent || qp->st.cg_iters != 1 || qp->st.use_mfma != 1) return false;
@@ -750,8 +609,8 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   const int64_t C = qp->C, nx = (int64_t)K * C;
   const int variant = persist_variant_for(qp);
   if (variant < 0) { *ran = 0; return SCP_OK; }
-  const bool lean = variant >= 1;
-  const int apb = variant_apb(variant, D);
+  const PersistKernel pk = persist_kernel(variant, D);
+  const int apb = pk.apb;
   const int nblk = (qp->N + apb - 1) / apb;
   *ran = 0;
   if (!qp->cg1_ready) {
@@ -764,18 +623,16 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   if (qp->persist_cap_nW == qp->nW) return SCP_OK;  // this working set overflowed before
   {
     const int nb = nblk + 1;  // (+1: the fault-injection hook below may announce one more workgroup)
-    const size_t fixed = lean ? scp_persist16_lds_bytes(K, 0, nb, D, apb) : persist_lds_bytes(K, D, 0, nb);
-    const size_t per_entry = lean ? scp_persist16_entry_bytes(D) : (size_t)(4 * D + 4) * sizeof(double) + 3 * sizeof(int);
-    const size_t budget_lds = 160 * 1024 - (lean ? 2048 : 1024);  // minus the static __shared__ of the kernel (580 B / 1.2 KB)
-    if (fixed + 64 * per_entry > budget_lds) return SCP_OK;
-    qp->persist_cap = (int)((budget_lds - fixed) / per_entry / 64 * 64);
+    const size_t fixed = pk.lds_bytes(K, 0, nb, D, apb);
+    const size_t budget_lds = 160 * 1024 - pk.static_lds;
+    if (fixed + 64 * pk.entry_bytes > budget_lds) return SCP_OK;
+    qp->persist_cap = (int)((budget_lds - fixed) / pk.entry_bytes / 64 * 64);
   }
   // test hook (scp_qp_debug_set "persist_fault"): expect one workgroup more than is launched, so that the all-gather can
   // never complete -- the bounded spins must time out, every workgroup must leave without writing state back, and the
   // host must carry on with the three-launch pipeline
   const int nblk_expected = nblk + (qp->persist_fault > 0 ? 1 : 0);
-  const size_t lds = lean ? scp_persist16_lds_bytes(K, qp->persist_cap, nblk_expected, D, apb)
-                          : persist_lds_bytes(K, D, qp->persist_cap, nblk_expected);
+  const size_t lds = pk.lds_bytes(K, qp->persist_cap, nblk_expected, D, apb);
   if (lds > 160 * 1024) return SCP_OK;  // too many rows around one block of agents: three-launch pipeline
   const int budget = st.max_iter - it0;  // at most this many steps in this launch
   if (budget <= 0) return SCP_OK;  // nothing to run (the kernel's check would read tags and delta-y of an earlier launch)
@@ -854,18 +711,10 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   }
   a.epoch0 = (unsigned)qp->persist_epoch;
   qp->persist_variant = variant;
-  if (lean) {
-    int rc = scp_persist16_launch(ctx, a, nblk, lds, D, apb);
-    if (rc) return rc;
-  } else if (D == 2) {
-    if (lds > 64 * 1024)
-      SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, reinterpret_cast<const void*>(cg1_persist_kernel<2>), lds));
-    hipLaunchKernelGGL(cg1_persist_kernel<2>, dim3(nblk), dim3(64 * persist_apb(2)), lds, s, a);
-  } else {
-    if (lds > 64 * 1024)
-      SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, reinterpret_cast<const void*>(cg1_persist_kernel<3>), lds));
-    hipLaunchKernelGGL(cg1_persist_kernel<3>, dim3(nblk), dim3(64 * persist_apb(3)), lds, s, a);
-  }
+  if (!pk.kernel)
+    return scp_fail(ctx, SCP_ERR_INVALID, "persistent kernel: no instantiation for D = %d with %d agents per workgroup", D, apb);
+  if (lds > 64 * 1024) SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, reinterpret_cast<const void*>(pk.kernel), lds));
+  hipLaunchKernelGGL(pk.kernel, dim3(nblk), dim3(64 * apb), lds, s, a);
   SCP_HIP_CHECK(ctx, hipGetLastError());
   *ran = 1;
   {

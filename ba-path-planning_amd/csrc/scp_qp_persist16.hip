@@ -151,20 +151,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   const int a1 = min(a0 + APB16, N);
   const int ebase = A.cell_ptr[cell_of(0, a0, K)];
   const int ne = A.cell_ptr[cell_of(0, a1, K)] - ebase;
-  {  // more incident rows around some block than the tables hold: every workgroup finds out by itself and leaves at once
-    int worst = 0;
-    for (int b = threadIdx.x; b < (N + APB16 - 1) / APB16; b += NT16) {
-      const int b0 = b * APB16, b1 = min(b0 + APB16, N);
-      worst = max(worst, A.cell_ptr[cell_of(0, b1, K)] - A.cell_ptr[cell_of(0, b0, K)]);
-    }
-    if (__syncthreads_or(worst > cap)) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(A.host_status, (unsigned)EXIT_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-      return;
-    }
-  }
+  if (entries_overflow<APB16>(A)) return;
   if (threadIdx.x == 0) fail_s = 0;
   for (int i = threadIdx.x; i <= (a1 - a0) * K; i += NT16) cptr[i] = A.cell_ptr[cell_of(0, a0, K) + i] - ebase;
   for (int e = threadIdx.x; e < ne; e += NT16) {
@@ -399,30 +386,17 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         const int ek = code & 63, al = (code >> 6) & 15, side = (code >> 10) & 1, par = code >> 11;
         const u64* pc = A.cells + ((size_t)((int64_t)ek * N + par) * D) * 2;
         u32x4 w[D];
-        for (;;) {
-          ld_cell<D>(pc, w);
-          bool here = true;
-#pragma unroll
-          for (int d = 0; d < D; ++d) here = here && pair_ok(w[d], tag);
-          if (here) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
+        if (!wait_cell<D>(A, pc, tag, spins, w)) {
+          bad = true;
+          break;
         }
-        if (bad) break;
         double s = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) s += e_c[(size_t)e * D + d] * (Qt[(size_t)(al * D + d) * RSK + ek] - pair_value(w[d]));
         e_s[e] = s;              // (both copies of a row: the same bits, c and the difference change sign together)
         if (!side) sq += s * s;  // every row once
       }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
+      if (bad) raise_give_up(A, fail_s);
       sq = wave_incl_sum(sq);
       if (lane == 63) red[1][wave] = sq;
     }
@@ -433,12 +407,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
     // (A two-level form -- group leaders sum 16 partials, everybody polls 16 group sums: a sixteenth of the polls -- was
     // measured at 4096 x 50 and is SLOWER, 4.8 against 4.0 us: what this phase waits for is the slowest workgroup of the
     // step, not the fabric.)
-    if (threadIdx.x < 2) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < APB16; ++w) t += red[threadIdx.x][w];
-      st_granules(gpart + (size_t)blockIdx.x * 4 + 2 * threadIdx.x, tag, t);
-    }
+    publish_partials(red, 2, 3u, gpart + (size_t)blockIdx.x * 4, tag);
     // what the fixed-row update needs and a does not change, formed while the partials are in flight: z = Pi(v)
     double zcl[D][4];
 #pragma unroll
@@ -454,44 +423,11 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         for (int t = 0; t < 4; ++t) zcl[d][t] = v[d][t];
       }
     }
-    {
-      unsigned spins = 0;
-      bool bad = false;
-      for (int q = threadIdx.x; q < 2 * nblk; q += NT16) {  // one double (two granules) per thread and pass
-        u32x4 w;
-        for (;;) {
-          w = ld_pair(gpart + 2 * q);
-          if (pair_ok(w, tag)) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
-        }
-        if (bad) break;
-        gp[q] = pair_value(w);
-      }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
-    }
+    gather_pairs<NT16>(A, gpart, 2 * nblk, tag, gp, fail_s);
     __syncthreads();
     if (fail_s) { ok = false; break; }
     PSTAMP(5);
-    double a;
-    {  // every wave sums the partials in the same order: the same bits everywhere, no further barrier
-      double vr = 0.0, vs = 0.0;
-      for (int b = lane; b < nblk; b += 64) {
-        vr += gp[2 * b];
-        vs += gp[2 * b + 1];
-      }
-      const double rzt = read_lane(wave_incl_sum(vr), 63);
-      const double sqt = read_lane(wave_incl_sum(vs), 63);
-      const double pHp = rzt + rho_c * sqt;
-      a = (pHp > 0.0 && rzt != 0.0) ? rzt / pHp : 0.0;
-    }
+    const double a = step_length(gp, nblk, rho_c);
     const double aa = alpha * a;
     PSTAMP(6);
     // ---- collision rows first (the certificate of the last step needs their delta-y before the lanes' chain) ----------------
@@ -641,20 +577,10 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
         const int ek = code & 63, al = (code >> 6) & 15, side = (code >> 10) & 1, par = code >> 11;
         const u64* pc = A.cells + ((size_t)((int64_t)ek * N + par) * D) * 2;
         u32x4 w[D];
-        for (;;) {
-          ld_cell<D>(pc, w);
-          bool here = true;
-#pragma unroll
-          for (int d = 0; d < D; ++d) here = here && pair_ok(w[d], ctag);
-          if (here) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
+        if (!wait_cell<D>(A, pc, ctag, spins, w)) {
+          bad = true;
+          break;
         }
-        if (bad) break;
         double ax = 0.0;
 #pragma unroll
         for (int d = 0; d < D; ++d) {
@@ -675,10 +601,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
           }
         }
       }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
+      if (bad) raise_give_up(A, fail_s);
     }
 #pragma unroll
     for (int j = 0; j < NCHK; ++j) {
@@ -692,44 +615,12 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
     }
     __syncthreads();
     if (fail_s) { ok = false; break; }
-    if (threadIdx.x < NCHK) {
-      double t = 0.0;
-#pragma unroll
-      for (int w = 0; w < APB16; ++w) t = threadIdx.x == CK_SUPP ? t + red[threadIdx.x][w] : fmax(t, red[threadIdx.x][w]);
-      st_granules(A.gcheck + ((size_t)blockIdx.x * NCHK + threadIdx.x) * 2, ctag, t);
-    }
-    {
-      unsigned spins = 0;
-      bool bad = false;
-      for (int q = threadIdx.x; q < NCHK * nblk; q += NT16) {
-        u32x4 w;
-        for (;;) {
-          w = ld_pair(A.gcheck + 2 * q);
-          if (pair_ok(w, ctag)) break;
-          if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
-                                       __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-            bad = true;
-            break;
-          }
-          spin_nap(A.spin_sleep);
-        }
-        if (bad) break;
-        gck[q] = pair_value(w);
-      }
-      if (bad) {
-        __hip_atomic_store(A.give_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        fail_s = 1;
-      }
-    }
+    publish_partials(red, NCHK, 1u << CK_SUPP, A.gcheck + (size_t)blockIdx.x * NCHK * 2, ctag);
+    gather_pairs<NT16>(A, A.gcheck, NCHK * nblk, ctag, gck, fail_s);
     __syncthreads();
     if (fail_s) { ok = false; break; }
     double chk[NCHK];
-#pragma unroll
-    for (int j = 0; j < NCHK; ++j) {  // the same reduction order in every wave of every workgroup: identical decisions
-      double v = 0.0;
-      for (int b = lane; b < nblk; b += 64) v = j == CK_SUPP ? v + gck[b * NCHK + j] : fmax(v, gck[b * NCHK + j]);
-      chk[j] = read_lane(j == CK_SUPP ? wave_incl_sum(v) : wave_max_nn(v), 63);
-    }
+    reduce_checks(gck, nblk, chk);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int j = 0; j < NCHK; ++j) chk_s[j] = chk[j];
@@ -739,75 +630,46 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
       for (int i = threadIdx.x; i < NC16 * RSK; i += NT16) Rt[i] = 0.0;
       // (Pt: the cells of rows are rewritten by the next step before anybody reads them)
     }
-    // ---- decide (the host repeats these tests on the same nine numbers, scp_qp_solve) ------------------------------------
-    const double np_ = fmax(chk[CK_NAX], chk[CK_NZ]), nd_ = fmax(chk[CK_NPX], chk[CK_NATY]);
-    const double tol_p = A.eps_abs + A.eps_rel * np_, tol_d = A.eps_abs + A.eps_rel * nd_;
-    if (chk[CK_RP] <= tol_p && chk[CK_RD] <= tol_d) { exit_code = EXIT_SOLVED; break; }
-    if (A.check_fine > 0)  // (the same decision as scp_qp_solve's, from the same nine numbers)
-      cad = (chk[CK_RP] < A.fine_ratio * tol_p && chk[CK_RD] < A.fine_ratio * tol_d) ? A.check_fine : A.check_every;
-    if (it_done >= A.max_iter) { exit_code = EXIT_MAX_ITER; break; }
-    if (with_dy && chk[CK_NDY] > A.eps_prim_inf && chk[CK_SUPP] < -A.eps_prim_inf * chk[CK_NDY] &&
-        chk[CK_NATDY] < A.eps_prim_inf * chk[CK_NDY]) { exit_code = EXIT_INFEASIBLE; break; }
-    if (A.rho_tol > 0.0 && it_done % A.rho_interval == 0) {
-      // OSQP's rho estimate snapped to the 2^(1/4) grid; the candidate only SELECTS the host-computed double of the table
-      const double prim = chk[CK_RP] / fmax(np_, 1e-10), dual = chk[CK_RD] / fmax(nd_, 1e-10);
-      const double nr = fmin(fmax(rho * sqrt(prim / fmax(dual, 1e-10)), 1e-6), 1e6);
-      const double cand = exp2(round(4.0 * log2(nr)) * 0.25);
-      if (cand > rho * A.rho_tol * (1.0 - 1e-9) || cand < rho / A.rho_tol * (1.0 + 1e-9)) {  // (else: clearly no update)
-        int slot = -1;
-        for (int i = 0; i < A.n_tab; ++i)
-          if (fabs(A.tab[i].rho - cand) <= 1e-12 * cand) slot = i;
-        if (slot < 0) { exit_code = EXIT_RHO; break; }  // not cached yet: the host builds the blocks and relaunches
-        const double nrs = A.tab[slot].rho;
-        if (nrs > rho * A.rho_tol || nrs < rho / A.rho_tol) {
-          // ---- switch rho in place (what the host does between two launches: build_kkt hit + rows_value_kernel) -------------
-          {  // y = rho (v - Pi(v)) must survive the switch.  EXACTLY the arithmetic of leaving (write-back: z = Pi(v), y = rho_old
-             // (v - Pi(v))) and re-entering with the new rho (load: v = z + y / rho_new), so that a solver object whose cache
-             // already holds the new rho's blocks (switch here) and a fresh one (exit, host builds the blocks, relaunch)
-             // produce the same bits -- records of pooled and one-at-a-time solves stay identical
+    int slot;
+    exit_code = check_decision(A, chk, it_done, rho, with_dy, cad, slot);
+    if (exit_code) break;
+    if (slot >= 0) {
+      // ---- switch rho in place (what the host does between two launches: build_kkt hit + rows_value_kernel) -----------------
+      const double nrs = A.tab[slot].rho;
+      {  // y = rho (v - Pi(v)) must survive the switch.  EXACTLY the arithmetic of leaving (write-back: z = Pi(v), y = rho_old
+         // (v - Pi(v))) and re-entering with the new rho (load: v = z + y / rho_new), so that a solver object whose cache
+         // already holds the new rho's blocks (switch here) and a fresh one (exit, host builds the blocks, relaunch)
+         // produce the same bits -- records of pooled and one-at-a-time solves stay identical
 #pragma unroll
-            for (int d = 0; d < D; ++d) {
-              double lo[2], hi[2];
-              bounds(d, lo, hi);
-              const double zc[4] = {fmin(fmax(v[d][0], jlo), jhi), fmin(fmax(v[d][1], alo), ahi),
-                                    fmin(fmax(v[d][2], lo[0]), hi[0]), fmin(fmax(v[d][3], lo[1]), hi[1])};
+        for (int d = 0; d < D; ++d) {
+          double lo[2], hi[2];
+          bounds(d, lo, hi);
+          const double zc[4] = {fmin(fmax(v[d][0], jlo), jhi), fmin(fmax(v[d][1], alo), ahi),
+                                fmin(fmax(v[d][2], lo[0]), hi[0]), fmin(fmax(v[d][3], lo[1]), hi[1])};
 #pragma unroll
-              for (int t = 0; t < 4; ++t) {
-                const double rr_old = (t >= 2 && lastk) ? rho * A.rho_eq : rho, rr_new = (t >= 2 && lastk) ? nrs * A.rho_eq : nrs;
-                const double yv = rr_old * (v[d][t] - zc[t]);
-                v[d][t] = zc[t] + yv / rr_new;
-              }
-            }
+          for (int t = 0; t < 4; ++t) {
+            const double rr_old = (t >= 2 && lastk) ? rho * A.rho_eq : rho, rr_new = (t >= 2 && lastk) ? nrs * A.rho_eq : nrs;
+            const double yv = rr_old * (v[d][t] - zc[t]);
+            v[d][t] = zc[t] + yv / rr_new;
           }
-          rho = nrs;
-          rho_c = rho * A.rho_col_scale;
-          for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) {
-            Ml[i] = A.tab[slot].pMinv[i];
-            if constexpr (TQ) Tl[i] = A.tab[slot].pT[i];
-          }
-          for (int e = threadIdx.x; e < ne; e += NT16)  // row values of the next right-hand side from the exact S0 x cells
-            e_g[e] = (rho_c * e_z[e] - e_y[e]) - rho_c * e_ax[e];
-          ++n_rho;
-          if (A.check_fine > 0) cad = A.check_fine;
         }
       }
+      rho = nrs;
+      rho_c = rho * A.rho_col_scale;
+      for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) {
+        Ml[i] = A.tab[slot].pMinv[i];
+        if constexpr (TQ) Tl[i] = A.tab[slot].pT[i];
+      }
+      for (int e = threadIdx.x; e < ne; e += NT16)  // row values of the next right-hand side from the exact S0 x cells
+        e_g[e] = (rho_c * e_z[e] - e_y[e]) - rho_c * e_ax[e];
+      ++n_rho;
     }
     __syncthreads();  // Rt zeroed, operands / row values of a new rho in place
     PSTAMP(9);
   }
   }  // batches
 
-  // The exit decision is collective (see the 8-agent kernel): a workgroup that got through re-reads the give-up word
-  if (ok && __syncthreads_or(threadIdx.x == 0 &&
-                             __hip_atomic_load(A.give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u))
-    ok = false;
-  if (!ok) {
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(A.host_status, (unsigned)EXIT_GAVE_UP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    return;  // nothing was written back: the state in global memory is the state before this launch
-  }
+  if (leave_if_gave_up(A, ok)) return;
   // ---- write the state back (F x and S0 x from the exact prefix sums the last check left) ------------------------------------
 #pragma unroll
   for (int d = 0; d < D; ++d) {
@@ -847,18 +709,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   if (prof_t)
     for (int i = 0; i < 16; ++i) scp_persist16_clk[i] = i == 15 ? (unsigned long long)steps : pacc_s[i];
 #endif
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // the nine check results in the slots the host reads (scp_qp::h_scal), then the exit code and the completion word
-    const int slot[NCHK] = {SL_RP, SL_NAX, SL_NZ, SL_RD, SL_NPX, SL_NATY, SL_NDY, SL_SUPP, SL_NATDY};
-#pragma unroll
-    for (int j = 0; j < NCHK; ++j)
-      __hip_atomic_store((u64*)(A.host_scal + slot[j]), (u64)__double_as_longlong(chk_s[j]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_status + 1, (unsigned)it_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_status + 2, n_rho, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store((u64*)A.host_rho, (u64)__double_as_longlong(rho), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_status, exit_code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  publish_exit(A, chk_s, it_done, n_rho, rho, exit_code);
 }
 
 }  // namespace
@@ -879,18 +730,9 @@ size_t scp_persist16_lds_bytes(int K, int cap, int nblk, int D, int apb) {
   return L.n_dbl * sizeof(double) + ((ints + 1) / 2 * 2) * sizeof(int);
 }
 
-template <int D, int APB>
-static int launch16(scp_ctx* ctx, const PersistArgs& a, int nblk, size_t lds) {
-  if (lds > 64 * 1024)
-    SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, reinterpret_cast<const void*>(cg1_persist16_kernel<D, APB>), lds));
-  hipLaunchKernelGGL((cg1_persist16_kernel<D, APB>), dim3(nblk), dim3(64 * APB), lds, ctx->stream, a);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-int scp_persist16_launch(scp_ctx* ctx, const PersistArgs& a, int nblk, size_t lds, int D, int apb) {
-  if (D == 2 && apb == 16) return launch16<2, 16>(ctx, a, nblk, lds);
-  if (D == 2 && apb == 8) return launch16<2, 8>(ctx, a, nblk, lds);
-  if (D == 3 && apb == 8) return launch16<3, 8>(ctx, a, nblk, lds);
-  return scp_fail(ctx, SCP_ERR_INVALID, "persistent kernel: no instantiation for D = %d with %d agents per workgroup", D, apb);
+KernelFn scp_persist16_kernel(int D, int apb) {
+  if (D == 2 && apb == 16) return cg1_persist16_kernel<2, 16>;
+  if (D == 2 && apb == 8) return cg1_persist16_kernel<2, 8>;
+  if (D == 3 && apb == 8) return cg1_persist16_kernel<3, 8>;
+  return nullptr;
 }
