@@ -512,12 +512,6 @@ size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
 
 inline dim3 grid1(int64_t n) { return dim3(scp_cdiv(n, 256)); }
 
-#define QP_CHECK(call)            \
-  do {                            \
-    int rc_ = (call);             \
-    if (rc_ != SCP_OK) return rc_; \
-  } while (0)
-
 #define QP_LAUNCHED(qp) SCP_HIP_CHECK((qp)->ctx, hipGetLastError())
 
 int gemm(scp_qp* qp, int R, int M, double alpha, const double* A, const double* X, double beta, double* Y) {
@@ -532,7 +526,6 @@ int gemm(scp_qp* qp, int R, int M, double alpha, const double* A, const double* 
 //   ROW_VEC : vec                    (an arbitrary row vector)
 template <int MODE>
 int row_scatter(scp_qp* qp, const double* Q, const double* vec = nullptr) {
-  if (!qp->csr_valid) QP_CHECK(scp_qp_csr_build(qp));
   if (MODE == ROW_HMUL) return scp_qp_rows_gather(qp, Q);
   return scp_qp_csr_scatter(qp, MODE == ROW_RHS ? 0 : (MODE == ROW_Y ? 1 : 2), vec);
 }
@@ -723,6 +716,14 @@ int certificate_atdy(scp_qp* qp) {
 
 }  // namespace
 
+int scp_qp_exact_qx(scp_qp* qp, bool with_fx) {
+  if (qp->dv.qx) return SCP_OK;
+  QP_CHECK(gemm(qp, qp->K, qp->K, 1.0, qp->d.S0, qp->d.x, 0.0, qp->d.HQ + (int64_t)qp->K * qp->C));
+  if (with_fx) QP_CHECK(gemm(qp, qp->Rf, qp->K, 1.0, qp->d.F, qp->d.x, 0.0, qp->d.fx));
+  qp_on_qx_built(qp, with_fx);
+  return SCP_OK;
+}
+
 // ----------------------------------------------------------------------------------------------------
 // C-ABI
 // ----------------------------------------------------------------------------------------------------
@@ -786,8 +787,6 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
   qp->row_cap = row_capacity;
   qp->nW = 0;
   qp->problem_set = qp->reset_done = false;
-  qp->cg1_ready = qp->csr_valid = qp->qx_fresh = qp->gval_valid = false;
-  qp->qx_sel = 0;
   qp->rho = s->rho;
   carve(qp->d, workspace, K, qp->C, row_capacity, D);
   {
@@ -928,14 +927,13 @@ static int reset_impl(scp_qp* qp, const double* x0, int64_t n, const int64_t* ro
   if (one_launch && at && ctx->small_pass && qp->st.cg_iters == 1 && n > 0 && n <= qp->row_cap)
     QP_CHECK(scp_qp_reset_install_small(qp, x0, n, rows, at->pos_prev, at->p0, at->v0, at->R, d.HQ + nx, &with_rows));
   if (with_rows) {
-    qp->qx_sel = 0;
+    // (the install launch did the reset too)
   } else if (one_launch) {
     // z = A x (primal warm start, scp.py:443), y = 0 and the single-step pipeline's carried F x, S0 x in one launch
     hipLaunchKernelGGL(qp_reset_kernel, dim3(scp_cdiv(qp->C, RESET_COLS)), dim3(256),
                        (size_t)qp->K * RESET_COLS * sizeof(double), ctx->stream, qp->N, qp->K, qp->D, qp->Rf, x0, d.F, d.S0,
                        d.x, d.zf, d.fx, d.HQ + nx, d.yf);
     QP_LAUNCHED(qp);
-    qp->qx_sel = 0;
   } else {
     if (x0) QP_CHECK(scp_launch_to_time_major(ctx, qp->N, qp->K, qp->D, x0, d.x));
     else SCP_HIP_CHECK(ctx, hipMemsetAsync(d.x, 0, nx * sizeof(double), ctx->stream));
@@ -946,10 +944,8 @@ static int reset_impl(scp_qp* qp, const double* x0, int64_t n, const int64_t* ro
   qp->persist_cap_nW = -1;
   qp->persist_off = false;  // every new QP tries the persistent path again
   qp->steps_since_reset = 0;
-  qp->cg1_ready = false;
-  qp->gval_valid = with_rows;  // (incidence lists and row values of the installed rows, at gval_rho_c)
-  qp->csr_valid = with_rows;
-  qp->qx_fresh = one_launch;  // F x and S0 x of this x are in place
+  qp_on_x_set(qp, one_launch);
+  if (with_rows) qp_on_rows_added(qp, true);
   QP_CHECK(build_kkt(qp));
   qp->reset_done = true;
   if (installed) *installed = with_rows;
@@ -966,8 +962,7 @@ extern "C" int scp_qp_set_rho(scp_qp* qp, double rho) {
   if (!qp->reset_done) return scp_fail(qp->ctx, SCP_ERR_STATE, "qp_set_rho: call scp_qp_reset first");
   SCP_REQUIRE(qp->ctx, rho >= 1e-6 && rho <= 1e6, "qp_set_rho: rho out of range");
   qp->rho = rho;
-  qp->cg1_ready = false;  // the carried row values depend on rho
-  qp->gval_valid = false;
+  qp_on_rho_changed(qp, false);
   return build_kkt(qp);
 }
 
@@ -981,14 +976,8 @@ static int add_rows_impl(scp_qp* qp, int64_t n, const int64_t* rows, const doubl
     return scp_fail(ctx, SCP_ERR_CAPACITY, "qp_add_rows: %lld + %lld rows exceed the capacity %lld",
                     (long long)qp->nW, (long long)n, (long long)qp->row_cap);
   const QpDev& d = qp->d;
-  const int64_t nx = (int64_t)qp->K * qp->C;
-  // S0 x for z_c = max(A_c x, l): the single-step pipeline's exact copy when there is one (after a reset, after a solve's
-  // last check), else computed into the spare slab
-  const double* Qx = qp->qx_sel ? d.HQ : d.HQ + nx;
-  if (!qp->qx_fresh) {
-    QP_CHECK(gemm(qp, qp->K, qp->K, 1.0, d.S0, d.x, 0.0, d.HQ + nx));  // (HQ is scratch whenever qx_fresh is false)
-    Qx = d.HQ + nx;
-  }
+  QP_CHECK(scp_qp_exact_qx(qp, false));  // S0 x for z_c = max(A_c x, l)
+  const double* Qx = scp_qp_qx(qp);
   if (at) {
     bool installed = false;
     if (qp->st.use_mfma == 1 && qp->st.cg_iters == 1 && qp->K <= SCP_FUSED_MAX_K)  // (the single-step pipelines' lists)
@@ -996,7 +985,7 @@ static int add_rows_impl(scp_qp* qp, int64_t n, const int64_t* rows, const doubl
     if (installed) {
       qp->nW += n;
       qp->persist_cap_nW = -1;
-      qp->cg1_ready = false;
+      qp_on_rows_added(qp, true);
       return SCP_OK;
     }
     QP_CHECK(scp_launch_add_rows_at(ctx, qp->N, qp->K, qp->D, qp->nW, n, rows, at->pos_prev, at->p0, at->v0, at->R, qp->h, Qx,
@@ -1009,9 +998,7 @@ static int add_rows_impl(scp_qp* qp, int64_t n, const int64_t* rows, const doubl
   }
   qp->nW += n;
   qp->persist_cap_nW = -1;
-  qp->cg1_ready = false;
-  qp->gval_valid = false;
-  qp->csr_valid = false;
+  qp_on_rows_added(qp, false);
   return SCP_OK;
 }
 
@@ -1082,7 +1069,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
   static constexpr int persist_pipe[] = {SCP_PIPE_PERSIST, SCP_PIPE_PERSIST16, SCP_PIPE_PERSIST8L};  // by persist_variant
   memset(info, 0, sizeof(*info));
   info->status_val = -2;  // OSQP_MAX_ITER_REACHED
-  qp->cg1_ready = false;  // settings may have changed between calls
+  qp_on_solve_start(qp);
   qp->persist_skip_solve = false;
   const auto wall0 = std::chrono::steady_clock::now();
   if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -1112,12 +1099,12 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
         cg_total += it_done - it;
         qp->steps_since_reset += it_done - it;
         it = it_done;
-        qp->qx_fresh = true;  // the kernel's last check left F x and S0 x exact
         persist_done = true;
         if (qp->persist_rho_switches > 0) {
           // adaptive-rho updates whose blocks were cached happened inside the kernel (same test, same values as below):
           // adopt the result; build_kkt finds the slot and points d.* at it
           qp->rho = qp->persist_rho;
+          qp_on_rho_changed(qp, true);
           info->rho_updates += qp->persist_rho_switches;
           QP_CHECK(build_kkt(qp));
         }
@@ -1157,8 +1144,9 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
       } else {
         QP_CHECK(residuals(qp, with_dy));
       }
-      if (pipe != QpPipe::CG1) { qp->cg1_ready = false; qp->gval_valid = false; qp->qx_fresh = false; }  // residuals() used G and the Q slabs as scratch (the fused check keeps
-                                           // the pipeline's carried state and refreshes S0 x, F x exactly)
+      // QP0 takes the generic check's rule although its fused check refreshes S0 x and F x: rows added after QP#0 go in
+      // by the general installation
+      if (pipe != QpPipe::CG1) qp_on_scratch_used(qp);
       const double* hs = qp->h_scal;
       rp = hs[SL_RP];
       rd = hs[SL_RD];
@@ -1196,8 +1184,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
         nr = std::exp2(std::round(4.0 * std::log2(nr)) / 4.0);
         if (nr > qp->rho * st.adaptive_rho_tolerance || nr < qp->rho / st.adaptive_rho_tolerance) {
           qp->rho = nr;
-          qp->cg1_ready = false;  // the carried row values depend on rho
-          qp->gval_valid = false;
+          qp_on_rho_changed(qp, false);
           QP_CHECK(build_kkt(qp));
           ++info->rho_updates;
           if (fine) cad = fine;  // (the residuals usually fall below the tolerances within a few steps)
@@ -1254,10 +1241,7 @@ extern "C" int scp_qp_clone_state(scp_qp* dst, const scp_qp* src) {
   dst->rho = src->rho;
   dst->st = src->st;
   dst->problem_set = true;
-  dst->cg1_ready = false;
-  dst->gval_valid = false;
-  dst->csr_valid = false;
-  dst->qx_fresh = false;
+  qp_on_x_set(dst, false);
   QP_CHECK(build_kkt(dst));
   dst->reset_done = true;
   SCP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // src's workspace may be released by the caller right after
@@ -1306,7 +1290,7 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
   const double* src = nullptr;
   int64_t n = 0;
   if (!strcmp(name, "fx")) { src = d.fx; n = nf; }
-  else if (!strcmp(name, "qx")) { src = qp->qx_sel ? d.HQ : d.HQ + nx; n = nx; }
+  else if (!strcmp(name, "qx")) { src = scp_qp_qx(qp); n = nx; }
   else if (!strcmp(name, "gval")) { src = d.gval; n = 2 * qp->nW; }
   else if (!strcmp(name, "zf")) { src = d.zf; n = nf; }
   else if (!strcmp(name, "yf")) { src = d.yf; n = nf; }

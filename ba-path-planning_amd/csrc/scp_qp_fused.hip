@@ -762,51 +762,35 @@ __global__ void csr_small_kernel(int64_t nW, int K, int ncell, int D, int64_t C,
                                  int* __restrict__ pos_i, int* __restrict__ pos_j, double* __restrict__ gval, CsrNewRows nr);
 }  // namespace
 
-// Bring the single-step pipeline's carried state in line with (x, zc, yc, rho): S0 x and F x exact, row values g.
 int scp_qp_cg1_prepare(scp_qp* qp) {
+  if (qp->dv.carried) return SCP_OK;
   const QpDev& d = qp->d;
   hipStream_t s = qp->ctx->stream;
   const int K = qp->K;
-  const int64_t C = qp->C, nx = (int64_t)K * C;
+  const int64_t C = qp->C;
   const double rho_c = qp->rho * qp->st.rho_col_scale;
-  if (!qp->qx_fresh) {
-    qp->qx_sel = 0;
-    qp->gval_valid = false;
-    int rc = scp_launch_gemm(qp->ctx, 1, K, K, (int)C, 1.0, d.S0, d.x, 0.0, d.HQ + nx);
-    if (!rc) rc = scp_launch_gemm(qp->ctx, 1, qp->Rf, K, (int)C, 1.0, d.F, d.x, 0.0, d.fx);
-    if (rc) return rc;
-  }
-  qp->qx_fresh = false;
-  const double* Qx = qp->qx_sel ? d.HQ : d.HQ + nx;
-  if (qp->csr_valid && qp->gval_valid && qp->gval_rho_c == rho_c) {  // scp_qp_install_rows_small built lists and values already
-    qp->gval_valid = false;  // (the iterations about to run carry them on)
-    qp->cg1_ready = true;
-    return SCP_OK;
-  }
-  qp->gval_valid = false;
-  if (!qp->csr_valid && qp->nW > 0 && qp->nW <= CSR1_MAX_ROWS && qp->N * K <= CSR1_MAX_CELLS) {
+  QP_CHECK(scp_qp_exact_qx(qp, true));
+  const double* Qx = scp_qp_qx(qp);
+  if (qp->dv.vals_rho_c == rho_c) {
+    // scp_qp_install_rows_small built lists and values already
+  } else if (!qp->dv.lists && qp->nW > 0 && qp->nW <= CSR1_MAX_ROWS && qp->N * K <= CSR1_MAX_CELLS) {
     const int ncell = qp->N * K;
     hipLaunchKernelGGL(csr_small_kernel, dim3(1), dim3(1024), (size_t)ncell * sizeof(int), s, qp->nW, K, ncell, qp->D, C, rho_c,
                        d.w_k, d.w_i, d.w_j, d.w_eta, Qx, d.zc, d.yc, d.cell_ptr, d.ent_code, d.coef, d.pos_i, d.pos_j, d.gval,
                        CsrNewRows{});
     FUSED_LAUNCHED(qp);
-    qp->csr_valid = true;
-    qp->cg1_ready = true;
-    return SCP_OK;
+  } else {
+    QP_CHECK(scp_qp_csr_ensure(qp));
+    const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
+    if (qp->D == 2)
+      hipLaunchKernelGGL((rows_value_kernel<2, true>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx,
+                         d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
+    else
+      hipLaunchKernelGGL((rows_value_kernel<3, true>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx,
+                         d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
+    FUSED_LAUNCHED(qp);
   }
-  if (!qp->csr_valid) {
-    int rc = scp_qp_csr_build(qp);
-    if (rc) return rc;
-  }
-  const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
-  if (qp->D == 2)
-    hipLaunchKernelGGL((rows_value_kernel<2, true>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx,
-                       d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
-  else
-    hipLaunchKernelGGL((rows_value_kernel<3, true>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx,
-                       d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
-  FUSED_LAUNCHED(qp);
-  qp->cg1_ready = true;
+  qp_on_cg1_prepared(qp);
   return SCP_OK;
 }
 
@@ -816,7 +800,7 @@ int scp_qp_install_rows_small(scp_qp* qp, int64_t n, const int64_t* rows, const 
   const QpDev& d = qp->d;
   const int K = qp->K;
   const int64_t nW = qp->nW + n;
-  if (!qp->qx_fresh || n <= 0 || nW > CSR1_MAX_ROWS || qp->N * K > CSR1_MAX_CELLS) return SCP_OK;
+  if (!qp->dv.qx || n <= 0 || nW > CSR1_MAX_ROWS || qp->N * K > CSR1_MAX_CELLS) return SCP_OK;
   const int ncell = qp->N * K;
   const double rho_c = qp->rho * qp->st.rho_col_scale;
   CsrNewRows nr{n, qp->nW, rows, pos_prev, p0, v0, R, qp->h, qp->N, d.w_row, d.w_l};
@@ -824,9 +808,6 @@ int scp_qp_install_rows_small(scp_qp* qp, int64_t n, const int64_t* rows, const 
                      qp->C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx, d.zc, d.yc, d.cell_ptr, d.ent_code, d.coef, d.pos_i,
                      d.pos_j, d.gval, nr);
   FUSED_LAUNCHED(qp);
-  qp->csr_valid = true;
-  qp->gval_valid = true;
-  qp->gval_rho_c = rho_c;
   *done = true;
   return SCP_OK;
 }
@@ -839,19 +820,16 @@ int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy) {
   double* dyc = emit_dy ? d.dyc : nullptr;
   hipStream_t s = qp->ctx->stream;
   const int K = qp->K, Rf = qp->Rf;
-  const int64_t C = qp->C, nx = (int64_t)K * C;
+  const int64_t C = qp->C;
   const int nblk = (int)((C + CB - 1) / CB);
   double* Qp = d.s0p;  // S0 p
   double* Fp = d.tf;   // F p
   double* part_rz = d.part;
   double* part_sq = d.part + SCP_PART_CAP / 2;
   const double rho_c = qp->rho * qp->st.rho_col_scale;
-  if (!qp->cg1_ready) {
-    int rc = scp_qp_cg1_prepare(qp);
-    if (rc) return rc;
-  }
-  double* Qx = qp->qx_sel ? d.HQ : d.HQ + nx;  // S0 x (carried)
-  double* Qn = qp->qx_sel ? d.HQ + nx : d.HQ;  // S0 x of the next iteration
+  QP_CHECK(scp_qp_cg1_prepare(qp));
+  double* Qx = scp_qp_qx(qp);        // S0 x (carried)
+  double* Qn = scp_qp_qx(qp, true);  // S0 x of the next iteration
   const size_t lds = (size_t)CB * (pad_col(Rf) + 5 * pad_col(K)) * sizeof(double);
   int npart = nblk;  // partial sums of r.p: one per column block, or one per column (long horizons)
   if (K > SCP_FUSED_MAX_K) {
@@ -894,7 +872,7 @@ int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy) {
                        part_rz, part_sq, d.wrow, d.lf, d.uf, d.zf, d.yf, d.fx, Fp, d.x, d.p, Qp, Qx, Qn, qp->nW, d.w_k,
                        d.w_i, d.w_j, d.w_eta, d.w_l, d.zc, d.yc, d.pos_i, d.pos_j, d.gval, dyf, dyc, inline_sq);
   FUSED_LAUNCHED(qp);
-  qp->qx_sel ^= 1;
+  qp_on_cg1_step(qp);
   ++*cg_count;
   return SCP_OK;
 }
@@ -1169,7 +1147,6 @@ int scp_qp_reset_install_small(scp_qp* qp, const double* x0, int64_t n, const in
                      K, ncell, qp->D, qp->C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx, d.zc, d.yc, d.cell_ptr, d.ent_code,
                      d.coef, d.pos_i, d.pos_j, d.gval, nr, qp->ctx->d_ticket + 2);  // ([0], [1]: the passes, the checks)
   FUSED_LAUNCHED(qp);
-  qp->gval_rho_c = rho_c;
   *done = true;
   return SCP_OK;
 }
@@ -1211,7 +1188,8 @@ __global__ __launch_bounds__(256) void csr_gather_kernel(int K, int N, int D, co
 
 }  // namespace
 
-int scp_qp_csr_build(scp_qp* qp) {
+int scp_qp_csr_ensure(scp_qp* qp) {
+  if (qp->dv.lists) return SCP_OK;
   const QpDev& d = qp->d;
   hipStream_t s = qp->ctx->stream;
   const int ncell = qp->N * qp->K;
@@ -1229,11 +1207,12 @@ int scp_qp_csr_build(scp_qp* qp) {
                        d.ent_code, d.w_eta, d.coef, d.pos_i, d.pos_j);
     FUSED_LAUNCHED(qp);
   }
-  qp->csr_valid = true;
+  qp_on_lists_built(qp);
   return SCP_OK;
 }
 
 int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec) {
+  QP_CHECK(scp_qp_csr_ensure(qp));
   const QpDev& d = qp->d;
   hipStream_t s = qp->ctx->stream;
   const int64_t nx = (int64_t)qp->K * qp->C;
@@ -1249,10 +1228,7 @@ int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec) {
 int scp_qp_rows_gather(scp_qp* qp, const double* Q) {
   const QpDev& d = qp->d;
   hipStream_t s = qp->ctx->stream;
-  if (!qp->csr_valid) {
-    int rc = scp_qp_csr_build(qp);
-    if (rc) return rc;
-  }
+  QP_CHECK(scp_qp_csr_ensure(qp));
   const int64_t C = qp->C, nx = (int64_t)qp->K * C;
   const double rho_c = qp->rho * qp->st.rho_col_scale;
   const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
@@ -1265,7 +1241,6 @@ int scp_qp_rows_gather(scp_qp* qp, const double* Q) {
   hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, qp->K, qp->N, qp->D,
                      d.cell_ptr, d.coef, d.gval, d.G);
   FUSED_LAUNCHED(qp);
-  qp->cg1_ready = false;  // gval is the single-step pipeline's carried row value too
   return SCP_OK;
 }
 
@@ -1562,9 +1537,9 @@ int scp_qp_fused_residuals(scp_qp* qp, bool with_dy) {
   scp_ctx* ctx = qp->ctx;
   hipStream_t s = ctx->stream;
   const int K = qp->K, Rf = qp->Rf;
-  const int64_t C = qp->C, nx = (int64_t)K * C;
+  const int64_t C = qp->C;
   const int nblk = (int)((C + CB - 1) / CB);
-  double* Qx = qp->qx_sel ? d.HQ : d.HQ + nx;
+  double* Qx = scp_qp_qx(qp);
   double* part = qp->h_scal_dev + SL_COUNT;  // [nblk column blocks | RESID_ROW_BLOCKS row blocks][SCP_RESID_STRIDE]
   const int has_rows = qp->nW > 0 ? 1 : 0;
   if (has_rows)
@@ -1619,7 +1594,7 @@ int scp_qp_fused_residuals(scp_qp* qp, bool with_dy) {
       else hs[slot[j]] = fmax(hs[slot[j]], o[j]);
     }
   }
-  qp->qx_fresh = true;
+  qp_on_fused_check(qp);
   return SCP_OK;
 }
 

@@ -8,6 +8,12 @@ constexpr int SCP_KKT_SLOTS_MAX = 32;  // ... and up to this many while the pool
 constexpr size_t SCP_KKT_POOL_BYTES = (size_t)48 << 20;
 constexpr int NPART = 128;  // partial sums of a dot product (fixed -> deterministic summation order)
 
+#define QP_CHECK(call)            \
+  do {                            \
+    int rc_ = (call);             \
+    if (rc_ != SCP_OK) return rc_; \
+  } while (0)
+
 enum Slot {  // device scalar slots (doubles)
   SL_RZ0 = 0, SL_RZ1 = 1,
   SL_RP = 8, SL_NAX = 9, SL_NZ = 10, SL_RD = 11, SL_NPX = 12, SL_NATY = 13,
@@ -59,6 +65,16 @@ struct QpDev {
   unsigned long long* gcheck;      // SCP_GCHECK_WORDS tagged granules: termination-check partials
 };
 
+// Which derived device state still matches the primary state (x, z / y, the working rows, rho).  Only the qp_on_*
+// transitions at the end of this header write it.
+struct QpDerived {
+  bool lists = false;       // the incidence lists (cell_ptr, ent_code, coef, pos_i / pos_j) match the working set
+  bool qx = false;          // the S0 x half of HQ and the F x slab are exact for x
+  int qx_half = 0;          // which half of HQ holds S0 x: 0 -> rows [K, 2K), 1 -> [0, K) (swapped by every single step)
+  double vals_rho_c = 0.0;  // > 0: the small install built lists and row values with the latest rows, at this column rho
+  bool carried = false;     // the single-step pipeline's carried state (S0 x, F x, row values gval) matches (x, zc, yc, rho)
+};
+
 struct scp_qp {
   scp_ctx* ctx;
   int N, K, D, Rf;
@@ -67,12 +83,7 @@ struct scp_qp {
   scp_qp_settings st;
   int64_t row_cap, nW;
   bool problem_set, reset_done;
-  bool cg1_ready;  // carried state (Qx, gval) of the single-step pipeline matches (x, zc, yc, rho)
-  bool gval_valid;   // the incidence lists and row values were built together with the latest rows (scp_qp_install_rows_small)
-  double gval_rho_c; // ... at this column rho: scp_qp_cg1_prepare has nothing left to launch
-  bool csr_valid;  // incidence lists match the working set
-  bool qx_fresh;   // the current S0 x buffer and the F x slab are exact for x (written by the fused residual kernel)
-  int qx_sel;      // which half of HQ holds S0 x (the single-step pipeline ping-pongs: 0 -> rows [K, 2K), 1 -> [0, K))
+  QpDerived dv;
   double rho;
   QpDev d;
   // rho-dependent blocks (H_f, [H_f; S0], H_f^{-1}, T and the packed H_f^{-1}, T) are cached per rho: adaptive rho is
@@ -136,13 +147,20 @@ constexpr int SCP_PART_CAP = 4096;  // capacity of each partial-sum array (colum
 int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy);
 // nW == 0: `nit` complete ADMM iterations in one launch (everything is column-local)
 int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out);
-// Deterministic A_W^T g into the G slab (valid incidence lists required): mode 0: g = rho_c zc - yc, 1: g = yc,
-// 2: g = vec[n].  Two launches, no atomics.
+// Deterministic A_W^T g into the G slab: mode 0: g = rho_c zc - yc, 1: g = yc, 2: g = vec[n].  Two launches, no atomics.
 int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec);
-int scp_qp_csr_build(scp_qp* qp);
+// the incidence lists of the working set, built when they are stale
+int scp_qp_csr_ensure(scp_qp* qp);
 // G = A_W^T g, g = rho A_W v with Q = S0 v: deterministic (gather over the incidence lists)
 int scp_qp_rows_gather(scp_qp* qp, const double* Q);
+// the single-step pipeline's carried state (S0 x, F x, row values), brought in line with (x, zc, yc, rho) when it is not
 int scp_qp_cg1_prepare(scp_qp* qp);
+// S0 x exact for x, formed into rows [K, 2K) of HQ unless the carried copy is exact; with_fx: F x too (scp_qp.hip)
+int scp_qp_exact_qx(scp_qp* qp, bool with_fx);
+// the half of HQ that holds S0 x; other: the half the next single step writes
+inline double* scp_qp_qx(const scp_qp* qp, bool other = false) {
+  return (qp->dv.qx_half != 0) != other ? qp->d.HQ : qp->d.HQ + (int64_t)qp->K * qp->C;
+}
 // small problems: working rows [nW, nW + n) recomputed from the linearisation point (scp_qp_add_rows_at) AND the incidence
 // lists + row values of all nW + n rows in ONE launch; *done = false: not eligible, nothing was launched
 int scp_qp_install_rows_small(scp_qp* qp, int64_t n, const int64_t* rows, const double* pos_prev, const double* p0,
@@ -173,3 +191,33 @@ static inline size_t scp_packed_count(int R, int M) { return (size_t)((R + 15) /
 // fills qp->h_scal[SL_RP .. SL_SUPP] like residuals() in scp_qp.hip and leaves S0 x and F x in their slabs.  Synchronises.
 // with_dy: dyf / dyc hold delta-y of the last iteration (cg1_update_kernel); also fills h_scal[SL_NATDY].
 int scp_qp_fused_residuals(scp_qp* qp, bool with_dy);
+
+// ---- the only writers of QpDerived: one transition per event that happens to the primary state ---------------------------
+// x set by a reset or a clone; qx: the reset's own launch formed S0 x (into rows [K, 2K) of HQ) and F x
+inline void qp_on_x_set(scp_qp* qp, bool qx) {
+  QpDerived& v = qp->dv;
+  v.lists = v.carried = false; v.vals_rho_c = 0.0; v.qx = qx;
+  if (qx) v.qx_half = 0;
+}
+// rows added; small_install: by the small install, which built the lists and every row value at the current rho
+inline void qp_on_rows_added(scp_qp* qp, bool small_install) {
+  qp->dv.lists = small_install; qp->dv.vals_rho_c = small_install ? qp->rho * qp->st.rho_col_scale : 0.0;
+  qp->dv.carried = false;
+}
+// rho changed: the row values depend on it (in_kernel: the persistent kernel's own switch recomputed the carried ones)
+inline void qp_on_rho_changed(scp_qp* qp, bool in_kernel) { qp->dv.vals_rho_c = 0.0; qp->dv.carried &= in_kernel; }
+inline void qp_on_solve_start(scp_qp* qp) { qp->dv.carried = false; }  // (the settings may have changed)
+// a check other than CG1's fused one: it and the generic iterations before it used G, gval and HQ as scratch
+inline void qp_on_scratch_used(scp_qp* qp) { qp->dv.carried = qp->dv.qx = false; qp->dv.vals_rho_c = 0.0; }
+inline void qp_on_fused_check(scp_qp* qp) { qp->dv.qx = true; }  // (S0 x and F x refreshed, the carried state kept)
+inline void qp_on_cg1_step(scp_qp* qp) { qp->dv.qx = false; qp->dv.qx_half ^= 1; }
+// a persistent launch ended: its last check left S0 x and F x exact.  After a give-up a workgroup may still have written
+// back (the kernel's exit decision closes that window but cannot exclude it): the carried slabs may not match x / z / y.
+inline void qp_on_persist_exit(scp_qp* qp, int code) {
+  qp->dv.qx = code != SCP_PERSIST_GAVE_UP;
+  if (code == SCP_PERSIST_GAVE_UP) qp->dv.carried = false;
+}
+// what the rebuilds made (the iterations after scp_qp_cg1_prepare carry its row values on)
+inline void qp_on_qx_built(scp_qp* qp, bool with_fx) { qp->dv.qx_half = 0; qp->dv.qx = with_fx; }
+inline void qp_on_lists_built(scp_qp* qp) { qp->dv.lists = true; }
+inline void qp_on_cg1_prepared(scp_qp* qp) { qp->dv.lists = qp->dv.carried = true; qp->dv.vals_rho_c = 0.0; }

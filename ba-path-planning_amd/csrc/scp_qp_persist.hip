@@ -606,17 +606,14 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   hipStream_t s = ctx->stream;
   const scp_qp_settings& st = qp->st;
   const int K = qp->K, D = qp->D;
-  const int64_t C = qp->C, nx = (int64_t)K * C;
+  const int64_t C = qp->C;
   const int variant = persist_variant_for(qp);
   if (variant < 0) { *ran = 0; return SCP_OK; }
   const PersistKernel pk = persist_kernel(variant, D);
   const int apb = pk.apb;
   const int nblk = (qp->N + apb - 1) / apb;
   *ran = 0;
-  if (!qp->cg1_ready) {
-    int rc = scp_qp_cg1_prepare(qp);
-    if (rc) return rc;
-  }
+  QP_CHECK(scp_qp_cg1_prepare(qp));
   // Entry tables: the workgroup is alone on its CU anyway (228 VGPRs x 8 waves), so it simply takes all the LDS there is
   // -- no read-back of the largest block's entry count.  A block of agents with more incident rows than fit (> ~1300 at
   // K = 50) makes the kernel leave at once with EXIT_OVERFLOW; that working set then runs on the three-launch pipeline.
@@ -674,7 +671,7 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   a.pMinv = d.pMinv;
   a.pT = d.pT;
   a.lf = d.lf; a.uf = d.uf; a.zf = d.zf; a.yf = d.yf; a.fx = d.fx; a.x = d.x;
-  a.Qx = qp->qx_sel ? d.HQ : d.HQ + nx;
+  a.Qx = scp_qp_qx(qp);
   a.dyf = d.dyf;
   a.cells = d.cells;
   a.gpart = d.gpart;
@@ -730,14 +727,10 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
     *ran = 0;
     return SCP_OK;
   }
+  qp_on_persist_exit(qp, *code);
   if (*code == SCP_PERSIST_GAVE_UP) {
-    // Nothing should have been written back; if a workgroup got through after another had timed out (the kernel's exit
-    // decision closes that window but cannot exclude it), the carried slabs no longer match x / z / y: rebuild them.
-    qp->cg1_ready = false;
-    qp->qx_fresh = false;
     ++qp->persist_gave_up_total;
-  }
-  if (*code != SCP_PERSIST_GAVE_UP) {
+  } else {
     qp->persist_epoch += (u64)(*it_done - it0);  // one tag per ADMM step
     // rho switches the kernel made by itself (scp_qp_solve adopts the value and points d.* at that slot)
     qp->persist_rho_switches = (int)((volatile unsigned*)qp->h_persist)[2];
