@@ -52,6 +52,9 @@ struct scp_ctx {
   unsigned long long rel_seq;     // of the latest scp_rel_step (completion word: h_scratch[64]; partials: h_scratch[0..64))
   void* gen_ws;                   // device workspace of scp_generate_grid_swap (grown on demand)
   size_t gen_ws_bytes;
+  void* sep_ws;                   // device workspace of scp_check_separation (time-major records + partials; grown on demand)
+  size_t sep_ws_bytes;
+  unsigned long long* sep_n_solved;  // inside it: segments of the latest scp_check_separation that reached the quartic
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;
 };
@@ -92,6 +95,9 @@ hipError_t scp_raise_lds_limit(int device, const void* kernel, size_t bytes);
 // ~20 us, then poll every ~20 us from a sleep, for many solver threads on few cores (compute-trajectories-batch).
 // Returns false after `timeout_s` seconds.
 bool scp_wait_host_word(volatile unsigned long long* word, unsigned long long seq, int timeout_s);
+
+// shape / pair-range validation shared by every pairwise pass (scp_kernels.hip)
+int scp_check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end);
 
 // Stats of the latest scp_linearize_pairs / scp_collision_violations[_at] call of this ctx, from the host mirror: waits for
 // that pass's last kernel only (no stream drain, no copy launch).

@@ -81,6 +81,7 @@ extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
   if (ctx->cmp_tot) (void)hipFree(ctx->cmp_tot);
   if (ctx->tm_scratch) (void)hipFree(ctx->tm_scratch);
   if (ctx->gen_ws) (void)hipFree(ctx->gen_ws);
+  if (ctx->sep_ws) (void)hipFree(ctx->sep_ws);
   if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
   (void)hipHostFree(ctx->h_scratch);
   (void)hipHostFree(ctx->h_mirror);
@@ -1956,6 +1957,10 @@ static int check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, 
               "pair pass: %lld pairs per call exceed the 32-bit lane offsets; shard the pair range",
               (long long)(q_end - q_begin));
   return SCP_OK;
+}
+
+int scp_check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end) {
+  return check_pair_range(ctx, N, K, D, q_begin, q_end);
 }
 
 extern "C" int scp_linearize_pairs(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin,

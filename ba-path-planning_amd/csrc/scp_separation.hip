@@ -1,0 +1,483 @@
+// Continuous-time separation check (scp_check_separation, include/scp_hip.h): the minimum over every SEGMENT of a
+// trajectory -- not only over its K samples -- of the distance of every pair of vehicles.  Over segment k vehicle i flies
+//   p_i[k] + t v_i[k] + t^2/2 a_i[k],  t in [0, h]   (the kinematics of scp_kinematics, constant acceleration per step),
+// so with d = p_i - p_j, w = v_i - v_j, b = a_i - a_j at sample k the squared distance of a pair is the quartic
+//   f(t) = |d + t w + t^2/2 b|^2 = c0 + c1 t + c2 t^2 + c3 t^3 + c4 t^4,
+//   c0 = d.d, c1 = 2 d.w, c2 = w.w + d.b, c3 = w.b, c4 = b.b / 4.
+//
+// Three kernels, all on the ctx stream:
+//   sep_prep_kernel    [N][K][D] pos / vel / acc -> one time-major record per (k, vehicle): pos, vel, acc and the vehicle's
+//                      REACH rho = h |v| + h^2/2 |a| (how far it can be from its sample within the segment);
+//   sep_pass_kernel    one workgroup = one 64 x 64 tile of the (i, j) triangle over a chunk of time steps.  Tiles, not the
+//                      N-wide k-slices of the sampled passes: the LDS footprint (128 records) does not depend on N.
+//                      Phase A (every segment, ~10 fp64 operations): sampled distance, and ONE conservative comparison
+//                      |d| > (T + rho_i + rho_j)(1 + 3e-6): such a segment stays above T = max(R - 0.01, an upper bound of the
+//                      minimum that is already known), so it is neither a violation nor the argmin and is dropped.  The
+//                      others are queued in LDS.  Phase B (the queue, dense over the threads -- no wave runs the solve for
+//                      one near lane and 63 idle ones): the quartic's minimum over [0, h];
+//   sep_finish_kernel  the per-workgroup partials -> scp_separation_stats.
+// Every reduction is a minimum of (value, row id) pairs or an integer sum: exact and commutative, so the result depends
+// neither on scheduling nor on how the pair range was cut.
+#include "scp_common.h"
+#include "scp_pair_device.h"
+
+namespace {
+
+constexpr int SEP_THREADS = 256;
+constexpr int SEP_TILE = 64;                               // vehicles per tile side: j = lane, i = wave + 4 s
+constexpr int SEP_STEPS = SEP_TILE * SEP_TILE / SEP_THREADS;  // 16 pairs per thread and time step
+constexpr double SEP_SKIP_FACTOR = 1.0 + 7e-6;             // on squared distances: (1 + 3e-6)^2 rounded up (derivation below)
+constexpr double SEP_INF = __builtin_huge_val();
+constexpr unsigned long long SEP_NO_ROW = 0xFFFFFFFFFFFFFFFFULL;
+
+// Per-workgroup partial result; the finishing kernel folds them in any order.
+struct SepPartial {
+  double m;                      // smallest segment minimum of f (may be slightly negative where vehicles cross), +inf: none
+  unsigned long long row;        // its row id; ties: the smallest
+  double t;                      // where in the segment
+  unsigned long long first;      // smallest violating row id
+  unsigned long long n_viol;     // violating segments
+  double sample;                 // smallest sampled distance, as pair_geom computes it (= scp_check_avoidance's)
+  unsigned long long n_solved;   // segments that reached the quartic (reported by tools/separation_times.py)
+  unsigned long long pad;
+};
+
+struct SepArgs {
+  int N, K, D, kc;               // kc: time steps per workgroup
+  double h, thr;                 // thr = R - 0.01 (scp.py:610)
+  int64_t q_begin, q_end, pairs;
+  const double* rec;             // [K][N][3 D + 1]
+  SepPartial* part;              // [gridDim.y][gridDim.x]
+  int64_t tile0;                 // index of the first tile of this launch in the upper triangle (diagonal included) of tiles
+  int nt;                        // tiles per side
+};
+
+__global__ __launch_bounds__(256) void sep_prep_kernel(int N, int K, int D, double h, const double* __restrict__ pos,
+                                                        const double* __restrict__ vel, const double* __restrict__ acc,
+                                                        double* __restrict__ rec) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (k, i): one record
+  if (t >= (int64_t)N * K) return;
+  const int k = (int)(t / N), i = (int)(t % N);
+  const int64_t src = ((int64_t)i * K + k) * D;
+  double* o = rec + t * (3 * D + 1);
+  double vv = 0.0, aa = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double p = pos[src + d], v = vel[src + d], a = acc[src + d];
+    o[d] = p;
+    o[D + d] = v;
+    o[2 * D + d] = a;
+    vv = fma(v, v, vv);
+    aa = fma(a, a, aa);
+  }
+  // an upper bound of h |v| + h^2/2 |a| (the roundings of the sums, roots and products stay far below the 3e-6 of the test)
+  o[3 * D] = (h * sqrt(vv) + (0.5 * h * h) * sqrt(aa)) * (1.0 + 1e-12);
+}
+
+__device__ inline double wave_min_f64(double v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v = fmin(v, __shfl_xor(v, s, 64));
+  return v;
+}
+
+// tile index u in the upper triangle (diagonal included) of an nt x nt grid, row major -> (ti, tj), ti <= tj
+__device__ inline void decode_tile(int64_t u, int nt, int& ti, int& tj) {
+  const double b = 2.0 * nt + 1.0;
+  int64_t r = (int64_t)((b - sqrt(b * b - 8.0 * (double)u)) * 0.5);
+  if (r < 0) r = 0;
+  if (r > nt - 1) r = nt - 1;
+  auto start = [nt](int64_t x) { return x * nt - x * (x - 1) / 2; };
+  while (start(r) > u) --r;
+  while (r < nt - 1 && start(r + 1) <= u) ++r;
+  ti = (int)r;
+  tj = (int)(u - start(r) + r);
+}
+
+struct Quartic {
+  double c0, c1, c2, c3, c4;
+  __device__ double f(double t) const { return fma(t, fma(t, fma(t, fma(t, c4, c3), c2), c1), c0); }
+  __device__ double g(double t) const { return fma(t, fma(t, fma(t, 4.0 * c4, 3.0 * c3), 2.0 * c2), c1); }  // f'
+};
+
+// Minimum of the quartic over [0, h] and where.  Candidates: 0 (f = c0, the sampled value exactly), h, the stationary
+// points of f' inside (0, h) -- they split [0, h] into at most three pieces on which f' is monotone --, and in every piece
+// over which f' goes from negative to positive the root of f' by bisection (48 halvings: to 4e-15 h; f' = 0 there, so the
+// value of f is exact to second order).  No case is special: b = 0 makes f' linear (no split points), b = w = 0 makes f
+// constant (no sign change), a double root of f' is a split point and hence a candidate itself.  Strict comparisons: a
+// constant f reports t = 0.
+__device__ inline void quartic_min(const Quartic& q, double h, double& m_out, double& t_out) {
+  double m = q.c0, tm = 0.0;
+  auto offer = [&](double t) {
+    const double v = q.f(t);
+    if (v < m) {
+      m = v;
+      tm = t;
+    }
+  };
+  offer(h);
+  // f''(t) / 2 = c2 + 3 c3 t + 6 c4 t^2
+  double s1 = -1.0, s2 = -1.0;  // split points (outside (0, h): none)
+  const double qa = 6.0 * q.c4, qb = 3.0 * q.c3, qc = q.c2;
+  if (qa != 0.0) {
+    const double disc = fma(qb, qb, -4.0 * qa * qc);
+    if (disc > 0.0) {
+      const double qd = -0.5 * (qb + copysign(sqrt(disc), qb));
+      s1 = qd / qa;
+      s2 = qc / qd;
+    }
+  } else if (qb != 0.0) {
+    s1 = -qc / qb;
+  }
+  if (!(s1 > 0.0 && s1 < h)) s1 = -1.0;
+  if (!(s2 > 0.0 && s2 < h)) s2 = -1.0;
+  if (s1 < 0.0 || (s2 >= 0.0 && s2 < s1)) {
+    const double x = s1;
+    s1 = s2;
+    s2 = x;
+  }
+  // now: s1 <= s2 where both exist, s1 exists if any does.  Pieces [0, pa], [pa, pb], [pb, h]; an empty one has no sign change
+  const double pa = s1 >= 0.0 ? s1 : 0.0, pb = s2 >= 0.0 ? s2 : pa;
+  if (s1 >= 0.0) offer(s1);
+  if (s2 >= 0.0) offer(s2);
+#pragma nounroll
+  for (int e = 0; e < 3; ++e) {
+    double lo = e == 0 ? 0.0 : (e == 1 ? pa : pb), hi = e == 0 ? pa : (e == 1 ? pb : h);
+    if (q.g(lo) < 0.0 && q.g(hi) > 0.0) {
+      for (int it = 0; it < 48; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        if (q.g(mid) < 0.0) lo = mid;
+        else hi = mid;
+      }
+      offer(0.5 * (lo + hi));
+    }
+  }
+  m_out = m;
+  t_out = tm;
+}
+
+// (m, row) pairs order lexicographically; t rides along
+__device__ inline void fold_min(double& m, unsigned long long& row, double& t, double m2, unsigned long long row2, double t2) {
+  if (m2 < m || (m2 == m && row2 < row)) {
+    m = m2;
+    row = row2;
+    t = t2;
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
+  constexpr int NC = 3 * D + 1;
+  __shared__ double sm[NC][2 * SEP_TILE];            // component planes; [0, 64): the i side, [64, 128): the j side
+  __shared__ unsigned short queue[SEP_TILE * SEP_TILE];
+  __shared__ unsigned int q_count;
+  __shared__ SepPartial red[SEP_THREADS / 64];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = a.N;
+  int ti, tj;
+  decode_tile(a.tile0 + blockIdx.x, a.nt, ti, tj);
+  const int i0 = ti * SEP_TILE, j0 = tj * SEP_TILE;
+  const int k_begin = blockIdx.y * a.kc, k_end = min(a.K, k_begin + a.kc);
+
+  double best_m = SEP_INF, best_t = 0.0, min_ss = SEP_INF, min_raw = SEP_INF;
+  unsigned long long best_row = SEP_NO_ROW, first = SEP_NO_ROW, n_viol = 0, n_solved = 0;
+
+  // the tile's pairs in [q_begin, q_end): rows of the triangle are contiguous in q, so the tile's own range decides
+  const int i_last = min(i0 + SEP_TILE, N - 1) - 1;  // last vehicle that can be an `i` (i < j <= N - 1)
+  const int j_lo = max(j0, i0 + 1), j_hi = min(j0 + SEP_TILE, N) - 1;
+  bool live = i_last >= i0 && j_hi >= j_lo && j_hi > i0;
+  if (live) {
+    const int64_t q_min = tri_off(i0, N) + (j_lo - i0 - 1);
+    const int64_t q_max = tri_off(i_last, N) + (j_hi - i_last - 1);
+    live = q_max >= a.q_begin && q_min < a.q_end;
+  }
+
+  if (live) {
+    // this thread's j (fixed) and its 16 i's: validity and row offset of each pair, once
+    const int j = j0 + lane;
+    unsigned int valid = 0;
+    for (int s = 0; s < SEP_STEPS; ++s) {
+      const int i = i0 + wave + 4 * s;
+      if (i < j && j < N) {
+        const int64_t q = tri_off(i, N) + (j - i - 1);
+        if (q >= a.q_begin && q < a.q_end) valid |= 1u << s;
+      }
+    }
+    // staging: 2 x 64 records of NC doubles, contiguous per side in the time-major array; vehicles beyond N - 1 repeat it
+    // (their pairs are not valid)
+    constexpr int PER_THREAD = (2 * SEP_TILE * NC + SEP_THREADS - 1) / SEP_THREADS;
+    double pre[PER_THREAD];
+    auto fetch = [&](int k) {
+#pragma unroll
+      for (int e = 0; e < PER_THREAD; ++e) {
+        const int x = tid + e * SEP_THREADS;
+        if (x < 2 * SEP_TILE * NC) {
+          const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
+          const int v = min((side ? j0 : i0) + y / NC, N - 1);
+          pre[e] = a.rec[((int64_t)k * N + v) * NC + y % NC];
+        }
+      }
+    };
+    auto stash = [&]() {
+#pragma unroll
+      for (int e = 0; e < PER_THREAD; ++e) {
+        const int x = tid + e * SEP_THREADS;
+        if (x < 2 * SEP_TILE * NC) {
+          const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
+          sm[y % NC][side * SEP_TILE + y / NC] = pre[e];
+        }
+      }
+    };
+    double ub = SEP_INF;  // an upper bound of this call's minimum distance: the smallest sampled distance this wave has seen
+    fetch(k_begin);
+    for (int k = k_begin; k < k_end; ++k) {
+      __syncthreads();  // (the previous step's phase B has read sm and the queue)
+      stash();
+      if (tid == 0) q_count = 0;
+      __syncthreads();
+      if (k + 1 < k_end) fetch(k + 1);  // in flight during this step's arithmetic
+
+      // ---- phase A ------------------------------------------------------------------------------------------------
+      double pj[D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) pj[d] = sm[d][SEP_TILE + lane];
+      const double rho_j = sm[3 * D][SEP_TILE + lane];
+      double ss[SEP_STEPS];
+      double ss_min = SEP_INF;
+#pragma unroll
+      for (int s = 0; s < SEP_STEPS; ++s) {
+        const int il = wave + 4 * s;
+        double acc_ss = 0.0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          const double df = sm[d][il] - pj[d];  // the operands and the order of pair_geom: the same bits
+          acc_ss = fma(df, df, acc_ss);
+        }
+        ss[s] = (valid >> s) & 1u ? acc_ss : SEP_INF;
+        ss_min = fmin(ss_min, ss[s]);
+      }
+      // sampled minimum, bit for bit scp_check_avoidance's: pair_geom's distance is within an ulp of sqrt(ss), so only a
+      // pair whose ss is within 1e-12 of the smallest one seen can carry a smaller distance -- it alone pays for pair_geom
+      if (ss_min <= min_ss * (1.0 + 1e-12)) {
+#pragma unroll
+        for (int s = 0; s < SEP_STEPS; ++s)
+          if (((valid >> s) & 1u) && ss[s] <= min_ss * (1.0 + 1e-12)) {
+            Pt<D> Pi, Pj;
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+              Pi.v[d] = sm[d][wave + 4 * s];
+              Pj.v[d] = pj[d];
+            }
+            min_raw = fmin(min_raw, pair_geom<D>(Pi, Pj).raw);
+          }
+        min_ss = fmin(min_ss, ss_min);
+      }
+      // The skip test.  L = |d| - rho_i - rho_j bounds the segment's distance from below, S = |d| + rho_i + rho_j bounds
+      // every term of f.  Skipping needs the COMPUTED minimum of f above T^2, and the evaluation of f errs by a few eps S^2:
+      // L >= T (1 + 1e-6) + 1e-6 S gives L^2 >= T^2 + 1e-12 S^2, four orders above that error.  Rearranged:
+      // |d| >= (T + rho) (1 + 1e-6) / (1 - 1e-6); tested as d.d > (T + rho)^2 (1 + 7e-6).  T >= this wave's smallest sampled
+      // distance >= the call's minimum, so a skipped segment is strictly above the minimum: never the argmin, not even tied.
+      ub = fmin(ub, sqrt(wave_min_f64(ss_min)) * (1.0 + 1e-15));
+      const double T = fmax(a.thr, ub);
+#pragma unroll
+      for (int s = 0; s < SEP_STEPS; ++s) {
+        const double reach = T + (sm[3 * D][wave + 4 * s] + rho_j);
+        if (((valid >> s) & 1u) && !(ss[s] > reach * reach * SEP_SKIP_FACTOR)) {
+          const unsigned int slot = atomicAdd(&q_count, 1u);
+          queue[slot] = (unsigned short)(((wave + 4 * s) << 6) | lane);
+        }
+      }
+      __syncthreads();
+
+      // ---- phase B: the queued segments, dense over the threads (the queue's order does not matter: exact reductions) ----
+      const unsigned int n_q = q_count;
+      for (unsigned int e = tid; e < n_q; e += SEP_THREADS) {
+        const int il = queue[e] >> 6, jl = queue[e] & 63;
+        const int i = i0 + il, jj = j0 + jl;
+        double dd = 0.0, dw = 0.0, db = 0.0, ww = 0.0, wb = 0.0, bb = 0.0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          const double dx = sm[d][il] - sm[d][SEP_TILE + jl];
+          const double wx = sm[D + d][il] - sm[D + d][SEP_TILE + jl];
+          const double bx = sm[2 * D + d][il] - sm[2 * D + d][SEP_TILE + jl];
+          dd = fma(dx, dx, dd);
+          dw = fma(dx, wx, dw);
+          db = fma(dx, bx, db);
+          ww = fma(wx, wx, ww);
+          wb = fma(wx, bx, wb);
+          bb = fma(bx, bx, bb);
+        }
+        const Quartic q{dd, 2.0 * dw, ww + db, wb, 0.25 * bb};
+        double m, t;
+        quartic_min(q, a.h, m, t);
+        const unsigned long long row =
+            (unsigned long long)((int64_t)k * a.pairs + tri_off(i, N) + (jj - i - 1));
+        fold_min(best_m, best_row, best_t, m, row, t);
+        if (sqrt(fmax(m, 0.0)) < a.thr) {
+          ++n_viol;
+          first = row < first ? row : first;
+        }
+        ++n_solved;
+      }
+    }
+  }
+
+  // ---- workgroup reduction: wave shuffles, then the four wave results through LDS ---------------------------------------
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    const double m2 = __shfl_xor(best_m, s, 64), t2 = __shfl_xor(best_t, s, 64);
+    const unsigned long long r2 = __shfl_xor(best_row, s, 64);
+    fold_min(best_m, best_row, best_t, m2, r2, t2);
+    const unsigned long long f2 = __shfl_xor(first, s, 64);
+    first = f2 < first ? f2 : first;
+    n_viol += __shfl_xor(n_viol, s, 64);
+    n_solved += __shfl_xor(n_solved, s, 64);
+    min_raw = fmin(min_raw, __shfl_xor(min_raw, s, 64));
+  }
+  if (lane == 0) red[wave] = SepPartial{best_m, best_row, best_t, first, n_viol, min_raw, n_solved, 0};
+  __syncthreads();
+  if (tid == 0) {
+    SepPartial p = red[0];
+    for (int w = 1; w < SEP_THREADS / 64; ++w) {
+      fold_min(p.m, p.row, p.t, red[w].m, red[w].row, red[w].t);
+      p.first = red[w].first < p.first ? red[w].first : p.first;
+      p.n_viol += red[w].n_viol;
+      p.n_solved += red[w].n_solved;
+      p.sample = fmin(p.sample, red[w].sample);
+    }
+    a.part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = p;
+  }
+}
+
+// one workgroup: fold the partials (any order gives the same result) and write the stats
+__global__ __launch_bounds__(SEP_THREADS) void sep_finish_kernel(const SepPartial* __restrict__ part, int64_t n,
+                                                                 scp_separation_stats* __restrict__ stats,
+                                                                 unsigned long long* __restrict__ n_solved_out) {
+  __shared__ SepPartial red[SEP_THREADS];
+  SepPartial p{SEP_INF, SEP_NO_ROW, 0.0, SEP_NO_ROW, 0, SEP_INF, 0, 0};
+  for (int64_t e = threadIdx.x; e < n; e += SEP_THREADS) {
+    const SepPartial o = part[e];
+    fold_min(p.m, p.row, p.t, o.m, o.row, o.t);
+    p.first = o.first < p.first ? o.first : p.first;
+    p.n_viol += o.n_viol;
+    p.n_solved += o.n_solved;
+    p.sample = fmin(p.sample, o.sample);
+  }
+  red[threadIdx.x] = p;
+  __syncthreads();
+  for (int s = SEP_THREADS / 2; s >= 1; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      SepPartial& x = red[threadIdx.x];
+      const SepPartial& o = red[threadIdx.x + s];
+      fold_min(x.m, x.row, x.t, o.m, o.row, o.t);
+      x.first = o.first < x.first ? o.first : x.first;
+      x.n_viol += o.n_viol;
+      x.n_solved += o.n_solved;
+      x.sample = fmin(x.sample, o.sample);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const SepPartial& r = red[0];
+    // an empty pair range: the values scp_check_avoidance leaves (min_dist = +inf, no violation)
+    stats->min_dist = r.row == SEP_NO_ROW ? SEP_INF : sqrt(fmax(r.m, 0.0));  // crossing vehicles: f a few ulps below 0
+    stats->sample_min_dist = r.sample;
+    stats->argmin_t = r.t;
+    stats->argmin_row = r.row;
+    stats->first_violation = r.first;
+    stats->n_violating = r.n_viol;
+    *n_solved_out = r.n_solved;
+  }
+}
+
+int ensure_sep_ws(scp_ctx* ctx, size_t bytes) {
+  if (ctx->sep_ws_bytes >= bytes) return SCP_OK;
+  if (ctx->sep_ws) {
+    SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    SCP_HIP_CHECK(ctx, hipFree(ctx->sep_ws));
+    ctx->sep_ws = nullptr;
+    ctx->sep_ws_bytes = 0;
+  }
+  SCP_HIP_CHECK(ctx, hipMalloc(&ctx->sep_ws, bytes));
+  ctx->sep_ws_bytes = bytes;
+  return SCP_OK;
+}
+
+int64_t tile_start(int64_t r, int64_t nt) { return r * nt - r * (r - 1) / 2; }
+
+}  // namespace
+
+extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                                    const double* pos, const double* vel, const double* acc, scp_separation_stats* stats) {
+  if (!ctx) return SCP_ERR_INVALID;
+  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, pos && vel && acc && stats, "check_separation: null pointer");
+  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "check_separation: bad time step h=%g", h);
+  const int NC = 3 * D + 1;
+  const int nt = scp_cdiv(N, SEP_TILE);
+  // the tile rows that hold the pair range: vehicle rows i_lo .. i_hi of the triangle
+  int64_t n_tiles = 0, tile0 = 0;
+  if (q_end > q_begin) {
+    auto row_of = [N](int64_t q) {
+      int64_t lo = 0, hi = N - 2;  // largest i with tri_off(i) <= q
+      while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (tri_off(mid, N) <= q) lo = mid;
+        else hi = mid - 1;
+      }
+      return lo;
+    };
+    const int64_t t_lo = row_of(q_begin) / SEP_TILE, t_hi = row_of(q_end - 1) / SEP_TILE;
+    tile0 = tile_start(t_lo, nt);
+    n_tiles = tile_start(t_hi + 1, nt) - tile0;
+  }
+  SCP_REQUIRE(ctx, n_tiles < ((int64_t)1 << 31), "check_separation: %lld tiles exceed grid.x; shard the pair range",
+              (long long)n_tiles);
+  // time steps per workgroup: as many as still leave ~8 workgroups per compute unit (the records of a step are staged once per
+  // workgroup and step, so longer chunks only save the per-workgroup reduction)
+  int kc = K;
+  if (n_tiles > 0) {
+    const int64_t want = 8 * (int64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
+    const int64_t chunks = std::min<int64_t>(K, std::max<int64_t>(1, (want + n_tiles - 1) / n_tiles));
+    kc = scp_cdiv(K, chunks);
+  }
+  const int n_chunks = scp_cdiv(K, kc);
+  const int64_t n_part = n_tiles * n_chunks;
+  const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
+  rc = ensure_sep_ws(ctx, rec_bytes + (size_t)std::max<int64_t>(n_part, 1) * sizeof(SepPartial) + 64);
+  if (rc) return rc;
+  double* rec = (double*)ctx->sep_ws;
+  SepPartial* part = (SepPartial*)((char*)ctx->sep_ws + rec_bytes);
+  unsigned long long* n_solved = (unsigned long long*)(part + std::max<int64_t>(n_part, 1));
+
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
+  if (n_part > 0) {
+    hipLaunchKernelGGL(sep_prep_kernel, dim3(scp_cdiv((int64_t)N * K, 256)), dim3(256), 0, ctx->stream, N, K, D, h, pos, vel,
+                       acc, rec);
+    SepArgs a{};
+    a.N = N; a.K = K; a.D = D; a.kc = kc;
+    a.h = h; a.thr = R - 0.01;
+    a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
+    a.rec = rec; a.part = part; a.tile0 = tile0; a.nt = nt;
+    const dim3 grid((unsigned)n_tiles, (unsigned)n_chunks);
+    if (D == 2) hipLaunchKernelGGL(sep_pass_kernel<2>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(sep_pass_kernel<3>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
+    SCP_HIP_CHECK(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(sep_finish_kernel, dim3(1), dim3(SEP_THREADS), 0, ctx->stream, part, n_part, stats, n_solved);
+  SCP_HIP_CHECK(ctx, hipGetLastError());
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
+  ctx->pair_timed = ctx->timing != 0;
+  ctx->pair_ran = true;
+  ctx->sep_n_solved = n_solved;
+  return SCP_OK;
+}
+
+// segments of the latest scp_check_separation of this ctx that reached the quartic (developer figure; synchronises)
+extern "C" int scp_ctx_last_separation_solved(scp_ctx* ctx, uint64_t* n) {
+  if (!ctx || !n) return SCP_ERR_INVALID;
+  SCP_REQUIRE(ctx, ctx->sep_n_solved, "check_separation has not run yet");
+  SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  SCP_HIP_CHECK(ctx, hipMemcpy(n, ctx->sep_n_solved, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return SCP_OK;
+}

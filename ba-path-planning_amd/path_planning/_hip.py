@@ -140,12 +140,21 @@ GEN_STATS_DTYPE = np.dtype([("sweeps", np.int32), ("unmet_blocks", np.int32), ("
                             ("min_approach", np.float64), ("ok", np.int32), ("reserved", np.int32)])
 
 
-ABI_VERSION = 6  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
+class SeparationStats(C.Structure):
+    """struct scp_separation_stats (scp_check_separation)"""
+    _fields_ = [("min_dist", C.c_double), ("sample_min_dist", C.c_double), ("argmin_t", C.c_double),
+                ("argmin_row", C.c_uint64), ("first_violation", C.c_uint64), ("n_violating", C.c_uint64)]
+
+
+NO_ROW = 2**64 - 1  # UINT64_MAX: "no such row" in the stats of the pairwise passes
+
+ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
 
 EXPORTS = [
     "scp_set_host_wait", "scp_abi_version", "scp_ctx_create", "scp_ctx_destroy", "scp_last_error", "scp_ctx_synchronize",
     "scp_ctx_last_pair_ms", "scp_ctx_set_option",
     "scp_kinematics", "scp_fixed_bounds", "scp_linearize_pairs", "scp_select_pairs", "scp_check_avoidance", "scp_qp_add_rows_at",
+    "scp_check_separation", "scp_ctx_last_separation_solved",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
     "scp_qp_reset", "scp_qp_set_rho", "scp_qp_add_rows", "scp_qp_solve", "scp_qp_clone_state", "scp_qp_get_solution",
@@ -197,6 +206,8 @@ def load_library():
     lib.scp_linearize_pairs.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_select_pairs.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, f64, vp, i64, vp, vp]
     lib.scp_check_avoidance.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp]
+    lib.scp_check_separation.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp]
+    lib.scp_ctx_last_separation_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_collision_violations_at.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_gather_rows.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]
@@ -368,6 +379,24 @@ class Context:
         self.check(self.lib.scp_check_avoidance(self.h, N, K, D, R, q_begin, q_end, pos.data_ptr(),
                                                 self.stats.data_ptr()))
         return self.read_stats()
+
+    def check_separation(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None):
+        """scp_check_separation over the pair range [q_begin, q_end): the continuous-time minimum distance of the trajectories
+        pos / vel / acc ([N][K][D] device tensors).  Returns the stats as a dictionary -- synchronises."""
+        torch = _torch()
+        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        if getattr(self, "sep_stats", None) is None:
+            self.sep_stats = torch.zeros(C.sizeof(SeparationStats) // 8, dtype=torch.float64, device=self.tdev)
+        self.check(self.lib.scp_check_separation(self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(),
+                                                 acc.data_ptr(), self.sep_stats.data_ptr()))
+        st = SeparationStats.from_buffer_copy(self.sep_stats.cpu().numpy().tobytes())
+        return {f: getattr(st, f) for f, _ in SeparationStats._fields_}
+
+    def last_separation_solved(self):
+        """segments of the latest check_separation that needed the quartic's minimum (the rest: one comparison)"""
+        n = C.c_uint64()
+        self.check(self.lib.scp_ctx_last_separation_solved(self.h, C.byref(n)))
+        return int(n.value)
 
     def rel_step(self, a_new, a_prev):
         out = (C.c_double * 3)()

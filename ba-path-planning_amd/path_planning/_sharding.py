@@ -193,6 +193,26 @@ class Shard:
         dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
         return int(t.item())
 
+    def all_sum_int(self, value: int) -> int:
+        """sum over ranks of a non-negative integer (counts of violating segments; the sum must stay below 2^63)."""
+        if self.alone:
+            return int(value)
+        t = torch.tensor([int(value)], dtype=torch.int64, device=self._dev())
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return int(t.item())
+
+    def all_argmin(self, value: float, row: int, extra: float):
+        """The smallest (value, row) pair over the ranks, in lexicographic order, and the `extra` of the rank that holds it
+        (the continuous-time check: minimum distance, its row id and the time within the segment).  Three exact reductions;
+        row ids are unique over the ranks' pair ranges, so exactly one rank supplies `extra`."""
+        if self.alone:
+            return value, int(row), extra
+        best = self.all_min(value)
+        none = (1 << 63) - 1
+        best_row = self.all_min_int(int(row) if value == best else none)
+        mine = value == best and min(int(row), none) == best_row
+        return best, best_row, self.all_min(extra if mine else float("inf"))
+
     def _dev(self):
         if dist.get_backend(self.group) == "nccl":
             return torch.device("cuda", torch.cuda.current_device())

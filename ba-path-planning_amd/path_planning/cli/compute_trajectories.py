@@ -29,6 +29,9 @@ def build_parser():
                    help="one more joint QP at 1e-8 after the SCP loop: the result meets every constraint to ~1e-6")
     p.add_argument("--cg-iters", type=int, default=None,
                    help="PCG steps per ADMM step of the joint QP (scp_qp_settings.cg_iters; default 1)")
+    p.add_argument("--continuous-check", action="store_true",
+                   help="after the solve, print the minimum distance over the whole flight (between the samples too), "
+                        "the vehicles and the time of that closest approach")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -84,6 +87,15 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
+        if args.continuous_check:
+            rep = solver.validate_solution(continuous=True)
+            ca = rep["closest_approach"]
+            if ca is None:
+                print("Continuous-time check: no pair of vehicles")
+            else:
+                print(f"Continuous-time check: minimum distance {ca['distance']:.4f} m between vehicles {ca['vehicles'][0]} and "
+                      f"{ca['vehicles'][1]} at t = {ca['time']:.4f} s (at the samples: {rep['min_pair_distance']:.4f} m; "
+                      f"{rep['n_violating_segments']} segments below {min_distance - 0.01:.2f} m)")
 
         if not args.no_plots:
             pre = args.save_prefix

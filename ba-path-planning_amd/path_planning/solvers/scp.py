@@ -731,10 +731,15 @@ class SCP:
     # ------------------------------------------------------------------------------------------------
     # post-solve validation: one device pass over all pairs + the fixed rows on the host copy
     # ------------------------------------------------------------------------------------------------
-    def validate_solution(self):
+    def validate_solution(self, continuous=False):
         """Feasibility report of the stored trajectories: minimum pair distance over all stored samples and its
         first violation of R - 0.01 (device reduction, generalises scp.py:597-615), worst violation of every bound
-        the reference imposes (scp.py:182-257) and of the final-state equalities (state K)."""
+        the reference imposes (scp.py:182-257) and of the final-state equalities (state K).
+
+        continuous=True adds what the samples cannot show: ``min_pair_distance_continuous`` (minimum over every segment,
+        not only its end points), ``collision_free_continuous`` (no segment below R - 0.01), ``n_violating_segments``,
+        ``first_violation_continuous`` and ``closest_approach`` (each ``{"timestep", "time", "vehicles", "distance"}`` or
+        None)."""
         if self.trajectories is None:
             raise ValueError("Trajectories not generated yet")
         N, K, D, h = self.N, self.K, self.D, self.h
@@ -764,7 +769,35 @@ class SCP:
             i, j = pair_from_index(q, N)
             report["first_violation"] = {"timestep": int(k), "vehicles": (i, j),
                                          "distance": float(np.linalg.norm(p[i, k] - p[j, k]))}
+        if continuous:
+            report.update(self._continuous_separation(p, v, a, q0, q1))
         return report
+
+    def _continuous_separation(self, p, v, a, q0, q1):
+        """The continuous-time part of validate_solution: between two samples a vehicle flies p + t v + t^2/2 a (the
+        kinematics of the stored trajectories), so two vehicles can pass each other inside a segment while every sampled
+        distance is fine.  One device pass (scp_check_separation) over this rank's pair range, combined over the ranks."""
+        N, K, D, h = self.N, self.K, self.D, self.h
+        c = self._ctx
+        st = c.check_separation(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)
+        min_dist, row, t = self.shard.all_argmin(st["min_dist"], st["argmin_row"], st["argmin_t"])
+        first = self.shard.all_min_int(st["first_violation"])
+        n_viol = self.shard.all_sum_int(st["n_violating"])
+
+        def where(r):
+            k, q = divmod(int(r), self.shard.pairs)
+            return int(k), pair_from_index(q, N)
+
+        out = {"min_pair_distance_continuous": min_dist, "collision_free_continuous": n_viol == 0,
+               "n_violating_segments": n_viol, "first_violation_continuous": None, "closest_approach": None}
+        if self.shard.pairs and row < (1 << 63) - 1:
+            k, (i, j) = where(row)
+            out["closest_approach"] = {"timestep": k, "time": k * h + t, "vehicles": (i, j), "distance": min_dist}
+        if n_viol:
+            k, (i, j) = where(first)
+            m, t1 = segment_min_distance(p[i, k] - p[j, k], v[i, k] - v[j, k], a[i, k] - a[j, k], h)
+            out["first_violation_continuous"] = {"timestep": k, "time": k * h + t1, "vehicles": (i, j), "distance": m}
+        return out
 
     # ------------------------------------------------------------------------------------------------
     # visualisation passthroughs (scp.py:644-840): host-side matplotlib over the stored numpy trajectories
@@ -782,6 +815,23 @@ class SCP:
         from ..viz.plot_trajectories import plot_time_snapshots
 
         return plot_time_snapshots(self, num_snapshots=num_snapshots, save_path=save_path)
+
+
+def segment_min_distance(d, w, b, h):
+    """Minimum over t in [0, h] of ||d + t w + t^2/2 b|| for ONE pair and segment, and the t it is attained at (host helper
+    of validate_solution(continuous=True): the report's details for a row the device pass has already picked).  The squared
+    distance is a quartic; its minimum is at 0, at h or at a real root of its derivative inside (0, h)."""
+    d, w, b = (np.asarray(x, dtype=np.float64) for x in (d, w, b))
+    c = [d @ d, 2.0 * (d @ w), w @ w + d @ b, w @ b, 0.25 * (b @ b)]
+    f = lambda t: c[0] + t * (c[1] + t * (c[2] + t * (c[3] + t * c[4])))  # noqa: E731
+    cand = [0.0, float(h)]
+    der = np.trim_zeros([4.0 * c[4], 3.0 * c[3], 2.0 * c[2], c[1]], "f")
+    if len(der) > 1:
+        # the real part of every root, clipped: a point of [0, h] can only over-estimate the minimum, a real root is kept as it is
+        cand += [float(min(max(r.real, 0.0), h)) for r in np.roots(der)]
+    vals = [f(t) for t in cand]
+    m = int(np.argmin(vals))
+    return float(np.sqrt(max(vals[m], 0.0))), cand[m]
 
 
 def pair_from_index(q, N):

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SCP_ABI_VERSION 6
+#define SCP_ABI_VERSION 7
 
 typedef enum scp_status {
   SCP_OK = 0,
@@ -193,6 +193,29 @@ int scp_select_pairs(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begi
  * stats->first_violation = first row (k -> i -> j order) with ||p_i - p_j|| < R - 0.01, stats->min_dist. */
 int scp_check_avoidance(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begin, int64_t q_end,
                         const double* pos, scp_pair_stats* stats);
+
+/* ---- continuous-time separation: what a8 cannot see between two samples -------------------------------
+ * Over segment k (k = 0..K-1; the last one ends in the final state) vehicle i flies p_i[k] + t v_i[k] + t^2/2 a_i[k],
+ * t in [0, h] (the kinematics of scp_kinematics), so the squared distance of a pair is a quartic in t.  One pass over the
+ * K * (q_end - q_begin) segments; pos, vel, acc are [N][K][D] as scp_kinematics leaves them.  A segment's distance is
+ * sqrt(max(min over [0, h] of the quartic, 0)).  Rows are numbered as everywhere: k*pairs + q.  The result is deterministic and
+ * does not depend on how a pair range is cut: over shards, the smallest (min_dist, argmin_row), the smallest
+ * first_violation and the sum of n_violating are bit for bit those of the full range.  `stats` is DEVICE memory (48 bytes);
+ * an empty pair range leaves min_dist = sample_min_dist = +inf and no violation.  Argument checks, error codes and stream
+ * behaviour as scp_check_avoidance; scp_ctx_last_pair_ms then reports this call's kernels (staging, pass, final reduction). */
+typedef struct scp_separation_stats {
+  double min_dist;           /* smallest segment distance */
+  double sample_min_dist;    /* smallest distance at the samples (t = 0) of the same rows: scp_check_avoidance's min_dist, bitwise */
+  double argmin_t;           /* min_dist is attained argmin_t seconds into the segment ... */
+  uint64_t argmin_row;       /* ... of this row; bitwise equal minima: the smallest row id.  UINT64_MAX: empty pair range */
+  uint64_t first_violation;  /* smallest row id whose segment distance is < R - 0.01 (the a8 threshold), UINT64_MAX if none */
+  uint64_t n_violating;      /* number of such segments */
+} scp_separation_stats;
+int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                         const double* pos, const double* vel, const double* acc, scp_separation_stats* stats);
+/* Segments of the latest scp_check_separation of this ctx whose quartic was minimised (the others were excluded by one
+ * comparison: too far apart to be a violation or the minimum); a cost figure, results never depend on it.  Synchronises. */
+int scp_ctx_last_separation_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
 
 /* ---- constraint generation for the joint QP (a6): full pass over the linearised rows ------------------
  * For every local row not yet marked in sel_bitmap: if (A_col x)_r < l_r - feas_tol, mark it and append its

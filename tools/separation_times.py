@@ -1,0 +1,87 @@
+"""Device time of the continuous-time separation check (scp_check_separation) next to the sampled check
+(scp_check_avoidance) on the same trajectories, and the share of segments that reached the quartic.
+
+    python tools/separation_times.py [--reps 30] [--warmup 5]
+
+Shapes: 1024 x 50 x 2, 4096 x 50 x 2, 1024 x 50 x 3.  Data: (a) the grid-swap scenario of bench.py, solved trajectories
+(QP#0 + SCP iterations, max 15); (b) random kinematically consistent trajectories in a 20^D box (|v| <= 2, |a| <= 15 per
+axis).  Times are HIP events around each call's kernels (scp_ctx_last_pair_ms), the two passes alternating in one process:
+median, min and max over the repetitions after the warm-up."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "ba-path-planning_amd")):
+    sys.path.insert(0, p)
+
+
+def random_case(N, K, D, seed, h=0.2, side=20.0):
+    rng = np.random.default_rng(seed)
+    p0 = rng.uniform(0.0, side, (N, D))
+    v0 = rng.uniform(-2.0, 2.0, (N, D))
+    acc = np.empty((N, K, D))
+    v = v0.copy()
+    for k in range(K):
+        a = np.clip(rng.uniform(-15.0, 15.0, (N, D)), (-2.0 - v) / h, (2.0 - v) / h)
+        acc[:, k] = a
+        v = v + h * a
+    return p0, v0, acc
+
+
+def measure(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
+    t_sep, t_chk = [], []
+    for r in range(warmup + reps):
+        st = ctx.check_separation(N, K, D, h, R, pos, vel, acc)
+        a = ctx.last_pair_ms()
+        chk = ctx.check_avoidance(N, K, D, R, pos)
+        b = ctx.last_pair_ms()
+        if r >= warmup:
+            t_sep.append(a)
+            t_chk.append(b)
+    ctx.check_separation(N, K, D, h, R, pos, vel, acc)
+    solved = ctx.last_separation_solved()
+    seg = K * N * (N - 1) // 2
+    q = lambda x: (float(np.median(x)), float(np.min(x)), float(np.max(x)))  # noqa: E731
+    s, c = q(t_sep), q(t_chk)
+    print(f"{label:28s} {N:5d} x {K} x {D}  separation {s[0]*1e3:8.1f} us (min {s[1]*1e3:.1f}, max {s[2]*1e3:.1f})   "
+          f"sampled check {c[0]*1e3:8.1f} us (min {c[1]*1e3:.1f}, max {c[2]*1e3:.1f})   ratio {s[0]/c[0]:.2f}   "
+          f"quartic: {solved} of {seg} segments ({100.0*solved/seg:.3f} %)   min distance continuous {st['min_dist']:.4f} "
+          f"sampled {st['sample_min_dist']:.4f} violating {st['n_violating']}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--skip-solves", action="store_true")
+    args = ap.parse_args()
+    from path_planning import _hip
+    from path_planning.scenarios.position_generator import generate_grid_swap
+    from path_planning.solvers.scp import SCP
+
+    h, R, K = 0.2, 0.8, 50
+    ctx = _hip.Context(0)
+    for N, D in ((1024, 2), (4096, 2), (1024, 3)):
+        p0, v0, acc = random_case(N, K, D, 100 + N + D)
+        a = ctx.tensor(acc)
+        pos, vel = ctx.kinematics(N, K, D, h, a, ctx.tensor(p0), ctx.tensor(v0))
+        measure(ctx, N, K, D, h, R, pos, vel, a, args.reps, args.warmup, "random, 20^D box")
+        if args.skip_solves:
+            continue
+        g0, gf, space = generate_grid_swap(N, seed=1000 * N, dim=D)
+        s = SCP(N, K * h + 1e-9, h, R, space, dim=D, device=0, verbose=False)
+        s.set_initial_states(g0)
+        s.set_final_states(gf)
+        tr = s.generate_trajectories(max_iterations=15)
+        dev = [ctx.tensor(np.ascontiguousarray(tr[k])) for k in ("positions", "velocities", "accelerations")]
+        measure(ctx, N, K, D, h, R, *dev, args.reps, args.warmup,
+                f"grid-swap solved ({s.last_info['n_iterations']} it.)")
+        del s
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
