@@ -85,6 +85,10 @@ static inline int scp_fail(scp_ctx* ctx, int code, const char* fmt, ...) {
 static inline int64_t scp_pairs(int N) { return (int64_t)N * (N - 1) / 2; }
 static inline int scp_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// At least `need` bytes behind one of the ctx's grown-on-demand buffers (tm_scratch, cmp_map, ...): `buf` and `have` are
+// the addresses of its pointer and size fields.  Drains the ctx stream before it frees the old buffer.  (scp_ctx.hip)
+int scp_ctx_ensure_bytes(scp_ctx* ctx, void** buf, size_t* have, size_t need);
+
 // Raise a kernel's dynamic-LDS limit to at least `bytes` (gfx950: up to 160 KiB per workgroup).  The attribute belongs to
 // the (device, kernel) pair and is only ever raised, so concurrent solves of different sizes cannot lower each other's
 // limit.  Thread safe.
@@ -100,7 +104,7 @@ bool scp_wait_host_word(volatile unsigned long long* word, unsigned long long se
 int scp_check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end);
 
 // Stats of the latest scp_linearize_pairs / scp_collision_violations[_at] call of this ctx, from the host mirror: waits for
-// that pass's last kernel only (no stream drain, no copy launch).
+// that pass's last kernel only (no stream drain, no copy launch).  (scp_ctx.hip)
 int scp_ctx_wait_stats(scp_ctx* ctx, scp_pair_stats* out);
 
 // scp_qp_get_solution + scp_kinematics + scp_collision_violations_at of a small problem in one launch (scp_kernels.hip)
@@ -110,13 +114,14 @@ int scp_violations_from_solution(scp_ctx* ctx, int N, int K, int D, double R, do
                                  scp_pair_stats* stats, const double* rel_prev /* [N][K][D] or NULL */,
                                  int64_t* spec_rows /* or NULL: + the selection around the new positions */, int64_t spec_cap,
                                  uint32_t* spec_bitmap, double spec_margin, bool* fused);
-// scp_rel_step's numbers from the sums that pass left in the mirror (after its stats have arrived)
+// scp_rel_step's numbers from the sums that pass left in the mirror (after its stats have arrived)  (scp_ctx.hip)
 void scp_ctx_mirror_rel(scp_ctx* ctx, int64_t n, double* out);
 // scp_qp_get_solution + scp_kinematics + scp_check_avoidance + scp_select_pairs of a small problem in one launch
 int scp_select_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end,
                              const double* x_tm, const double* p0, const double* v0, double* x_out, double* pos_out,
                              double margin, int64_t* sel_rows, int64_t sel_cap, uint32_t* sel_bitmap, scp_pair_stats* stats,
                              bool* fused);
+// scp_kinematics + a copy of `acc` to acc_copy in the same launch (scp_traj.hip)
 int scp_launch_kinematics_copy(scp_ctx* ctx, int N, int K, int D, double h, const double* acc, const double* p0,
                                const double* v0, double* pos_out, double* vel_out, double* acc_copy);
 // the QP's current iterate in its own layout ([K][N D], device pointer)
@@ -135,14 +140,14 @@ int scp_launch_add_rows_at(scp_ctx* ctx, int N, int K, int D, int64_t base, int6
                            int64_t* w_row, int* wk, int* wi, int* wj, double* weta, double* wl, double* zc, double* yc);
 
 // ---- internal launchers (time-major device layout [K][C], C = N*D) --------------------------------
-// Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y   (row-major; A small and L2 resident)
+// Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y   (row-major; A small and L2 resident)  (scp_gemm.hip)
 int scp_launch_gemm(scp_ctx* ctx, int use_mfma, int R, int M, int C, double alpha, const double* A,
                     const double* X, double beta, double* Y);
-// [N][K][D] <-> [K][N*D]
+// [N][K][D] <-> [K][N*D]  (scp_traj.hip)
 int scp_launch_to_time_major(scp_ctx* ctx, int N, int K, int D, const double* src, double* dst);
 int scp_launch_from_time_major(scp_ctx* ctx, int N, int K, int D, const double* src, double* dst);
 // fixed-row bounds in time-major stacked layout: rows [0,K-1) jerk, [K-1,2K-1) acc, [2K-1,3K-1) vel,
-// [3K-1,4K-1) pos, each row C = N*D wide.
+// [3K-1,4K-1) pos, each row C = N*D wide.  (scp_traj.hip)
 int scp_launch_bounds_time_major(scp_ctx* ctx, int N, int K, int D, double h, const double* limits_host,
                                  const double* space_host, const double* p0, const double* v0,
                                  const double* pf, const double* vf, double* l_tm, double* u_tm,

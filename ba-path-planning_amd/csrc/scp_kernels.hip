@@ -1,443 +1,14 @@
-// Assembly half of the SCP hot path on gfx950: context, kinematics (a4/a7), fixed bounds (a2), the O(N^2 K)
-// pairwise passes (a5, a8, constraint generation) and the SCP relative step (a1).
-// Reference: /root/reference/src/path_planning/solvers/scp.py (line numbers cited per kernel).
+// The O(N^2 K) pairwise passes of the SCP hot path on gfx950 (a5, a8, constraint generation): their kernels, the bitmap
+// compaction that turns their marks into sorted row lists, and the one host path into them.
+// Reference: src/path_planning/solvers/scp.py (line numbers cited per kernel).
 #include "scp_common.h"
+#include "scp_compact_device.h"
 #include "scp_pair_device.h"
+#include "scp_traj_device.h"
+#include "scp_wave_device.h"
 
-#include <sys/prctl.h>
-#include <time.h>
-
-#include <atomic>
-#include <chrono>
-#include <cmath>
+#include <algorithm>
 #include <cstdlib>
-#include <map>
-#include <mutex>
-#include <type_traits>
-#include <utility>
-
-// ----------------------------------------------------------------------------------------------------
-// context
-// ----------------------------------------------------------------------------------------------------
-extern "C" int scp_abi_version(void) { return SCP_ABI_VERSION; }
-
-extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
-  if (!out) return SCP_ERR_INVALID;
-  *out = nullptr;
-  if (hipSetDevice(device) != hipSuccess) return SCP_ERR_HIP;
-  scp_ctx* ctx = new scp_ctx();
-  memset(ctx, 0, sizeof(*ctx));
-  ctx->device = device;
-  ctx->stream = (hipStream_t)hip_stream;
-  ctx->timing = 1;
-  ctx->small_pass = getenv("SCP_NO_SMALL_PASS") ? 0 : 1;  // (developer switch; scp_ctx_set_option at run time)
-  if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->n_cu = 0;
-  if (hipMalloc(&ctx->d_scratch, 72 * sizeof(double)) != hipSuccess ||
-      hipMemset(ctx->d_scratch, 0, 72 * sizeof(double)) != hipSuccess ||  // ([64]: ticket counter of scp_rel_step)
-      hipHostMalloc(&ctx->h_scratch, 72 * sizeof(double)) != hipSuccess ||
-      memset(ctx->h_scratch, 0, 72 * sizeof(double)) == nullptr ||        // ([64]: its completion word)
-      hipHostGetDevicePointer((void**)&ctx->h_scratch_dev, ctx->h_scratch, 0) != hipSuccess ||
-      hipHostMalloc(&ctx->h_mirror, sizeof(scp_stats_mirror)) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&ctx->d_mirror, ctx->h_mirror, 0) != hipSuccess ||
-      hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
-      hipEventCreate(&ctx->pair_ev0) != hipSuccess || hipEventCreate(&ctx->pair_ev1) != hipSuccess ||
-      hipMalloc(&ctx->wg_part, 4 * SCP_SMALL_MAX_WG * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc(&ctx->d_ticket, 64) != hipSuccess || hipMemset(ctx->d_ticket, 0, 64) != hipSuccess) {
-    delete ctx;
-    return SCP_ERR_HIP;
-  }
-  *out = ctx;
-  return SCP_OK;
-}
-
-// Per-context switches (include/scp_hip.h).  "kernel_timing": HIP events around every pairwise kernel and every QP solve
-// (two queue packets each) are what `linearize_ms`, `violations_ms` and `solve_ms` are read from; 0: none are recorded --
-// the pass times read 0, solve_ms becomes the host's wall clock around the solve (the host waits for its result anyway).
-// "single_launch_passes": the one-launch form of the pairwise passes of small problems (pair_pass_kernel<.., SMALL>); 0:
-// prep kernel + pass + compaction as for large problems (same results; tests compare the two).
-extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
-  if (!ctx || !key) return SCP_ERR_INVALID;
-  if (strcmp(key, "kernel_timing") == 0) {
-    ctx->timing = value ? 1 : 0;
-    if (!ctx->timing) ctx->pair_timed = false;
-    return SCP_OK;
-  }
-  if (strcmp(key, "single_launch_passes") == 0) {
-    ctx->small_pass = value ? 1 : 0;
-    return SCP_OK;
-  }
-  return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: unknown key '%s'", key);
-}
-
-extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
-  if (!ctx) return;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(ctx->d_scratch);
-  if (ctx->wg_part) (void)hipFree(ctx->wg_part);
-  if (ctx->wg_rows) (void)hipFree(ctx->wg_rows);
-  if (ctx->d_ticket) (void)hipFree(ctx->d_ticket);
-  if (ctx->cmp_map) (void)hipFree(ctx->cmp_map);
-  if (ctx->cmp_tot) (void)hipFree(ctx->cmp_tot);
-  if (ctx->tm_scratch) (void)hipFree(ctx->tm_scratch);
-  if (ctx->gen_ws) (void)hipFree(ctx->gen_ws);
-  if (ctx->sep_ws) (void)hipFree(ctx->sep_ws);
-  if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
-  (void)hipHostFree(ctx->h_scratch);
-  (void)hipHostFree(ctx->h_mirror);
-  (void)hipEventDestroy(ctx->ev0);
-  (void)hipEventDestroy(ctx->ev1);
-  (void)hipEventDestroy(ctx->pair_ev0);
-  (void)hipEventDestroy(ctx->pair_ev1);
-  delete ctx;
-}
-
-hipError_t scp_raise_lds_limit(int device, const void* kernel, size_t bytes) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, size_t> allowed;
-  std::lock_guard<std::mutex> lock(mu);
-  size_t& have = allowed[std::make_pair(device, kernel)];
-  if (have >= bytes) return hipSuccess;
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) have = bytes;
-  return e;
-}
-
-static std::atomic<int> g_host_wait_mode{0};
-
-extern "C" void scp_set_host_wait(int mode) {
-  g_host_wait_mode.store(mode == 1 || mode == 2 ? mode : 0, std::memory_order_relaxed);
-}
-
-bool scp_wait_host_word(volatile unsigned long long* word, unsigned long long seq, int timeout_s) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const int wait_mode = g_host_wait_mode.load(std::memory_order_relaxed);
-  const bool sleepy = wait_mode != 0;
-  const unsigned spin_first = wait_mode == 2 ? 0u : 2000u;  // mode 2: nap at once (more solver threads than cores)
-  if (sleepy) {
-    // the kernel's default timer slack (50 us) would stretch every 20 us nap to ~75 us -- a third of a 25-step persistent
-    // launch; 1 us of slack for this thread
-    static thread_local bool slack_set = false;
-    if (!slack_set) {
-      (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0UL, 0UL, 0UL);
-      slack_set = true;
-    }
-  }
-  unsigned spins = 0;
-  while (*word != seq) {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#endif
-    ++spins;
-    if (sleepy && spins > spin_first) {  // mode 1: ~20 us of spinning first: the kernel is a long one, give the core away
-      struct timespec ts = {0, 20000};
-      nanosleep(&ts, nullptr);
-      if ((spins & 0x3FF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(timeout_s)) break;
-    } else if ((spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(timeout_s)) {
-      break;
-    }
-  }
-  const bool ok = *word == seq;
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  return ok;
-}
-
-int scp_ctx_wait_stats(scp_ctx* ctx, scp_pair_stats* out) {
-  if (ctx->mirror_seq == 0) return scp_fail(ctx, SCP_ERR_STATE, "no pass with a row list has run yet");
-  if (!scp_wait_host_word(&ctx->h_mirror->seq, ctx->mirror_seq, 30)) {
-    SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // surfaces a launch failure, if that is why nothing arrived
-    if (ctx->h_mirror->seq != ctx->mirror_seq) return scp_fail(ctx, SCP_ERR_HIP, "pair pass: the stats mirror was not written");
-  }
-  *out = ctx->h_mirror->stats;
-  return SCP_OK;
-}
-
-// scp_rel_step's result from the partial sums the latest small-problem violations pass left in the mirror (call after
-// scp_ctx_wait_stats): the same sums in the same order as scp_rel_step's host side
-void scp_ctx_mirror_rel(scp_ctx* ctx, int64_t n, double* out) {
-  const int blocks = (int)((n + 256 * 8 - 1) / (256 * 8)) < 32 ? (int)((n + 256 * 8 - 1) / (256 * 8)) : 32;
-  double d2 = 0.0, b2 = 0.0;
-  for (int b = 0; b < blocks; ++b) {
-    d2 += ctx->h_mirror->rel[2 * b];
-    b2 += ctx->h_mirror->rel[2 * b + 1];
-  }
-  out[0] = std::sqrt(d2);
-  out[1] = std::sqrt(b2);
-  out[2] = out[0] / out[1];
-}
-
-extern "C" const char* scp_last_error(const scp_ctx* ctx) { return ctx ? ctx->err : "null context"; }
-
-extern "C" int scp_ctx_synchronize(scp_ctx* ctx) {
-  if (!ctx) return SCP_ERR_INVALID;
-  SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  return SCP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// layout changes [N][K][D] <-> [K][N*D]
-// ----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void to_time_major_kernel(int N, int K, int D, const double* __restrict__ src,
-                                                             double* __restrict__ dst) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;  // destination index (coalesced writes)
-  const int64_t C = (int64_t)N * D;
-  if (t >= C * K) return;
-  const int k = (int)(t / C);
-  const int c = (int)(t % C);
-  const int i = c / D, d = c % D;
-  dst[t] = src[((int64_t)i * K + k) * D + d];
-}
-
-__global__ __launch_bounds__(256) void from_time_major_kernel(int N, int K, int D, const double* __restrict__ src,
-                                                               double* __restrict__ dst) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;  // source index (coalesced reads)
-  const int64_t C = (int64_t)N * D;
-  if (t >= C * K) return;
-  const int k = (int)(t / C);
-  const int c = (int)(t % C);
-  const int i = c / D, d = c % D;
-  dst[((int64_t)i * K + k) * D + d] = src[t];
-}
-
-int scp_launch_to_time_major(scp_ctx* ctx, int N, int K, int D, const double* src, double* dst) {
-  const int64_t n = (int64_t)N * K * D;
-  hipLaunchKernelGGL(to_time_major_kernel, dim3(scp_cdiv(n, 256)), dim3(256), 0, ctx->stream, N, K, D, src, dst);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-int scp_launch_from_time_major(scp_ctx* ctx, int N, int K, int D, const double* src, double* dst) {
-  const int64_t n = (int64_t)N * K * D;
-  hipLaunchKernelGGL(from_time_major_kernel, dim3(scp_cdiv(n, 256)), dim3(256), 0, ctx->stream, N, K, D, src, dst);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// a4 / a7 kinematics (scp.py:371-397, :559-595).  One thread per output sample; the inner sum runs in the
-// reference's order with separately rounded multiply and add (no FMA) so the result is bitwise the
-// reference's.
-// ----------------------------------------------------------------------------------------------------
-// one term of scp_rel_step's two sums (scp.py:157-159): ONE definition for rel_step_partial_kernel and for the tail of the
-// small-problem violations pass, which emulates that kernel's blocks one after the other (same sums, same bits)
-__device__ inline void rel_accum(double x, double y, double& d2, double& b2) {
-  d2 += (x - y) * (x - y);
-  b2 += y * y;
-}
-__host__ __device__ inline int rel_step_blocks(int64_t n) {
-  const int b = (int)((n + 256 * 8 - 1) / (256 * 8));
-  return b < 32 ? b : 32;
-}
-
-// position (and velocity) of one coordinate at step k from its acceleration samples a[0], a[stride], ...: ONE definition for
-// the kinematics kernel and for the small-problem violations pass that derives its positions from the QP's time-major
-// solution itself (pair_pass_kernel<.., SMALL>), so that both produce the same bits
-__device__ inline void kin_point(const double* __restrict__ a, int64_t stride, int k, double h, double pi, double vi,
-                                 double& p_out, double& v_out) {
-#pragma clang fp contract(off)  // every product below is rounded before it is added, as numpy does
-  double v = vi;
-  const double hk = h * (double)k;
-  const double hkv = hk * vi;
-  double p = pi + hkv;  // p0 + (h*k)*v0   scp.py:393
-  const double hh = h * h;
-  constexpr int KIN_CHUNK = 32;  // loads in flight per pass; the sums stay in the reference's order
-  for (int j0 = 0; j0 < k; j0 += KIN_CHUNK) {
-    double av[KIN_CHUNK];
-#pragma unroll
-    for (int u = 0; u < KIN_CHUNK; ++u) av[u] = j0 + u < k ? a[(int64_t)(j0 + u) * stride] : 0.0;
-#pragma unroll
-    for (int u = 0; u < KIN_CHUNK; ++u) {
-      if (j0 + u < k) {
-        const int j = j0 + u;
-        const double aj = av[u];
-        const double hv = h * aj;
-        v = v + hv;  // scp.py:390
-        const double w = hh * ((double)(k - j) - 0.5);
-        const double wa = w * aj;
-        p = p + wa;  // scp.py:395
-      }
-    }
-  }
-  p_out = p;
-  v_out = v;
-}
-
-__global__ __launch_bounds__(256) void kinematics_kernel(int N, int K, int D, double h,
-                                                          const double* __restrict__ acc,
-                                                          const double* __restrict__ p0,
-                                                          const double* __restrict__ v0, double* __restrict__ pos,
-                                                          double* __restrict__ vel, double* __restrict__ acc_copy) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= (int64_t)N * K * D) return;
-  if (acc_copy) acc_copy[t] = acc[t];  // (the solver's final launch also hands the accelerations out: no copy launch)
-  const int d = (int)(t % D);
-  const int k = (int)((t / D) % K);
-  const int i = (int)(t / ((int64_t)D * K));
-  double p, v;
-  kin_point(acc + (int64_t)i * K * D + d, D, k, h, p0[i * D + d], v0[i * D + d], p, v);
-  pos[t] = p;
-  if (vel) vel[t] = v;
-}
-
-extern "C" int scp_kinematics(scp_ctx* ctx, int N, int K, int D, double h, const double* acc, const double* p0,
-                              const double* v0, double* pos_out, double* vel_out) {
-  if (!ctx) return SCP_ERR_INVALID;
-  SCP_REQUIRE(ctx, N > 0 && K > 0 && (D == 2 || D == 3), "kinematics: bad shape N=%d K=%d D=%d", N, K, D);
-  SCP_REQUIRE(ctx, acc && p0 && v0 && pos_out, "kinematics: null pointer");
-  const int64_t n = (int64_t)N * K * D;
-  hipLaunchKernelGGL(kinematics_kernel, dim3(scp_cdiv(n, 256)), dim3(256), 0, ctx->stream, N, K, D, h, acc, p0,
-                     v0, pos_out, vel_out, (double*)nullptr);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-// scp_kinematics + a copy of `acc` to acc_copy in the same launch (scp_common.h)
-int scp_launch_kinematics_copy(scp_ctx* ctx, int N, int K, int D, double h, const double* acc, const double* p0,
-                               const double* v0, double* pos_out, double* vel_out, double* acc_copy) {
-  const int64_t n = (int64_t)N * K * D;
-  hipLaunchKernelGGL(kinematics_kernel, dim3(scp_cdiv(n, 256)), dim3(256), 0, ctx->stream, N, K, D, h, acc, p0,
-                     v0, pos_out, vel_out, acc_copy);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// a2 bounds (scp.py:189-190, :194-195, :206-224, :234-257)
-// ----------------------------------------------------------------------------------------------------
-struct BoundParams {
-  double vel_min, vel_max, acc_min, acc_max, jerk_min, jerk_max;
-  double pmin[3], pmax[3];
-};
-
-__device__ inline void bound_of(const BoundParams& bp, int block, int i, int k, int d, int K, int D, double h,
-                                const double* p0, const double* v0, const double* pf, const double* vf,
-                                double& lo, double& hi) {
-#pragma clang fp contract(off)
-  const int s = i * D + d;
-  if (block == 0) {  // jerk
-    lo = bp.jerk_min;
-    hi = bp.jerk_max;
-  } else if (block == 1) {  // acc
-    lo = bp.acc_min;
-    hi = bp.acc_max;
-  } else if (block == 2) {  // vel: row k is the state k+1
-    if (k < K - 1) {
-      lo = bp.vel_min - v0[s];  // scp.py:218-221
-      hi = bp.vel_max - v0[s];
-    } else {
-      lo = hi = vf[s] - v0[s];  // scp.py:223-224
-    }
-  } else {  // pos
-    const double hk = h * (double)(k + 1);
-    const double hkv = hk * v0[s];
-    const double off = p0[s] + hkv;  // scp.py:246-247
-    if (k < K - 1) {
-      lo = bp.pmin[d] - off;  // scp.py:251-254
-      hi = bp.pmax[d] - off;
-    } else {
-      lo = hi = pf[s] - off;  // scp.py:256-257
-    }
-  }
-}
-
-// reference stacking order: [jerk (N,K-1,D) | acc (N,K,D) | vel | pos]
-__global__ __launch_bounds__(256) void bounds_ref_order_kernel(BoundParams bp, int N, int K, int D, double h,
-                                                                const double* p0, const double* v0,
-                                                                const double* pf, const double* vf,
-                                                                double* __restrict__ l, double* __restrict__ u) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t nj = (int64_t)N * (K - 1) * D, na = (int64_t)N * K * D;
-  if (t >= nj + 3 * na) return;
-  int block, i, k, d;
-  if (t < nj) {
-    block = 0;
-    d = (int)(t % D);
-    k = (int)((t / D) % (K - 1));
-    i = (int)(t / ((int64_t)D * (K - 1)));
-  } else {
-    const int64_t r = t - nj;
-    block = 1 + (int)(r / na);
-    const int64_t e = r % na;
-    d = (int)(e % D);
-    k = (int)((e / D) % K);
-    i = (int)(e / ((int64_t)D * K));
-  }
-  double lo, hi;
-  bound_of(bp, block, i, k, d, K, D, h, p0, v0, pf, vf, lo, hi);
-  l[t] = lo;
-  u[t] = hi;
-}
-
-// time-major stacked layout used by the QP: row = block offset + k, column c = i*D + d
-__global__ __launch_bounds__(256) void bounds_time_major_kernel(BoundParams bp, int N, int K, int D, double h,
-                                                                 const double* p0, const double* v0,
-                                                                 const double* pf, const double* vf,
-                                                                 double* __restrict__ l, double* __restrict__ u,
-                                                                 double* __restrict__ states_out) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t C = (int64_t)N * D;
-  const int rows = 4 * K - 1;
-  if (states_out && t < 4 * C) {  // the QP's own copy of [p0 | v0 | pf | vf] (lean persistent kernels), no copy launches
-    const int which = (int)(t / C);
-    const int64_t c = t - which * C;
-    states_out[t] = which == 0 ? p0[c] : (which == 1 ? v0[c] : (which == 2 ? pf[c] : vf[c]));
-  }
-  if (t >= C * rows) return;
-  const int row = (int)(t / C);
-  const int c = (int)(t % C);
-  int block, k;
-  if (row < K - 1) {
-    block = 0;
-    k = row;
-  } else {
-    block = 1 + (row - (K - 1)) / K;
-    k = (row - (K - 1)) % K;
-  }
-  double lo, hi;
-  bound_of(bp, block, c / D, k, c % D, K, D, h, p0, v0, pf, vf, lo, hi);
-  l[t] = lo;
-  u[t] = hi;
-}
-
-static void fill_bound_params(BoundParams& bp, int D, const double* limits, const double* space) {
-  bp.vel_min = limits[0];
-  bp.vel_max = limits[1];
-  bp.acc_min = limits[2];
-  bp.acc_max = limits[3];
-  bp.jerk_min = limits[4];
-  bp.jerk_max = limits[5];
-  for (int d = 0; d < 3; ++d) {
-    bp.pmin[d] = d < D ? space[d] : 0.0;
-    bp.pmax[d] = d < D ? space[D + d] : 0.0;
-  }
-}
-
-extern "C" int scp_fixed_bounds(scp_ctx* ctx, int N, int K, int D, double h, const double* limits,
-                                const double* space, const double* p0, const double* v0, const double* pf,
-                                const double* vf, double* l_out, double* u_out) {
-  if (!ctx) return SCP_ERR_INVALID;
-  SCP_REQUIRE(ctx, N > 0 && K > 1 && (D == 2 || D == 3), "fixed_bounds: bad shape N=%d K=%d D=%d", N, K, D);
-  SCP_REQUIRE(ctx, limits && space && p0 && v0 && pf && vf && l_out && u_out, "fixed_bounds: null pointer");
-  BoundParams bp;
-  fill_bound_params(bp, D, limits, space);
-  const int64_t m = (int64_t)N * D * (4 * K - 1);
-  hipLaunchKernelGGL(bounds_ref_order_kernel, dim3(scp_cdiv(m, 256)), dim3(256), 0, ctx->stream, bp, N, K, D, h,
-                     p0, v0, pf, vf, l_out, u_out);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-int scp_launch_bounds_time_major(scp_ctx* ctx, int N, int K, int D, double h, const double* limits,
-                                 const double* space, const double* p0, const double* v0, const double* pf,
-                                 const double* vf, double* l_tm, double* u_tm, double* states_out) {
-  BoundParams bp;
-  fill_bound_params(bp, D, limits, space);
-  const int64_t m = (int64_t)N * D * (4 * K - 1);  // (4K - 1 >= 4 rows: the grid covers the 4 N D states too)
-  hipLaunchKernelGGL(bounds_time_major_kernel, dim3(scp_cdiv(m, 256)), dim3(256), 0, ctx->stream, bp, N, K, D, h,
-                     p0, v0, pf, vf, l_tm, u_tm, states_out);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
 
 // ----------------------------------------------------------------------------------------------------
 // pairwise passes
@@ -448,57 +19,6 @@ __device__ inline void pair_stats_init(scp_pair_stats* s) {
   s->first_violation = 0xFFFFFFFFFFFFFFFFULL;
   s->n_selected = 0;
   s->max_violation = -__longlong_as_double(0x7FF0000000000000LL);
-}
-
-// Wavefront reductions on DPP moves (row_shr 1, 2, 4, 8, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows
-// 2, 3): result in LANE 63.  Lanes without a source keep their own value (idempotent operators only).  The
-// __shfl_xor butterfly goes through the LDS crossbar and costs about ten times as much.
-template <int CTRL, int ROW_MASK>
-__device__ inline unsigned long long dpp_self_u64(unsigned long long v) {
-  const int lo = (int)(v & 0xFFFFFFFFu), hi = (int)(v >> 32);
-  const unsigned int l2 = (unsigned int)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false);
-  const unsigned int h2 = (unsigned int)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false);
-  return ((unsigned long long)h2 << 32) | l2;
-}
-template <typename Op>
-__device__ inline unsigned long long wave_reduce_u64(unsigned long long v, Op op) {
-  v = op(v, dpp_self_u64<0x111, 0xF>(v));
-  v = op(v, dpp_self_u64<0x112, 0xF>(v));
-  v = op(v, dpp_self_u64<0x114, 0xF>(v));
-  v = op(v, dpp_self_u64<0x118, 0xF>(v));
-  v = op(v, dpp_self_u64<0x142, 0xA>(v));
-  v = op(v, dpp_self_u64<0x143, 0xC>(v));
-  return v;
-}
-__device__ inline double wave_min(double v) {
-  return __longlong_as_double((long long)wave_reduce_u64((unsigned long long)__double_as_longlong(v),
-      [](unsigned long long a, unsigned long long b) {
-        return (unsigned long long)__double_as_longlong(fmin(__longlong_as_double((long long)a), __longlong_as_double((long long)b)));
-      }));
-}
-__device__ inline double wave_max(double v) {
-  return __longlong_as_double((long long)wave_reduce_u64((unsigned long long)__double_as_longlong(v),
-      [](unsigned long long a, unsigned long long b) {
-        return (unsigned long long)__double_as_longlong(fmax(__longlong_as_double((long long)a), __longlong_as_double((long long)b)));
-      }));
-}
-__device__ inline unsigned long long wave_min_u64(unsigned long long v) {
-  return wave_reduce_u64(v, [](unsigned long long a, unsigned long long b) { return b < a ? b : a; });
-}
-
-// positive doubles compare like their bit patterns
-__device__ inline void atomic_min_pos_double(double* addr, double v) {
-  atomicMin((unsigned long long*)addr, (unsigned long long)__double_as_longlong(v));
-}
-__device__ inline void atomic_max_double(double* addr, double v) {
-  // general sign: CAS loop (rare: once per wave)
-  unsigned long long* a = (unsigned long long*)addr;
-  unsigned long long old = *a;
-  while (__longlong_as_double((long long)old) < v) {
-    const unsigned long long assumed = old;
-    old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(v));
-    if (old == assumed) break;
-  }
 }
 
 constexpr int PAIR_THREADS = 256;
@@ -516,7 +36,6 @@ constexpr int PAIR_LDS_SLICE_BYTES = 16 * 1024;            // largest slice of a
 constexpr int PAIR_LDS_Q_OFF = PAIR_LDS_SLICE_BYTES / 8;   // doubles between the P slice and the Q slice of a two-slice pass
 constexpr int SMALL_STEPS = 4;                             // ... of a small-problem pass: 2048 rows per workgroup, so that a
 constexpr int SMALL_ROWS = PAIR_THREADS * SMALL_STEPS * 2; // 128-agent problem still spreads over 200 compute units
-constexpr int64_t CMP1_MAX_WORDS = 64 * 1024;             // bitmap words (2 M rows) one workgroup compacts (compact_small_body)
 
 enum PairMode { MODE_LINEARIZE = 0, MODE_CHECK = 1, MODE_VIOLATIONS = 2, MODE_VIOL_RECOMPUTE = 3, MODE_SELECT = 4 };
 // MODE_SELECT: the linearisation pass WITHOUT its row stream (scp_select_pairs): the same distances, the same selection test
@@ -637,7 +156,6 @@ __device__ unsigned long long scp_small_clk[16];
 #define SMALL_STAMP(i) do { } while (0)
 #endif
 
-__device__ inline int block_exclusive_scan(int v, int* total);  // (256 threads; defined with the compaction kernels below)
 
 
 // SMALL (problems whose bitmap one workgroup compacts: <= 2 M rows, e.g. 128 agents x 50 steps): the pass is ONE launch.
@@ -1438,20 +956,6 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_pass_kernel(PairArgs a) {
 #endif
 }
 
-// scratch for the time-major slices (grown on demand, owned by the ctx)
-static int ensure_tm(scp_ctx* ctx, size_t bytes) {
-  if (ctx->tm_bytes >= bytes) return SCP_OK;
-  if (ctx->tm_scratch) {
-    SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    SCP_HIP_CHECK(ctx, hipFree(ctx->tm_scratch));
-    ctx->tm_scratch = nullptr;
-    ctx->tm_bytes = 0;
-  }
-  SCP_HIP_CHECK(ctx, hipMalloc(&ctx->tm_scratch, bytes));
-  ctx->tm_bytes = bytes;
-  return SCP_OK;
-}
-
 // [N][K][D] -> time-major P_prev and dP = P_new - P_prev (MODE_VIOL_RECOMPUTE)
 __global__ __launch_bounds__(256) void pair_prep_delta_kernel(int N, int K, int D, const double* __restrict__ pos_prev,
                                                                const double* __restrict__ pos_new,
@@ -1470,226 +974,9 @@ __global__ __launch_bounds__(256) void pair_prep_delta_kernel(int N, int K, int 
   dP_tm[t] = pos_new[g] - pp;
 }
 
-// What follows a pass: its marks become the sorted row list `rows` and are merged into (violations) / replace (select) the
-// working-set bitmap `merge_into`.  Small problems run it as the tail of the pass kernel itself (*done = true), the others
-// in launch_compaction afterwards.
-struct PassTail {
-  int64_t* rows;
-  int64_t cap;
-  uint32_t* merge_into;
-  bool overwrite;
-  int64_t words;
-  bool done;
-};
-
-// a pass over nq pairs x K steps that runs as ONE launch (pair_pass_kernel<.., SMALL>): its bitmap fits the one-workgroup
-// compaction, its time-step slices (n_slices of them) the LDS budget of the pass, its partials the ctx scratch
-static bool small_pass_ok(const scp_ctx* ctx, int N, int K, int D, int64_t nq, int n_slices) {
-  if (!ctx->small_pass || nq <= 0) return false;
-  const int64_t words = (K * nq + 31) / 32;
-  const int64_t n_wg = (int64_t)scp_cdiv(nq + 1, SMALL_ROWS) * K;
-  return words <= CMP1_MAX_WORDS && (size_t)n_slices * N * D * sizeof(double) <= 32 * 1024 && n_wg <= SCP_SMALL_MAX_WG;
-}
-
-// MODE_VIOL_RECOMPUTE: pos_ref_layout = the linearisation point, p0 = the new positions (v0 unused)
-template <int MODE>
-static int launch_pair_pass(scp_ctx* ctx, PairArgs& a, const double* pos_ref_layout, const double* p0,
-                            const double* v0, uint32_t* clear_map = nullptr, int64_t clear_words = 0,
-                            PassTail* tail = nullptr) {
-  const int N = a.N, K = a.K, D = a.D;
-  const int64_t nq = a.q_end - a.q_begin;
-  if (tail) tail->done = false;
-  if constexpr (MODE == MODE_SELECT || MODE == MODE_VIOL_RECOMPUTE || MODE == MODE_CHECK)
-  if (tail) {
-    const int n_slices = MODE == MODE_VIOL_RECOMPUTE ? (a.spec_rows ? 3 : 2) : 1;
-    const size_t lds_small = (size_t)n_slices * N * D * sizeof(double);
-    if (small_pass_ok(ctx, N, K, D, nq, n_slices)) {
-      a.pos_a = pos_ref_layout;
-      if (MODE == MODE_VIOL_RECOMPUTE && !a.x_tm) a.pos_b = p0;
-      if (MODE != MODE_CHECK) {  // per-workgroup sub-lists of the marked rows (grown on demand, owned by the ctx)
-        const size_t need = (size_t)(a.spec_rows ? 2 : 1) * scp_cdiv(nq + 1, SMALL_ROWS) * K * SMALL_ROWS * sizeof(uint32_t);
-        if (ctx->wg_rows_bytes < need) {
-          if (ctx->wg_rows) {
-            SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            SCP_HIP_CHECK(ctx, hipFree(ctx->wg_rows));
-            ctx->wg_rows = nullptr;
-            ctx->wg_rows_bytes = 0;
-          }
-          SCP_HIP_CHECK(ctx, hipMalloc(&ctx->wg_rows, need));
-          ctx->wg_rows_bytes = need;
-        }
-      }
-      a.wg_rows = ctx->wg_rows;
-      a.wg_part = ctx->wg_part;
-      a.ticket = ctx->d_ticket;
-      a.rows = tail->rows; a.cap = tail->cap; a.merge_into = tail->merge_into; a.overwrite = tail->overwrite ? 1 : 0;
-      a.words = tail->words;
-      a.mirror = ctx->d_mirror;
-      a.seq = ++ctx->mirror_seq;
-#ifdef SCP_PHASE_PROFILE
-      a.ablate = getenv("SCP_PAIR_ABLATE") ? atoi(getenv("SCP_PAIR_ABLATE")) : 0;
-#else
-      a.ablate = 0;
-#endif
-      dim3 grid(scp_cdiv(nq + 1, SMALL_ROWS), K);
-      if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
-      if (D == 2) hipLaunchKernelGGL((pair_pass_kernel<2, MODE, true, true>), grid, dim3(PAIR_THREADS), lds_small, ctx->stream, a);
-      else hipLaunchKernelGGL((pair_pass_kernel<3, MODE, true, true>), grid, dim3(PAIR_THREADS), lds_small, ctx->stream, a);
-      SCP_HIP_CHECK(ctx, hipGetLastError());
-      if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
-      ctx->pair_timed = ctx->timing != 0;
-      ctx->pair_ran = true;
-      tail->done = true;
-      ctx->last_pass_small = true;
-      return SCP_OK;
-    }
-  }
-  ctx->last_pass_small = false;
-  const size_t slice = ((size_t)N * K * D + 1) & ~(size_t)1;  // keep the second array 16-byte aligned
-  int rc = ensure_tm(ctx, 2 * slice * sizeof(double));
-  if (rc) return rc;
-  double* P_tm = MODE != MODE_VIOLATIONS ? ctx->tm_scratch : nullptr;
-  double* Q_tm = (MODE != MODE_CHECK && MODE != MODE_SELECT) ? ctx->tm_scratch + slice : nullptr;
-  if (MODE == MODE_VIOL_RECOMPUTE)
-    hipLaunchKernelGGL(pair_prep_delta_kernel, dim3(scp_cdiv((int64_t)N * K * D, 256)), dim3(256), 0, ctx->stream, N, K, D,
-                       pos_ref_layout, p0, P_tm, Q_tm, a.stats);
-  else
-    hipLaunchKernelGGL(pair_prep_kernel, dim3(scp_cdiv((int64_t)N * K * D, 256)), dim3(256), 0, ctx->stream, N, K, D,
-                       a.h, pos_ref_layout, p0, v0, P_tm, Q_tm, a.stats, clear_map, clear_words);
-  a.P_tm = P_tm;
-  a.Q_tm = Q_tm;
-  if (nq <= 0) return SCP_OK;
-  const size_t slice_bytes = (size_t)N * D * sizeof(double);
-  const bool two_slices = MODE == MODE_LINEARIZE || MODE == MODE_VIOL_RECOMPUTE;  // (the second one PAIR_LDS_Q_OFF doubles in)
-  const size_t lds_bytes = two_slices ? PAIR_LDS_SLICE_BYTES + slice_bytes : slice_bytes;
-  // the k-slice must start 16-byte aligned in global memory for the double2 staging loads: N*D even
-#ifdef SCP_PHASE_PROFILE  // developer build only (make prof): ablation switch of tools/pair_bench.py
-  const char* abl = getenv("SCP_PAIR_ABLATE");
-  a.ablate = abl ? atoi(abl) : 0;
-#else
-  a.ablate = 0;
-#endif
-  // slices beyond 32 KB cut the occupancy below 5 workgroups per CU and the L1/L2 path wins (measured at 2048 x 50:
-  // 5.43 TB/s without LDS, 4.74 with; at 1024 x 50, 32 KB: 5.0 with, 4.6 without)
-  const bool use_lds = slice_bytes <= (size_t)(two_slices ? 1 : 2) * PAIR_LDS_SLICE_BYTES && ((N * D) % 2 == 0) && !(a.ablate & 2);
-  dim3 grid(scp_cdiv(nq + 1, PAIR_ROWS), K);
-  dim3 block(PAIR_THREADS);
-  if constexpr (MODE == MODE_LINEARIZE) {
-    // work items ordered large -> small (PairItems): the bulk in chunks of PAIR_STEPS steps, then about one round of the
-    // resident workgroups in half-size and one in quarter-size chunks (whole time steps per class; measured sweep at
-    // 1024 x 50: profiles/r03_pair_tail_sweep.txt)
-    int per_cu = 0;
-    const void* kern = D == 2 ? (use_lds ? (const void*)pair_pass_kernel<2, MODE_LINEARIZE, true> : (const void*)pair_pass_kernel<2, MODE_LINEARIZE, false>)
-                              : (use_lds ? (const void*)pair_pass_kernel<3, MODE_LINEARIZE, true> : (const void*)pair_pass_kernel<3, MODE_LINEARIZE, false>);
-    SCP_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, PAIR_THREADS, use_lds ? lds_bytes : 0));
-    const int64_t slots = (int64_t)std::max(per_cu, 1) * ctx->n_cu;
-    PairItems& it = a.items;
-    it = PairItems{};
-    const int64_t big_per_k = scp_cdiv(nq + 1, PAIR_ROWS);
-    int nk_quarter = 0, nk_half = 0;
-    if (big_per_k * K > slots) {  // (otherwise every item is resident from the start)
-      nk_quarter = (int)((slots * (PAIR_ROWS / 4) + nq / 2) / nq);
-      nk_half = (int)((slots * (PAIR_ROWS / 2) + nq / 2) / nq);
-      if (nk_quarter + nk_half > K / 2) nk_quarter = nk_half = 0;  // few, long time steps: the classes cannot be cut this way
-    }
-#ifdef SCP_PHASE_PROFILE
-    if (const char* e = getenv("SCP_PAIR_TAIL")) {  // "half quarter": time steps cut in half- / quarter-size chunks
-      int h_ = 0, q_ = 0;
-      if (sscanf(e, "%d %d", &h_, &q_) == 2 && h_ >= 0 && q_ >= 0 && h_ + q_ < K) { nk_half = h_; nk_quarter = q_; }
-    }
-#endif
-    const int nk[3] = {K - nk_half - nk_quarter, nk_half, nk_quarter};
-    const int st[3] = {PAIR_STEPS, PAIR_STEPS / 2, PAIR_STEPS / 4};
-    int k0 = 0, item0 = 0;
-    for (int c = 0; c < 3; ++c) {
-      if (nk[c] <= 0) continue;
-      const int m = it.n_classes++;
-      it.item0[m] = item0;
-      it.k0[m] = k0;
-      it.steps[m] = st[c];
-      it.cpk[m] = (int)scp_cdiv(nq + 1, (int64_t)2 * PAIR_THREADS * st[c]);
-      item0 += nk[c] * it.cpk[m];
-      k0 += nk[c];
-    }
-    it.n_items = item0;
-    grid = dim3((unsigned)it.n_items, 1);
-  }
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
-#define SCP_LAUNCH_PAIR(DD, LDS)                                                                        \
-  hipLaunchKernelGGL((pair_pass_kernel<DD, MODE, LDS>), grid, block, (LDS) ? lds_bytes : 0, ctx->stream, a)
-  if (D == 2) {
-    if (use_lds) SCP_LAUNCH_PAIR(2, true);
-    else SCP_LAUNCH_PAIR(2, false);
-  } else {
-    if (use_lds) SCP_LAUNCH_PAIR(3, true);
-    else SCP_LAUNCH_PAIR(3, false);
-  }
-#undef SCP_LAUNCH_PAIR
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
-  ctx->pair_timed = ctx->timing != 0;
-  ctx->pair_ran = true;
-  return SCP_OK;
-}
-
-#ifdef SCP_PHASE_PROFILE
-// developer hook of the profiling build only (not declared in include/scp_hip.h): the per-workgroup stamps above
-extern "C" int scp_debug_small_clocks(unsigned long long* out, int n) {
-  if (n > 16) n = 16;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_small_clk), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-extern "C" int scp_debug_pair_starts(unsigned long long* out, int n) {
-  if (n > SCP_PAIR_CLK_WGS) n = SCP_PAIR_CLK_WGS;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_pair_t0), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-extern "C" int scp_debug_pair_clocks(unsigned long long* out, int n) {
-  if (n > 2 * SCP_PAIR_CLK_WGS) n = 2 * SCP_PAIR_CLK_WGS;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_pair_clk), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif
-
-// Device time of the most recent pairwise kernel alone (HIP events on the ctx stream around that one launch).
-extern "C" int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms) {
-  if (!ctx || !ms) return SCP_ERR_INVALID;
-  if (!ctx->pair_timed && ctx->pair_ran) {  // timing is off (scp_ctx_set_timing): no events were recorded
-    *ms = 0.f;
-    return SCP_OK;
-  }
-  if (!ctx->pair_timed) return scp_fail(ctx, SCP_ERR_STATE, "no pairwise pass has run yet");
-  SCP_HIP_CHECK(ctx, hipEventSynchronize(ctx->pair_ev1));
-  SCP_HIP_CHECK(ctx, hipEventElapsedTime(ms, ctx->pair_ev0, ctx->pair_ev1));
-  return SCP_OK;
-}
-
 // ----------------------------------------------------------------------------------------------------
 // bitmap -> sorted row list (three tiny launches; the list order is the row order, hence deterministic)
 // ----------------------------------------------------------------------------------------------------
-constexpr int CMP_THREADS = 256;
-constexpr int CMP_WPT = 4;                              // bitmap words per thread
-constexpr int CMP_WORDS = CMP_THREADS * CMP_WPT;        // per workgroup
-
-__device__ inline int block_exclusive_scan(int v, int* total) {
-  __shared__ int wsum[CMP_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < CMP_THREADS / 64; ++w) {
-    if (w < wave) base += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + incl - v;
-}
-
 __global__ __launch_bounds__(CMP_THREADS) void compact_count_kernel(const uint32_t* __restrict__ map, int64_t words,
                                                                      uint32_t* __restrict__ block_tot) {
   const int64_t w0 = (int64_t)blockIdx.x * CMP_WORDS + (int64_t)threadIdx.x * CMP_WPT;
@@ -1700,24 +987,6 @@ __global__ __launch_bounds__(CMP_THREADS) void compact_count_kernel(const uint32
   int tot;
   block_exclusive_scan(c, &tot);
   if (threadIdx.x == 0) block_tot[blockIdx.x] = (uint32_t)tot;
-}
-
-// The finished stats of a pass with a row list also go to the ctx's mapped host mirror (sequence number last): the
-// native SCP loop reads them from there without a copy launch and without draining the stream.
-__device__ inline void publish_stats(const scp_pair_stats* stats, unsigned long long n_selected, scp_stats_mirror* mirror,
-                                     unsigned long long seq) {
-  if (!mirror) return;
-  const double mind = __hip_atomic_load(&stats->min_dist, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const double maxv = __hip_atomic_load(&stats->max_violation, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long fv =
-      __hip_atomic_load((const unsigned long long*)&stats->first_violation, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store((unsigned long long*)&mirror->stats.min_dist, (unsigned long long)__double_as_longlong(mind),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store((unsigned long long*)&mirror->stats.first_violation, fv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store((unsigned long long*)&mirror->stats.n_selected, n_selected, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store((unsigned long long*)&mirror->stats.max_violation, (unsigned long long)__double_as_longlong(maxv),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store((unsigned long long*)&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // exclusive scan of the block totals in place (one workgroup; nblocks is a few hundred), total -> stats
@@ -1792,100 +1061,6 @@ __global__ __launch_bounds__(CMP_THREADS) void compact_write_kernel(uint32_t* __
 // stats mirror in ONE workgroup -- the three-launch version costs more in launch boundaries than in work there.
 constexpr int CMP1_THREADS = 1024;
 
-// The body, for THREADS threads of ONE workgroup (all of them must call it): returns the number of set bits.
-// OVERWRITE: merge_into := map (every word, also the empty ones: the working-set bitmap of a NEW linearisation, no clearing
-// launch), map := 0.  COHERENT: the bits were set by other workgroups of the SAME kernel (the small-problem passes run this
-// as their tail): the words are read past this XCD's L2.
-template <int THREADS, bool COHERENT>
-__device__ inline int compact_small_body(uint32_t* __restrict__ map, int64_t words, int64_t nq, int64_t q_begin,
-                                         int64_t pairs, int64_t* __restrict__ rows, int64_t cap,
-                                         uint32_t* __restrict__ merge_into, bool overwrite) {
-  __shared__ int wsum[THREADS / 64];
-  __shared__ int total_sh;
-  constexpr int CHUNK = THREADS * CMP_WPT;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  auto load = [&](int64_t w) -> uint32_t {
-    return COHERENT ? __hip_atomic_load(map + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : map[w];
-  };
-  // pass 1: the total (decides whether a merging pass may merge at all)
-  int c_all = 0;
-  for (int64_t w = threadIdx.x; w < words; w += THREADS) c_all += __popc(load(w));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c_all += __shfl_xor(c_all, o);
-  __syncthreads();  // (wsum / total_sh of an earlier call in the same kernel have been read)
-  if (lane == 0) wsum[wave] = c_all;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < THREADS / 64; ++w) t += wsum[w];
-    total_sh = t;
-  }
-  __syncthreads();
-  const int total = total_sh;
-  const bool overflow = merge_into != nullptr && !overwrite && (int64_t)total > cap;
-  // pass 2: chunk by chunk in row order, block scan per chunk
-  int64_t carry = 0;
-  for (int64_t base = 0; base < words && (total > 0 || overwrite); base += CHUNK) {
-    const int64_t w0 = base + (int64_t)threadIdx.x * CMP_WPT;
-    uint32_t wd[CMP_WPT];
-    int c = 0;
-#pragma unroll
-    for (int i = 0; i < CMP_WPT; ++i) {
-      wd[i] = (w0 + i < words) ? load(w0 + i) : 0u;
-      c += __popc(wd[i]);
-    }
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    __syncthreads();  // wsum of the previous chunk (or of pass 1) has been read by everyone
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) {
-      if (w < wave) before += wsum[w];
-      tot += wsum[w];
-    }
-    int64_t slot = carry + before + incl - c;
-    carry += tot;
-    if (overwrite) {
-#pragma unroll
-      for (int i = 0; i < CMP_WPT; ++i)
-        if (w0 + i < words) merge_into[w0 + i] = wd[i];
-    }
-    if (c == 0) continue;
-#pragma unroll
-    for (int i = 0; i < CMP_WPT; ++i) {
-      uint32_t m = wd[i];
-      if (m && merge_into) {
-        if (!overflow && !overwrite) merge_into[w0 + i] |= m;
-        map[w0 + i] = 0u;
-      }
-      if (m) {
-        // local row lr = 32 (w0 + i) + bit -> global id (lr / nq) pairs + q_begin + lr % nq with ONE 64-bit division per
-        // word (its bits belong to at most two time steps when nq >= 32; the inner loop covers tiny pair ranges)
-        const int64_t base = (w0 + i) * 32;
-        const int64_t kk = base / nq, rr = base - kk * nq;
-        while (m) {
-          const int bit = __ffs((int)m) - 1;
-          m &= m - 1;
-          int64_t k2 = kk, r2 = rr + bit;
-          while (r2 >= nq) {
-            r2 -= nq;
-            ++k2;
-          }
-          if (!overflow && slot < cap) rows[slot] = k2 * pairs + q_begin + r2;
-          ++slot;
-        }
-      }
-    }
-  }
-  return total;
-}
-
 __global__ __launch_bounds__(CMP1_THREADS) void compact_small_kernel(uint32_t* __restrict__ map, int64_t words, int64_t nq,
                                                                       int64_t q_begin, int64_t pairs,
                                                                       int64_t* __restrict__ rows, int64_t cap,
@@ -1900,31 +1075,19 @@ __global__ __launch_bounds__(CMP1_THREADS) void compact_small_kernel(uint32_t* _
   }
 }
 
+// ----------------------------------------------------------------------------------------------------
+// host side: one path into the pairwise pass
+// ----------------------------------------------------------------------------------------------------
+// scratch bitmap of the violations passes and block totals of the three-launch compaction (grown on demand, owned by the ctx)
 static int ensure_cmp(scp_ctx* ctx, int64_t words) {
   const size_t need_map = (size_t)words * sizeof(uint32_t);
   const size_t need_tot = (size_t)(scp_cdiv(words, CMP_WORDS) + 1) * sizeof(uint32_t);
   if (ctx->cmp_map_bytes < need_map) {
-    if (ctx->cmp_map) {
-      SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      SCP_HIP_CHECK(ctx, hipFree(ctx->cmp_map));
-      ctx->cmp_map = nullptr;
-      ctx->cmp_map_bytes = 0;
-    }
-    SCP_HIP_CHECK(ctx, hipMalloc(&ctx->cmp_map, need_map));
+    const int rc = scp_ctx_ensure_bytes(ctx, (void**)&ctx->cmp_map, &ctx->cmp_map_bytes, need_map);
+    if (rc) return rc;
     SCP_HIP_CHECK(ctx, hipMemsetAsync(ctx->cmp_map, 0, need_map, ctx->stream));  // self-cleaning afterwards
-    ctx->cmp_map_bytes = need_map;
   }
-  if (ctx->cmp_tot_bytes < need_tot) {
-    if (ctx->cmp_tot) {
-      SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      SCP_HIP_CHECK(ctx, hipFree(ctx->cmp_tot));
-      ctx->cmp_tot = nullptr;
-      ctx->cmp_tot_bytes = 0;
-    }
-    SCP_HIP_CHECK(ctx, hipMalloc(&ctx->cmp_tot, need_tot));
-    ctx->cmp_tot_bytes = need_tot;
-  }
-  return SCP_OK;
+  return scp_ctx_ensure_bytes(ctx, (void**)&ctx->cmp_tot, &ctx->cmp_tot_bytes, need_tot);
 }
 
 static int launch_compaction(scp_ctx* ctx, uint32_t* map, int64_t words, int64_t nq, int64_t q_begin, int64_t pairs,
@@ -1947,7 +1110,236 @@ static int launch_compaction(scp_ctx* ctx, uint32_t* map, int64_t words, int64_t
   return SCP_OK;
 }
 
-static int check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end) {
+
+// What happens to the marks of a pass, the rows it selects.  NONE: it selects nothing (check).  REPLACE: it marks the
+// working-set bitmap `bitmap` itself, cleared first: a new linearisation (linearize, select).  MERGE: it marks the ctx's
+// scratch map, and those bits are then merged into `bitmap` (violations; the scratch map is left clean).  Either way the
+// marked rows become the sorted list `rows` of capacity `cap`: in the tail of the pass kernel itself when the pass is one
+// launch, in launch_compaction otherwise.
+struct PassMarks {
+  enum Kind { NONE, REPLACE, MERGE } kind;
+  int64_t* rows;
+  int64_t cap;
+  uint32_t* bitmap;
+};
+
+// the fields every pass fills the same way; the entry points add what is specific to them
+static PairArgs pair_args(int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end, scp_pair_stats* stats) {
+  PairArgs a{};
+  a.N = N; a.K = K; a.D = D; a.R = R; a.h = h;
+  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
+  a.stats = stats;
+  a.eta_stride = scp_eta_stride(K, q_end - q_begin);
+  a.words = (K * (q_end - q_begin) + 31) / 32;
+  return a;
+}
+
+typedef void (*PairKernel)(PairArgs);
+
+// the D x LDS instantiations of one mode (the one-launch form of small problems always stages its slices in LDS)
+template <int MODE, bool SMALL>
+static PairKernel pair_kernel_of(int D, bool use_lds) {
+  if constexpr (SMALL) {
+    return D == 2 ? pair_pass_kernel<2, MODE, true, true> : pair_pass_kernel<3, MODE, true, true>;
+  } else {
+    if (D == 2) return use_lds ? pair_pass_kernel<2, MODE, true> : pair_pass_kernel<2, MODE, false>;
+    return use_lds ? pair_pass_kernel<3, MODE, true> : pair_pass_kernel<3, MODE, false>;
+  }
+}
+// select, check and the recomputing violations pass have a one-launch form
+static bool pair_mode_has_small(int mode) { return mode == MODE_SELECT || mode == MODE_VIOL_RECOMPUTE || mode == MODE_CHECK; }
+static PairKernel pair_kernel(int mode, int D, bool use_lds, bool small) {
+  switch (mode) {
+    case MODE_LINEARIZE: return pair_kernel_of<MODE_LINEARIZE, false>(D, use_lds);
+    case MODE_VIOLATIONS: return pair_kernel_of<MODE_VIOLATIONS, false>(D, use_lds);
+    case MODE_CHECK: return small ? pair_kernel_of<MODE_CHECK, true>(D, true) : pair_kernel_of<MODE_CHECK, false>(D, use_lds);
+    case MODE_SELECT: return small ? pair_kernel_of<MODE_SELECT, true>(D, true) : pair_kernel_of<MODE_SELECT, false>(D, use_lds);
+    default: return small ? pair_kernel_of<MODE_VIOL_RECOMPUTE, true>(D, true) : pair_kernel_of<MODE_VIOL_RECOMPUTE, false>(D, use_lds);
+  }
+}
+
+// the pass kernel itself, between the two events scp_ctx_last_pair_ms reads
+static int launch_pair_kernel(scp_ctx* ctx, PairKernel kern, dim3 grid, size_t lds_bytes, const PairArgs& a) {
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
+  hipLaunchKernelGGL(kern, grid, dim3(PAIR_THREADS), lds_bytes, ctx->stream, a);
+  SCP_HIP_CHECK(ctx, hipGetLastError());
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
+  ctx->pair_timed = ctx->timing != 0;
+  ctx->pair_ran = true;
+  return SCP_OK;
+}
+
+// a pass over nq pairs x K steps that runs as ONE launch (pair_pass_kernel<.., SMALL>): its bitmap fits the one-workgroup
+// compaction, its time-step slices (n_slices of them) the LDS budget of the pass, its partials the ctx scratch
+static bool small_pass_ok(const scp_ctx* ctx, int N, int K, int D, int64_t nq, int n_slices) {
+  if (!ctx->small_pass || nq <= 0) return false;
+  const int64_t words = (K * nq + 31) / 32;
+  const int64_t n_wg = (int64_t)scp_cdiv(nq + 1, SMALL_ROWS) * K;
+  return words <= CMP1_MAX_WORDS && (size_t)n_slices * N * D * sizeof(double) <= 32 * 1024 && n_wg <= SCP_SMALL_MAX_WG;
+}
+// slices of N D doubles the one-launch form stages: the pass's positions, the new ones, and the latter's speculative selection
+static int small_pass_slices(int mode, const PairArgs& a) { return mode == MODE_VIOL_RECOMPUTE ? (a.spec_rows ? 3 : 2) : 1; }
+
+// The pass of a small problem, tail included, in one launch.  pos: the pass's positions (select / check) or the
+// linearisation point (violations); pos_new: the new positions of a violations pass that does not derive them from a.x_tm.
+static int launch_small_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos,
+                             const double* pos_new) {
+  const int wgs_per_k = scp_cdiv(a.q_end - a.q_begin + 1, SMALL_ROWS);
+  a.pos_a = pos;
+  if (mode == MODE_VIOL_RECOMPUTE && !a.x_tm) a.pos_b = pos_new;
+  if (mode != MODE_CHECK) {  // per-workgroup sub-lists of the marked rows (grown on demand, owned by the ctx)
+    const size_t need = (size_t)(a.spec_rows ? 2 : 1) * wgs_per_k * a.K * SMALL_ROWS * sizeof(uint32_t);
+    const int rc = scp_ctx_ensure_bytes(ctx, (void**)&ctx->wg_rows, &ctx->wg_rows_bytes, need);
+    if (rc) return rc;
+  }
+  a.wg_rows = ctx->wg_rows;
+  a.wg_part = ctx->wg_part;
+  a.ticket = ctx->d_ticket;
+  a.rows = marks.rows; a.cap = marks.cap; a.merge_into = marks.bitmap; a.overwrite = marks.kind == PassMarks::REPLACE ? 1 : 0;
+  a.mirror = ctx->d_mirror;
+  a.seq = ++ctx->mirror_seq;
+  const size_t lds_bytes = (size_t)small_pass_slices(mode, a) * a.N * a.D * sizeof(double);
+  const int rc = launch_pair_kernel(ctx, pair_kernel(mode, a.D, true, true), dim3(wgs_per_k, a.K), lds_bytes, a);
+  if (rc) return rc;
+  ctx->last_pass_small = true;
+  return SCP_OK;
+}
+
+// Work items of the linearisation pass of a large problem, ordered large -> small (PairItems): the bulk in chunks of
+// PAIR_STEPS steps, then about one round of the resident workgroups in half-size and one in quarter-size chunks (whole time
+// steps per class; measured sweep at 1024 x 50: profiles/r03_pair_tail_sweep.txt)
+static int split_linearize_items(scp_ctx* ctx, PairArgs& a, PairKernel kern, size_t lds_bytes) {
+  const int K = a.K;
+  const int64_t nq = a.q_end - a.q_begin;
+  int per_cu = 0;
+  SCP_HIP_CHECK(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, PAIR_THREADS, lds_bytes));
+  const int64_t slots = (int64_t)std::max(per_cu, 1) * ctx->n_cu;
+  PairItems& it = a.items;
+  it = PairItems{};
+  const int64_t big_per_k = scp_cdiv(nq + 1, PAIR_ROWS);
+  int nk_quarter = 0, nk_half = 0;
+  if (big_per_k * K > slots) {  // (otherwise every item is resident from the start)
+    nk_quarter = (int)((slots * (PAIR_ROWS / 4) + nq / 2) / nq);
+    nk_half = (int)((slots * (PAIR_ROWS / 2) + nq / 2) / nq);
+    if (nk_quarter + nk_half > K / 2) nk_quarter = nk_half = 0;  // few, long time steps: the classes cannot be cut this way
+  }
+#ifdef SCP_PHASE_PROFILE
+  if (const char* e = getenv("SCP_PAIR_TAIL")) {  // "half quarter": time steps cut in half- / quarter-size chunks
+    int h_ = 0, q_ = 0;
+    if (sscanf(e, "%d %d", &h_, &q_) == 2 && h_ >= 0 && q_ >= 0 && h_ + q_ < K) { nk_half = h_; nk_quarter = q_; }
+  }
+#endif
+  const int nk[3] = {K - nk_half - nk_quarter, nk_half, nk_quarter};
+  const int st[3] = {PAIR_STEPS, PAIR_STEPS / 2, PAIR_STEPS / 4};
+  int k0 = 0, item0 = 0;
+  for (int c = 0; c < 3; ++c) {
+    if (nk[c] <= 0) continue;
+    const int m = it.n_classes++;
+    it.item0[m] = item0;
+    it.k0[m] = k0;
+    it.steps[m] = st[c];
+    it.cpk[m] = (int)scp_cdiv(nq + 1, (int64_t)2 * PAIR_THREADS * st[c]);
+    item0 += nk[c] * it.cpk[m];
+    k0 += nk[c];
+  }
+  it.n_items = item0;
+  return SCP_OK;
+}
+
+// The pass of a large problem: a prep kernel (time-major slices, the stats' initial values, the cleared map of a REPLACE
+// pass), then the pass kernel; the compaction follows in pair_pass.  pos, p0, v0: the pass's positions in the reference
+// layout and the initial states; MODE_VIOL_RECOMPUTE: pos = the linearisation point, p0 = the new positions (v0 unused).
+static int launch_large_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
+                             const double* v0) {
+  const int N = a.N, K = a.K, D = a.D;
+  const int64_t nq = a.q_end - a.q_begin;
+  ctx->last_pass_small = false;
+  const size_t slice = ((size_t)N * K * D + 1) & ~(size_t)1;  // keep the second array 16-byte aligned
+  const int rc = scp_ctx_ensure_bytes(ctx, (void**)&ctx->tm_scratch, &ctx->tm_bytes, 2 * slice * sizeof(double));
+  if (rc) return rc;
+  double* P_tm = mode != MODE_VIOLATIONS ? ctx->tm_scratch : nullptr;
+  double* Q_tm = (mode != MODE_CHECK && mode != MODE_SELECT) ? ctx->tm_scratch + slice : nullptr;
+  const dim3 prep_grid(scp_cdiv((int64_t)N * K * D, 256));
+  const bool clear = marks.kind == PassMarks::REPLACE;
+  if (mode == MODE_VIOL_RECOMPUTE)
+    hipLaunchKernelGGL(pair_prep_delta_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, pos, p0, P_tm, Q_tm, a.stats);
+  else
+    hipLaunchKernelGGL(pair_prep_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, a.h, pos, p0, v0, P_tm, Q_tm,
+                       a.stats, clear ? marks.bitmap : nullptr, clear ? a.words : (int64_t)0);
+  a.P_tm = P_tm;
+  a.Q_tm = Q_tm;
+  if (nq <= 0) return SCP_OK;
+  const size_t slice_bytes = (size_t)N * D * sizeof(double);
+  const bool two_slices = mode == MODE_LINEARIZE || mode == MODE_VIOL_RECOMPUTE;  // (the second one PAIR_LDS_Q_OFF doubles in)
+  // the k-slice must start 16-byte aligned in global memory for the double2 staging loads: N*D even.
+  // slices beyond 32 KB cut the occupancy below 5 workgroups per CU and the L1/L2 path wins (measured at 2048 x 50:
+  // 5.43 TB/s without LDS, 4.74 with; at 1024 x 50, 32 KB: 5.0 with, 4.6 without)
+  const bool use_lds = slice_bytes <= (size_t)(two_slices ? 1 : 2) * PAIR_LDS_SLICE_BYTES && ((N * D) % 2 == 0) && !(a.ablate & 2);
+  const size_t lds_bytes = !use_lds ? 0 : (two_slices ? PAIR_LDS_SLICE_BYTES + slice_bytes : slice_bytes);
+  const PairKernel kern = pair_kernel(mode, D, use_lds, false);
+  dim3 grid(scp_cdiv(nq + 1, PAIR_ROWS), K);
+  if (mode == MODE_LINEARIZE) {  // a 1-D grid over its work items
+    const int rc_items = split_linearize_items(ctx, a, kern, lds_bytes);
+    if (rc_items) return rc_items;
+    grid = dim3((unsigned)a.items.n_items, 1);
+  }
+  return launch_pair_kernel(ctx, kern, grid, lds_bytes, a);
+}
+
+// Every pairwise pass: as one launch when the problem is small and the mode has that form (ctx->last_pass_small tells),
+// otherwise prep kernel, pass kernel and the compaction of its marks.
+static int pair_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
+                     const double* v0) {
+  if (marks.kind != PassMarks::NONE) {
+    const int rc = ensure_cmp(ctx, a.words);
+    if (rc) return rc;
+  }
+  a.bitmap = marks.bitmap;
+  a.mark = marks.kind == PassMarks::MERGE ? ctx->cmp_map : marks.bitmap;
+#ifdef SCP_PHASE_PROFILE  // developer build only (make prof): ablation switch of tools/pair_bench.py
+  const char* abl = getenv("SCP_PAIR_ABLATE");
+  a.ablate = abl ? atoi(abl) : 0;
+#endif
+  if (pair_mode_has_small(mode) && small_pass_ok(ctx, a.N, a.K, a.D, a.q_end - a.q_begin, small_pass_slices(mode, a)))
+    return launch_small_pass(ctx, mode, a, marks, pos, p0);
+  const int rc = launch_large_pass(ctx, mode, a, marks, pos, p0, v0);
+  if (rc || marks.kind == PassMarks::NONE) return rc;
+  // (the marks of a MERGE pass are the bits of the scratch map; merging them into the working-set bitmap also clears it)
+  return launch_compaction(ctx, a.mark, a.words, a.q_end - a.q_begin, a.q_begin, a.pairs, marks.rows, marks.cap,
+                           marks.kind == PassMarks::MERGE ? marks.bitmap : nullptr, a.stats);
+}
+
+#ifdef SCP_PHASE_PROFILE
+// developer hook of the profiling build only (not declared in include/scp_hip.h): the per-workgroup stamps above
+extern "C" int scp_debug_small_clocks(unsigned long long* out, int n) {
+  if (n > 16) n = 16;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_small_clk), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
+}
+extern "C" int scp_debug_pair_starts(unsigned long long* out, int n) {
+  if (n > SCP_PAIR_CLK_WGS) n = SCP_PAIR_CLK_WGS;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_pair_t0), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
+}
+extern "C" int scp_debug_pair_clocks(unsigned long long* out, int n) {
+  if (n > 2 * SCP_PAIR_CLK_WGS) n = 2 * SCP_PAIR_CLK_WGS;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(scp_pair_clk), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
+}
+#endif
+
+// Device time of the most recent pairwise kernel alone (HIP events on the ctx stream around that one launch).
+extern "C" int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return SCP_ERR_INVALID;
+  if (!ctx->pair_timed && ctx->pair_ran) {  // timing is off (scp_ctx_set_timing): no events were recorded
+    *ms = 0.f;
+    return SCP_OK;
+  }
+  if (!ctx->pair_timed) return scp_fail(ctx, SCP_ERR_STATE, "no pairwise pass has run yet");
+  SCP_HIP_CHECK(ctx, hipEventSynchronize(ctx->pair_ev1));
+  SCP_HIP_CHECK(ctx, hipEventElapsedTime(ms, ctx->pair_ev0, ctx->pair_ev1));
+  return SCP_OK;
+}
+
+
+int scp_check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end) {
   SCP_REQUIRE(ctx, N >= 1 && K >= 1 && (D == 2 || D == 3), "pair pass: bad shape N=%d K=%d D=%d", N, K, D);
   SCP_REQUIRE(ctx, q_begin >= 0 && q_end >= q_begin && q_end <= scp_pairs(N),
               "pair pass: bad pair range [%lld, %lld) of %lld", (long long)q_begin, (long long)q_end,
@@ -1959,57 +1351,120 @@ static int check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, 
   return SCP_OK;
 }
 
-int scp_check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end) {
-  return check_pair_range(ctx, N, K, D, q_begin, q_end);
-}
-
 extern "C" int scp_linearize_pairs(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin,
                                    int64_t q_end, const double* pos_prev, const double* p0, const double* v0,
                                    double* eta_out, double* l_out, double margin, int64_t* sel_rows,
                                    int64_t sel_cap, uint32_t* sel_bitmap, scp_pair_stats* stats) {
   if (!ctx) return SCP_ERR_INVALID;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
+  const int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
   if (rc) return rc;
   SCP_REQUIRE(ctx, pos_prev && p0 && v0 && eta_out && l_out && sel_bitmap && stats && (sel_rows || sel_cap == 0),
               "linearize_pairs: null pointer");
   SCP_REQUIRE(ctx, ((uintptr_t)eta_out % 16 == 0) && ((uintptr_t)l_out % 16 == 0),
               "linearize_pairs: eta/l must be 16-byte aligned");
-  const int64_t nq = q_end - q_begin;
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = R; a.h = h;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
+  PairArgs a = pair_args(N, K, D, R, h, q_begin, q_end, stats);
   a.eta = eta_out; a.l = l_out; a.margin = margin;
-  a.bitmap = sel_bitmap; a.mark = sel_bitmap; a.stats = stats;
-  a.eta_stride = scp_eta_stride(K, nq);
-  const int64_t words = (K * nq + 31) / 32;
-  rc = ensure_cmp(ctx, words);
-  if (rc) return rc;
-  rc = launch_pair_pass<MODE_LINEARIZE>(ctx, a, pos_prev, p0, v0, sel_bitmap, words);  // (its prep kernel clears the map)
-  if (rc) return rc;
-  return launch_compaction(ctx, sel_bitmap, words, nq, q_begin, a.pairs, sel_rows, sel_cap, nullptr, stats);
+  return pair_pass(ctx, MODE_LINEARIZE, a, {PassMarks::REPLACE, sel_rows, sel_cap, sel_bitmap}, pos_prev, p0, v0);
 }
 
 extern "C" int scp_select_pairs(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begin, int64_t q_end,
                                 const double* pos_prev, double margin, int64_t* sel_rows, int64_t sel_cap,
                                 uint32_t* sel_bitmap, scp_pair_stats* stats) {
   if (!ctx) return SCP_ERR_INVALID;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
+  const int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
   if (rc) return rc;
   SCP_REQUIRE(ctx, pos_prev && sel_bitmap && stats && (sel_rows || sel_cap == 0), "select_pairs: null pointer");
-  const int64_t nq = q_end - q_begin;
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = R; a.h = 0.0;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
+  PairArgs a = pair_args(N, K, D, R, 0.0, q_begin, q_end, stats);
   a.margin = margin;
-  a.bitmap = sel_bitmap; a.mark = sel_bitmap; a.stats = stats;
-  a.eta_stride = scp_eta_stride(K, nq);
-  const int64_t words = (K * nq + 31) / 32;
-  rc = ensure_cmp(ctx, words);
+  return pair_pass(ctx, MODE_SELECT, a, {PassMarks::REPLACE, sel_rows, sel_cap, sel_bitmap}, pos_prev, nullptr, nullptr);
+}
+
+extern "C" int scp_check_avoidance(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begin, int64_t q_end,
+                                   const double* pos, scp_pair_stats* stats) {
+  if (!ctx) return SCP_ERR_INVALID;
+  const int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
   if (rc) return rc;
-  PassTail tail{sel_rows, sel_cap, sel_bitmap, true, words, false};
-  rc = launch_pair_pass<MODE_SELECT>(ctx, a, pos_prev, nullptr, nullptr, sel_bitmap, words, &tail);  // (its prep kernel clears the map)
-  if (rc || tail.done) return rc;
-  return launch_compaction(ctx, sel_bitmap, words, nq, q_begin, a.pairs, sel_rows, sel_cap, nullptr, stats);
+  SCP_REQUIRE(ctx, pos && stats, "check_avoidance: null pointer");
+  PairArgs a = pair_args(N, K, D, R, 0.0, q_begin, q_end, stats);
+  return pair_pass(ctx, MODE_CHECK, a, {PassMarks::NONE, nullptr, 0, nullptr}, pos, nullptr, nullptr);
+}
+
+extern "C" int scp_collision_violations(scp_ctx* ctx, int N, int K, int D, double h, int64_t q_begin,
+                                        int64_t q_end, const double* eta, const double* l_col, const double* pos,
+                                        const double* p0, const double* v0, double feas_tol, int64_t* new_rows,
+                                        int64_t new_cap, uint32_t* sel_bitmap, scp_pair_stats* stats) {
+  if (!ctx) return SCP_ERR_INVALID;
+  const int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, eta && l_col && pos && p0 && v0 && sel_bitmap && stats && (new_rows || new_cap == 0),
+              "collision_violations: null pointer");
+  PairArgs a = pair_args(N, K, D, 0.0, h, q_begin, q_end, stats);
+  a.eta = const_cast<double*>(eta); a.l = const_cast<double*>(l_col); a.margin = feas_tol;
+  return pair_pass(ctx, MODE_VIOLATIONS, a, {PassMarks::MERGE, new_rows, new_cap, sel_bitmap}, pos, p0, v0);
+}
+
+extern "C" int scp_collision_violations_at(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begin, int64_t q_end,
+                                           const double* pos_prev, const double* pos_new, double feas_tol,
+                                           int64_t* new_rows, int64_t new_cap, uint32_t* sel_bitmap,
+                                           scp_pair_stats* stats) {
+  if (!ctx) return SCP_ERR_INVALID;
+  const int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, pos_prev && pos_new && sel_bitmap && stats && (new_rows || new_cap == 0),
+              "collision_violations_at: null pointer");
+  PairArgs a = pair_args(N, K, D, R, 0.0, q_begin, q_end, stats);
+  a.margin = feas_tol;
+  return pair_pass(ctx, MODE_VIOL_RECOMPUTE, a, {PassMarks::MERGE, new_rows, new_cap, sel_bitmap}, pos_prev, pos_new, nullptr);
+}
+
+// internal (scp_common.h): scp_qp_get_solution + scp_kinematics + scp_collision_violations_at of a SMALL problem in ONE
+// launch -- the pass derives the new positions from the QP's time-major solution x_tm itself and leaves them (pos_out) and
+// the solution in the reference layout (x_out) behind; bit-identical to the three calls.  *fused = false: not a small
+// problem, nothing was launched.
+int scp_violations_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end,
+                                 const double* pos_prev, const double* x_tm, const double* p0, const double* v0, double* x_out,
+                                 double* pos_out, double feas_tol, int64_t* new_rows, int64_t new_cap, uint32_t* sel_bitmap,
+                                 scp_pair_stats* stats, const double* rel_prev, int64_t* spec_rows, int64_t spec_cap,
+                                 uint32_t* spec_bitmap, double spec_margin, bool* fused) {
+  *fused = false;
+  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  const int64_t nq = q_end - q_begin;
+  if (!small_pass_ok(ctx, N, K, D, nq, 2)) return SCP_OK;
+  if (!spec_bitmap || !small_pass_ok(ctx, N, K, D, nq, 3)) spec_rows = nullptr;  // (no LDS for the third slice: no speculation)
+  PairArgs a = pair_args(N, K, D, R, h, q_begin, q_end, stats);
+  a.margin = feas_tol;
+  a.x_tm = x_tm; a.p0 = p0; a.v0 = v0; a.x_out = x_out; a.pos_out = pos_out;
+  a.rel_prev = rel_prev;
+  a.rel_blocks = rel_step_blocks((int64_t)N * K * D);
+  a.spec_rows = spec_rows; a.spec_cap = spec_cap; a.spec_bitmap = spec_bitmap; a.spec_margin = spec_margin;
+  rc = pair_pass(ctx, MODE_VIOL_RECOMPUTE, a, {PassMarks::MERGE, new_rows, new_cap, sel_bitmap}, pos_prev, nullptr, nullptr);
+  if (rc) return rc;
+  if (!ctx->last_pass_small) return scp_fail(ctx, SCP_ERR_STATE, "violations_from_solution: the small-problem pass did not run");
+  *fused = true;
+  return SCP_OK;
+}
+
+// internal (scp_common.h): scp_qp_get_solution + scp_kinematics + scp_check_avoidance + scp_select_pairs of a SMALL problem
+// in ONE launch (after QP#0): the select pass stages the kinematics of the QP's time-major solution, leaves positions and
+// solution in the reference layout behind, reduces the a8 statistics (the same ones the check pass reduces) and, for the
+// reference's print, leaves the two positions of the first violating pair in the mirror.
+int scp_select_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end,
+                             const double* x_tm, const double* p0, const double* v0, double* x_out, double* pos_out,
+                             double margin, int64_t* sel_rows, int64_t sel_cap, uint32_t* sel_bitmap, scp_pair_stats* stats,
+                             bool* fused) {
+  *fused = false;
+  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  if (!small_pass_ok(ctx, N, K, D, q_end - q_begin, 1)) return SCP_OK;
+  PairArgs a = pair_args(N, K, D, R, h, q_begin, q_end, stats);
+  a.margin = margin;
+  a.x_tm = x_tm; a.p0 = p0; a.v0 = v0; a.x_out = x_out; a.pos_out = pos_out;
+  rc = pair_pass(ctx, MODE_SELECT, a, {PassMarks::REPLACE, sel_rows, sel_cap, sel_bitmap}, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  if (!ctx->last_pass_small) return scp_fail(ctx, SCP_ERR_STATE, "select_from_solution: the small-problem pass did not run");
+  *fused = true;
+  return SCP_OK;
 }
 
 // Working rows appended with eta / l RECOMPUTED from the linearisation point (the row-free loop: scp_select_pairs wrote no
@@ -2045,134 +1500,6 @@ int scp_launch_add_rows_at(scp_ctx* ctx, int N, int K, int D, int64_t base, int6
   return SCP_OK;
 }
 
-extern "C" int scp_check_avoidance(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begin, int64_t q_end,
-                                   const double* pos, scp_pair_stats* stats) {
-  if (!ctx) return SCP_ERR_INVALID;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  SCP_REQUIRE(ctx, pos && stats, "check_avoidance: null pointer");
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = R; a.h = 0.0;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  a.stats = stats;
-  PassTail tail{nullptr, 0, nullptr, false, (K * (q_end - q_begin) + 31) / 32, false};
-  return launch_pair_pass<MODE_CHECK>(ctx, a, pos, nullptr, nullptr, nullptr, 0, &tail);
-}
-
-extern "C" int scp_collision_violations(scp_ctx* ctx, int N, int K, int D, double h, int64_t q_begin,
-                                        int64_t q_end, const double* eta, const double* l_col, const double* pos,
-                                        const double* p0, const double* v0, double feas_tol, int64_t* new_rows,
-                                        int64_t new_cap, uint32_t* sel_bitmap, scp_pair_stats* stats) {
-  if (!ctx) return SCP_ERR_INVALID;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  SCP_REQUIRE(ctx, eta && l_col && pos && p0 && v0 && sel_bitmap && stats && (new_rows || new_cap == 0),
-              "collision_violations: null pointer");
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = 0.0; a.h = h;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  a.eta = const_cast<double*>(eta); a.l = const_cast<double*>(l_col); a.margin = feas_tol;
-  const int64_t nq = q_end - q_begin;
-  const int64_t words = (K * nq + 31) / 32;
-  rc = ensure_cmp(ctx, words);
-  if (rc) return rc;
-  a.bitmap = sel_bitmap; a.mark = ctx->cmp_map; a.stats = stats;
-  a.eta_stride = scp_eta_stride(K, nq);
-  rc = launch_pair_pass<MODE_VIOLATIONS>(ctx, a, pos, p0, v0);
-  if (rc) return rc;
-  // new rows = bits of the scratch map; merging them into the working-set bitmap also clears the scratch map
-  return launch_compaction(ctx, ctx->cmp_map, words, nq, q_begin, a.pairs, new_rows, new_cap, sel_bitmap, stats);
-}
-
-extern "C" int scp_collision_violations_at(scp_ctx* ctx, int N, int K, int D, double R, int64_t q_begin, int64_t q_end,
-                                           const double* pos_prev, const double* pos_new, double feas_tol,
-                                           int64_t* new_rows, int64_t new_cap, uint32_t* sel_bitmap,
-                                           scp_pair_stats* stats) {
-  if (!ctx) return SCP_ERR_INVALID;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  SCP_REQUIRE(ctx, pos_prev && pos_new && sel_bitmap && stats && (new_rows || new_cap == 0),
-              "collision_violations_at: null pointer");
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = R; a.h = 0.0;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  a.margin = feas_tol;
-  const int64_t nq = q_end - q_begin;
-  const int64_t words = (K * nq + 31) / 32;
-  rc = ensure_cmp(ctx, words);
-  if (rc) return rc;
-  a.bitmap = sel_bitmap; a.mark = ctx->cmp_map; a.stats = stats;
-  a.eta_stride = scp_eta_stride(K, nq);
-  PassTail tail{new_rows, new_cap, sel_bitmap, false, words, false};
-  rc = launch_pair_pass<MODE_VIOL_RECOMPUTE>(ctx, a, pos_prev, pos_new, nullptr, nullptr, 0, &tail);
-  if (rc || tail.done) return rc;
-  return launch_compaction(ctx, ctx->cmp_map, words, nq, q_begin, a.pairs, new_rows, new_cap, sel_bitmap, stats);
-}
-
-// internal (scp_common.h): scp_qp_get_solution + scp_kinematics + scp_collision_violations_at of a SMALL problem in ONE
-// launch -- the pass derives the new positions from the QP's time-major solution x_tm itself and leaves them (pos_out) and
-// the solution in the reference layout (x_out) behind; bit-identical to the three calls.  *fused = false: not a small
-// problem, nothing was launched.
-int scp_violations_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end,
-                                 const double* pos_prev, const double* x_tm, const double* p0, const double* v0, double* x_out,
-                                 double* pos_out, double feas_tol, int64_t* new_rows, int64_t new_cap, uint32_t* sel_bitmap,
-                                 scp_pair_stats* stats, const double* rel_prev, int64_t* spec_rows, int64_t spec_cap,
-                                 uint32_t* spec_bitmap, double spec_margin, bool* fused) {
-  *fused = false;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  const int64_t nq = q_end - q_begin;
-  if (!small_pass_ok(ctx, N, K, D, nq, 2)) return SCP_OK;
-  if (!spec_bitmap || !small_pass_ok(ctx, N, K, D, nq, 3)) spec_rows = nullptr;  // (no LDS for the third slice: no speculation)
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = R; a.h = h;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  a.margin = feas_tol;
-  const int64_t words = (K * nq + 31) / 32;
-  rc = ensure_cmp(ctx, words);
-  if (rc) return rc;
-  a.bitmap = sel_bitmap; a.mark = ctx->cmp_map; a.stats = stats;
-  a.eta_stride = scp_eta_stride(K, nq);
-  a.x_tm = x_tm; a.p0 = p0; a.v0 = v0; a.x_out = x_out; a.pos_out = pos_out;
-  a.rel_prev = rel_prev;
-  a.rel_blocks = rel_step_blocks((int64_t)N * K * D);
-  a.spec_rows = spec_rows; a.spec_cap = spec_cap; a.spec_bitmap = spec_bitmap; a.spec_margin = spec_margin;
-  PassTail tail{new_rows, new_cap, sel_bitmap, false, words, false};
-  rc = launch_pair_pass<MODE_VIOL_RECOMPUTE>(ctx, a, pos_prev, nullptr, nullptr, nullptr, 0, &tail);
-  if (rc) return rc;
-  if (!tail.done) return scp_fail(ctx, SCP_ERR_STATE, "violations_from_solution: the small-problem pass did not run");
-  *fused = true;
-  return SCP_OK;
-}
-
-// internal (scp_common.h): scp_qp_get_solution + scp_kinematics + scp_check_avoidance + scp_select_pairs of a SMALL problem
-// in ONE launch (after QP#0): the select pass stages the kinematics of the QP's time-major solution, leaves positions and
-// solution in the reference layout behind, reduces the a8 statistics (the same ones the check pass reduces) and, for the
-// reference's print, leaves the two positions of the first violating pair in the mirror.
-int scp_select_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end,
-                             const double* x_tm, const double* p0, const double* v0, double* x_out, double* pos_out,
-                             double margin, int64_t* sel_rows, int64_t sel_cap, uint32_t* sel_bitmap, scp_pair_stats* stats,
-                             bool* fused) {
-  *fused = false;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  const int64_t nq = q_end - q_begin;
-  if (!small_pass_ok(ctx, N, K, D, nq, 1)) return SCP_OK;
-  PairArgs a{};
-  a.N = N; a.K = K; a.D = D; a.R = R; a.h = h;
-  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  a.margin = margin;
-  a.bitmap = sel_bitmap; a.mark = sel_bitmap; a.stats = stats;
-  a.eta_stride = scp_eta_stride(K, nq);
-  a.x_tm = x_tm; a.p0 = p0; a.v0 = v0; a.x_out = x_out; a.pos_out = pos_out;
-  PassTail tail{sel_rows, sel_cap, sel_bitmap, true, (K * nq + 31) / 32, false};
-  rc = launch_pair_pass<MODE_SELECT>(ctx, a, nullptr, nullptr, nullptr, nullptr, 0, &tail);
-  if (rc) return rc;
-  if (!tail.done) return scp_fail(ctx, SCP_ERR_STATE, "select_from_solution: the small-problem pass did not run");
-  *fused = true;
-  return SCP_OK;
-}
-
 // ----------------------------------------------------------------------------------------------------
 // gather compact rows
 // ----------------------------------------------------------------------------------------------------
@@ -2194,7 +1521,7 @@ extern "C" int scp_gather_rows(scp_ctx* ctx, int N, int K, int D, int64_t q_begi
                                const double* eta, const double* l_col, const int64_t* rows, int64_t n,
                                double* w_eta, double* w_l) {
   if (!ctx) return SCP_ERR_INVALID;
-  int rc = check_pair_range(ctx, N, K, D, q_begin, q_end);
+  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
   if (rc) return rc;
   if (n <= 0) return SCP_OK;
   SCP_REQUIRE(ctx, eta && l_col && rows && w_eta && w_l, "gather_rows: null pointer");
@@ -2202,72 +1529,5 @@ extern "C" int scp_gather_rows(scp_ctx* ctx, int N, int K, int D, int64_t q_begi
                      scp_eta_stride(K, q_end - q_begin), D, scp_pairs(N), q_begin, q_end - q_begin, eta, l_col, rows,
                      n, w_eta, w_l);
   SCP_HIP_CHECK(ctx, hipGetLastError());
-  return SCP_OK;
-}
-
-// ----------------------------------------------------------------------------------------------------
-// a1: relative step (scp.py:157-159)
-// ----------------------------------------------------------------------------------------------------
-// partial[2 b], partial[2 b + 1] = block b's sums; the partials live in mapped host memory and the LAST block to finish
-// (a ticket counter in device memory, at most 32 tickets) raises the completion word, so the host needs neither a copy
-// launch nor a stream drain to read them.
-__global__ __launch_bounds__(256) void rel_step_partial_kernel(int64_t n, const double* __restrict__ a,
-                                                                const double* __restrict__ b,
-                                                                double* __restrict__ partial,
-                                                                unsigned* __restrict__ ticket,
-                                                                unsigned long long* __restrict__ done,
-                                                                unsigned long long seq) {
-  __shared__ double s0[4], s1[4];
-  double d2 = 0.0, b2 = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
-    rel_accum(a[t], b[t], d2, b2);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    d2 += __shfl_xor(d2, o);
-    b2 += __shfl_xor(b2, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s0[threadIdx.x >> 6] = d2;
-    s1[threadIdx.x >> 6] = b2;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __hip_atomic_store((unsigned long long*)&partial[2 * blockIdx.x],
-                       (unsigned long long)__double_as_longlong((s0[0] + s0[1]) + (s0[2] + s0[3])), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store((unsigned long long*)&partial[2 * blockIdx.x + 1],
-                       (unsigned long long)__double_as_longlong((s1[0] + s1[1]) + (s1[2] + s1[3])), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
-      *ticket = 0u;  // (the next launch on this stream starts after this kernel has ended)
-      __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-
-extern "C" int scp_rel_step(scp_ctx* ctx, int64_t n, const double* a_new, const double* a_prev, double* out) {
-  if (!ctx) return SCP_ERR_INVALID;
-  SCP_REQUIRE(ctx, n > 0 && a_new && a_prev && out, "rel_step: bad arguments");
-  const int blocks = rel_step_blocks(n);
-  // the (at most 64) partial sums go straight to the mapped host scratch: no copy launch
-  const unsigned long long seq = ++ctx->rel_seq;
-  hipLaunchKernelGGL(rel_step_partial_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n, a_new, a_prev,
-                     ctx->h_scratch_dev, (unsigned*)(ctx->d_scratch + 64), (unsigned long long*)(ctx->h_scratch_dev + 64), seq);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  {
-    volatile unsigned long long* flag = (volatile unsigned long long*)(ctx->h_scratch + 64);
-    if (!scp_wait_host_word(flag, seq, 30)) SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // a fault surfaces here
-    if (*flag != seq) return scp_fail(ctx, SCP_ERR_HIP, "rel_step: completion word not written");
-  }
-  double d2 = 0.0, b2 = 0.0;
-  for (int b = 0; b < blocks; ++b) {
-    d2 += ctx->h_scratch[2 * b];
-    b2 += ctx->h_scratch[2 * b + 1];
-  }
-  out[0] = std::sqrt(d2);
-  out[1] = std::sqrt(b2);
-  out[2] = out[0] / out[1];
   return SCP_OK;
 }

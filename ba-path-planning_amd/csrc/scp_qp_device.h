@@ -2,6 +2,7 @@
 // scans on data-parallel-primitive (DPP) moves, MFMA operand prefetch, LDS padding.  gfx950 only.
 #pragma once
 #include "scp_qp_internal.h"
+#include "scp_wave_device.h"
 
 namespace scpdev {
 
@@ -20,35 +21,29 @@ __device__ inline void tile_prefetch(const double* __restrict__ P, int nks, int 
 }
 
 // ---- wave-wide prefix sums over the time index: the integrator blocks V, S, S0 and their transposes are first and
-// second cumulative sums.  DPP moves (no LDS round trip, unlike __shfl): lanes without a source read 0 -----------------
-template <int CTRL, int ROW_MASK>
-__device__ inline double dpp_mov0(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
+// second cumulative sums.  DPP moves (scp_wave_device.h; no LDS round trip, unlike __shfl): lanes without a source read 0
 // inclusive sum over the 64 lanes: row_shr 1, 2, 4, 8, then row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2, 3
 __device__ inline double wave_incl_sum(double v) {
-  v += dpp_mov0<0x111, 0xF>(v);
-  v += dpp_mov0<0x112, 0xF>(v);
-  v += dpp_mov0<0x114, 0xF>(v);
-  v += dpp_mov0<0x118, 0xF>(v);
-  v += dpp_mov0<0x142, 0xA>(v);
-  v += dpp_mov0<0x143, 0xC>(v);
+  v += dpp_move<0x111, 0xF, false>(v);
+  v += dpp_move<0x112, 0xF, false>(v);
+  v += dpp_move<0x114, 0xF, false>(v);
+  v += dpp_move<0x118, 0xF, false>(v);
+  v += dpp_move<0x142, 0xA, false>(v);
+  v += dpp_move<0x143, 0xC, false>(v);
   return v;
 }
 // maximum of non-negative values over the 64 lanes, valid in lane 63
 __device__ inline double wave_max_nn(double v) {
-  v = fmax(v, dpp_mov0<0x111, 0xF>(v));
-  v = fmax(v, dpp_mov0<0x112, 0xF>(v));
-  v = fmax(v, dpp_mov0<0x114, 0xF>(v));
-  v = fmax(v, dpp_mov0<0x118, 0xF>(v));
-  v = fmax(v, dpp_mov0<0x142, 0xA>(v));
-  v = fmax(v, dpp_mov0<0x143, 0xC>(v));
+  v = fmax(v, dpp_move<0x111, 0xF, false>(v));
+  v = fmax(v, dpp_move<0x112, 0xF, false>(v));
+  v = fmax(v, dpp_move<0x114, 0xF, false>(v));
+  v = fmax(v, dpp_move<0x118, 0xF, false>(v));
+  v = fmax(v, dpp_move<0x142, 0xA, false>(v));
+  v = fmax(v, dpp_move<0x143, 0xC, false>(v));
   return v;
 }
-__device__ inline double lane_below(double v) { return dpp_mov0<0x138, 0xF>(v); }  // wave_shr:1 (lane 0 <- 0)
-__device__ inline double lane_above(double v) { return dpp_mov0<0x130, 0xF>(v); }  // wave_shl:1 (lane 63 <- 0)
+__device__ inline double lane_below(double v) { return dpp_move<0x138, 0xF, false>(v); }  // wave_shr:1 (lane 0 <- 0)
+__device__ inline double lane_above(double v) { return dpp_move<0x130, 0xF, false>(v); }  // wave_shl:1 (lane 63 <- 0)
 
 __device__ inline double read_lane(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
@@ -58,10 +53,10 @@ __device__ inline double read_lane(double v, int lane) {
 // inclusive SUFFIX sum over the 64 lanes (lane l <- sum of lanes >= l): row_shl 1, 2, 4, 8 inside the rows of 16, then
 // the totals of the higher rows (lanes 16, 32, 48 after the row scans) are added through scalar registers
 __device__ inline double wave_incl_rsum(double v) {
-  v += dpp_mov0<0x101, 0xF>(v);
-  v += dpp_mov0<0x102, 0xF>(v);
-  v += dpp_mov0<0x104, 0xF>(v);
-  v += dpp_mov0<0x108, 0xF>(v);
+  v += dpp_move<0x101, 0xF, false>(v);
+  v += dpp_move<0x102, 0xF, false>(v);
+  v += dpp_move<0x104, 0xF, false>(v);
+  v += dpp_move<0x108, 0xF, false>(v);
   const double t1 = read_lane(v, 16), t2 = read_lane(v, 32), t3 = read_lane(v, 48);
   const int lane = threadIdx.x & 63;
   const double t23 = t2 + t3;

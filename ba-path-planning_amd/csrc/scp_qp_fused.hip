@@ -895,10 +895,6 @@ __global__ __launch_bounds__(256) void csr_count_kernel(int64_t nW, int K, const
 // exclusive scan of cnt[0..ncell) into ptr (in place: cnt and ptr are the same array), cursors = ptr.  Two launches that
 // fill the chip instead of one workgroup walking the array (67 us at N K = 51 200, a fortieth of the benchmark step):
 // (1) every workgroup scans its own 4096 cells and leaves their total, (2) every workgroup adds the totals before it.
-template <int CTRL, int ROW_MASK>
-__device__ inline int dpp_mov0_i32(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xF, true);
-}
 constexpr int SCAN_SC = 16;                 // consecutive cells per thread
 constexpr int SCAN_CELLS = 256 * SCAN_SC;   // per workgroup
 __global__ __launch_bounds__(256) void csr_scan_local_kernel(int ncell, int* __restrict__ ptr, int* __restrict__ blk_tot) {
@@ -912,12 +908,12 @@ __global__ __launch_bounds__(256) void csr_scan_local_kernel(int ncell, int* __r
     tot += v[e];
   }
   int incl = tot;
-  incl += dpp_mov0_i32<0x111, 0xF>(incl);
-  incl += dpp_mov0_i32<0x112, 0xF>(incl);
-  incl += dpp_mov0_i32<0x114, 0xF>(incl);
-  incl += dpp_mov0_i32<0x118, 0xF>(incl);
-  incl += dpp_mov0_i32<0x142, 0xA>(incl);
-  incl += dpp_mov0_i32<0x143, 0xC>(incl);
+  incl += dpp_move<0x111, 0xF, false>(incl);
+  incl += dpp_move<0x112, 0xF, false>(incl);
+  incl += dpp_move<0x114, 0xF, false>(incl);
+  incl += dpp_move<0x118, 0xF, false>(incl);
+  incl += dpp_move<0x142, 0xA, false>(incl);
+  incl += dpp_move<0x143, 0xC, false>(incl);
   if (lane == 63) wsum[wave] = incl;
   __syncthreads();
   int run = incl - tot;

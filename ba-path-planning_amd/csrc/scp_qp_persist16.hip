@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
       }
     }
   }
-  // The velocity / position bounds of this lane's rows are re-derived where they are needed -- bound_of() of scp_kernels.hip,
+  // The velocity / position bounds of this lane's rows are re-derived where they are needed -- bound_of() of scp_traj.hip,
   // the same arithmetic on the same operands (scp.py:212-224, :242-257), so the same bits as the lf / uf slabs -- from 4
   // registers (the free position of the row's state, k + 1) and eight per-agent scalars in LDS, instead of being held in 16.
   if (threadIdx.x < APB16 * D) {

@@ -472,16 +472,7 @@ extern "C" int scp_generate_grid_swap(scp_ctx* ctx, int B, int N, int D, const u
   const size_t o_swept = gen_align(o_unmet + sizeof(int) * (size_t)B * nblk), o_min = gen_align(o_swept + sizeof(int) * B);
   const size_t o_cnt = gen_align(o_min + 8 * (size_t)B), total = gen_align(o_cnt + 8 * (size_t)B);
   SCP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (ctx->gen_ws_bytes < total) {
-    if (ctx->gen_ws) {
-      SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-      SCP_HIP_CHECK(ctx, hipFree(ctx->gen_ws));
-      ctx->gen_ws = nullptr;
-      ctx->gen_ws_bytes = 0;
-    }
-    SCP_HIP_CHECK(ctx, hipMalloc(&ctx->gen_ws, total));
-    ctx->gen_ws_bytes = total;
-  }
+  if (const int rc = scp_ctx_ensure_bytes(ctx, &ctx->gen_ws, &ctx->gen_ws_bytes, total)) return rc;
   if (!ctx->h_gen_flag) {
     SCP_HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->h_gen_flag, 64, hipHostMallocMapped));
     SCP_HIP_CHECK(ctx, hipHostGetDevicePointer((void**)&ctx->d_gen_flag, ctx->h_gen_flag, 0));

@@ -389,19 +389,6 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_finish_kernel(const SepPartia
   }
 }
 
-int ensure_sep_ws(scp_ctx* ctx, size_t bytes) {
-  if (ctx->sep_ws_bytes >= bytes) return SCP_OK;
-  if (ctx->sep_ws) {
-    SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    SCP_HIP_CHECK(ctx, hipFree(ctx->sep_ws));
-    ctx->sep_ws = nullptr;
-    ctx->sep_ws_bytes = 0;
-  }
-  SCP_HIP_CHECK(ctx, hipMalloc(&ctx->sep_ws, bytes));
-  ctx->sep_ws_bytes = bytes;
-  return SCP_OK;
-}
-
 int64_t tile_start(int64_t r, int64_t nt) { return r * nt - r * (r - 1) / 2; }
 
 }  // namespace
@@ -444,7 +431,8 @@ extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h,
   const int n_chunks = scp_cdiv(K, kc);
   const int64_t n_part = n_tiles * n_chunks;
   const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
-  rc = ensure_sep_ws(ctx, rec_bytes + (size_t)std::max<int64_t>(n_part, 1) * sizeof(SepPartial) + 64);
+  rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes,
+                            rec_bytes + (size_t)std::max<int64_t>(n_part, 1) * sizeof(SepPartial) + 64);
   if (rc) return rc;
   double* rec = (double*)ctx->sep_ws;
   SepPartial* part = (SepPartial*)((char*)ctx->sep_ws + rec_bytes);
