@@ -1,6 +1,6 @@
 // Device functions of the pairwise geometry shared by the translation units of libscp_hip.so (gfx950 only): the pairwise
 // passes (scp_kernels.hip) and the kernel that installs recomputed working rows together with their incidence lists
-// (scp_qp_fused.hip) must produce the same bits, so there is ONE definition of each.
+// (scp_qp_rows.hip) must produce the same bits, so there is ONE definition of each.
 #pragma once
 #include <hip/hip_runtime.h>
 

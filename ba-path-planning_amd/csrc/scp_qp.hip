@@ -16,394 +16,19 @@
 //
 // Device layout: every vector lives time-major, [rows][C] with C = N*D columns (c = i*D + d).  Fixed rows are
 // stacked as  [0,K-1) jerk | [K-1,2K-1) acc | [2K-1,3K-1) vel | [3K-1,4K-1) pos.
-// oracle/qp_oracle.py:admm_structured is the line-by-line CPU statement of this file.
+// oracle/qp_oracle.py:admm_structured is the line-by-line CPU statement of the solve.
+//
+// This file owns the solver object: the C-ABI (scp_qp_* of include/scp_hip.h), lifecycle and settings, the workspace
+// carving, the host logic of reset / add rows, the choice of the ADMM pipeline and the scp_qp_solve loop, and the
+// clone / get / peek / debug hooks.  The kernels live with their owners: scp_qp_generic.hip (one product per launch),
+// scp_qp_columns.hip (column-block kernels), scp_qp_rows.hip (working rows, incidence lists), scp_qp_kkt.hip (per rho),
+// scp_qp_persist*.hip (persistent kernels).  The one kernel here is the reset's own launch.
 #include "scp_qp_internal.h"
 #include "scp_reset_device.h"
 
 #include <chrono>
 #include <cmath>
 #include <vector>
-
-// ----------------------------------------------------------------------------------------------------
-// kernels
-// ----------------------------------------------------------------------------------------------------
-__device__ inline double sum_partials(const double* part) {
-  double s = 0.0;
-  for (int b = 0; b < NPART; ++b) s += part[b];
-  return s;
-}
-
-// part[b] = sum over this block's grid-stride share of a.b (fixed tree, deterministic)
-__global__ __launch_bounds__(256) void dot_partial_kernel(int64_t n, const double* __restrict__ a,
-                                                           const double* __restrict__ b, double* __restrict__ part) {
-  __shared__ double s[4];
-  double acc = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)NPART * 256) acc += a[t] * b[t];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// wf = rho * w[row] * zf - yf   (Rf x C);  rhs = sigma * x  (K x C, first K*C threads)
-__global__ __launch_bounds__(256) void admm_rhs_prep_kernel(int64_t nf, int64_t nx, int64_t C, double rho, double sigma,
-                                                             const double* __restrict__ wrow,
-                                                             const double* __restrict__ zf,
-                                                             const double* __restrict__ yf, double* __restrict__ wf,
-                                                             const double* __restrict__ x, double* __restrict__ rhs) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < nf) wf[t] = rho * wrow[t / C] * zf[t] - yf[t];
-  if (t < nx) rhs[t] = sigma * x[t];
-}
-
-enum RowMode { ROW_RHS = 0, ROW_HMUL = 1, ROW_Y = 2, ROW_VEC = 3 };
-
-// r = rhs - Hx
-__global__ __launch_bounds__(256) void cg_residual_kernel(int64_t n, const double* __restrict__ rhs,
-                                                           const double* __restrict__ Hx, double* __restrict__ r) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < n) r[t] = rhs[t] - Hx[t];
-}
-
-// p = zz ; scal[SL_RZ0] = sum(part)
-__global__ __launch_bounds__(256) void cg_start_kernel(int64_t n, const double* __restrict__ zz, double* __restrict__ p,
-                                                        const double* __restrict__ part, double* __restrict__ scal) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < n) p[t] = zz[t];
-  if (t == 0) scal[SL_RZ0] = sum_partials(part);
-}
-
-// alpha = rz / pHp ; xt += alpha p ; r -= alpha Hp
-__global__ __launch_bounds__(256) void cg_update_kernel(int64_t n, int slot, const double* __restrict__ scal,
-                                                         const double* __restrict__ part_pHp,
-                                                         const double* __restrict__ p, const double* __restrict__ Hp,
-                                                         double* __restrict__ xt, double* __restrict__ r) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const double rz = scal[slot];
-  const double pHp = sum_partials(part_pHp);
-  const double alpha = (pHp > 0.0 && rz != 0.0) ? rz / pHp : 0.0;
-  if (t < n) {
-    xt[t] += alpha * p[t];
-    r[t] -= alpha * Hp[t];
-  }
-}
-
-// beta = rz_new / rz ; p = zz + beta p ; scal[slot^1] = rz_new
-__global__ __launch_bounds__(256) void cg_direction_kernel(int64_t n, int slot, double* __restrict__ scal,
-                                                            const double* __restrict__ part_rz,
-                                                            const double* __restrict__ zz, double* __restrict__ p) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const double rz = scal[slot];
-  const double rz_new = sum_partials(part_rz);
-  const double beta = rz != 0.0 ? rz_new / rz : 0.0;
-  if (t < n) p[t] = zz[t] + beta * p[t];
-  if (t == 0) scal[slot ^ 1] = rz_new;
-}
-
-// fixed rows: relaxation, projection, dual update (OSQP steps 4-6);  x = alpha xt + (1-alpha) x
-__global__ __launch_bounds__(256) void admm_fixed_update_kernel(int64_t nf, int64_t nx, int64_t C, double rho,
-                                                                 double alpha, const double* __restrict__ wrow,
-                                                                 const double* __restrict__ tf,
-                                                                 const double* __restrict__ lf,
-                                                                 const double* __restrict__ uf, double* __restrict__ zf,
-                                                                 double* __restrict__ yf, const double* __restrict__ xt,
-                                                                 double* __restrict__ x) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t < nf) {
-    const double rr = rho * wrow[t / C];
-    const double zh = alpha * tf[t] + (1.0 - alpha) * zf[t];
-    const double y = yf[t];
-    const double zn = fmin(fmax(zh + y / rr, lf[t]), uf[t]);
-    yf[t] = y + rr * (zh - zn);
-    zf[t] = zn;
-  }
-  if (t < nx) x[t] = alpha * xt[t] + (1.0 - alpha) * x[t];
-}
-
-// collision rows: same update with u = +inf
-template <int D>
-__global__ __launch_bounds__(256) void admm_row_update_kernel(int64_t nW, int64_t C, double rho, double alpha,
-                                                               const int* __restrict__ wk, const int* __restrict__ wi,
-                                                               const int* __restrict__ wj,
-                                                               const double* __restrict__ weta,
-                                                               const double* __restrict__ wl,
-                                                               const double* __restrict__ Q, double* __restrict__ zc,
-                                                               double* __restrict__ yc) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nW) return;
-  const int64_t bi = (int64_t)wk[n] * C + (int64_t)wi[n] * D;
-  const int64_t bj = (int64_t)wk[n] * C + (int64_t)wj[n] * D;
-  double tc = 0.0;
-#pragma unroll
-  for (int d = 0; d < D; ++d) tc += weta[n * D + d] * (Q[bi + d] - Q[bj + d]);
-  const double zh = alpha * tc + (1.0 - alpha) * zc[n];
-  const double y = yc[n];
-  const double zn = fmax(zh + y / rho, wl[n]);
-  yc[n] = y + rho * (zh - zn);
-  zc[n] = zn;
-}
-
-__device__ inline void atomic_max_nonneg(double* addr, double v) {
-  atomicMax((unsigned long long*)addr, (unsigned long long)__double_as_longlong(v));
-}
-
-__device__ inline double block_max(double v) {
-  __shared__ double s[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double m = fmax(fmax(s[0], s[1]), fmax(s[2], s[3]));
-  __syncthreads();
-  return m;
-}
-
-// primal residual pieces over the fixed rows: max|Fx - z|, max|Fx|, max|z|
-__global__ __launch_bounds__(256) void resid_fixed_kernel(int64_t nf, const double* __restrict__ tf,
-                                                           const double* __restrict__ zf, double* __restrict__ scal) {
-  double rp = 0.0, na = 0.0, nz = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nf; t += (int64_t)gridDim.x * 256) {
-    const double a = tf[t], z = zf[t];
-    rp = fmax(rp, fabs(a - z));
-    na = fmax(na, fabs(a));
-    nz = fmax(nz, fabs(z));
-  }
-  rp = block_max(rp);
-  na = block_max(na);
-  nz = block_max(nz);
-  if (threadIdx.x == 0) {
-    atomic_max_nonneg(scal + SL_RP, rp);
-    atomic_max_nonneg(scal + SL_NAX, na);
-    atomic_max_nonneg(scal + SL_NZ, nz);
-  }
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void resid_rows_kernel(int64_t nW, int64_t C, const int* __restrict__ wk,
-                                                          const int* __restrict__ wi, const int* __restrict__ wj,
-                                                          const double* __restrict__ weta,
-                                                          const double* __restrict__ Q, const double* __restrict__ zc,
-                                                          double* __restrict__ scal) {
-  double rp = 0.0, na = 0.0, nz = 0.0;
-  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < nW; n += (int64_t)gridDim.x * 256) {
-    const int64_t bi = (int64_t)wk[n] * C + (int64_t)wi[n] * D;
-    const int64_t bj = (int64_t)wk[n] * C + (int64_t)wj[n] * D;
-    double a = 0.0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) a += weta[n * D + d] * (Q[bi + d] - Q[bj + d]);
-    const double z = zc[n];
-    rp = fmax(rp, fabs(a - z));
-    na = fmax(na, fabs(a));
-    nz = fmax(nz, fabs(z));
-  }
-  rp = block_max(rp);
-  na = block_max(na);
-  nz = block_max(nz);
-  if (threadIdx.x == 0) {
-    atomic_max_nonneg(scal + SL_RP, rp);
-    atomic_max_nonneg(scal + SL_NAX, na);
-    atomic_max_nonneg(scal + SL_NZ, nz);
-  }
-}
-
-// dual residual pieces: max|2x + ATy|, max|2x|, max|ATy|
-__global__ __launch_bounds__(256) void resid_dual_kernel(int64_t nx, const double* __restrict__ x,
-                                                          const double* __restrict__ aty, double* __restrict__ scal) {
-  double rd = 0.0, npx = 0.0, nat = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nx; t += (int64_t)gridDim.x * 256) {
-    const double px = 2.0 * x[t], a = aty[t];
-    rd = fmax(rd, fabs(px + a));
-    npx = fmax(npx, fabs(px));
-    nat = fmax(nat, fabs(a));
-  }
-  rd = block_max(rd);
-  npx = block_max(npx);
-  nat = block_max(nat);
-  if (threadIdx.x == 0) {
-    atomic_max_nonneg(scal + SL_RD, rd);
-    atomic_max_nonneg(scal + SL_NPX, npx);
-    atomic_max_nonneg(scal + SL_NATY, nat);
-  }
-}
-
-// primal infeasibility certificate, fixed rows: dy = y - snapshot (in place), max |dy|, sum u dy+ + l dy-
-__global__ __launch_bounds__(256) void dy_fixed_kernel(int64_t nf, const double* __restrict__ yf,
-                                                        const double* __restrict__ lf, const double* __restrict__ uf,
-                                                        double* __restrict__ dyf, double* __restrict__ scal) {
-  __shared__ double ssum[4];
-  double mx = 0.0, sup = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < nf; t += (int64_t)gridDim.x * 256) {
-    const double d = yf[t] - dyf[t];
-    dyf[t] = d;
-    mx = fmax(mx, fabs(d));
-    sup += uf[t] * fmax(d, 0.0) + lf[t] * fmin(d, 0.0);
-  }
-  mx = block_max(mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sup += __shfl_xor(sup, o);
-  if ((threadIdx.x & 63) == 0) ssum[threadIdx.x >> 6] = sup;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomic_max_nonneg(scal + SL_NDY, mx);
-    atomicAdd(scal + SL_SUPP, (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]));
-  }
-}
-
-// collision rows (u = +inf): dy = min(y - snapshot, 0)
-__global__ __launch_bounds__(256) void dy_rows_kernel(int64_t nW, const double* __restrict__ yc,
-                                                       const double* __restrict__ wl, double* __restrict__ dyc,
-                                                       double* __restrict__ scal) {
-  __shared__ double ssum[4];
-  double mx = 0.0, sup = 0.0;
-  for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < nW; n += (int64_t)gridDim.x * 256) {
-    const double d = fmin(yc[n] - dyc[n], 0.0);
-    dyc[n] = d;
-    mx = fmax(mx, fabs(d));
-    sup += wl[n] * d;
-  }
-  mx = block_max(mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sup += __shfl_xor(sup, o);
-  if ((threadIdx.x & 63) == 0) ssum[threadIdx.x >> 6] = sup;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    atomic_max_nonneg(scal + SL_NDY, mx);
-    atomicAdd(scal + SL_SUPP, (ssum[0] + ssum[1]) + (ssum[2] + ssum[3]));
-  }
-}
-
-__global__ __launch_bounds__(256) void max_abs_kernel(int64_t n, const double* __restrict__ v, double* __restrict__ slot) {
-  double mx = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) mx = fmax(mx, fabs(v[t]));
-  mx = block_max(mx);
-  if (threadIdx.x == 0) atomic_max_nonneg(slot, mx);
-}
-
-// G0[a][b] = sum_r w_r F[r][a] F[r][b]  (constant per problem shape: once at create)
-__global__ __launch_bounds__(256) void build_g0_kernel(int K, int Rf, const double* __restrict__ F,
-                                                        const double* __restrict__ wrow, double* __restrict__ G0) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= K * K) return;
-  const int a = t / K, b = t % K;
-  double s = 0.0;
-  for (int r = 0; r < Rf; ++r) s += wrow[r] * F[(int64_t)r * K + a] * F[(int64_t)r * K + b];
-  G0[t] = s;
-}
-
-// Hf[a][b] = (2 + sigma) delta_ab + rho G0[a][b];  HS = [Hf ; S0];  aug = [Hf | I]
-__global__ __launch_bounds__(256) void build_hf_kernel(int K, double rho, double sigma, const double* __restrict__ G0,
-                                                        const double* __restrict__ S0, double* __restrict__ Hf,
-                                                        double* __restrict__ HS, double* __restrict__ aug) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= K * K) return;
-  const int a = t / K, b = t % K;
-  const double v = rho * G0[t] + (a == b ? 2.0 + sigma : 0.0);
-  Hf[t] = v;
-  HS[t] = v;
-  HS[K * K + t] = S0[t];
-  aug[(int64_t)a * 2 * K + b] = v;
-  aug[(int64_t)a * 2 * K + K + b] = a == b ? 1.0 : 0.0;
-}
-
-// Gauss-Jordan inverse with [Hf | I] resident in LDS (K <= SCP_INV_LDS_MAX_K); same operations as the global one.
-// Thread (ty, tx): column tx of the augmented matrix, rows ty, ty + TY, ... (no integer divisions in the pivot loop).
-__global__ __launch_bounds__(1024) void spd_inverse_lds_kernel(int K, const double* __restrict__ Hf, double* __restrict__ Minv) {
-  extern __shared__ double sh[];  // aug[K][2K] | prow[2K] | col[K]
-  const int W = 2 * K;
-  double* aug = sh;
-  double* prow = aug + K * W;
-  double* col = prow + W;
-  const int TX = W <= 128 ? 128 : 256, TY = 1024 / TX;
-  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
-  if (tx < W)
-    for (int r = ty; r < K; r += TY) aug[r * W + tx] = tx < K ? Hf[r * K + tx] : (tx - K == r ? 1.0 : 0.0);
-  __syncthreads();
-  for (int p = 0; p < K; ++p) {
-    const double piv = aug[p * W + p];
-    if (threadIdx.x < W) prow[threadIdx.x] = aug[p * W + threadIdx.x] / piv;
-    else if (threadIdx.x >= 512 && threadIdx.x - 512 < K) col[threadIdx.x - 512] = aug[(threadIdx.x - 512) * W + p];
-    __syncthreads();
-    if (tx < W) {
-      const double pr = prow[tx];
-      for (int r = ty; r < K; r += TY) {
-        if (r == p) aug[r * W + tx] = pr;
-        else aug[r * W + tx] -= col[r] * pr;
-      }
-    }
-    __syncthreads();
-  }
-  if (tx < K)
-    for (int r = ty; r < K; r += TY) Minv[r * K + tx] = aug[r * W + K + tx];
-}
-
-// Gauss-Jordan inverse for K > SCP_INV_LDS_MAX_K, two small launches per pivot over the whole chip: the pivot row (scaled)
-// and the pivot column are first copied out, then every element of aug = [Hf | I] is updated from them -- the same
-// operation per element as the one-workgroup kernels (bit-identical result), but a pivot's K x 2K update is spread over
-// all CUs instead of dragging the 4 MB matrix (K = 500) through one CU 500 times (61 ms -> ~3 ms per inverse; the
-// reference's demo, K = 500, spent 88 % of its 0.65 s there).
-__global__ __launch_bounds__(256) void gj_extract_kernel(int K, int p, const double* __restrict__ aug, double* __restrict__ prow,
-                                                          double* __restrict__ pcol) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int W = 2 * K;
-  if (t < W) prow[t] = aug[(int64_t)p * W + t] / aug[(int64_t)p * W + p];
-  else if (t - W < K) pcol[t - W] = aug[(int64_t)(t - W) * W + p];
-}
-__global__ __launch_bounds__(256) void gj_update_kernel(int K, int p, double* __restrict__ aug, const double* __restrict__ prow,
-                                                         const double* __restrict__ pcol) {
-  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int W = 2 * K;
-  if (e >= (int64_t)K * W) return;
-  const int r = (int)(e / W), c = (int)(e % W);
-  if (r == p) aug[e] = prow[c];
-  else aug[e] -= pcol[r] * prow[c];
-}
-__global__ __launch_bounds__(256) void gj_finish_kernel(int K, const double* __restrict__ aug, double* __restrict__ Minv) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < K * K) Minv[t] = aug[(int64_t)(t / K) * 2 * K + K + (t % K)];
-}
-
-// append working rows: decode (k, i, j), copy eta / l, z = max(A x, l), y = 0
-// eta_stride == 0: eta_in / l_in are the gathered [n][D] / [n] arrays of scp_gather_rows; otherwise they are the arrays of
-// the pairwise pass itself (pair range [q_begin, q_begin + nq)) and the gather happens here.
-__global__ __launch_bounds__(256) void add_rows_kernel(int N, int D, int64_t C, int64_t pairs, int64_t base, int64_t n,
-                                                        const int64_t* __restrict__ rows,
-                                                        const double* __restrict__ eta_in,
-                                                        const double* __restrict__ l_in, int64_t eta_stride,
-                                                        int64_t q_begin, int64_t nq, const double* __restrict__ Q,
-                                                        int64_t* __restrict__ w_row, int* __restrict__ wk,
-                                                        int* __restrict__ wi, int* __restrict__ wj,
-                                                        double* __restrict__ weta, double* __restrict__ wl,
-                                                        double* __restrict__ zc, double* __restrict__ yc) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= n) return;
-  const int64_t r = rows[t];
-  const int64_t k = r / pairs, q = r % pairs;
-  // lexicographic pair index -> (i, j)
-  const double b = 2.0 * N - 1.0;
-  int64_t ii = (int64_t)((b - sqrt(b * b - 8.0 * (double)q)) * 0.5);
-  if (ii < 0) ii = 0;
-  if (ii > N - 2) ii = N - 2;
-  while (ii * (2LL * N - ii - 1) / 2 > q) --ii;
-  while (ii < N - 2 && (ii + 1) * (2LL * N - ii - 2) / 2 <= q) ++ii;
-  const int64_t jj = q - ii * (2LL * N - ii - 1) / 2 + ii + 1;
-  const int64_t o = base + t;
-  w_row[o] = r;
-  wk[o] = (int)k;
-  wi[o] = (int)ii;
-  wj[o] = (int)jj;
-  const int64_t lr = k * nq + (q - q_begin);
-  double ax = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double e = eta_stride ? eta_in[(int64_t)d * eta_stride + lr] : eta_in[t * D + d];
-    weta[o * D + d] = e;
-    ax += e * (Q[k * C + ii * D + d] - Q[k * C + jj * D + d]);
-  }
-  const double lo = eta_stride ? l_in[lr] : l_in[t];
-  wl[o] = lo;
-  zc[o] = fmax(ax, lo);
-  yc[o] = 0.0;
-}
 
 // scp_qp_reset in one launch (K <= SCP_FUSED_MAX_K): x0 in reference order [N][K][D] (null: zeros) -> x (time-major),
 // z_f = F x, the carried F x and S0 x of the single-step pipeline (exact), y_f = 0.  16 columns per workgroup (256 columns
@@ -435,19 +60,6 @@ struct Carver {
   }
 };
 
-size_t kkt_slot_doubles(int K) {  // Hf, HS, Minv, T + packed Minv, T, each 256-byte aligned
-  auto al = [](size_t n) { return (n + 31) / 32 * 32; };
-  return al((size_t)K * K) * 3 + al((size_t)2 * K * K) + 2 * al(scp_packed_count(K, K));
-}
-
-// Adaptive rho moves on a geometric grid (steps of 2^(1/4)), so a solver object that is reused from scenario to scenario
-// (compute-trajectories-batch) keeps meeting the same values: short horizons get enough slots to hold them all.
-int kkt_slots(int K) {
-  const size_t per = kkt_slot_doubles(K) * sizeof(double);
-  const size_t fit = SCP_KKT_POOL_BYTES / per;
-  return (int)std::min<size_t>(SCP_KKT_SLOTS_MAX, std::max<size_t>(SCP_KKT_SLOTS, fit));
-}
-
 size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
   const int Rf = 4 * K - 1;
   Carver c{static_cast<char*>(ws), 0};
@@ -455,13 +67,13 @@ size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
   d.Ft = c.take<double>((size_t)Rf * K);
   d.S0 = c.take<double>((size_t)K * K);
   d.S0t = c.take<double>((size_t)K * K);
-  d.HS = d.Hf = d.Minv = nullptr;  // rho-dependent blocks live in the cache slots (carve_kkt_slots), set by build_kkt
+  d.HS = d.Hf = d.Minv = nullptr;  // rho-dependent blocks live in the cache slots (scp_qp_kkt_init_slots), set by scp_qp_build_kkt
   d.aug = c.take<double>((size_t)2 * K * K);
   d.gj_tmp = c.take<double>((size_t)3 * K);
   d.wrow = c.take<double>((size_t)Rf);
   d.G0 = c.take<double>((size_t)K * K);
   d.pMinv = d.T = d.pT = nullptr;
-  d.kkt_pool = c.take<double>((size_t)kkt_slots(K) * kkt_slot_doubles(K));
+  d.kkt_pool = c.take<double>(scp_qp_kkt_pool_doubles(K));
   const size_t nf = (size_t)Rf * C, nx = (size_t)K * C;
   d.lf = c.take<double>(nf);
   d.uf = c.take<double>(nf);
@@ -510,219 +122,7 @@ size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
   return c.off;
 }
 
-inline dim3 grid1(int64_t n) { return dim3(scp_cdiv(n, 256)); }
-
-#define QP_LAUNCHED(qp) SCP_HIP_CHECK((qp)->ctx, hipGetLastError())
-
-int gemm(scp_qp* qp, int R, int M, double alpha, const double* A, const double* X, double beta, double* Y) {
-  return scp_launch_gemm(qp->ctx, qp->st.use_mfma, R, M, (int)qp->C, alpha, A, X, beta, Y);
-}
-
-// G = A_W^T g over the working rows, g by mode (a gather over the sorted incidence lists: fixed summation order; the
-// round-1 version scattered with atomics):
-//   ROW_RHS : rho zc - yc            (right-hand side of the x-update)
-//   ROW_HMUL: rho eta.(Q_i - Q_j)    (A_W^T R_c A_W v, Q = S0 v)
-//   ROW_Y   : yc                     (A_W^T y for the dual residual)
-//   ROW_VEC : vec                    (an arbitrary row vector)
-template <int MODE>
-int row_scatter(scp_qp* qp, const double* Q, const double* vec = nullptr) {
-  if (MODE == ROW_HMUL) return scp_qp_rows_gather(qp, Q);
-  return scp_qp_csr_scatter(qp, MODE == ROW_RHS ? 0 : (MODE == ROW_Y ? 1 : 2), vec);
-}
-
-// HQ[0:K] = H v = Hf v + A_W^T R_c A_W v ; HQ[K:2K] = S0 v
-int hmul(scp_qp* qp, const double* v) {
-  const QpDev& d = qp->d;
-  const int K = qp->K;
-  QP_CHECK(gemm(qp, 2 * K, K, 1.0, d.HS, v, 0.0, d.HQ));
-  if (qp->nW > 0) {
-    QP_CHECK(row_scatter<ROW_HMUL>(qp, d.HQ + (size_t)K * qp->C));
-    QP_CHECK(gemm(qp, K, K, 1.0, d.S0t, d.G, 1.0, d.HQ));
-  }
-  return SCP_OK;
-}
-
-int dot_partial(scp_qp* qp, const double* a, const double* b, double* part) {
-  hipLaunchKernelGGL(dot_partial_kernel, dim3(NPART), dim3(256), 0, qp->ctx->stream, (int64_t)qp->K * qp->C, a, b,
-                     part);
-  QP_LAUNCHED(qp);
-  return SCP_OK;
-}
-
-int build_kkt(scp_qp* qp) {
-  QpDev& d = qp->d;
-  const int K = qp->K;
-  hipStream_t s = qp->ctx->stream;
-  // cache lookup: the blocks of this (rho, sigma) may still be resident
-  scp_qp::KktSlot* slot = nullptr;
-  for (int i = 0; i < qp->n_kkt; ++i)
-    if (qp->kkt[i].used && qp->kkt[i].rho == qp->rho && qp->kkt[i].sigma == qp->st.sigma) slot = &qp->kkt[i];
-  const bool hit = slot != nullptr;
-  if (!hit) {
-    slot = &qp->kkt[0];
-    for (int i = 0; i < qp->n_kkt; ++i)
-      if (qp->kkt[i].used < slot->used) slot = &qp->kkt[i];  // empty (0) or least recently used
-  }
-  slot->used = ++qp->kkt_clock;
-  d.Hf = slot->Hf; d.HS = slot->HS; d.Minv = slot->Minv; d.T = slot->T;
-  d.pMinv = slot->pMinv; d.pT = slot->pT;
-  if (hit) return SCP_OK;
-  slot->rho = qp->rho;
-  slot->sigma = qp->st.sigma;
-  hipLaunchKernelGGL(build_hf_kernel, grid1((int64_t)K * K), dim3(256), 0, s, K, qp->rho, qp->st.sigma, d.G0, d.S0, d.Hf,
-                     d.HS, d.aug);
-  QP_LAUNCHED(qp);
-  if (K <= SCP_INV_LDS_MAX_K) {
-    const size_t lds = ((size_t)K * 2 * K + 3 * K) * sizeof(double);
-    if (lds > 64 * 1024)
-      SCP_HIP_CHECK(qp->ctx, scp_raise_lds_limit(qp->ctx->device, reinterpret_cast<const void*>(spd_inverse_lds_kernel), lds));
-    hipLaunchKernelGGL(spd_inverse_lds_kernel, dim3(1), dim3(1024), lds, s, K, d.Hf, d.Minv);
-  } else {
-    double* prow = d.gj_tmp;
-    double* pcol = d.gj_tmp + 2 * K;
-    for (int p = 0; p < K; ++p) {
-      hipLaunchKernelGGL(gj_extract_kernel, grid1((int64_t)3 * K), dim3(256), 0, s, K, p, d.aug, prow, pcol);
-      hipLaunchKernelGGL(gj_update_kernel, grid1((int64_t)K * 2 * K), dim3(256), 0, s, K, p, d.aug, prow, pcol);
-    }
-    hipLaunchKernelGGL(gj_finish_kernel, grid1((int64_t)K * K), dim3(256), 0, s, K, d.aug, d.Minv);
-  }
-  QP_LAUNCHED(qp);
-  // T = S0 H_f^{-1}: the persistent kernel forms S0 p = T r on spare matrix-core waves next to p = H_f^{-1} r
-  QP_CHECK(scp_launch_gemm(qp->ctx, 1, K, K, K, 1.0, d.S0, d.Minv, 0.0, d.T));
-  return scp_qp_pack_operands(qp);
-}
-
-int admm_iteration(scp_qp* qp, int* cg_count) {
-  const QpDev& d = qp->d;
-  scp_ctx* ctx = qp->ctx;
-  hipStream_t s = ctx->stream;
-  const int K = qp->K, Rf = qp->Rf;
-  const int64_t C = qp->C, nf = (int64_t)Rf * C, nx = (int64_t)K * C;
-  // rhs = sigma x + F^T (R_f z_f - y_f) + A_W^T (R_c z_c - y_c)
-  hipLaunchKernelGGL(admm_rhs_prep_kernel, grid1(nf), dim3(256), 0, s, nf, nx, C, qp->rho, qp->st.sigma, d.wrow, d.zf,
-                     d.yf, d.wf, d.x, d.rhs);
-  QP_LAUNCHED(qp);
-  QP_CHECK(gemm(qp, K, Rf, 1.0, d.Ft, d.wf, 1.0, d.rhs));
-  if (qp->nW > 0) {
-    QP_CHECK(row_scatter<ROW_RHS>(qp, nullptr));
-    QP_CHECK(gemm(qp, K, K, 1.0, d.S0t, d.G, 1.0, d.rhs));
-    // PCG on H x~ = rhs, preconditioner Minv, warm start x~ = x
-    SCP_HIP_CHECK(ctx, hipMemcpyAsync(d.xt, d.x, nx * sizeof(double), hipMemcpyDeviceToDevice, s));
-    QP_CHECK(hmul(qp, d.xt));
-    hipLaunchKernelGGL(cg_residual_kernel, grid1(nx), dim3(256), 0, s, nx, d.rhs, d.HQ, d.r);
-    QP_LAUNCHED(qp);
-    QP_CHECK(gemm(qp, K, K, 1.0, d.Minv, d.r, 0.0, d.zz));
-    QP_CHECK(dot_partial(qp, d.r, d.zz, d.part));
-    hipLaunchKernelGGL(cg_start_kernel, grid1(nx), dim3(256), 0, s, nx, d.zz, d.p, d.part, d.scal);
-    QP_LAUNCHED(qp);
-    int slot = SL_RZ0;
-    for (int it = 0; it < qp->st.cg_iters; ++it) {
-      QP_CHECK(hmul(qp, d.p));
-      QP_CHECK(dot_partial(qp, d.p, d.HQ, d.part));
-      hipLaunchKernelGGL(cg_update_kernel, grid1(nx), dim3(256), 0, s, nx, slot, d.scal, d.part, d.p, d.HQ, d.xt, d.r);
-      QP_LAUNCHED(qp);
-      QP_CHECK(gemm(qp, K, K, 1.0, d.Minv, d.r, 0.0, d.zz));
-      QP_CHECK(dot_partial(qp, d.r, d.zz, d.part + NPART));
-      hipLaunchKernelGGL(cg_direction_kernel, grid1(nx), dim3(256), 0, s, nx, slot, d.scal, d.part + NPART, d.zz, d.p);
-      QP_LAUNCHED(qp);
-      slot ^= 1;
-      ++*cg_count;
-    }
-  } else {
-    QP_CHECK(gemm(qp, K, K, 1.0, d.Minv, d.rhs, 0.0, d.xt));
-  }
-  // z~ = A x~, relaxation, projection, duals
-  QP_CHECK(gemm(qp, Rf, K, 1.0, d.F, d.xt, 0.0, d.tf));
-  if (qp->nW > 0) {
-    QP_CHECK(gemm(qp, K, K, 1.0, d.S0, d.xt, 0.0, d.HQ + nx));
-    if (qp->D == 2)
-      hipLaunchKernelGGL(admm_row_update_kernel<2>, grid1(qp->nW), dim3(256), 0, s, qp->nW, C,
-                         qp->rho * qp->st.rho_col_scale, qp->st.alpha,
-                         d.w_k, d.w_i, d.w_j, d.w_eta, d.w_l, d.HQ + nx, d.zc, d.yc);
-    else
-      hipLaunchKernelGGL(admm_row_update_kernel<3>, grid1(qp->nW), dim3(256), 0, s, qp->nW, C,
-                         qp->rho * qp->st.rho_col_scale, qp->st.alpha,
-                         d.w_k, d.w_i, d.w_j, d.w_eta, d.w_l, d.HQ + nx, d.zc, d.yc);
-    QP_LAUNCHED(qp);
-  }
-  hipLaunchKernelGGL(admm_fixed_update_kernel, grid1(nf), dim3(256), 0, s, nf, nx, C, qp->rho, qp->st.alpha, d.wrow,
-                     d.tf, d.lf, d.uf, d.zf, d.yf, d.xt, d.x);
-  QP_LAUNCHED(qp);
-  return SCP_OK;
-}
-
-// residuals -> qp->h_scal[SL_RP..SL_NATY]; with_dy: also delta-y = y - snapshot, its max norm and support value
-// (SL_NDY, SL_SUPP).  Synchronises the stream.
-int residuals(scp_qp* qp, bool with_dy) {
-  const QpDev& d = qp->d;
-  scp_ctx* ctx = qp->ctx;
-  hipStream_t s = ctx->stream;
-  const int K = qp->K, Rf = qp->Rf;
-  const int64_t C = qp->C, nf = (int64_t)Rf * C, nx = (int64_t)K * C;
-  SCP_HIP_CHECK(ctx, hipMemsetAsync(d.scal + SL_RP, 0, 9 * sizeof(double), s));
-  if (with_dy) {
-    hipLaunchKernelGGL(dy_fixed_kernel, dim3(256), dim3(256), 0, s, nf, d.yf, d.lf, d.uf, d.dyf, d.scal);
-    QP_LAUNCHED(qp);
-    if (qp->nW > 0) {
-      const int blocks = (int)((qp->nW + 255) / 256) < 256 ? (int)((qp->nW + 255) / 256) : 256;
-      hipLaunchKernelGGL(dy_rows_kernel, dim3(blocks), dim3(256), 0, s, qp->nW, d.yc, d.w_l, d.dyc, d.scal);
-      QP_LAUNCHED(qp);
-    }
-  }
-  QP_CHECK(gemm(qp, Rf, K, 1.0, d.F, d.x, 0.0, d.tf));
-  hipLaunchKernelGGL(resid_fixed_kernel, dim3(256), dim3(256), 0, s, nf, d.tf, d.zf, d.scal);
-  QP_LAUNCHED(qp);
-  // ATy -> rhs (scratch)
-  QP_CHECK(gemm(qp, K, Rf, 1.0, d.Ft, d.yf, 0.0, d.rhs));
-  if (qp->nW > 0) {
-    QP_CHECK(gemm(qp, K, K, 1.0, d.S0, d.x, 0.0, d.HQ + nx));
-    const int blocks = (int)((qp->nW + 255) / 256) < 256 ? (int)((qp->nW + 255) / 256) : 256;
-    if (qp->D == 2)
-      hipLaunchKernelGGL(resid_rows_kernel<2>, dim3(blocks), dim3(256), 0, s, qp->nW, C, d.w_k, d.w_i, d.w_j, d.w_eta,
-                         d.HQ + nx, d.zc, d.scal);
-    else
-      hipLaunchKernelGGL(resid_rows_kernel<3>, dim3(blocks), dim3(256), 0, s, qp->nW, C, d.w_k, d.w_i, d.w_j, d.w_eta,
-                         d.HQ + nx, d.zc, d.scal);
-    QP_LAUNCHED(qp);
-    QP_CHECK(row_scatter<ROW_Y>(qp, nullptr));
-    QP_CHECK(gemm(qp, K, K, 1.0, d.S0t, d.G, 1.0, d.rhs));
-  }
-  hipLaunchKernelGGL(resid_dual_kernel, dim3(128), dim3(256), 0, s, nx, d.x, d.rhs, d.scal);
-  QP_LAUNCHED(qp);
-  SCP_HIP_CHECK(ctx, hipMemcpyAsync(qp->h_scal, d.scal, SL_COUNT * sizeof(double), hipMemcpyDeviceToHost, s));
-  SCP_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  return SCP_OK;
-}
-
-// second half of the certificate: || A^T dy ||_inf -> h_scal[SL_NATDY] (synchronises)
-int certificate_atdy(scp_qp* qp) {
-  const QpDev& d = qp->d;
-  scp_ctx* ctx = qp->ctx;
-  hipStream_t s = ctx->stream;
-  const int K = qp->K, Rf = qp->Rf;
-  const int64_t nx = (int64_t)K * qp->C;
-  SCP_HIP_CHECK(ctx, hipMemsetAsync(d.scal + SL_NATDY, 0, sizeof(double), s));
-  QP_CHECK(gemm(qp, K, Rf, 1.0, d.Ft, d.dyf, 0.0, d.rhs));
-  if (qp->nW > 0) {
-    QP_CHECK(row_scatter<ROW_VEC>(qp, nullptr, d.dyc));
-    QP_CHECK(gemm(qp, K, K, 1.0, d.S0t, d.G, 1.0, d.rhs));
-  }
-  hipLaunchKernelGGL(max_abs_kernel, dim3(128), dim3(256), 0, s, nx, d.rhs, d.scal + SL_NATDY);
-  QP_LAUNCHED(qp);
-  SCP_HIP_CHECK(ctx, hipMemcpyAsync(qp->h_scal + SL_NATDY, d.scal + SL_NATDY, sizeof(double), hipMemcpyDeviceToHost, s));
-  SCP_HIP_CHECK(ctx, hipStreamSynchronize(s));
-  return SCP_OK;
-}
-
 }  // namespace
-
-int scp_qp_exact_qx(scp_qp* qp, bool with_fx) {
-  if (qp->dv.qx) return SCP_OK;
-  QP_CHECK(gemm(qp, qp->K, qp->K, 1.0, qp->d.S0, qp->d.x, 0.0, qp->d.HQ + (int64_t)qp->K * qp->C));
-  if (with_fx) QP_CHECK(gemm(qp, qp->Rf, qp->K, 1.0, qp->d.F, qp->d.x, 0.0, qp->d.fx));
-  qp_on_qx_built(qp, with_fx);
-  return SCP_OK;
-}
 
 // ----------------------------------------------------------------------------------------------------
 // C-ABI
@@ -789,25 +189,7 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
   qp->problem_set = qp->reset_done = false;
   qp->rho = s->rho;
   carve(qp->d, workspace, K, qp->C, row_capacity, D);
-  {
-    auto al = [](size_t n) { return (n + 31) / 32 * 32; };
-    double* base = qp->d.kkt_pool;
-    qp->n_kkt = kkt_slots(K);
-    for (int i = 0; i < qp->n_kkt; ++i) {
-      auto& k = qp->kkt[i];
-      double* q = base;
-      k.rho = k.sigma = 0.0;
-      k.used = 0;
-      k.Hf = q; q += al((size_t)K * K);
-      k.Minv = q; q += al((size_t)K * K);
-      k.T = q; q += al((size_t)K * K);
-      k.HS = q; q += al((size_t)2 * K * K);
-      k.pMinv = q; q += al(scp_packed_count(K, K));
-      k.pT = q;
-      base += kkt_slot_doubles(K);
-    }
-    qp->kkt_clock = 0;
-  }
+  scp_qp_kkt_init_slots(qp);
   qp->check_seq = 0;
   qp->persist_off = false;
   qp->persist_skip_solve = false;
@@ -862,8 +244,7 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
     delete qp;
     return scp_fail(ctx, SCP_ERR_HIP, "qp_create: constant upload failed");
   }
-  hipLaunchKernelGGL(build_g0_kernel, grid1((int64_t)K * K), dim3(256), 0, st, K, Rf, d.F, d.wrow, d.G0);
-  if (hipGetLastError() != hipSuccess) {
+  if (scp_qp_build_g0(qp) != SCP_OK) {
     (void)hipHostFree(qp->h_scal);
     delete qp;
     return scp_fail(ctx, SCP_ERR_HIP, "qp_create: launch failed");
@@ -930,14 +311,14 @@ static int reset_impl(scp_qp* qp, const double* x0, int64_t n, const int64_t* ro
     // (the install launch did the reset too)
   } else if (one_launch) {
     // z = A x (primal warm start, scp.py:443), y = 0 and the single-step pipeline's carried F x, S0 x in one launch
-    hipLaunchKernelGGL(qp_reset_kernel, dim3(scp_cdiv(qp->C, RESET_COLS)), dim3(256),
-                       (size_t)qp->K * RESET_COLS * sizeof(double), ctx->stream, qp->N, qp->K, qp->D, qp->Rf, x0, d.F, d.S0,
-                       d.x, d.zf, d.fx, d.HQ + nx, d.yf);
-    QP_LAUNCHED(qp);
+    QP_CHECK(qp_launch(qp, qp_reset_kernel, dim3(scp_cdiv(qp->C, RESET_COLS)), dim3(256),
+                       (size_t)qp->K * RESET_COLS * sizeof(double), qp->N, qp->K, qp->D, qp->Rf, x0, d.F, d.S0, d.x, d.zf, d.fx,
+                       d.HQ + nx, d.yf));
   } else {
     if (x0) QP_CHECK(scp_launch_to_time_major(ctx, qp->N, qp->K, qp->D, x0, d.x));
     else SCP_HIP_CHECK(ctx, hipMemsetAsync(d.x, 0, nx * sizeof(double), ctx->stream));
-    QP_CHECK(gemm(qp, qp->Rf, qp->K, 1.0, d.F, d.x, 0.0, d.zf));  // z = A x  (primal warm start, scp.py:443)
+    // z = A x  (primal warm start, scp.py:443)
+    QP_CHECK(scp_launch_gemm(ctx, qp->st.use_mfma, qp->Rf, qp->K, (int)qp->C, 1.0, d.F, d.x, 0.0, d.zf));
     SCP_HIP_CHECK(ctx, hipMemsetAsync(d.yf, 0, nf * sizeof(double), ctx->stream));
   }
   qp->nW = with_rows ? n : 0;
@@ -946,7 +327,7 @@ static int reset_impl(scp_qp* qp, const double* x0, int64_t n, const int64_t* ro
   qp->steps_since_reset = 0;
   qp_on_x_set(qp, one_launch);
   if (with_rows) qp_on_rows_added(qp, true);
-  QP_CHECK(build_kkt(qp));
+  QP_CHECK(scp_qp_build_kkt(qp));
   qp->reset_done = true;
   if (installed) *installed = with_rows;
   return SCP_OK;
@@ -963,7 +344,7 @@ extern "C" int scp_qp_set_rho(scp_qp* qp, double rho) {
   SCP_REQUIRE(qp->ctx, rho >= 1e-6 && rho <= 1e6, "qp_set_rho: rho out of range");
   qp->rho = rho;
   qp_on_rho_changed(qp, false);
-  return build_kkt(qp);
+  return scp_qp_build_kkt(qp);
 }
 
 static int add_rows_impl(scp_qp* qp, int64_t n, const int64_t* rows, const double* eta, const double* l, int64_t eta_stride,
@@ -991,10 +372,7 @@ static int add_rows_impl(scp_qp* qp, int64_t n, const int64_t* rows, const doubl
     QP_CHECK(scp_launch_add_rows_at(ctx, qp->N, qp->K, qp->D, qp->nW, n, rows, at->pos_prev, at->p0, at->v0, at->R, qp->h, Qx,
                                     d.w_row, d.w_k, d.w_i, d.w_j, d.w_eta, d.w_l, d.zc, d.yc));
   } else {
-    hipLaunchKernelGGL(add_rows_kernel, grid1(n), dim3(256), 0, ctx->stream, qp->N, qp->D, qp->C, scp_pairs(qp->N),
-                       qp->nW, n, rows, eta, l, eta_stride, q_begin, nq, Qx, d.w_row, d.w_k, d.w_i, d.w_j, d.w_eta, d.w_l,
-                       d.zc, d.yc);
-    QP_LAUNCHED(qp);
+    QP_CHECK(scp_qp_append_rows(qp, n, rows, eta, l, eta_stride, q_begin, nq, Qx));
   }
   qp->nW += n;
   qp->persist_cap_nW = -1;
@@ -1102,11 +480,11 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
         persist_done = true;
         if (qp->persist_rho_switches > 0) {
           // adaptive-rho updates whose blocks were cached happened inside the kernel (same test, same values as below):
-          // adopt the result; build_kkt finds the slot and points d.* at it
+          // adopt the result; scp_qp_build_kkt finds the slot and points d.* at it
           qp->rho = qp->persist_rho;
           qp_on_rho_changed(qp, true);
           info->rho_updates += qp->persist_rho_switches;
-          QP_CHECK(build_kkt(qp));
+          QP_CHECK(scp_qp_build_kkt(qp));
         }
       }
     }
@@ -1133,7 +511,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
         case QpPipe::QP0: QP_CHECK(scp_qp_qp0_iterations(qp, n_it, with_dy ? qp->d.dyf : nullptr)); pipes |= 1 << SCP_PIPE_QP0; break;
         case QpPipe::CG1: QP_CHECK(scp_qp_cg1_iteration(qp, &cg_total, with_dy)); pipes |= 1 << SCP_PIPE_CG1; break;
         case QpPipe::CG1_BIGK: QP_CHECK(scp_qp_cg1_iteration(qp, &cg_total, false)); pipes |= 1 << SCP_PIPE_CG1_BIGK; break;
-        case QpPipe::GENERIC: QP_CHECK(admm_iteration(qp, &cg_total)); pipes |= 1 << SCP_PIPE_GENERIC; break;
+        case QpPipe::GENERIC: QP_CHECK(scp_qp_generic_iteration(qp, &cg_total)); pipes |= 1 << SCP_PIPE_GENERIC; break;
       }
     }
     if (will_check) {
@@ -1142,7 +520,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
       } else if (own_check) {
         QP_CHECK(scp_qp_fused_residuals(qp, with_dy));
       } else {
-        QP_CHECK(residuals(qp, with_dy));
+        QP_CHECK(scp_qp_generic_residuals(qp, with_dy));
       }
       // QP0 takes the generic check's rule although its fused check refreshes S0 x and F x: rows added after QP#0 go in
       // by the general installation
@@ -1166,7 +544,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
       if (with_dy) {  // OSQP's is_primal_infeasible on the unscaled problem
         const double ndy = hs[SL_NDY], supp = hs[SL_SUPP];
         if (ndy > st.eps_prim_inf && supp < -st.eps_prim_inf * ndy) {
-          if (!own_check) QP_CHECK(certificate_atdy(qp));  // the fused check has |A^T dy| already
+          if (!own_check) QP_CHECK(scp_qp_generic_certificate_atdy(qp));  // the fused check has |A^T dy| already
           if (qp->h_scal[SL_NATDY] < st.eps_prim_inf * ndy) {
             info->status_val = -3;
             break;
@@ -1185,7 +563,7 @@ extern "C" int scp_qp_solve(scp_qp* qp, scp_qp_info* info) {
         if (nr > qp->rho * st.adaptive_rho_tolerance || nr < qp->rho / st.adaptive_rho_tolerance) {
           qp->rho = nr;
           qp_on_rho_changed(qp, false);
-          QP_CHECK(build_kkt(qp));
+          QP_CHECK(scp_qp_build_kkt(qp));
           ++info->rho_updates;
           if (fine) cad = fine;  // (the residuals usually fall below the tolerances within a few steps)
         }
@@ -1242,7 +620,7 @@ extern "C" int scp_qp_clone_state(scp_qp* dst, const scp_qp* src) {
   dst->st = src->st;
   dst->problem_set = true;
   qp_on_x_set(dst, false);
-  QP_CHECK(build_kkt(dst));
+  QP_CHECK(scp_qp_build_kkt(dst));
   dst->reset_done = true;
   SCP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // src's workspace may be released by the caller right after
   return SCP_OK;

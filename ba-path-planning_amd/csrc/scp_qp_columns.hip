@@ -1,17 +1,15 @@
-// Column-block kernels of the joint QP (use_mfma = 1: the single-step pipeline, K <= SCP_FUSED_MAX_K with 16 columns
-// per workgroup, K <= SCP_BIGK_MAX_K with one workgroup per column; QP#0's column-local kernel; the termination check).
+// Column-block kernels of the joint QP (use_mfma = 1) and what launches them: the three launches of the single-step
+// pipeline (K <= SCP_FUSED_MAX_K with 16 columns per workgroup, K <= SCP_BIGK_MAX_K with one workgroup per column), QP#0's
+// column-local kernel and the fused termination check with its host reduction.
 //
 // Every operation of an ADMM step except the working-row gather/scatter is local to a column c = (agent, axis):
 // the fixed rows, the K x K KKT block and the Toeplitz block S0 act along the time index only.
 // One workgroup (16 waves) therefore owns 16 columns and keeps their K-vectors in LDS: F, F^T, S0 and S0^T are
 // jerk stencils and cumulative sums (wave-wide scans), and the only dense product left, H_f^{-1}, runs on the fp64
-// matrix cores (v_mfma_f64_16x16x4_f64, operand pre-packed in lane order: scp_qp_pack_operands).  Kernel boundaries
-// remain only where the algorithm needs the whole grid: the inner products and the row gather/scatter.
-// cg_iters > 1 and use_mfma = 0 / 2 run on the generic pipeline of scp_qp.hip (one product per launch).
+// matrix cores (v_mfma_f64_16x16x4_f64, operand pre-packed in lane order by scp_qp_kkt.hip).  Kernel boundaries
+// remain only where the algorithm needs the whole grid: the inner products and the row gather/scatter (scp_qp_rows.hip).
+// cg_iters > 1 and use_mfma = 0 / 2 run on the generic pipeline of scp_qp_generic.hip (one product per launch).
 #include "scp_qp_device.h"
-#include "scp_pair_device.h"
-#include "scp_reset_device.h"
-#include <cstdlib>
 
 namespace {
 
@@ -683,132 +681,24 @@ __global__ __launch_bounds__(256) void cg1_update_kernel(int K, int Rf, int64_t 
   gval[posj] = g;
 }
 
-// row values g written to BOTH incidence-list entries of a row (pos_i, pos_j); the per-cell gathers then need no atomics:
-//   INIT: g = (rho zc - yc) - rho eta.(Q_i - Q_j)   right-hand side minus the collision part of H x (Q = S0 x); also the
-//         first row values of the single-step pipeline after (x, zc, yc, rho) changed outside it
-//   else: g = rho eta.(Q_i - Q_j)                   collision part of H v (Q = S0 v)
-template <int D, bool INIT>
-__global__ __launch_bounds__(256) void rows_value_kernel(int64_t nW, int64_t C, double rho, const int* __restrict__ wk,
-                                                          const int* __restrict__ wi, const int* __restrict__ wj,
-                                                          const double* __restrict__ weta, const double* __restrict__ Q,
-                                                          const double* __restrict__ zc, const double* __restrict__ yc,
-                                                          const int* __restrict__ pos_i, const int* __restrict__ pos_j,
-                                                          double* __restrict__ gval) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nW) return;
-  const int64_t bi = (int64_t)wk[n] * C + (int64_t)wi[n] * D;
-  const int64_t bj = (int64_t)wk[n] * C + (int64_t)wj[n] * D;
-  double ax = 0.0;
-#pragma unroll
-  for (int d = 0; d < D; ++d) ax += weta[n * D + d] * (Q[bi + d] - Q[bj + d]);
-  const double g = INIT ? (rho * zc[n] - yc[n]) - rho * ax : rho * ax;
-  gval[pos_i[n]] = g;
-  gval[pos_j[n]] = g;
-}
-
-#define FUSED_LAUNCHED(qp) SCP_HIP_CHECK((qp)->ctx, hipGetLastError())
-
-// Tiles beyond 64 KiB of dynamic LDS (K > 50) need the limit raised per (device, kernel): scp_raise_lds_limit.
-template <typename Kern>
-int allow_lds(scp_qp* qp, Kern kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return SCP_OK;
-  SCP_HIP_CHECK(qp->ctx, scp_raise_lds_limit(qp->ctx->device, reinterpret_cast<const void*>(kernel), bytes));
-  return SCP_OK;
-}
-
 }  // namespace
 
 // `nit` ADMM iterations on the fixed rows alone in one launch (qp->nW == 0); dy_out: where to leave delta-y of the last
 // iteration for scp_qp_fused_residuals (NULL: not needed)
 int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out) {
   const QpDev& d = qp->d;
-  hipStream_t s = qp->ctx->stream;
   const int K = qp->K, Rf = qp->Rf;
-  const int64_t C = qp->C;
-  const int nblk = (int)((C + CB - 1) / CB);
+  const int nblk = (int)((qp->C + CB - 1) / CB);
   const size_t lds = (size_t)CB * (pad_col(Rf) + 3 * pad_col(K)) * sizeof(double);
-  if (K <= 64) {
-    int rc = allow_lds(qp, qp0_col_kernel<1>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(qp0_col_kernel<1>, dim3(nblk), dim3(FT), lds, s, K, Rf, C, qp->rho, qp->st.sigma, qp->st.alpha, qp->h,
-                       nit, d.pMinv, d.wrow, d.lf, d.uf, d.x, d.zf, d.yf, dy_out);
-  } else {
-    int rc = allow_lds(qp, qp0_col_kernel<2>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(qp0_col_kernel<2>, dim3(nblk), dim3(FT), lds, s, K, Rf, C, qp->rho, qp->st.sigma, qp->st.alpha, qp->h,
-                       nit, d.pMinv, d.wrow, d.lf, d.uf, d.x, d.zf, d.yf, dy_out);
-  }
-  FUSED_LAUNCHED(qp);
-  return SCP_OK;
+  return qp_launch(qp, K <= 64 ? qp0_col_kernel<1> : qp0_col_kernel<2>, dim3(nblk), dim3(FT), lds, K, Rf, qp->C, qp->rho,
+                   qp->st.sigma, qp->st.alpha, qp->h, nit, d.pMinv, d.wrow, d.lf, d.uf, d.x, d.zf, d.yf, dy_out);
 }
-
-namespace {
-constexpr int CSR1_MAX_CELLS = 16384;
-constexpr int64_t CSR1_MAX_ROWS = 1 << 18;
-// rows [base, base + n) that the kernel recomputes from the linearisation point first (scp_qp_add_rows_at); n = 0: none
-struct CsrNewRows {
-  int64_t n, base;
-  const int64_t* rows;
-  const double *pos_prev, *p0, *v0;
-  double R, h;
-  int N;
-  int64_t* w_row;
-  double* wl;
-};
-__global__ void csr_small_kernel(int64_t nW, int K, int ncell, int D, int64_t C, double rho, int* __restrict__ wk,
-                                 int* __restrict__ wi, int* __restrict__ wj, double* __restrict__ weta,
-                                 const double* __restrict__ Qx, double* __restrict__ zc, double* __restrict__ yc,
-                                 int* __restrict__ ptr, int* __restrict__ ent, double* __restrict__ coef,
-                                 int* __restrict__ pos_i, int* __restrict__ pos_j, double* __restrict__ gval, CsrNewRows nr);
-}  // namespace
 
 int scp_qp_cg1_prepare(scp_qp* qp) {
   if (qp->dv.carried) return SCP_OK;
-  const QpDev& d = qp->d;
-  hipStream_t s = qp->ctx->stream;
-  const int K = qp->K;
-  const int64_t C = qp->C;
-  const double rho_c = qp->rho * qp->st.rho_col_scale;
   QP_CHECK(scp_qp_exact_qx(qp, true));
-  const double* Qx = scp_qp_qx(qp);
-  if (qp->dv.vals_rho_c == rho_c) {
-    // scp_qp_install_rows_small built lists and values already
-  } else if (!qp->dv.lists && qp->nW > 0 && qp->nW <= CSR1_MAX_ROWS && qp->N * K <= CSR1_MAX_CELLS) {
-    const int ncell = qp->N * K;
-    hipLaunchKernelGGL(csr_small_kernel, dim3(1), dim3(1024), (size_t)ncell * sizeof(int), s, qp->nW, K, ncell, qp->D, C, rho_c,
-                       d.w_k, d.w_i, d.w_j, d.w_eta, Qx, d.zc, d.yc, d.cell_ptr, d.ent_code, d.coef, d.pos_i, d.pos_j, d.gval,
-                       CsrNewRows{});
-    FUSED_LAUNCHED(qp);
-  } else {
-    QP_CHECK(scp_qp_csr_ensure(qp));
-    const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
-    if (qp->D == 2)
-      hipLaunchKernelGGL((rows_value_kernel<2, true>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx,
-                         d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
-    else
-      hipLaunchKernelGGL((rows_value_kernel<3, true>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx,
-                         d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
-    FUSED_LAUNCHED(qp);
-  }
+  QP_CHECK(scp_qp_rows_first_values(qp, scp_qp_qx(qp)));
   qp_on_cg1_prepared(qp);
-  return SCP_OK;
-}
-
-int scp_qp_install_rows_small(scp_qp* qp, int64_t n, const int64_t* rows, const double* pos_prev, const double* p0,
-                              const double* v0, double R, const double* Qx, bool* done) {
-  *done = false;
-  const QpDev& d = qp->d;
-  const int K = qp->K;
-  const int64_t nW = qp->nW + n;
-  if (!qp->dv.qx || n <= 0 || nW > CSR1_MAX_ROWS || qp->N * K > CSR1_MAX_CELLS) return SCP_OK;
-  const int ncell = qp->N * K;
-  const double rho_c = qp->rho * qp->st.rho_col_scale;
-  CsrNewRows nr{n, qp->nW, rows, pos_prev, p0, v0, R, qp->h, qp->N, d.w_row, d.w_l};
-  hipLaunchKernelGGL(csr_small_kernel, dim3(1), dim3(1024), (size_t)ncell * sizeof(int), qp->ctx->stream, nW, K, ncell, qp->D,
-                     qp->C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx, d.zc, d.yc, d.cell_ptr, d.ent_code, d.coef, d.pos_i,
-                     d.pos_j, d.gval, nr);
-  FUSED_LAUNCHED(qp);
-  *done = true;
   return SCP_OK;
 }
 
@@ -818,7 +708,6 @@ int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy) {
   const QpDev& d = qp->d;
   double* dyf = emit_dy ? d.dyf : nullptr;  // delta-y of this iteration, consumed by scp_qp_fused_residuals(.., 2)
   double* dyc = emit_dy ? d.dyc : nullptr;
-  hipStream_t s = qp->ctx->stream;
   const int K = qp->K, Rf = qp->Rf;
   const int64_t C = qp->C;
   const int nblk = (int)((C + CB - 1) / CB);
@@ -830,450 +719,31 @@ int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy) {
   QP_CHECK(scp_qp_cg1_prepare(qp));
   double* Qx = scp_qp_qx(qp);        // S0 x (carried)
   double* Qn = scp_qp_qx(qp, true);  // S0 x of the next iteration
-  const size_t lds = (size_t)CB * (pad_col(Rf) + 5 * pad_col(K)) * sizeof(double);
   int npart = nblk;  // partial sums of r.p: one per column block, or one per column (long horizons)
   if (K > SCP_FUSED_MAX_K) {
     npart = (int)C;
-    hipLaunchKernelGGL(cg1_colK_kernel, dim3((unsigned)C), dim3((unsigned)((K + 63) / 64 * 64)), (size_t)2 * K * sizeof(double), s, K, Rf,
-                       C, qp->rho, qp->h, d.Minv, d.wrow, d.x, d.fx, d.zf, d.yf, qp->N, qp->D, d.cell_ptr, d.coef, d.gval, d.p,
-                       Qp, Fp, part_rz);
-  } else if (K <= 64) {
-    int rc = allow_lds(qp, cg1_col_kernel<1>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg1_col_kernel<1>, dim3(nblk), dim3(FT), lds, s, K, Rf, C, qp->rho, qp->h, d.pMinv, d.wrow, d.x, d.fx,
-                       d.zf, d.yf, qp->N, qp->D, d.cell_ptr, d.coef, d.gval, d.p, Qp, Fp, part_rz);
+    QP_CHECK(qp_launch(qp, cg1_colK_kernel, dim3((unsigned)C), dim3((unsigned)((K + 63) / 64 * 64)), (size_t)2 * K * sizeof(double),
+                       K, Rf, C, qp->rho, qp->h, d.Minv, d.wrow, d.x, d.fx, d.zf, d.yf, qp->N, qp->D, d.cell_ptr, d.coef, d.gval,
+                       d.p, Qp, Fp, part_rz));
   } else {
-    int rc = allow_lds(qp, cg1_col_kernel<2>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg1_col_kernel<2>, dim3(nblk), dim3(FT), lds, s, K, Rf, C, qp->rho, qp->h, d.pMinv, d.wrow, d.x, d.fx,
-                       d.zf, d.yf, qp->N, qp->D, d.cell_ptr, d.coef, d.gval, d.p, Qp, Fp, part_rz);
+    const size_t lds = (size_t)CB * (pad_col(Rf) + 5 * pad_col(K)) * sizeof(double);
+    QP_CHECK(qp_launch(qp, K <= 64 ? cg1_col_kernel<1> : cg1_col_kernel<2>, dim3(nblk), dim3(FT), lds, K, Rf, C, qp->rho, qp->h,
+                       d.pMinv, d.wrow, d.x, d.fx, d.zf, d.yf, qp->N, qp->D, d.cell_ptr, d.coef, d.gval, d.p, Qp, Fp, part_rz));
   }
-  FUSED_LAUNCHED(qp);
   const dim3 rblock(256);
   const int inline_sq = qp->nW <= SQ_INLINE_MAX ? 1 : 0;  // small working set: the update kernel sums p.Hp's row term itself
-  if (!inline_sq) {
-    if (qp->D == 2)
-      hipLaunchKernelGGL(cg1_rows_sq_kernel<2>, dim3(SQ_BLOCKS), rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j,
-                         d.w_eta, Qp, part_sq);
-    else
-      hipLaunchKernelGGL(cg1_rows_sq_kernel<3>, dim3(SQ_BLOCKS), rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j,
-                         d.w_eta, Qp, part_sq);
-    FUSED_LAUNCHED(qp);
-  }
+  if (!inline_sq)
+    QP_CHECK(qp_launch(qp, qp->D == 2 ? cg1_rows_sq_kernel<2> : cg1_rows_sq_kernel<3>, dim3(SQ_BLOCKS), rblock, 0, qp->nW, C,
+                       rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qp, part_sq));
   const int nblk8 = (nblk + 7) & ~7;
   const int eblocks = nblk8 * ((Rf + K + 16 * UPD_RPT - 1) / (16 * UPD_RPT));
   const dim3 ugrid((unsigned)(eblocks + (qp->nW + 255) / 256));
-  if (qp->D == 2)
-    hipLaunchKernelGGL(cg1_update_kernel<2>, ugrid, rblock, 0, s, K, Rf, C, nblk, npart, eblocks, nblk8, qp->rho, rho_c, qp->st.alpha,
-                       part_rz, part_sq, d.wrow, d.lf, d.uf, d.zf, d.yf, d.fx, Fp, d.x, d.p, Qp, Qx, Qn, qp->nW, d.w_k,
-                       d.w_i, d.w_j, d.w_eta, d.w_l, d.zc, d.yc, d.pos_i, d.pos_j, d.gval, dyf, dyc, inline_sq);
-  else
-    hipLaunchKernelGGL(cg1_update_kernel<3>, ugrid, rblock, 0, s, K, Rf, C, nblk, npart, eblocks, nblk8, qp->rho, rho_c, qp->st.alpha,
-                       part_rz, part_sq, d.wrow, d.lf, d.uf, d.zf, d.yf, d.fx, Fp, d.x, d.p, Qp, Qx, Qn, qp->nW, d.w_k,
-                       d.w_i, d.w_j, d.w_eta, d.w_l, d.zc, d.yc, d.pos_i, d.pos_j, d.gval, dyf, dyc, inline_sq);
-  FUSED_LAUNCHED(qp);
+  QP_CHECK(qp_launch(qp, qp->D == 2 ? cg1_update_kernel<2> : cg1_update_kernel<3>, ugrid, rblock, 0, K, Rf, C, nblk, npart,
+                     eblocks, nblk8, qp->rho, rho_c, qp->st.alpha, part_rz, part_sq, d.wrow, d.lf, d.uf, d.zf, d.yf, d.fx, Fp,
+                     d.x, d.p, Qp, Qx, Qn, qp->nW, d.w_k, d.w_i, d.w_j, d.w_eta, d.w_l, d.zc, d.yc, d.pos_i, d.pos_j, d.gval,
+                     dyf, dyc, inline_sq));
   qp_on_cg1_step(qp);
   ++*cg_count;
-  return SCP_OK;
-}
-
-// =====================================================================================================
-// Incidence lists of the working rows per (time step, agent) cell: the deterministic replacement of the atomic
-// row scatter.  Built once per change of the working set (count, scan, fill, sort inside the cells, finish).
-// =====================================================================================================
-namespace {
-
-__global__ __launch_bounds__(256) void csr_count_kernel(int64_t nW, int K, const int* __restrict__ wk,
-                                                         const int* __restrict__ wi, const int* __restrict__ wj,
-                                                         int* __restrict__ cnt) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nW) return;
-  atomicAdd(cnt + cell_of(wk[n], wi[n], K), 1);  // integer counts: order independent
-  atomicAdd(cnt + cell_of(wk[n], wj[n], K), 1);
-}
-
-// exclusive scan of cnt[0..ncell) into ptr (in place: cnt and ptr are the same array), cursors = ptr.  Two launches that
-// fill the chip instead of one workgroup walking the array (67 us at N K = 51 200, a fortieth of the benchmark step):
-// (1) every workgroup scans its own 4096 cells and leaves their total, (2) every workgroup adds the totals before it.
-constexpr int SCAN_SC = 16;                 // consecutive cells per thread
-constexpr int SCAN_CELLS = 256 * SCAN_SC;   // per workgroup
-__global__ __launch_bounds__(256) void csr_scan_local_kernel(int ncell, int* __restrict__ ptr, int* __restrict__ blk_tot) {
-  __shared__ int wsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * SCAN_CELLS + SCAN_SC * (int)threadIdx.x;
-  int v[SCAN_SC], tot = 0;
-#pragma unroll
-  for (int e = 0; e < SCAN_SC; ++e) {
-    v[e] = c + e < ncell ? ptr[c + e] : 0;
-    tot += v[e];
-  }
-  int incl = tot;
-  incl += dpp_move<0x111, 0xF, false>(incl);
-  incl += dpp_move<0x112, 0xF, false>(incl);
-  incl += dpp_move<0x114, 0xF, false>(incl);
-  incl += dpp_move<0x118, 0xF, false>(incl);
-  incl += dpp_move<0x142, 0xA, false>(incl);
-  incl += dpp_move<0x143, 0xC, false>(incl);
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int run = incl - tot;
-  for (int w = 0; w < wave; ++w) run += wsum[w];
-#pragma unroll
-  for (int e = 0; e < SCAN_SC; ++e) {
-    if (c + e < ncell) ptr[c + e] = run;
-    run += v[e];
-  }
-  if (threadIdx.x == 255) blk_tot[blockIdx.x] = run;
-}
-
-__global__ __launch_bounds__(256) void csr_scan_add_kernel(int ncell, int nblk, int* __restrict__ ptr, int* __restrict__ cur,
-                                                            const int* __restrict__ blk_tot) {
-  int off = 0;
-  for (int b = 0; b < (int)blockIdx.x; ++b) off += blk_tot[b];  // (wave-uniform: scalar loads)
-  const int c = blockIdx.x * SCAN_CELLS + SCAN_SC * (int)threadIdx.x;
-#pragma unroll
-  for (int e = 0; e < SCAN_SC; ++e) {
-    if (c + e < ncell) {
-      const int v = ptr[c + e] + off;
-      ptr[c + e] = v;
-      cur[c + e] = v;
-    }
-  }
-  if (blockIdx.x == nblk - 1 && threadIdx.x == 0) ptr[ncell] = off + blk_tot[nblk - 1];
-}
-
-__global__ __launch_bounds__(256) void csr_fill_kernel(int64_t nW, int K, const int* __restrict__ wk,
-                                                        const int* __restrict__ wi, const int* __restrict__ wj,
-                                                        int* __restrict__ cur, int* __restrict__ ent) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nW) return;
-  ent[atomicAdd(cur + cell_of(wk[n], wi[n], K), 1)] = (int)(2 * n);
-  ent[atomicAdd(cur + cell_of(wk[n], wj[n], K), 1)] = (int)(2 * n + 1);
-}
-
-// entries of a cell arrive in atomic order: sort them (ascending code) so that every sum has a fixed order
-__global__ __launch_bounds__(256) void csr_sort_kernel(int ncell, const int* __restrict__ ptr, int* __restrict__ ent) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncell) return;
-  const int b = ptr[c], e = ptr[c + 1];
-  for (int i = b + 1; i < e; ++i) {
-    const int v = ent[i];
-    int j = i - 1;
-    while (j >= b && ent[j] > v) {
-      ent[j + 1] = ent[j];
-      --j;
-    }
-    ent[j + 1] = v;
-  }
-}
-
-__global__ __launch_bounds__(256) void csr_finish_kernel(int64_t nent, int D, const int* __restrict__ ent,
-                                                          const double* __restrict__ weta, double* __restrict__ coef,
-                                                          int* __restrict__ pos_i, int* __restrict__ pos_j) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= nent) return;
-  const int code = ent[t];
-  const int n = code >> 1, side = code & 1;
-  for (int d = 0; d < D; ++d) coef[t * D + d] = side ? -weta[(int64_t)n * D + d] : weta[(int64_t)n * D + d];
-  if (side) pos_j[n] = (int)t;
-  else pos_i[n] = (int)t;
-}
-
-// Small problems (N K <= CSR1_MAX_CELLS cells, e.g. 128 agents x 50 steps): the whole build -- count, scan, fill, sort,
-// finish -- and the first row values (rows_value_kernel<D, true>) in ONE workgroup; the cell counters live in LDS.  Same lists,
-// same order as the five-launch build.
-template <bool COH>
-__device__ inline void csr_small_body(int* csr_cnt, int64_t nW, int K, int ncell, int D, int64_t C, double rho,
-                                                          int* __restrict__ wk, int* __restrict__ wi,
-                                                          int* __restrict__ wj, double* __restrict__ weta,
-                                                          const double* __restrict__ Qx, double* __restrict__ zc,
-                                                          double* __restrict__ yc, int* __restrict__ ptr,
-                                                          int* __restrict__ ent, double* __restrict__ coef,
-                                                          int* __restrict__ pos_i, int* __restrict__ pos_j,
-                                                          double* __restrict__ gval, CsrNewRows nr) {
-  // csr_cnt: [ncell] ints of LDS: counts, then exclusive offsets, then fill cursors (= end of each cell)
-  __shared__ int wsum[16];
-  constexpr int SC = CSR1_MAX_CELLS / 1024;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (nr.n > 0) {  // scp_qp_add_rows_at's kernel first: the new rows [base, base + n) from the linearisation point
-    const int64_t pairs = (int64_t)nr.N * (nr.N - 1) / 2;
-    for (int64_t t = tid; t < nr.n; t += 1024) {
-      if (D == 2)
-        add_row_at<2, COH>(t, nr.N, K, C, pairs, nr.base, nr.rows, nr.pos_prev, nr.p0, nr.v0, nr.R, nr.h, Qx, nr.w_row, wk, wi, wj,
-                      weta, nr.wl, zc, yc);
-      else
-        add_row_at<3, COH>(t, nr.N, K, C, pairs, nr.base, nr.rows, nr.pos_prev, nr.p0, nr.v0, nr.R, nr.h, Qx, nr.w_row, wk, wi, wj,
-                      weta, nr.wl, zc, yc);
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-  for (int c = tid; c < ncell; c += 1024) csr_cnt[c] = 0;
-  __syncthreads();
-  for (int64_t n = tid; n < nW; n += 1024) {
-    atomicAdd(&csr_cnt[cell_of(wk[n], wi[n], K)], 1);
-    atomicAdd(&csr_cnt[cell_of(wk[n], wj[n], K)], 1);
-  }
-  __syncthreads();
-  {  // exclusive scan, SC consecutive cells per thread
-    int v[SC], tot = 0;
-#pragma unroll
-    for (int e = 0; e < SC; ++e) {
-      v[e] = SC * tid + e < ncell ? csr_cnt[SC * tid + e] : 0;
-      tot += v[e];
-    }
-    int incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int run = incl - tot;
-    for (int w = 0; w < wave; ++w) run += wsum[w];
-#pragma unroll
-    for (int e = 0; e < SC; ++e) {
-      if (SC * tid + e < ncell) {
-        csr_cnt[SC * tid + e] = run;
-        ptr[SC * tid + e] = run;
-      }
-      run += v[e];
-    }
-    if (tid == 1023) ptr[ncell] = run;
-  }
-  __syncthreads();
-  for (int64_t n = tid; n < nW; n += 1024) {
-    ent[atomicAdd(&csr_cnt[cell_of(wk[n], wi[n], K)], 1)] = (int)(2 * n);
-    ent[atomicAdd(&csr_cnt[cell_of(wk[n], wj[n], K)], 1)] = (int)(2 * n + 1);
-  }
-  __syncthreads();
-  for (int c = tid; c < ncell; c += 1024) {  // the cursor of a cell now stands at its end = the next cell's begin
-    const int b = c ? csr_cnt[c - 1] : 0, e = csr_cnt[c];
-    for (int i = b + 1; i < e; ++i) {
-      const int v = ent[i];
-      int j = i - 1;
-      while (j >= b && ent[j] > v) {
-        ent[j + 1] = ent[j];
-        --j;
-      }
-      ent[j + 1] = v;
-    }
-  }
-  __syncthreads();
-  for (int64_t t = tid; t < 2 * nW; t += 1024) {
-    const int code = ent[t];
-    const int n = code >> 1, side = code & 1;
-    for (int d = 0; d < D; ++d) coef[t * D + d] = side ? -weta[(int64_t)n * D + d] : weta[(int64_t)n * D + d];
-    if (side) pos_j[n] = (int)t;
-    else pos_i[n] = (int)t;
-  }
-  __syncthreads();
-  for (int64_t n = tid; n < nW; n += 1024) {  // rows_value_kernel<D, true>
-    const int64_t bi = (int64_t)wk[n] * C + (int64_t)wi[n] * D;
-    const int64_t bj = (int64_t)wk[n] * C + (int64_t)wj[n] * D;
-    double ax = 0.0;
-    for (int d = 0; d < D; ++d)
-      ax += weta[n * D + d] * (COH ? load_coherent(Qx + bi + d) - load_coherent(Qx + bj + d) : Qx[bi + d] - Qx[bj + d]);
-    const double g = (rho * zc[n] - yc[n]) - rho * ax;
-    gval[pos_i[n]] = g;
-    gval[pos_j[n]] = g;
-  }
-}
-
-__global__ __launch_bounds__(1024) void csr_small_kernel(int64_t nW, int K, int ncell, int D, int64_t C, double rho,
-                                                          int* __restrict__ wk, int* __restrict__ wi,
-                                                          int* __restrict__ wj, double* __restrict__ weta,
-                                                          const double* __restrict__ Qx, double* __restrict__ zc,
-                                                          double* __restrict__ yc, int* __restrict__ ptr,
-                                                          int* __restrict__ ent, double* __restrict__ coef,
-                                                          int* __restrict__ pos_i, int* __restrict__ pos_j,
-                                                          double* __restrict__ gval, CsrNewRows nr) {
-  extern __shared__ int csr_cnt[];
-  csr_small_body<false>(csr_cnt, nW, K, ncell, D, C, rho, wk, wi, wj, weta, Qx, zc, yc, ptr, ent, coef, pos_i, pos_j, gval, nr);
-}
-
-// scp_qp_reset AND the installation of the QP's first rows in ONE launch: every workgroup resets its 16 columns
-// (qp_reset_body: its first 256 threads), S0 x written through; the LAST workgroup to finish (a ticket) then runs
-// csr_small_body on all 1024 threads, reading S0 x past its L2.  Same values as the two launches.
-struct ResetArgs {
-  int N, Rf;
-  const double *x0, *F, *S0;
-  double *x, *zf, *fx, *yf;
-};
-__global__ __launch_bounds__(1024) void reset_install_kernel(ResetArgs ra, int64_t nW, int K, int ncell, int D, int64_t C,
-                                                              double rho, int* __restrict__ wk, int* __restrict__ wi,
-                                                              int* __restrict__ wj, double* __restrict__ weta,
-                                                              double* __restrict__ Qx, double* __restrict__ zc,
-                                                              double* __restrict__ yc, int* __restrict__ ptr,
-                                                              int* __restrict__ ent, double* __restrict__ coef,
-                                                              int* __restrict__ pos_i, int* __restrict__ pos_j,
-                                                              double* __restrict__ gval, CsrNewRows nr,
-                                                              unsigned* __restrict__ ticket) {
-  extern __shared__ __attribute__((aligned(16))) char ri_lds[];  // max([K][16] doubles, [ncell] ints)
-  __shared__ int last_sh;
-  qp_reset_body<true>(threadIdx.x, threadIdx.x < 256, reinterpret_cast<double*>(ri_lds), ra.N, K, D, ra.Rf, ra.x0, ra.F, ra.S0,
-                      ra.x, ra.zf, ra.fx, Qx, ra.yf);
-  wait_stores_performed();  // (S0 x, written through, is in place before the ticket is taken)
-  __syncthreads();
-  if (threadIdx.x == 0) last_sh = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
-  __syncthreads();
-  if (!last_sh) return;
-  if (threadIdx.x == 0) *ticket = 0u;  // (the next launch on this stream starts after this kernel has ended)
-  csr_small_body<true>(reinterpret_cast<int*>(ri_lds), nW, K, ncell, D, C, rho, wk, wi, wj, weta, Qx, zc, yc, ptr, ent, coef,
-                       pos_i, pos_j, gval, nr);
-}
-
-}  // namespace
-
-// The launch of scp_qp_reset(x0) + scp_qp_add_rows_at(rows) for small problems (scp_qp.hip: reset_impl keeps the host-side
-// state); *done = false: not eligible, nothing launched.  Qx: the slab S0 x goes to.  qp->rho is the QP's starting value.
-int scp_qp_reset_install_small(scp_qp* qp, const double* x0, int64_t n, const int64_t* rows, const double* pos_prev,
-                               const double* p0, const double* v0, double R, double* Qx, bool* done) {
-  *done = false;
-  const QpDev& d = qp->d;
-  const int K = qp->K;
-  if (n <= 0 || n > CSR1_MAX_ROWS || qp->N * K > CSR1_MAX_CELLS) return SCP_OK;
-  const int ncell = qp->N * K;
-  const double rho_c = qp->rho * qp->st.rho_col_scale;
-  const size_t lds = std::max((size_t)K * RESET_COLS * sizeof(double), (size_t)ncell * sizeof(int));
-  CsrNewRows nr{n, 0, rows, pos_prev, p0, v0, R, qp->h, qp->N, d.w_row, d.w_l};
-  ResetArgs ra{qp->N, qp->Rf, x0, d.F, d.S0, d.x, d.zf, d.fx, d.yf};
-  hipLaunchKernelGGL(reset_install_kernel, dim3((unsigned)scp_cdiv(qp->C, RESET_COLS)), dim3(1024), lds, qp->ctx->stream, ra, n,
-                     K, ncell, qp->D, qp->C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Qx, d.zc, d.yc, d.cell_ptr, d.ent_code,
-                     d.coef, d.pos_i, d.pos_j, d.gval, nr, qp->ctx->d_ticket + 2);  // ([0], [1]: the passes, the checks)
-  FUSED_LAUNCHED(qp);
-  *done = true;
-  return SCP_OK;
-}
-
-namespace {
-// row values for the residual / certificate scatters
-__global__ __launch_bounds__(256) void csr_rowval_kernel(int64_t nW, int mode, double rho, const double* __restrict__ zc,
-                                                          const double* __restrict__ yc, const double* __restrict__ vec,
-                                                          const int* __restrict__ pos_i, const int* __restrict__ pos_j,
-                                                          double* __restrict__ gval, const double* __restrict__ vec2,
-                                                          double* __restrict__ gval2) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= nW) return;
-  if (gval2) {  // a second row vector for the same gather
-    const double g2 = vec2[n];
-    gval2[pos_i[n]] = g2;
-    gval2[pos_j[n]] = g2;
-  }
-  const double g = mode == 0 ? rho * zc[n] - yc[n] : (mode == 1 ? yc[n] : vec[n]);
-  gval[pos_i[n]] = g;
-  gval[pos_j[n]] = g;
-}
-
-// G[k][col] = sum over the cell's entries of coef * gval
-__global__ __launch_bounds__(256) void csr_gather_kernel(int K, int N, int D, const int* __restrict__ ptr,
-                                                          const double* __restrict__ coef,
-                                                          const double* __restrict__ gval, double* __restrict__ G) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t C = (int64_t)N * D;
-  if (t >= C * K) return;
-  const int k = (int)(t / C), col = (int)(t % C);
-  const int agent = col / D, d = col - agent * D;
-  const int cell = cell_of(k, agent, K);
-  double acc = 0.0;
-  const int t1 = ptr[cell + 1];
-  for (int e = ptr[cell]; e < t1; ++e) acc += coef[(size_t)e * D + d] * gval[e];
-  G[t] = acc;
-}
-
-}  // namespace
-
-int scp_qp_csr_ensure(scp_qp* qp) {
-  if (qp->dv.lists) return SCP_OK;
-  const QpDev& d = qp->d;
-  hipStream_t s = qp->ctx->stream;
-  const int ncell = qp->N * qp->K;
-  SCP_REQUIRE(qp->ctx, 2 * qp->nW < 0x3FFFFFFF, "csr_build: too many working rows for 32-bit entry codes");
-  SCP_HIP_CHECK(qp->ctx, hipMemsetAsync(d.cell_ptr, 0, (size_t)(ncell + 1) * sizeof(int), s));
-  if (qp->nW > 0) {
-    const dim3 rgrid((unsigned)((qp->nW + 255) / 256));
-    hipLaunchKernelGGL(csr_count_kernel, rgrid, dim3(256), 0, s, qp->nW, qp->K, d.w_k, d.w_i, d.w_j, d.cell_ptr);
-    const int sblk = (ncell + SCAN_CELLS - 1) / SCAN_CELLS;
-    hipLaunchKernelGGL(csr_scan_local_kernel, dim3(sblk), dim3(256), 0, s, ncell, d.cell_ptr, d.scan_tot);
-    hipLaunchKernelGGL(csr_scan_add_kernel, dim3(sblk), dim3(256), 0, s, ncell, sblk, d.cell_ptr, d.cell_cur, d.scan_tot);
-    hipLaunchKernelGGL(csr_fill_kernel, rgrid, dim3(256), 0, s, qp->nW, qp->K, d.w_k, d.w_i, d.w_j, d.cell_cur, d.ent_code);
-    hipLaunchKernelGGL(csr_sort_kernel, dim3((ncell + 255) / 256), dim3(256), 0, s, ncell, d.cell_ptr, d.ent_code);
-    hipLaunchKernelGGL(csr_finish_kernel, dim3((unsigned)((2 * qp->nW + 255) / 256)), dim3(256), 0, s, 2 * qp->nW, qp->D,
-                       d.ent_code, d.w_eta, d.coef, d.pos_i, d.pos_j);
-    FUSED_LAUNCHED(qp);
-  }
-  qp_on_lists_built(qp);
-  return SCP_OK;
-}
-
-int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec) {
-  QP_CHECK(scp_qp_csr_ensure(qp));
-  const QpDev& d = qp->d;
-  hipStream_t s = qp->ctx->stream;
-  const int64_t nx = (int64_t)qp->K * qp->C;
-  hipLaunchKernelGGL(csr_rowval_kernel, dim3((unsigned)((qp->nW + 255) / 256)), dim3(256), 0, s, qp->nW, mode,
-                     qp->rho * qp->st.rho_col_scale, d.zc, d.yc, vec, d.pos_i, d.pos_j, d.gval, (const double*)nullptr, (double*)nullptr);
-  hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, qp->K, qp->N, qp->D,
-                     d.cell_ptr, d.coef, d.gval, d.G);
-  FUSED_LAUNCHED(qp);
-  return SCP_OK;
-}
-
-// G = A_W^T g with g = rho A_W v, Q = S0 v: row values, then the per-cell gather
-int scp_qp_rows_gather(scp_qp* qp, const double* Q) {
-  const QpDev& d = qp->d;
-  hipStream_t s = qp->ctx->stream;
-  QP_CHECK(scp_qp_csr_ensure(qp));
-  const int64_t C = qp->C, nx = (int64_t)qp->K * C;
-  const double rho_c = qp->rho * qp->st.rho_col_scale;
-  const dim3 rgrid((unsigned)((qp->nW + 255) / 256)), rblock(256);
-  if (qp->D == 2)
-    hipLaunchKernelGGL((rows_value_kernel<2, false>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Q,
-                       d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
-  else
-    hipLaunchKernelGGL((rows_value_kernel<3, false>), rgrid, rblock, 0, s, qp->nW, C, rho_c, d.w_k, d.w_i, d.w_j, d.w_eta, Q,
-                       d.zc, d.yc, d.pos_i, d.pos_j, d.gval);
-  hipLaunchKernelGGL(csr_gather_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, s, qp->K, qp->N, qp->D,
-                     d.cell_ptr, d.coef, d.gval, d.G);
-  FUSED_LAUNCHED(qp);
-  return SCP_OK;
-}
-
-// =====================================================================================================
-// Operand packing of the active KKT slot's H_f^{-1} and T (see QpDev::pMinv)
-// =====================================================================================================
-namespace {
-struct PackDesc {
-  const double* src;
-  double* dst;
-  int R, M;
-};
-struct PackArgs {
-  PackDesc m[2];
-};
-__global__ __launch_bounds__(256) void pack_operands_kernel(PackArgs a) {
-  const PackDesc d = a.m[blockIdx.y];
-  const int nks = (d.M + 3) >> 2;
-  const int64_t total = (int64_t)((d.R + 15) >> 4) * nks * 64;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(e & 63);
-    const int64_t q = e >> 6;
-    const int ks = (int)(q % nks), t = (int)(q / nks);
-    const int row = t * 16 + (lane & 15), k = 4 * ks + (lane >> 4);
-    d.dst[e] = (row < d.R && k < d.M) ? d.src[(size_t)row * d.M + k] : 0.0;
-  }
-}
-}  // namespace
-
-int scp_qp_pack_operands(scp_qp* qp) {
-  const QpDev& d = qp->d;
-  const int K = qp->K;
-  PackArgs a;
-  a.m[0] = {d.Minv, d.pMinv, K, K};
-  a.m[1] = {d.T, d.pT, K, K};
-  hipLaunchKernelGGL(pack_operands_kernel, dim3(16, 2), dim3(256), 0, qp->ctx->stream, a);
-  FUSED_LAUNCHED(qp);
   return SCP_OK;
 }
 
@@ -1518,9 +988,6 @@ __global__ __launch_bounds__(256) void cg1_resid_rows_kernel(int64_t nW, int64_t
   }
 }
 
-}  // namespace
-
-namespace {
 // last launch of a check: everything before it in the stream has completed and, the partials living in host memory,
 // is visible to the host; the host spins on this word instead of sleeping in hipStreamSynchronize (25 us per check)
 __global__ void check_done_kernel(unsigned long long* flag, unsigned long long seq) {
@@ -1531,55 +998,31 @@ __global__ void check_done_kernel(unsigned long long* flag, unsigned long long s
 int scp_qp_fused_residuals(scp_qp* qp, bool with_dy) {
   const QpDev& d = qp->d;
   scp_ctx* ctx = qp->ctx;
-  hipStream_t s = ctx->stream;
   const int K = qp->K, Rf = qp->Rf;
   const int64_t C = qp->C;
   const int nblk = (int)((C + CB - 1) / CB);
   double* Qx = scp_qp_qx(qp);
   double* part = qp->h_scal_dev + SL_COUNT;  // [nblk column blocks | RESID_ROW_BLOCKS row blocks][SCP_RESID_STRIDE]
   const int has_rows = qp->nW > 0 ? 1 : 0;
-  if (has_rows)
-    hipLaunchKernelGGL(csr_rowval_kernel, dim3((unsigned)((qp->nW + 255) / 256)), dim3(256), 0, s, qp->nW, 1, 0.0, d.zc,
-                       d.yc, (const double*)nullptr, d.pos_i, d.pos_j, d.gval2, with_dy ? d.dyc : (const double*)nullptr,
-                       with_dy ? d.gval3 : (double*)nullptr);
+  if (has_rows) QP_CHECK(scp_qp_rows_check_values(qp, with_dy));  // gval2 = yc, gval3 = delta-yc
   const size_t lds = (size_t)CB * (pad_col(Rf) + 4 * pad_col(K)) * sizeof(double);
   const unsigned long long seq = ++qp->check_seq;
   unsigned long long* flag_dev = (unsigned long long*)(qp->h_scal_dev + SL_COUNT + SCP_RESID_CAP);
   unsigned* ticket = ctx->d_ticket + 1;  // ([0]: the small-problem pairwise passes; same stream, never concurrent)
-  if (K <= 64) {
-    int rc = allow_lds(qp, cg1_resid_col_kernel<1>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg1_resid_col_kernel<1>, dim3(nblk), dim3(FT), lds, s, K, Rf, C, qp->h, qp->N, qp->D, with_dy ? 1 : 0,
-                       has_rows, d.x, d.zf, d.yf, d.lf, d.uf, d.dyf, d.cell_ptr, d.coef, d.gval2, d.gval3, Qx, d.fx, part,
-                       ticket, has_rows ? nullptr : flag_dev, seq);
-  } else {
-    int rc = allow_lds(qp, cg1_resid_col_kernel<2>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(cg1_resid_col_kernel<2>, dim3(nblk), dim3(FT), lds, s, K, Rf, C, qp->h, qp->N, qp->D, with_dy ? 1 : 0,
-                       has_rows, d.x, d.zf, d.yf, d.lf, d.uf, d.dyf, d.cell_ptr, d.coef, d.gval2, d.gval3, Qx, d.fx, part,
-                       ticket, has_rows ? nullptr : flag_dev, seq);
+  QP_CHECK(qp_launch(qp, K <= 64 ? cg1_resid_col_kernel<1> : cg1_resid_col_kernel<2>, dim3(nblk), dim3(FT), lds, K, Rf, C, qp->h,
+                     qp->N, qp->D, with_dy ? 1 : 0, has_rows, d.x, d.zf, d.yf, d.lf, d.uf, d.dyf, d.cell_ptr, d.coef, d.gval2,
+                     d.gval3, Qx, d.fx, part, ticket, has_rows ? nullptr : flag_dev, seq));
+  if (has_rows) {  // (QP#0: no row partials, and the column kernel's last workgroup raises the completion word)
+    QP_CHECK(qp_launch(qp, qp->D == 2 ? cg1_resid_rows_kernel<2> : cg1_resid_rows_kernel<3>, dim3(RESID_ROW_BLOCKS), dim3(256),
+                       0, qp->nW, C, with_dy ? 1 : 0, d.w_k, d.w_i, d.w_j, d.w_eta, d.w_l, Qx, d.zc, d.dyc,
+                       part + (size_t)nblk * SCP_RESID_STRIDE));
+    QP_CHECK(qp_launch(qp, check_done_kernel, dim3(1), dim3(1), 0, flag_dev, seq));
   }
-  double* rpart = part + (size_t)nblk * SCP_RESID_STRIDE;
-  if (!has_rows) {
-    // QP#0: no row partials
-  } else if (qp->D == 2)
-    hipLaunchKernelGGL(cg1_resid_rows_kernel<2>, dim3(RESID_ROW_BLOCKS), dim3(256), 0, s, qp->nW, C, with_dy ? 1 : 0, d.w_k,
-                       d.w_i, d.w_j, d.w_eta, d.w_l, Qx, d.zc, d.dyc, rpart);
-  else
-    hipLaunchKernelGGL(cg1_resid_rows_kernel<3>, dim3(RESID_ROW_BLOCKS), dim3(256), 0, s, qp->nW, C, with_dy ? 1 : 0, d.w_k,
-                       d.w_i, d.w_j, d.w_eta, d.w_l, Qx, d.zc, d.dyc, rpart);
-  FUSED_LAUNCHED(qp);
   const int npart = nblk + (has_rows ? RESID_ROW_BLOCKS : 0);
   volatile unsigned long long* flag = (volatile unsigned long long*)(qp->h_scal + SL_COUNT + SCP_RESID_CAP);
-  if (has_rows) {
-    hipLaunchKernelGGL(check_done_kernel, dim3(1), dim3(1), 0, s, flag_dev, seq);
-    FUSED_LAUNCHED(qp);
-  }
-  {
-    if (!scp_wait_host_word(flag, seq, 20)) SCP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // a fault surfaces here
-    if (*flag != seq) return scp_fail(ctx, SCP_ERR_HIP, "fused check: completion flag not written");
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  }
+  if (!scp_wait_host_word(flag, seq, 20)) SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // a fault surfaces here
+  if (*flag != seq) return scp_fail(ctx, SCP_ERR_HIP, "fused check: completion flag not written");
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
   double* hs = qp->h_scal;
   static const int slot[9] = {SL_RP, SL_NAX, SL_NZ, SL_RD, SL_NPX, SL_NATY, SL_NDY, SL_SUPP, SL_NATDY};
   for (int j = 0; j < 9; ++j) hs[slot[j]] = 0.0;

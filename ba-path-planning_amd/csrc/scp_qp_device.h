@@ -1,4 +1,4 @@
-// Device-side helpers shared by the column kernels of the joint QP (scp_qp_fused.hip, scp_qp_persist.hip): wave-wide
+// Device-side helpers shared by the column kernels of the joint QP (scp_qp_columns.hip, scp_qp_rows.hip, scp_qp_persist.hip): wave-wide
 // scans on data-parallel-primitive (DPP) moves, MFMA operand prefetch, LDS padding.  gfx950 only.
 #pragma once
 #include "scp_qp_internal.h"

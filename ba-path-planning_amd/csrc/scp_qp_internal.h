@@ -1,12 +1,13 @@
-// Declarations shared by scp_qp.hip (ADMM driver, generic kernels), scp_qp_fused.hip (column-block kernels) and the
-// persistent kernels (scp_qp_persist.hip, scp_qp_persist16.hip).
+// Declarations shared by the translation units of the joint QP, one block per owning file:
+//   scp_qp.hip          the solver object, the C-ABI, reset / add rows, the choice of the pipeline and the solve loop
+//   scp_qp_kkt.hip      the blocks rebuilt per rho and their cache
+//   scp_qp_generic.hip  the generic pipeline (one product per launch)
+//   scp_qp_rows.hip     the working rows and their incidence lists
+//   scp_qp_columns.hip  the column-block kernels: single-step pipeline, QP#0, fused termination check
+//   scp_qp_persist.hip, scp_qp_persist16.hip  the persistent kernels
+// then the one launch helper of these files and, at the end, the QpDerived transitions.
 #pragma once
 #include "scp_common.h"
-
-constexpr int SCP_KKT_SLOTS = 6;       // cached rho values per solver object: at least this many ...
-constexpr int SCP_KKT_SLOTS_MAX = 32;  // ... and up to this many while the pool stays below SCP_KKT_POOL_BYTES
-constexpr size_t SCP_KKT_POOL_BYTES = (size_t)48 << 20;
-constexpr int NPART = 128;  // partial sums of a dot product (fixed -> deterministic summation order)
 
 #define QP_CHECK(call)            \
   do {                            \
@@ -14,6 +15,19 @@ constexpr int NPART = 128;  // partial sums of a dot product (fixed -> determini
     if (rc_ != SCP_OK) return rc_; \
   } while (0)
 
+// ---- scp_qp_kkt.hip: the rho-dependent blocks and their cache -----------------------------------------------------------------
+constexpr int SCP_KKT_SLOTS = 6;       // cached rho values per solver object: at least this many ...
+constexpr int SCP_KKT_SLOTS_MAX = 32;  // ... and up to this many while the pool stays below SCP_KKT_POOL_BYTES
+constexpr size_t SCP_KKT_POOL_BYTES = (size_t)48 << 20;
+constexpr int SCP_INV_LDS_MAX_K = 96;  // [H_f | I] (K x 2K doubles) resident in LDS for the Gauss-Jordan inverse
+static inline size_t scp_packed_count(int R, int M) { return (size_t)((R + 15) / 16) * ((M + 3) / 4) * 64; }
+size_t scp_qp_kkt_pool_doubles(int K);    // doubles behind QpDev::kkt_pool: every slot of this K
+void scp_qp_kkt_init_slots(scp_qp* qp);  // points the slots into the pool, all empty (scp_qp_create)
+int scp_qp_build_g0(scp_qp* qp);          // G0 = F^T w F, once per object (scp_qp_create)
+// d.Hf / HS / Minv / T / pMinv / pT of the current (rho, sigma): the cached slot, or built into the least recently used one
+int scp_qp_build_kkt(scp_qp* qp);
+
+// ---- scp_qp.hip: the solver object ---------------------------------------------------------------------------------------
 enum Slot {  // device scalar slots (doubles)
   SL_RZ0 = 0, SL_RZ1 = 1,
   SL_RP = 8, SL_NAX = 9, SL_NZ = 10, SL_RD = 11, SL_NPX = 12, SL_NATY = 13,
@@ -26,7 +40,7 @@ struct QpDev {
   double *F, *Ft, *S0, *S0t, *HS, *Hf, *Minv, *aug, *wrow;
   double* gj_tmp;  // [3K]: pivot row and column of the per-pivot Gauss-Jordan launches (K > SCP_INV_LDS_MAX_K)
   double* G0;  // [K][K]: F^T w F (constant; H_f = (2 + sigma) I + rho G0)
-  // H_f^{-1} in MFMA A-operand order for the column kernels (scp_qp_pack_operands):
+  // H_f^{-1} in MFMA A-operand order for the column kernels (packed by scp_qp_kkt.hip):
   // [row tile][k step][lane] = A[16 tile + (lane & 15)][4 step + (lane >> 4)], zero beyond the matrix, so that one
   // wave-wide operand load is 512 contiguous bytes
   double* pMinv;
@@ -136,31 +150,52 @@ inline int scp_qp_fine_cadence(const scp_qp* qp) {
   return fine ? st.check_fine : 0;
 }
 
-// scp_qp_fused.hip: the column kernels of the single-step pipeline, QP#0 and the termination check (use_mfma = 1)
-constexpr int SCP_RESID_STRIDE = 12;  // doubles per workgroup in the partial results of a fused termination check
-constexpr int SCP_RESID_CAP = (4096 / 2 + 128) * SCP_RESID_STRIDE;  // (SCP_PART_CAP / 2 column blocks + row blocks)
-constexpr int SCP_INV_LDS_MAX_K = 96;  // [H_f | I] (K x 2K doubles) resident in LDS for the Gauss-Jordan inverse
-constexpr int SCP_BIGK_MAX_K = 1024;  // single-step pipeline with one workgroup per column and one thread per time step
-constexpr int SCP_FUSED_MAX_K = 120;  // the 16-column workgroups of scp_qp_fused.hip (wave scans of up to 128 time steps)
-constexpr int SCP_PART_CAP = 4096;  // capacity of each partial-sum array (column blocks of the single-step pipeline)
-// single-PCG-step pipeline (cg_iters == 1 and a non-empty working set): 3 launches per ADMM step
-int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy);
-// nW == 0: `nit` complete ADMM iterations in one launch (everything is column-local)
-int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out);
-// Deterministic A_W^T g into the G slab: mode 0: g = rho_c zc - yc, 1: g = yc, 2: g = vec[n].  Two launches, no atomics.
-int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec);
-// the incidence lists of the working set, built when they are stale
-int scp_qp_csr_ensure(scp_qp* qp);
-// G = A_W^T g, g = rho A_W v with Q = S0 v: deterministic (gather over the incidence lists)
-int scp_qp_rows_gather(scp_qp* qp, const double* Q);
-// the single-step pipeline's carried state (S0 x, F x, row values), brought in line with (x, zc, yc, rho) when it is not
-int scp_qp_cg1_prepare(scp_qp* qp);
-// S0 x exact for x, formed into rows [K, 2K) of HQ unless the carried copy is exact; with_fx: F x too (scp_qp.hip)
+// ---- the one way these files launch a kernel -------------------------------------------------------------------------------
+inline dim3 grid1(int64_t n) { return dim3(scp_cdiv(n, 256)); }  // 256-thread workgroups over n items
+// Launches `kernel` on the qp's stream and returns the hipGetLastError check.  The instantiations of one kernel template
+// share a signature, so a call site picks one with `qp->D == 2 ? kern<2> : kern<3>` and writes the arguments once.  Dynamic
+// LDS beyond 64 KiB (the column tiles from K = 51) needs the limit raised per (device, kernel): scp_raise_lds_limit
+// remembers what it has raised.  Up to 64 KiB the launch makes no other runtime call.
+template <typename... P, typename... A>
+int qp_launch(scp_qp* qp, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A&&... args) {
+  if (lds > 64 * 1024)
+    SCP_HIP_CHECK(qp->ctx, scp_raise_lds_limit(qp->ctx->device, reinterpret_cast<const void*>(kernel), lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, qp->ctx->stream, static_cast<P>(args)...);
+  SCP_HIP_CHECK(qp->ctx, hipGetLastError());
+  return SCP_OK;
+}
+
+// ---- scp_qp_generic.hip: the generic pipeline ---------------------------------------------------------------------------------
+constexpr int NPART = 128;  // partial sums of a dot product (fixed -> deterministic summation order)
+int scp_qp_generic_iteration(scp_qp* qp, int* cg_count);  // one ADMM iteration: cg_iters PCG steps on the x-update
+// residuals -> qp->h_scal[SL_RP..SL_NATY]; with_dy: also delta-y = y - snapshot (dyf / dyc, in place), its max norm and
+// support value (SL_NDY, SL_SUPP).  Synchronises the stream.
+int scp_qp_generic_residuals(scp_qp* qp, bool with_dy);
+// second half of the certificate: || A^T dy ||_inf -> h_scal[SL_NATDY] (synchronises)
+int scp_qp_generic_certificate_atdy(scp_qp* qp);
+// S0 x exact for x, formed into rows [K, 2K) of HQ unless the carried copy is exact; with_fx: F x too
 int scp_qp_exact_qx(scp_qp* qp, bool with_fx);
 // the half of HQ that holds S0 x; other: the half the next single step writes
 inline double* scp_qp_qx(const scp_qp* qp, bool other = false) {
   return (qp->dv.qx_half != 0) != other ? qp->d.HQ : qp->d.HQ + (int64_t)qp->K * qp->C;
 }
+
+// ---- scp_qp_rows.hip: the working rows and their incidence lists -------------------------------------------------------------
+// append working rows [nW, nW + n): decode (k, i, j), copy eta / l, z = max(A x, l), y = 0.  eta_stride == 0: eta / l are
+// gathered [n][D] / [n] arrays; > 0: the arrays of the pairwise pass over the pair range [q_begin, q_begin + nq)
+int scp_qp_append_rows(scp_qp* qp, int64_t n, const int64_t* rows, const double* eta, const double* l, int64_t eta_stride,
+                       int64_t q_begin, int64_t nq, const double* Qx);
+// the incidence lists of the working set, built when they are stale
+int scp_qp_csr_ensure(scp_qp* qp);
+// Deterministic A_W^T g into the G slab: mode 0: g = rho_c zc - yc, 1: g = yc, 2: g = vec[n].  Two launches, no atomics.
+int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec);
+// G = A_W^T g, g = rho A_W v with Q = S0 v: deterministic (gather over the incidence lists)
+int scp_qp_rows_gather(scp_qp* qp, const double* Q);
+// the lists (when stale) and the first row values g = (rho_c zc - yc) - rho_c eta.d(S0 x) of the single-step pipeline,
+// Qx = S0 x exact: nothing, one workgroup's launch, or scp_qp_csr_ensure + one row launch (for scp_qp_cg1_prepare)
+int scp_qp_rows_first_values(scp_qp* qp, const double* Qx);
+// the row vectors of a fused termination check into the entry arrays: gval2 = yc and, with_dy, gval3 = delta-yc
+int scp_qp_rows_check_values(scp_qp* qp, bool with_dy);
 // small problems: working rows [nW, nW + n) recomputed from the linearisation point (scp_qp_add_rows_at) AND the incidence
 // lists + row values of all nW + n rows in ONE launch; *done = false: not eligible, nothing was launched
 int scp_qp_install_rows_small(scp_qp* qp, int64_t n, const int64_t* rows, const double* pos_prev, const double* p0,
@@ -169,6 +204,25 @@ int scp_qp_install_rows_small(scp_qp* qp, int64_t n, const int64_t* rows, const 
 // scp_qp.hip keeps the host-side state); *done = false: not eligible, nothing was launched
 int scp_qp_reset_install_small(scp_qp* qp, const double* x0, int64_t n, const int64_t* rows, const double* pos_prev,
                                const double* p0, const double* v0, double R, double* Qx, bool* done);
+
+// ---- scp_qp_columns.hip: the column kernels of the single-step pipeline, QP#0 and the termination check (use_mfma = 1) ----
+constexpr int SCP_RESID_STRIDE = 12;  // doubles per workgroup in the partial results of a fused termination check
+constexpr int SCP_RESID_CAP = (4096 / 2 + 128) * SCP_RESID_STRIDE;  // (SCP_PART_CAP / 2 column blocks + row blocks)
+constexpr int SCP_BIGK_MAX_K = 1024;  // single-step pipeline with one workgroup per column and one thread per time step
+constexpr int SCP_FUSED_MAX_K = 120;  // the 16-column workgroups of scp_qp_columns.hip (wave scans of up to 128 time steps)
+constexpr int SCP_PART_CAP = 4096;  // capacity of each partial-sum array (column blocks of the single-step pipeline)
+// single-PCG-step pipeline (cg_iters == 1 and a non-empty working set): 3 launches per ADMM step
+int scp_qp_cg1_iteration(scp_qp* qp, int* cg_count, bool emit_dy);
+// nW == 0: `nit` complete ADMM iterations in one launch (everything is column-local)
+int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out);
+// the single-step pipeline's carried state (S0 x, F x, row values), brought in line with (x, zc, yc, rho) when it is not
+int scp_qp_cg1_prepare(scp_qp* qp);
+// Termination-check quantities of the single-step pipeline in 3 launches (row values, column blocks, rows):
+// fills qp->h_scal[SL_RP .. SL_SUPP] like scp_qp_generic_residuals and leaves S0 x and F x in their slabs.  Synchronises.
+// with_dy: dyf / dyc hold delta-y of the last iteration (cg1_update_kernel); also fills h_scal[SL_NATDY].
+int scp_qp_fused_residuals(scp_qp* qp, bool with_dy);
+
+// ---- scp_qp_persist.hip, scp_qp_persist16.hip: the persistent kernels ----------------------------------------------------------
 constexpr int SCP_SYNC_WORDS = 16;  // u64: give-up word | scratch
 // Workgroups of a persistent launch: at most one per CU (all resident), and the exchange buffers below are sized for
 // exactly this many (+1: the fault-injection hook announces one workgroup more than it launches).
@@ -184,13 +238,6 @@ bool scp_persist_claim(int device, int n_cu_total, int n_wg, int wait_ms);
 void scp_persist_release(int device, int n_wg);
 constexpr int SCP_PERSIST_GAVE_UP = 2;  // exit code of the persistent kernel: a spin timed out, nothing was written back
 int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* it_done);  // cad0: steps to the next check
-// pack the active slot's H_f^{-1} and T into the MFMA operand order; called at the end of build_kkt
-int scp_qp_pack_operands(scp_qp* qp);
-static inline size_t scp_packed_count(int R, int M) { return (size_t)((R + 15) / 16) * ((M + 3) / 4) * 64; }
-// Termination-check quantities of the single-step pipeline in 3 launches (row values, column blocks, rows):
-// fills qp->h_scal[SL_RP .. SL_SUPP] like residuals() in scp_qp.hip and leaves S0 x and F x in their slabs.  Synchronises.
-// with_dy: dyf / dyc hold delta-y of the last iteration (cg1_update_kernel); also fills h_scal[SL_NATDY].
-int scp_qp_fused_residuals(scp_qp* qp, bool with_dy);
 
 // ---- the only writers of QpDerived: one transition per event that happens to the primary state ---------------------------
 // x set by a reset or a clone; qx: the reset's own launch formed S0 x (into rows [K, 2K) of HQ) and F x

@@ -1,7 +1,7 @@
 // Persistent form of the single-PCG-step ADMM pipeline (settings.cg_iters == 1, K <= 64): ONE launch runs all ADMM
 // steps up to the next termination check with the whole solver state on chip.
 //
-// Same arithmetic as the three-launch pipeline of scp_qp_fused.hip (cg1_col_kernel / cg1_rows_sq_kernel /
+// Same arithmetic as the three-launch pipeline of scp_qp_columns.hip (cg1_col_kernel / cg1_rows_sq_kernel /
 // cg1_update_kernel; CPU statement: oracle/qp_oracle.py:admm_structured), replaces osqp's solve loop at
 // /root/reference/src/path_planning/solvers/scp.py:441-445.  What changes is where the state lives and how workgroups
 // talk:

@@ -1,5 +1,5 @@
 // Device body of scp_qp_reset's one-launch form, shared by qp_reset_kernel (scp_qp.hip) and by the kernel that resets a QP
-// AND installs its first rows in the same launch (scp_qp_fused.hip).  gfx950 only.
+// AND installs its first rows in the same launch (scp_qp_rows.hip).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -185,7 +185,7 @@ def osqp_explicit(P, q, A, l, u, x0=None, rho=0.1, sigma=1e-6, alpha=1.6, eps_ab
 # ---------------------------------------------------------------------------------------------
 # Structured working-set ADMM: the algorithm of the HIP path, in numpy
 # ---------------------------------------------------------------------------------------------
-FINE_MAX_COLUMNS = 4096  # (SCP_FINE_MAX_COLUMNS in scp_qp.hip)
+FINE_MAX_COLUMNS = 4096  # (SCP_FINE_MAX_COLUMNS in scp_qp_internal.h)
 
 
 @dataclasses.dataclass

@@ -1,4 +1,4 @@
-"""The column kernels of the QP (csrc/scp_qp_fused.hip: cg1_col_kernel, cg1_resid_col_kernel, qp0_col_kernel) apply the
+"""The column kernels of the QP (csrc/scp_qp_columns.hip: cg1_col_kernel, cg1_resid_col_kernel, qp0_col_kernel) apply the
 integrator blocks F = [J; I; V; S], S0 and their transposes as cumulative sums instead of dense products.  This pins
 the identities they rely on against the explicit blocks of the oracle (oracle/scp_oracle.py:time_blocks, which follows
 scp.py:10-28, :198-203, :227-232, :489-491)."""
