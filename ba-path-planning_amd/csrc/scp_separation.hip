@@ -18,6 +18,10 @@
 //   sep_finish_kernel  the per-workgroup partials -> scp_separation_stats.
 // Every reduction is a minimum of (value, row id) pairs or an integer sum: exact and commutative, so the result depends
 // neither on scheduling nor on how the pair range was cut.
+//
+// The conflict list (scp_list_conflicts) is the same pass instantiated with LIST = true: phase B keeps, for every violating
+// segment, one scp_conflict record (appended through a device counter), and sep_sort_* / sep_gather_kernel put the records
+// into ascending row order -- the keys are unique, so the sorted list depends neither on scheduling nor on the cut.
 #include "scp_common.h"
 #include "scp_pair_device.h"
 
@@ -42,6 +46,13 @@ struct SepPartial {
   unsigned long long pad;
 };
 
+// Where the LIST instantiation of the pass keeps its records
+struct SepList {
+  scp_conflict* raw;             // records in the order of arrival, `capacity` of them
+  unsigned long long* n_found;   // the caller's counter: counts every violating segment, stored or not
+  int64_t capacity;
+};
+
 struct SepArgs {
   int N, K, D, kc;               // kc: time steps per workgroup
   double h, thr;                 // thr = R - 0.01 (scp.py:610)
@@ -50,6 +61,7 @@ struct SepArgs {
   SepPartial* part;              // [gridDim.y][gridDim.x]
   int64_t tile0;                 // index of the first tile of this launch in the upper triangle (diagonal included) of tiles
   int nt;                        // tiles per side
+  SepList list;                  // LIST only (last: the offsets of the fields above are those of the check)
 };
 
 __global__ __launch_bounds__(256) void sep_prep_kernel(int N, int K, int D, double h, const double* __restrict__ pos,
@@ -154,6 +166,79 @@ __device__ inline void quartic_min(const Quartic& q, double h, double& m_out, do
   t_out = tm;
 }
 
+// Where a violating segment is below the threshold: g = f - thr2 over [0, h].  The scheme of quartic_min, with BOTH sign
+// changes of f', yields every stationary point of f in (0, h) (f' is monotone on each of the three pieces, so a piece holds
+// at most one).  Between consecutive breakpoints {0, stationary points, h} f is monotone, so g has at most one root there:
+// g is evaluated at the five breakpoint slots (a piece without a stationary point repeats the breakpoint before it, which
+// changes nothing) and the two outermost sub-intervals over which it changes sign are bisected (48 halvings).
+//   t_in   0 if the segment starts below the threshold, else the end of the first bisection that lies below it;
+//   t_out  h if it ends below, else the same from the right;
+//   pieces maximal runs of breakpoints below the threshold (f has at most one interior maximum: 1 or 2).
+// The caller's test is sqrt(max(min f, 0)) < thr, which can differ from min f < thr2 in the last bit, and quartic_min may
+// report a split point: if no breakpoint is below thr2 the window is the single point t_min.
+__device__ inline void quartic_window(const Quartic& q, double h, double thr2, double t_min, double& t_in, double& t_out,
+                                      unsigned int& pieces) {
+  double s1 = -1.0, s2 = -1.0;  // the split points, as in quartic_min
+  const double qa = 6.0 * q.c4, qb = 3.0 * q.c3, qc = q.c2;
+  if (qa != 0.0) {
+    const double disc = fma(qb, qb, -4.0 * qa * qc);
+    if (disc > 0.0) {
+      const double qd = -0.5 * (qb + copysign(sqrt(disc), qb));
+      s1 = qd / qa;
+      s2 = qc / qd;
+    }
+  } else if (qb != 0.0) {
+    s1 = -qc / qb;
+  }
+  if (!(s1 > 0.0 && s1 < h)) s1 = -1.0;
+  if (!(s2 > 0.0 && s2 < h)) s2 = -1.0;
+  if (s1 < 0.0 || (s2 >= 0.0 && s2 < s1)) {
+    const double x = s1;
+    s1 = s2;
+    s2 = x;
+  }
+  const double pa = s1 >= 0.0 ? s1 : 0.0, pb = s2 >= 0.0 ? s2 : pa;
+  // breakpoints b0 <= b1 <= b2 <= b3 <= b4 (named, not an array: nothing here is indexed at run time)
+  auto stationary = [&](double lo, double hi, double prev) {
+    const double gl = q.g(lo), gh = q.g(hi);
+    if (!((gl < 0.0 && gh > 0.0) || (gl > 0.0 && gh < 0.0))) return prev;
+    const bool rising = gl < 0.0;
+    for (int it = 0; it < 48; ++it) {
+      const double mid = 0.5 * (lo + hi);
+      if ((q.g(mid) < 0.0) == rising) lo = mid;
+      else hi = mid;
+    }
+    return 0.5 * (lo + hi);
+  };
+  const double b0 = 0.0;
+  const double b1 = stationary(0.0, pa, b0);
+  const double b2 = stationary(pa, pb, b1);
+  const double b3 = stationary(pb, h, b2);
+  const double b4 = h;
+  const bool u0 = q.f(b0) < thr2, u1 = q.f(b1) < thr2, u2 = q.f(b2) < thr2, u3 = q.f(b3) < thr2, u4 = q.f(b4) < thr2;
+  if (!(u0 || u1 || u2 || u3 || u4)) {
+    t_in = t_out = t_min;
+    pieces = 1;
+    return;
+  }
+  pieces = (unsigned int)u0 + (unsigned int)(u1 && !u0) + (unsigned int)(u2 && !u1) + (unsigned int)(u3 && !u2) +
+           (unsigned int)(u4 && !u3);
+  // lo: at or above the threshold, hi: below it (either may be the larger time); returns the end that is below
+  auto crossing = [&](double above, double below) {
+    for (int it = 0; it < 48; ++it) {
+      const double mid = 0.5 * (above + below);
+      if (q.f(mid) < thr2) below = mid;
+      else above = mid;
+    }
+    return below;
+  };
+  // the first breakpoint below the threshold and the one before it; the last one and the one after it
+  const double in_b = u0 ? b0 : u1 ? b1 : u2 ? b2 : u3 ? b3 : b4, in_a = u1 ? b0 : u2 ? b1 : u3 ? b2 : b3;
+  const double out_b = u4 ? b4 : u3 ? b3 : u2 ? b2 : u1 ? b1 : b0, out_a = u3 ? b4 : u2 ? b3 : u1 ? b2 : b1;
+  t_in = u0 ? 0.0 : crossing(in_a, in_b);
+  t_out = u4 ? h : crossing(out_a, out_b);
+}
+
 // (m, row) pairs order lexicographically; t rides along
 __device__ inline void fold_min(double& m, unsigned long long& row, double& t, double m2, unsigned long long row2, double t2) {
   if (m2 < m || (m2 == m && row2 < row)) {
@@ -163,7 +248,10 @@ __device__ inline void fold_min(double& m, unsigned long long& row, double& t, d
   }
 }
 
-template <int D>
+// The pass.  LIST = false: the reductions of scp_check_separation (a.list unused).  LIST = true: the records of
+// scp_list_conflicts and nothing else -- no partials, no sampled minimum, and the skip test with T = thr alone (the known
+// upper bound of the minimum only serves the argmin): a skipped segment stays above thr, so it is not a violation.
+template <int D, bool LIST = false>
 __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
   constexpr int NC = 3 * D + 1;
   __shared__ double sm[NC][2 * SEP_TILE];            // component planes; [0, 64): the i side, [64, 128): the j side
@@ -257,7 +345,7 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
       }
       // sampled minimum, bit for bit scp_check_avoidance's: pair_geom's distance is within an ulp of sqrt(ss), so only a
       // pair whose ss is within 1e-12 of the smallest one seen can carry a smaller distance -- it alone pays for pair_geom
-      if (ss_min <= min_ss * (1.0 + 1e-12)) {
+      if (!LIST && ss_min <= min_ss * (1.0 + 1e-12)) {
 #pragma unroll
         for (int s = 0; s < SEP_STEPS; ++s)
           if (((valid >> s) & 1u) && ss[s] <= min_ss * (1.0 + 1e-12)) {
@@ -276,8 +364,8 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
       // L >= T (1 + 1e-6) + 1e-6 S gives L^2 >= T^2 + 1e-12 S^2, four orders above that error.  Rearranged:
       // |d| >= (T + rho) (1 + 1e-6) / (1 - 1e-6); tested as d.d > (T + rho)^2 (1 + 7e-6).  T >= this wave's smallest sampled
       // distance >= the call's minimum, so a skipped segment is strictly above the minimum: never the argmin, not even tied.
-      ub = fmin(ub, sqrt(wave_min_f64(ss_min)) * (1.0 + 1e-15));
-      const double T = fmax(a.thr, ub);
+      if constexpr (!LIST) ub = fmin(ub, sqrt(wave_min_f64(ss_min)) * (1.0 + 1e-15));
+      const double T = LIST ? a.thr : fmax(a.thr, ub);
 #pragma unroll
       for (int s = 0; s < SEP_STEPS; ++s) {
         const double reach = T + (sm[3 * D][wave + 4 * s] + rho_j);
@@ -311,16 +399,27 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
         quartic_min(q, a.h, m, t);
         const unsigned long long row =
             (unsigned long long)((int64_t)k * a.pairs + tri_off(i, N) + (jj - i - 1));
-        fold_min(best_m, best_row, best_t, m, row, t);
-        if (sqrt(fmax(m, 0.0)) < a.thr) {
-          ++n_viol;
-          first = row < first ? row : first;
+        if constexpr (LIST) {
+          if (sqrt(fmax(m, 0.0)) < a.thr) {  // the test n_violating counts, on the same bits
+            double t_in, t_out;
+            unsigned int pieces;
+            quartic_window(q, a.h, a.thr * a.thr, t, t_in, t_out, pieces);
+            const unsigned long long slot = atomicAdd(a.list.n_found, 1ULL);
+            if (slot < (unsigned long long)a.list.capacity) a.list.raw[slot] = scp_conflict{row, sqrt(fmax(m, 0.0)), t, t_in, t_out, pieces, 0u};
+          }
+        } else {
+          fold_min(best_m, best_row, best_t, m, row, t);
+          if (sqrt(fmax(m, 0.0)) < a.thr) {
+            ++n_viol;
+            first = row < first ? row : first;
+          }
+          ++n_solved;
         }
-        ++n_solved;
       }
     }
   }
 
+  if constexpr (LIST) return;
   // ---- workgroup reduction: wave shuffles, then the four wave results through LDS ---------------------------------------
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) {
@@ -389,21 +488,115 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_finish_kernel(const SepPartia
   }
 }
 
+// ---- the conflict list's order: a bitonic sort of (row, arrival index) pairs, then one gather of the records ---------------
+// The length n is known on the device only, so the host sizes every launch for the capacity and each kernel leaves early
+// where n (rounded up to a power of two, at least one chunk) does not reach it.  Slots beyond n carry the key SEP_NO_ROW and
+// sort to the end.  An overflowed list (n > capacity) counts as empty: nothing in `out` is defined then.
+constexpr int SORT_CHUNK = 1024;  // pairs one workgroup sorts in LDS (12 KiB): short lists need this one launch
+
+__device__ inline unsigned long long list_len(const unsigned long long* n_found, int64_t capacity) {
+  const unsigned long long n = *n_found;
+  return n > (unsigned long long)capacity ? 0ULL : n;
+}
+
+__device__ inline unsigned long long sort_span(unsigned long long n) {  // the power of two the network runs over
+  unsigned long long p = SORT_CHUNK;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// comparator c of the step with distance j: elements i < partner = i + j
+__device__ inline unsigned long long comparator_low(unsigned long long c, unsigned long long j) {
+  return ((c & ~(j - 1)) << 1) | (c & (j - 1));
+}
+
+// One chunk per workgroup, in LDS.  init: keys from the records, then every stage k = 2 .. SORT_CHUNK of the network;
+// otherwise the steps j = SORT_CHUNK / 2 .. 1 of stage k (the ones that stay inside a chunk).
+__global__ __launch_bounds__(SEP_THREADS) void sep_sort_local_kernel(const scp_conflict* __restrict__ raw,
+                                                                     const unsigned long long* __restrict__ n_found,
+                                                                     int64_t capacity, unsigned long long* __restrict__ keys,
+                                                                     unsigned int* __restrict__ idx, unsigned long long k_stage,
+                                                                     int init) {
+  __shared__ unsigned long long sk[SORT_CHUNK];
+  __shared__ unsigned int si[SORT_CHUNK];
+  const unsigned long long n = list_len(n_found, capacity), span = sort_span(n);
+  const unsigned long long base = (unsigned long long)blockIdx.x * SORT_CHUNK;
+  if (base >= span || (!init && k_stage > span)) return;  // uniform over the workgroup
+  for (int e = threadIdx.x; e < SORT_CHUNK; e += SEP_THREADS) {
+    const unsigned long long g = base + e;
+    sk[e] = init ? (g < n ? raw[g].row : SEP_NO_ROW) : keys[g];
+    si[e] = init ? (unsigned int)g : idx[g];
+  }
+  __syncthreads();
+  auto steps = [&](unsigned long long k, int j_first) {
+    for (int j = j_first; j >= 1; j >>= 1) {
+      for (int c = threadIdx.x; c < SORT_CHUNK / 2; c += SEP_THREADS) {
+        const int i = (int)comparator_low(c, j), o = i + j;
+        const bool up = ((base + i) & k) == 0;
+        const unsigned long long a = sk[i], b = sk[o];
+        if ((a > b) == up) {
+          sk[i] = b;
+          sk[o] = a;
+          const unsigned int x = si[i];
+          si[i] = si[o];
+          si[o] = x;
+        }
+      }
+      __syncthreads();
+    }
+  };
+  if (init) {
+    for (int k = 2; k <= SORT_CHUNK; k <<= 1) steps(k, k >> 1);
+  } else {
+    steps(k_stage, SORT_CHUNK / 2);
+  }
+  for (int e = threadIdx.x; e < SORT_CHUNK; e += SEP_THREADS) {
+    keys[base + e] = sk[e];
+    idx[base + e] = si[e];
+  }
+}
+
+// one step (stage k, distance j >= SORT_CHUNK) over global memory
+__global__ __launch_bounds__(SEP_THREADS) void sep_sort_global_kernel(const unsigned long long* __restrict__ n_found,
+                                                                      int64_t capacity, unsigned long long* __restrict__ keys,
+                                                                      unsigned int* __restrict__ idx, unsigned long long k,
+                                                                      unsigned long long j) {
+  const unsigned long long span = sort_span(list_len(n_found, capacity));
+  const unsigned long long c = (unsigned long long)blockIdx.x * SEP_THREADS + threadIdx.x;
+  if (k > span || c >= span / 2) return;
+  const unsigned long long i = comparator_low(c, j), o = i + j;
+  const bool up = (i & k) == 0;
+  const unsigned long long a = keys[i], b = keys[o];
+  if ((a > b) == up) {
+    keys[i] = b;
+    keys[o] = a;
+    const unsigned int x = idx[i];
+    idx[i] = idx[o];
+    idx[o] = x;
+  }
+}
+
+__global__ __launch_bounds__(SEP_THREADS) void sep_gather_kernel(const scp_conflict* __restrict__ raw,
+                                                                 const unsigned long long* __restrict__ n_found,
+                                                                 int64_t capacity, const unsigned int* __restrict__ idx,
+                                                                 scp_conflict* __restrict__ out) {
+  const unsigned long long n = list_len(n_found, capacity);
+  const unsigned long long e = (unsigned long long)blockIdx.x * SEP_THREADS + threadIdx.x;
+  if (e < n) out[e] = raw[idx[e]];
+}
+
 int64_t tile_start(int64_t r, int64_t nt) { return r * nt - r * (r - 1) / 2; }
 
-}  // namespace
+// How a call covers its pair range: the tile rows that hold it and the time steps per workgroup
+struct SepPlan {
+  int nt, kc, n_chunks;
+  int64_t n_tiles, tile0;
+};
 
-extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
-                                    const double* pos, const double* vel, const double* acc, scp_separation_stats* stats) {
-  if (!ctx) return SCP_ERR_INVALID;
-  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  SCP_REQUIRE(ctx, pos && vel && acc && stats, "check_separation: null pointer");
-  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "check_separation: bad time step h=%g", h);
-  const int NC = 3 * D + 1;
-  const int nt = scp_cdiv(N, SEP_TILE);
+SepPlan sep_plan(const scp_ctx* ctx, int N, int K, int64_t q_begin, int64_t q_end) {
+  SepPlan p{};
+  p.nt = scp_cdiv(N, SEP_TILE);
   // the tile rows that hold the pair range: vehicle rows i_lo .. i_hi of the triangle
-  int64_t n_tiles = 0, tile0 = 0;
   if (q_end > q_begin) {
     auto row_of = [N](int64_t q) {
       int64_t lo = 0, hi = N - 2;  // largest i with tri_off(i) <= q
@@ -415,21 +608,45 @@ extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h,
       return lo;
     };
     const int64_t t_lo = row_of(q_begin) / SEP_TILE, t_hi = row_of(q_end - 1) / SEP_TILE;
-    tile0 = tile_start(t_lo, nt);
-    n_tiles = tile_start(t_hi + 1, nt) - tile0;
+    p.tile0 = tile_start(t_lo, p.nt);
+    p.n_tiles = tile_start(t_hi + 1, p.nt) - p.tile0;
   }
-  SCP_REQUIRE(ctx, n_tiles < ((int64_t)1 << 31), "check_separation: %lld tiles exceed grid.x; shard the pair range",
-              (long long)n_tiles);
   // time steps per workgroup: as many as still leave ~8 workgroups per compute unit (the records of a step are staged once per
   // workgroup and step, so longer chunks only save the per-workgroup reduction)
-  int kc = K;
-  if (n_tiles > 0) {
+  p.kc = K;
+  if (p.n_tiles > 0) {
     const int64_t want = 8 * (int64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
-    const int64_t chunks = std::min<int64_t>(K, std::max<int64_t>(1, (want + n_tiles - 1) / n_tiles));
-    kc = scp_cdiv(K, chunks);
+    const int64_t chunks = std::min<int64_t>(K, std::max<int64_t>(1, (want + p.n_tiles - 1) / p.n_tiles));
+    p.kc = scp_cdiv(K, chunks);
   }
-  const int n_chunks = scp_cdiv(K, kc);
-  const int64_t n_part = n_tiles * n_chunks;
+  p.n_chunks = scp_cdiv(K, p.kc);
+  return p;
+}
+
+SepArgs sep_args(int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end, const SepPlan& p, const double* rec,
+                 SepPartial* part) {
+  SepArgs a{};
+  a.N = N; a.K = K; a.D = D; a.kc = p.kc;
+  a.h = h; a.thr = R - 0.01;
+  a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
+  a.rec = rec; a.part = part; a.tile0 = p.tile0; a.nt = p.nt;
+  return a;
+}
+
+}  // namespace
+
+extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                                    const double* pos, const double* vel, const double* acc, scp_separation_stats* stats) {
+  if (!ctx) return SCP_ERR_INVALID;
+  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, pos && vel && acc && stats, "check_separation: null pointer");
+  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "check_separation: bad time step h=%g", h);
+  const int NC = 3 * D + 1;
+  const SepPlan plan = sep_plan(ctx, N, K, q_begin, q_end);
+  SCP_REQUIRE(ctx, plan.n_tiles < ((int64_t)1 << 31), "check_separation: %lld tiles exceed grid.x; shard the pair range",
+              (long long)plan.n_tiles);
+  const int64_t n_part = plan.n_tiles * plan.n_chunks;
   const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
   rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes,
                             rec_bytes + (size_t)std::max<int64_t>(n_part, 1) * sizeof(SepPartial) + 64);
@@ -442,12 +659,8 @@ extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h,
   if (n_part > 0) {
     hipLaunchKernelGGL(sep_prep_kernel, dim3(scp_cdiv((int64_t)N * K, 256)), dim3(256), 0, ctx->stream, N, K, D, h, pos, vel,
                        acc, rec);
-    SepArgs a{};
-    a.N = N; a.K = K; a.D = D; a.kc = kc;
-    a.h = h; a.thr = R - 0.01;
-    a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-    a.rec = rec; a.part = part; a.tile0 = tile0; a.nt = nt;
-    const dim3 grid((unsigned)n_tiles, (unsigned)n_chunks);
+    const SepArgs a = sep_args(N, K, D, h, R, q_begin, q_end, plan, rec, part);
+    const dim3 grid((unsigned)plan.n_tiles, (unsigned)plan.n_chunks);
     if (D == 2) hipLaunchKernelGGL(sep_pass_kernel<2>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
     else hipLaunchKernelGGL(sep_pass_kernel<3>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
     SCP_HIP_CHECK(ctx, hipGetLastError());
@@ -467,5 +680,68 @@ extern "C" int scp_ctx_last_separation_solved(scp_ctx* ctx, uint64_t* n) {
   SCP_REQUIRE(ctx, ctx->sep_n_solved, "check_separation has not run yet");
   SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   SCP_HIP_CHECK(ctx, hipMemcpy(n, ctx->sep_n_solved, sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return SCP_OK;
+}
+
+// The violating segments of the pair range, one record each, in ascending row order (include/scp_hip.h)
+extern "C" int scp_list_conflicts(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                                  const double* pos, const double* vel, const double* acc, scp_conflict* out, int64_t capacity,
+                                  uint64_t* n_found) {
+  if (!ctx) return SCP_ERR_INVALID;
+  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, pos && vel && acc && n_found, "list_conflicts: null pointer");
+  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "list_conflicts: bad time step h=%g", h);
+  SCP_REQUIRE(ctx, capacity >= 0 && capacity <= ((int64_t)1 << 30), "list_conflicts: bad capacity %lld", (long long)capacity);
+  SCP_REQUIRE(ctx, out || capacity == 0, "list_conflicts: null list of capacity %lld", (long long)capacity);
+  const int NC = 3 * D + 1;
+  const SepPlan plan = sep_plan(ctx, N, K, q_begin, q_end);
+  SCP_REQUIRE(ctx, plan.n_tiles < ((int64_t)1 << 31), "list_conflicts: %lld tiles exceed grid.x; shard the pair range",
+              (long long)plan.n_tiles);
+  int64_t span = SORT_CHUNK;  // sort_span(capacity)
+  while (span < capacity) span <<= 1;
+  const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
+  const size_t raw_bytes = ((size_t)capacity * sizeof(scp_conflict) + 63) & ~(size_t)63;
+  // the workspace is shared with scp_check_separation: growing it frees the place of that call's solved count
+  ctx->sep_n_solved = nullptr;
+  rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes,
+                            rec_bytes + raw_bytes + (size_t)span * (sizeof(unsigned long long) + sizeof(unsigned int)) + 64);
+  if (rc) return rc;
+  double* rec = (double*)ctx->sep_ws;
+  scp_conflict* raw = (scp_conflict*)((char*)ctx->sep_ws + rec_bytes);
+  unsigned long long* keys = (unsigned long long*)((char*)raw + raw_bytes);
+  unsigned int* idx = (unsigned int*)(keys + span);
+  unsigned long long* count = (unsigned long long*)n_found;
+
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
+  SCP_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
+  if (plan.n_tiles > 0) {
+    hipLaunchKernelGGL(sep_prep_kernel, dim3(scp_cdiv((int64_t)N * K, 256)), dim3(256), 0, ctx->stream, N, K, D, h, pos, vel,
+                       acc, rec);
+    SepArgs a = sep_args(N, K, D, h, R, q_begin, q_end, plan, rec, nullptr);
+    a.list = SepList{raw, count, capacity};
+    const dim3 grid((unsigned)plan.n_tiles, (unsigned)plan.n_chunks);
+    if (D == 2) hipLaunchKernelGGL((sep_pass_kernel<2, true>), grid, dim3(SEP_THREADS), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((sep_pass_kernel<3, true>), grid, dim3(SEP_THREADS), 0, ctx->stream, a);
+    SCP_HIP_CHECK(ctx, hipGetLastError());
+    if (capacity > 0) {
+      const dim3 chunks((unsigned)(span / SORT_CHUNK)), halves((unsigned)scp_cdiv(span / 2, SEP_THREADS));
+      hipLaunchKernelGGL(sep_sort_local_kernel, chunks, dim3(SEP_THREADS), 0, ctx->stream, raw, count, capacity, keys, idx,
+                         0ULL, 1);
+      for (int64_t k = 2 * SORT_CHUNK; k <= span; k <<= 1) {
+        for (int64_t j = k >> 1; j >= SORT_CHUNK; j >>= 1)
+          hipLaunchKernelGGL(sep_sort_global_kernel, halves, dim3(SEP_THREADS), 0, ctx->stream, count, capacity, keys, idx,
+                             (unsigned long long)k, (unsigned long long)j);
+        hipLaunchKernelGGL(sep_sort_local_kernel, chunks, dim3(SEP_THREADS), 0, ctx->stream, raw, count, capacity, keys, idx,
+                           (unsigned long long)k, 0);
+      }
+      hipLaunchKernelGGL(sep_gather_kernel, dim3((unsigned)scp_cdiv(capacity, SEP_THREADS)), dim3(SEP_THREADS), 0, ctx->stream,
+                         raw, count, capacity, idx, out);
+      SCP_HIP_CHECK(ctx, hipGetLastError());
+    }
+  }
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
+  ctx->pair_timed = ctx->timing != 0;
+  ctx->pair_ran = true;
   return SCP_OK;
 }

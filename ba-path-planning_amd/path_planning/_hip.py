@@ -146,6 +146,15 @@ class SeparationStats(C.Structure):
                 ("argmin_row", C.c_uint64), ("first_violation", C.c_uint64), ("n_violating", C.c_uint64)]
 
 
+class Conflict(C.Structure):
+    """struct scp_conflict (scp_list_conflicts): one violating segment"""
+    _fields_ = [("row", C.c_uint64), ("min_dist", C.c_double), ("t_min", C.c_double), ("t_enter", C.c_double),
+                ("t_exit", C.c_double), ("pieces", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CONFLICT_DTYPE = np.dtype([("row", np.uint64), ("min_dist", np.float64), ("t_min", np.float64), ("t_enter", np.float64),
+                           ("t_exit", np.float64), ("pieces", np.uint32), ("reserved", np.uint32)])
+
 NO_ROW = 2**64 - 1  # UINT64_MAX: "no such row" in the stats of the pairwise passes
 
 ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
@@ -154,7 +163,7 @@ EXPORTS = [
     "scp_set_host_wait", "scp_abi_version", "scp_ctx_create", "scp_ctx_destroy", "scp_last_error", "scp_ctx_synchronize",
     "scp_ctx_last_pair_ms", "scp_ctx_set_option",
     "scp_kinematics", "scp_fixed_bounds", "scp_linearize_pairs", "scp_select_pairs", "scp_check_avoidance", "scp_qp_add_rows_at",
-    "scp_check_separation", "scp_ctx_last_separation_solved",
+    "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
     "scp_qp_reset", "scp_qp_set_rho", "scp_qp_add_rows", "scp_qp_solve", "scp_qp_clone_state", "scp_qp_get_solution",
@@ -208,6 +217,7 @@ def load_library():
     lib.scp_check_avoidance.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp]
     lib.scp_check_separation.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp]
     lib.scp_ctx_last_separation_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.scp_list_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, i64, vp]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_collision_violations_at.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_gather_rows.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]
@@ -391,6 +401,24 @@ class Context:
                                                  acc.data_ptr(), self.sep_stats.data_ptr()))
         st = SeparationStats.from_buffer_copy(self.sep_stats.cpu().numpy().tobytes())
         return {f: getattr(st, f) for f, _ in SeparationStats._fields_}
+
+    def list_conflicts(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None, capacity=None):
+        """scp_list_conflicts over the pair range [q_begin, q_end): one record per segment whose continuous-time distance is
+        below R - 0.01, as a numpy structured array (CONFLICT_DTYPE) in ascending row order.  The list is sized here: `capacity`
+        records (default 1024) and, if more were found, ONE repetition with exactly that many -- synchronises."""
+        torch = _torch()
+        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        cap = 1024 if capacity is None else int(capacity)
+        n_found = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+        for _ in range(2):
+            out = torch.empty(max(cap, 1) * CONFLICT_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+            self.check(self.lib.scp_list_conflicts(self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(),
+                                                   acc.data_ptr(), out.data_ptr(), cap, n_found.data_ptr()))
+            n = int(n_found.item())
+            if n <= cap:
+                return out[: n * CONFLICT_DTYPE.itemsize].cpu().numpy().view(CONFLICT_DTYPE).copy()
+            cap = n
+        raise HipError(SCP_ERR_CAPACITY, f"list_conflicts: {n} records after a repetition sized for {cap}")
 
     def last_separation_solved(self):
         """segments of the latest check_separation that needed the quartic's minimum (the rest: one comparison)"""

@@ -126,28 +126,56 @@ class Shard:
         dev = rows.device
         staged = self._host_staged(rows)
         work = rows.cpu() if staged else rows
-        k = int(work.numel())
-        cap = getattr(self, "_ids_cap", 4096)
         ex = float("-inf") if extra is None else float(extra)
-        while True:
-            msg = torch.zeros(cap + 2, dtype=torch.int64, device=work.device)
-            msg[0] = k
-            msg[1] = torch.tensor([ex], dtype=torch.float64).view(torch.int64)[0]
-            if k:
-                msg[2:2 + min(k, cap)] = work[: min(k, cap)]
-            out = torch.empty(self.world * (cap + 2), dtype=torch.int64, device=work.device)
-            dist.all_gather_into_tensor(out, msg, group=self.group)
-            out = out.view(self.world, cap + 2)
-            head = out[:, :2].cpu()  # one host read: counts and the extras
-            counts = head[:, 0].tolist()
-            if max(counts) <= cap:
-                break
-            cap = self._ids_cap = 2 * max(counts)  # every rank sees the same counts: the same decision, the same retry
-        self._ids_cap = cap
-        parts = [out[r, 2:2 + c] for r, c in enumerate(counts) if c]
+        parts, head = self._gather_padded(work, (torch.tensor([ex], dtype=torch.float64).view(torch.int64)[0],), "_ids_cap", 4096)
+        parts = [p for p in parts if p.numel()]
         ids = torch.sort(torch.cat(parts)).values if parts else work[:0]
         mx = float(head[:, 1].contiguous().view(torch.float64).max().item())
         return (ids.to(dev) if staged else ids).contiguous(), (mx if extra is not None else None)
+
+    def _gather_padded(self, work, head, cap_attr, default_cap):
+        """Every rank's 1-D int64 message `work` (any length) in ONE collective: each rank sends [len(work), *head, work padded
+        to the capacity every rank agreed on]; a second, longer one only when some rank's message outgrew that capacity
+        (every rank sees the same counts: the same decision, the same retry).  Returns ([rank r's message ...], heads
+        (world, 1 + len(head)) on the host)."""
+        k = int(work.numel())
+        cap = getattr(self, cap_attr, default_cap)
+        nh = 1 + len(head)
+        while True:
+            msg = torch.zeros(cap + nh, dtype=torch.int64, device=work.device)
+            msg[0] = k
+            for x, v in enumerate(head):
+                msg[1 + x] = v
+            if k:
+                msg[nh:nh + min(k, cap)] = work[: min(k, cap)]
+            out = torch.empty(self.world * (cap + nh), dtype=torch.int64, device=work.device)
+            dist.all_gather_into_tensor(out, msg, group=self.group)
+            out = out.view(self.world, cap + nh)
+            heads = out[:, :nh].cpu()  # one host read
+            counts = heads[:, 0].tolist()
+            if max(counts) <= cap:
+                break
+            cap = 2 * max(counts)
+        setattr(self, cap_attr, cap)
+        return [out[r, nh:nh + c] for r, c in enumerate(counts)], heads
+
+    @_timed
+    def allgather_records(self, arr):
+        """Every rank's numpy structured array of records with a uint64 field ``row`` (any length; the item size a multiple of
+        8: scp_conflict) merged in ascending row order -- the rows of the ranks' pair ranges are disjoint, so this is the list
+        a single rank would have found.  The records travel as their bytes (int64 words, never reinterpreted as floating
+        point); one collective, a second one only when some rank's list outgrew the agreed capacity.  With one rank: `arr`."""
+        if self.alone:
+            return arr
+        import numpy as np
+
+        arr = np.ascontiguousarray(arr)
+        words = arr.dtype.itemsize // 8
+        assert arr.dtype.itemsize % 8 == 0 and arr.ndim == 1
+        work = torch.from_numpy(arr.view(np.int64).copy()).to(self._dev())
+        parts, _ = self._gather_padded(work, (), "_records_cap", 1024 * words)
+        merged = np.concatenate([p.cpu().numpy() for p in parts]).view(arr.dtype)
+        return merged[np.argsort(merged["row"], kind="stable")]
 
     @_timed
     def broadcast(self, tensor, src=0):

@@ -32,6 +32,9 @@ def build_parser():
     p.add_argument("--continuous-check", action="store_true",
                    help="after the solve, print the minimum distance over the whole flight (between the samples too), "
                         "the vehicles and the time of that closest approach")
+    p.add_argument("--list-conflicts", action="store_true",
+                   help="--continuous-check, and one more line per between-sample conflict: the two vehicles, when they are "
+                        "closer than the minimum distance - 0.01 m, and how close they come")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -87,8 +90,9 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
-        if args.continuous_check:
-            rep = solver.validate_solution(continuous=True)
+        if args.continuous_check or args.list_conflicts:
+            rep = (solver.validate_solution(continuous=True, conflicts=True) if args.list_conflicts
+                   else solver.validate_solution(continuous=True))
             ca = rep["closest_approach"]
             if ca is None:
                 print("Continuous-time check: no pair of vehicles")
@@ -96,6 +100,10 @@ def main(argv=None):
                 print(f"Continuous-time check: minimum distance {ca['distance']:.4f} m between vehicles {ca['vehicles'][0]} and "
                       f"{ca['vehicles'][1]} at t = {ca['time']:.4f} s (at the samples: {rep['min_pair_distance']:.4f} m; "
                       f"{rep['n_violating_segments']} segments below {min_distance - 0.01:.2f} m)")
+            for w in rep.get("conflicts", ()):
+                print(f"  conflict: vehicles {w['vehicles'][0]} and {w['vehicles'][1]} from t = {w['t_start']:.4f} s to "
+                      f"t = {w['t_end']:.4f} s, minimum distance {w['min_distance']:.4f} m at t = {w['t_min_distance']:.4f} s"
+                      + (" (hull of separate stretches)" if w["pieces"] > 1 else ""))
 
         if not args.no_plots:
             pre = args.save_prefix

@@ -26,6 +26,7 @@ import numpy as np
 
 from .. import _hip
 from .._sharding import Shard
+from .conflicts import conflict_windows
 
 # The reference's callers build a NEW solver object per scenario (compute_trajectories_batch.py:103-117).  Here an object owns a
 # library context and a native solver (device workspace, pinned host words, the K x K blocks cached per rho): ~0.7 ms to
@@ -731,7 +732,7 @@ class SCP:
     # ------------------------------------------------------------------------------------------------
     # post-solve validation: one device pass over all pairs + the fixed rows on the host copy
     # ------------------------------------------------------------------------------------------------
-    def validate_solution(self, continuous=False):
+    def validate_solution(self, continuous=False, conflicts=False):
         """Feasibility report of the stored trajectories: minimum pair distance over all stored samples and its
         first violation of R - 0.01 (device reduction, generalises scp.py:597-615), worst violation of every bound
         the reference imposes (scp.py:182-257) and of the final-state equalities (state K).
@@ -739,7 +740,13 @@ class SCP:
         continuous=True adds what the samples cannot show: ``min_pair_distance_continuous`` (minimum over every segment,
         not only its end points), ``collision_free_continuous`` (no segment below R - 0.01), ``n_violating_segments``,
         ``first_violation_continuous`` and ``closest_approach`` (each ``{"timestep", "time", "vehicles", "distance"}`` or
-        None)."""
+        None).
+
+        conflicts=True (with continuous=True) lists every between-sample conflict: ``conflicts``, one dictionary per pair and
+        contiguous stretch of time below R - 0.01 (conflicts.conflict_windows: vehicles, t_start, t_end, duration,
+        min_distance, t_min_distance, first_timestep, n_segments, pieces), sorted by start time, and ``n_conflicts``."""
+        if conflicts and not continuous:
+            raise ValueError("conflicts=True lists the conflicts of the continuous-time check: it needs continuous=True")
         if self.trajectories is None:
             raise ValueError("Trajectories not generated yet")
         N, K, D, h = self.N, self.K, self.D, self.h
@@ -771,6 +778,11 @@ class SCP:
                                          "distance": float(np.linalg.norm(p[i, k] - p[j, k]))}
         if continuous:
             report.update(self._continuous_separation(p, v, a, q0, q1))
+        if conflicts:
+            c = self._ctx
+            mine = c.list_conflicts(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)
+            report["conflicts"] = conflict_windows(self.shard.allgather_records(mine), N, K, h)
+            report["n_conflicts"] = len(report["conflicts"])
         return report
 
     def _continuous_separation(self, p, v, a, q0, q1):

@@ -217,6 +217,31 @@ int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h, double R, 
  * comparison: too far apart to be a violation or the minimum); a cost figure, results never depend on it.  Synchronises. */
 int scp_ctx_last_separation_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
 
+/* ---- the conflict list: WHICH segments scp_check_separation counts in n_violating, when, and how close -----------------
+ * A purely additive part of ABI version 7: one struct and one function, nothing else changes.
+ * One record per violating segment of the pair range -- a segment whose distance sqrt(max(min f, 0)) is < R - 0.01, the test
+ * of n_violating on the same bits (f: the quartic above; the arithmetic per segment is scp_check_separation's, so min_dist and
+ * t_min are bit for bit what that call reports for the row).  out[0 .. *n_found) is in ascending row order; the result is
+ * deterministic and does not depend on how a pair range is cut: the lists of disjoint shards, merged by row, are bit for
+ * bit the list of the full range.  `out` (capacity records) and `n_found` are DEVICE memory.  If *n_found > capacity
+ * NOTHING in `out` is defined and the call still returns SCP_OK: repeat it with a longer list (the protocol of
+ * scp_collision_violations).  An empty pair range gives *n_found = 0.  Argument checks, error codes, stream and timing
+ * behaviour as scp_check_separation (scp_ctx_last_pair_ms: staging, pass, sort); capacity in [0, 2^30]. */
+typedef struct scp_conflict {
+  uint64_t row;       /* k*pairs + q, as everywhere */
+  double min_dist;    /* the segment's distance: sqrt(max(min f, 0)) */
+  double t_min;       /* where in [0, h] it is attained */
+  double t_enter;     /* smallest t in [0, h] with f(t) < (R - 0.01)^2 (to the 2^-48 h of a bisection); exactly 0 if the
+                         segment starts inside */
+  double t_exit;      /* largest such t; exactly h if it ends inside */
+  uint32_t pieces;    /* 1 or 2: maximal sub-intervals of [t_enter, t_exit] below the threshold (2: the vehicles come within
+                         the threshold, part, and come within it again inside one segment; [t_enter, t_exit] is the hull) */
+  uint32_t reserved;  /* 0 */
+} scp_conflict;
+int scp_list_conflicts(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                       const double* pos, const double* vel, const double* acc, scp_conflict* out, int64_t capacity,
+                       uint64_t* n_found);
+
 /* ---- constraint generation for the joint QP (a6): full pass over the linearised rows ------------------
  * For every local row not yet marked in sel_bitmap: if (A_col x)_r < l_r - feas_tol, mark it and append its
  * global id to new_rows.  (A_col x)_r = eta_r . ((pos_i - c_i) - (pos_j - c_j))[k], c = p0 + k h v0,

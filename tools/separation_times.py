@@ -1,12 +1,17 @@
 """Device time of the continuous-time separation check (scp_check_separation) next to the sampled check
 (scp_check_avoidance) on the same trajectories, and the share of segments that reached the quartic.
 
-    python tools/separation_times.py [--reps 30] [--warmup 5]
+    python tools/separation_times.py [--reps 30] [--warmup 5] [--skip-solves] [--list]
 
 Shapes: 1024 x 50 x 2, 4096 x 50 x 2, 1024 x 50 x 3.  Data: (a) the grid-swap scenario of bench.py, solved trajectories
 (QP#0 + SCP iterations, max 15); (b) random kinematically consistent trajectories in a 20^D box (|v| <= 2, |a| <= 15 per
 axis).  Times are HIP events around each call's kernels (scp_ctx_last_pair_ms), the two passes alternating in one process:
-median, min and max over the repetitions after the warm-up."""
+median, min and max over the repetitions after the warm-up.
+
+--list adds the conflict list (scp_list_conflicts) on the same trajectories, alternating with the check in one loop, and a
+small shape (128 x 50 x 2).  Its sort is not timed by itself: the call is repeated with capacity 0, which runs the same
+pass and the same (then empty) sort launches but stores and sorts nothing, and the difference of the medians is reported
+as the share of storing, sorting and gathering the records."""
 import argparse
 import os
 import sys
@@ -52,11 +57,45 @@ def measure(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
           f"sampled {st['sample_min_dist']:.4f} violating {st['n_violating']}", flush=True)
 
 
+def measure_listing(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
+    import torch
+
+    from path_planning import _hip
+
+    n = len(ctx.list_conflicts(N, K, D, h, R, pos, vel, acc))
+    cap = max(n, 1024)
+    out = torch.empty(cap * _hip.CONFLICT_DTYPE.itemsize, dtype=torch.uint8, device=ctx.tdev)
+    found = torch.zeros(1, dtype=torch.int64, device=ctx.tdev)
+    pairs = N * (N - 1) // 2
+
+    def call(capacity):
+        ctx.check(ctx.lib.scp_list_conflicts(ctx.h, N, K, D, h, R, 0, pairs, pos.data_ptr(), vel.data_ptr(), acc.data_ptr(),
+                                             out.data_ptr(), capacity, found.data_ptr()))
+        return ctx.last_pair_ms()
+
+    t_chk, t_full, t_none = [], [], []
+    for r in range(warmup + reps):
+        ctx.check_separation(N, K, D, h, R, pos, vel, acc)
+        a = ctx.last_pair_ms()
+        b, c = call(cap), call(0)
+        if r >= warmup:
+            t_chk.append(a)
+            t_full.append(b)
+            t_none.append(c)
+    q = lambda x: (float(np.median(x)), float(np.min(x)), float(np.max(x)))  # noqa: E731
+    k, f, z = q(t_chk), q(t_full), q(t_none)
+    print(f"{label:28s} {N:5d} x {K} x {D}  check {k[0]*1e3:8.1f} us (min {k[1]*1e3:.1f}, max {k[2]*1e3:.1f})   "
+          f"list {f[0]*1e3:8.1f} us (min {f[1]*1e3:.1f}, max {f[2]*1e3:.1f})   list, capacity 0 {z[0]*1e3:8.1f} us "
+          f"(min {z[1]*1e3:.1f}, max {z[2]*1e3:.1f})   list / check {f[0]/k[0]:.2f}   store + sort + gather "
+          f"{(f[0]-z[0])*1e3:.1f} us = {100.0*(f[0]-z[0])/f[0]:.1f} % of the list   records {n} (capacity {cap})", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-solves", action="store_true")
+    ap.add_argument("--list", action="store_true", help="also time scp_list_conflicts, and add the shape 128 x 50 x 2")
     args = ap.parse_args()
     from path_planning import _hip
     from path_planning.scenarios.position_generator import generate_grid_swap
@@ -64,11 +103,13 @@ def main():
 
     h, R, K = 0.2, 0.8, 50
     ctx = _hip.Context(0)
-    for N, D in ((1024, 2), (4096, 2), (1024, 3)):
+    for N, D in ((1024, 2), (4096, 2), (1024, 3)) + (((128, 2),) if args.list else ()):
         p0, v0, acc = random_case(N, K, D, 100 + N + D)
         a = ctx.tensor(acc)
         pos, vel = ctx.kinematics(N, K, D, h, a, ctx.tensor(p0), ctx.tensor(v0))
         measure(ctx, N, K, D, h, R, pos, vel, a, args.reps, args.warmup, "random, 20^D box")
+        if args.list:
+            measure_listing(ctx, N, K, D, h, R, pos, vel, a, args.reps, args.warmup, "random, 20^D box")
         if args.skip_solves:
             continue
         g0, gf, space = generate_grid_swap(N, seed=1000 * N, dim=D)
@@ -79,6 +120,9 @@ def main():
         dev = [ctx.tensor(np.ascontiguousarray(tr[k])) for k in ("positions", "velocities", "accelerations")]
         measure(ctx, N, K, D, h, R, *dev, args.reps, args.warmup,
                 f"grid-swap solved ({s.last_info['n_iterations']} it.)")
+        if args.list:
+            measure_listing(ctx, N, K, D, h, R, *dev, args.reps, args.warmup,
+                            f"grid-swap solved ({s.last_info['n_iterations']} it.)")
         del s
     ctx.close()
 
