@@ -658,7 +658,8 @@ extern "C" int scp_qp_get_duals(scp_qp* qp, double* y_fixed, double* y_col) {
 
 // test hook: copy one internal array of the solver to `out` (device pointer, capacity `cap` doubles); *n_out [host] = its
 // length.  names: "fx" (carried F x, [4K-1][C]), "qx" (carried S0 x, [K][C]), "gval" (row value per incidence entry),
-// "zf", "yf" ([4K-1][C]), "zc", "yc" (per working row), "x" ([K][C]).
+// "zf", "yf" ([4K-1][C]), "zc", "yc" (per working row), "x" ([K][C]); "Hf", "Minv", "T" (K x K, row-major): the blocks of
+// the current rho (H_f, its inverse, T = S0 H_f^{-1}) in the active cache slot.
 extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t cap, int64_t* n_out) {
   if (!qp) return SCP_ERR_INVALID;
   scp_ctx* ctx = qp->ctx;
@@ -679,6 +680,9 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
   else if (!strcmp(name, "w_l")) { src = d.w_l; n = qp->nW; }
   else if (!strcmp(name, "p")) { src = d.p; n = nx; }
   else if (!strcmp(name, "qp")) { src = d.s0p; n = nx; }
+  else if (!strcmp(name, "Hf")) { src = d.Hf; n = (int64_t)qp->K * qp->K; }
+  else if (!strcmp(name, "Minv")) { src = d.Minv; n = (int64_t)qp->K * qp->K; }
+  else if (!strcmp(name, "T")) { src = d.T; n = (int64_t)qp->K * qp->K; }
   else return scp_fail(ctx, SCP_ERR_INVALID, "qp_peek: unknown array %s", name);
   *n_out = n;
   if (n > cap) return scp_fail(ctx, SCP_ERR_CAPACITY, "qp_peek: %lld doubles needed", (long long)n);

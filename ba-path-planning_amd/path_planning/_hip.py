@@ -661,7 +661,7 @@ class QP:
 
     def peek(self, name):
         """internal array `name` of the solver (test hook, see scp_qp_peek)"""
-        cap = (4 * self.K - 1) * self.N * self.D + 2 * max(self.n_rows, 1)
+        cap = max((4 * self.K - 1) * self.N * self.D, self.K * self.K) + 2 * max(self.n_rows, 1)
         out = self.ctx.empty(cap)
         n = C.c_int64()
         self.ctx.check(self.ctx.lib.scp_qp_peek(self.h_qp, name.encode(), out.data_ptr(), cap, C.byref(n)))

@@ -480,8 +480,9 @@ int scp_gemm_f64(scp_ctx* ctx, int use_mfma, int R, int M, int C, double alpha, 
                  const double* X, double beta, double* Y);
 /* Copy one internal array of the solver (time-major device layout) to `out` (device, capacity `cap` doubles);
  * *n_out [host] = its length.  name: "x" [K][C], "zf" / "yf" / "fx" [4K-1][C] (fx = carried F x), "qx" [K][C] (carried S0 x),
- * "zc" / "yc" per working row, "gval" per incidence-list entry.  tests/test_qp_gpu.py compares the state the persistent
- * and the three-launch pipelines leave behind. */
+ * "zc" / "yc" per working row, "gval" per incidence-list entry; "Hf" / "Minv" / "T" [K][K] row-major: the blocks of the
+ * current rho (H_f, its inverse, T = S0 H_f^-1; tests/test_pipeline_iterates_gpu.py).  tests/test_qp_gpu.py compares the
+ * state the persistent and the three-launch pipelines leave behind. */
 int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t cap, int64_t* n_out);
 /* "persist_fault" = n: the next n persistent launches wait for a workgroup that does not exist, so their bounded spins time
  * out (the give-up path: nothing written back, the solve continues on the three-launch pipeline); "persist_off": read

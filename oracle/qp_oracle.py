@@ -248,7 +248,7 @@ def working_rows(prob, rows):
 
 
 def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, st: Settings | None = None,
-                    rows0=None, trace=None, snapshots=None, snap_out=None):
+                    rows0=None, trace=None, snapshots=None, snap_out=None, zero_qx=None):
     """Joint QP  min ||x||^2  s.t. fixed rows and ALL collision rows (eta, l_col; None -> QP#0).
 
     Exact constraint generation: ADMM runs on the fixed rows plus a working set W of collision rows;
@@ -260,6 +260,9 @@ def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, 
     state after exactly m steps -- the state a solve with max_iter = m ends in: "x" (N, K, D); "zf" / "yf", the four
     fixed-row blocks (jerk, acc, vel, pos) as in `y` below; "rows", "zc", "yc" of the working collision rows (sorted row
     ids); "rho" (after that step's adaptive-rho test) and "round" (1-based).  Results are unchanged by it.
+
+    zero_qx = (m, c): a deliberate fault for the sensitivity controls of the step-level tests -- during ADMM step m (1-based)
+    the collision rows read S0 x of column c = i D + d as zero, the way a stale or skipped S0 x slab would look.
     """
     st = st or Settings()
     N, K, D, h = prob.N, prob.K, prob.D, prob.h
@@ -291,6 +294,8 @@ def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, 
 
     def col_apply(x_, wk, wi, wj_, we):
         Q = np.einsum("km,imd->ikd", ops.S0, x_)
+        if zero_qx is not None and total_it == zero_qx[0]:
+            Q[zero_qx[1] // D, :, zero_qx[1] % D] = 0.0
         return np.sum(we * (Q[wi, wk, :] - Q[wj_, wk, :]), axis=1)
 
     def col_apply_T(g, wk, wi, wj_, we):

@@ -235,15 +235,24 @@ static void build_hf(int K, double h, double sigma, double rho, double eq, doubl
   free(e); free(tj); free(ta); free(tv); free(tp); free(o);
 }
 static void spd_inverse(int K, const double* A, double* Ainv) {
+  /* Every sum below runs over k in ascending order, element by element; the loops are nested so that the inner one walks
+   * rows (L, and its transpose U for the back substitution) instead of columns. */
   double* L = malloc(sizeof(double) * K * K);
+  double* U = malloc(sizeof(double) * K * K);
   memcpy(L, A, sizeof(double) * K * K);
   for (int j = 0; j < K; ++j) {  /* Cholesky, lower */
-    for (int k = 0; k < j; ++k)
-      for (int i = j; i < K; ++i) L[(size_t)i * K + j] -= L[(size_t)i * K + k] * L[(size_t)j * K + k];
+    for (int i = j; i < K; ++i) {
+      double s = L[(size_t)i * K + j];
+      for (int k = 0; k < j; ++k) s -= L[(size_t)i * K + k] * L[(size_t)j * K + k];
+      L[(size_t)i * K + j] = s;
+    }
     const double dj = sqrt(L[(size_t)j * K + j]);
     for (int i = j; i < K; ++i) L[(size_t)i * K + j] /= dj;
   }
+  for (int i = 0; i < K; ++i)
+    for (int k = 0; k < K; ++k) U[(size_t)i * K + k] = L[(size_t)k * K + i];
   double* y = malloc(sizeof(double) * K);
+  double* col = malloc(sizeof(double) * K);
   for (int c = 0; c < K; ++c) {
     for (int i = 0; i < K; ++i) {
       double s = i == c ? 1.0 : 0.0;
@@ -252,11 +261,12 @@ static void spd_inverse(int K, const double* A, double* Ainv) {
     }
     for (int i = K - 1; i >= 0; --i) {
       double s = y[i];
-      for (int k = i + 1; k < K; ++k) s -= L[(size_t)k * K + i] * Ainv[(size_t)k * K + c];
-      Ainv[(size_t)i * K + c] = s / L[(size_t)i * K + i];
+      for (int k = i + 1; k < K; ++k) s -= U[(size_t)i * K + k] * col[k];
+      col[i] = s / L[(size_t)i * K + i];
     }
+    for (int i = 0; i < K; ++i) Ainv[(size_t)i * K + c] = col[i];
   }
-  free(L); free(y);
+  free(L); free(U); free(y); free(col);
 }
 static void dense_apply(int K, int C, const double* M, const double* v, double* out) {
   for (int c = 0; c < C; ++c) {

@@ -53,6 +53,7 @@ class Scenario:
     K: int
     dim: int
     margin: float = 0.5  # working set: rows with dist - R < margin at the QP#0 solution
+    qp0_iters: int = 4000  # cap of the oracle's QP#0 run behind x0 (long horizons: any x0 is a valid start)
 
     @property
     def T(self):
@@ -115,7 +116,7 @@ def make_problem(scen: Scenario):
 def setup(scen: Scenario):
     """(prob, x0, eta, l_col, dist, W): the QP#0 solution of the oracle, the linearisation there and the working set"""
     prob = make_problem(scen)
-    x0, _, _ = qo.admm_structured(prob, st=qo.Settings(eps_abs=1e-6, eps_rel=1e-6, max_iter=4000))
+    x0, _, _ = qo.admm_structured(prob, st=qo.Settings(eps_abs=1e-6, eps_rel=1e-6, max_iter=scen.qp0_iters))
     pos, _ = so.kinematics(prob, x0)
     eta, l_col, dist = so.linearize_pairs(prob, pos)
     W = np.nonzero(dist - prob.R < scen.margin)[0].astype(np.int64)
@@ -137,12 +138,14 @@ def gpu_step_settings(kernel, max_iter, **kw):
     return base
 
 
-def oracle_snapshots(scen: Scenario, steps=STEPS, l_col=None):
-    """{m: oracle state after m steps} (one oracle run up to max(steps)) and its info"""
+def oracle_snapshots(scen: Scenario, steps=STEPS, l_col=None, rows=None, zero_qx=None, **settings):
+    """{m: oracle state after m steps} (one oracle run up to max(steps)) and its info; rows: a working set other than the
+    scenario's; zero_qx: the oracle's deliberate fault; settings: over step_settings"""
     prob, x0, eta, l0, dist, W = setup(scen)
     snaps = {}
-    _, _, info = qo.admm_structured(prob, eta, l0 if l_col is None else l_col, dist, x0=x0, st=step_settings(max(steps)),
-                                    rows0=W, snapshots=set(steps), snap_out=snaps)
+    _, _, info = qo.admm_structured(prob, eta, l0 if l_col is None else l_col, dist, x0=x0,
+                                    st=step_settings(max(steps), **settings), rows0=W if rows is None else rows,
+                                    snapshots=set(steps), snap_out=snaps, zero_qx=zero_qx)
     return snaps, info
 
 
