@@ -115,6 +115,8 @@ size_t carve(QpDev& d, void* ws, int K, int64_t C, int64_t cap, int D) {
   d.gval3 = c.take<double>((size_t)2 * cap);
   d.pos_i = c.take<int>((size_t)cap);
   d.pos_j = c.take<int>((size_t)cap);
+  d.grow = c.take<double>((size_t)cap);
+  d.own_code = c.take<int>((size_t)(SCP_PERSIST_MAX_WG + 1) * SCP_PERSIST_CAP_MAX);
   d.sync_words = c.take<unsigned long long>(SCP_SYNC_WORDS);
   d.cells = c.take<unsigned long long>((size_t)2 * nx);
   d.gpart = c.take<unsigned long long>(SCP_GPART_WORDS);
@@ -198,6 +200,10 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
   qp->steps_since_reset = 0;
   memset(qp->lim, 0, sizeof(qp->lim));
   qp->persist_fault = 0;
+  {  // (the environment sets the hook's starting value: the QP objects inside scp_solver have no handle of their own)
+    const char* e = getenv("SCP_PERSIST_HOST_LISTS");
+    qp->persist_host_lists = e && atoi(e) != 0;
+  }
   qp->persist_cap_nW = -1;
   qp->persist_cap = 0;
   qp->persist_epoch = 0;
@@ -670,7 +676,10 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
   int64_t n = 0;
   if (!strcmp(name, "fx")) { src = d.fx; n = nf; }
   else if (!strcmp(name, "qx")) { src = scp_qp_qx(qp); n = nx; }
-  else if (!strcmp(name, "gval")) { src = d.gval; n = 2 * qp->nW; }
+  else if (!strcmp(name, "gval")) {
+    if (qp->dv.carried && qp->dv.vals_by_row) QP_CHECK(scp_qp_rows_values_to_entries(qp));
+    src = d.gval; n = 2 * qp->nW;
+  }
   else if (!strcmp(name, "zf")) { src = d.zf; n = nf; }
   else if (!strcmp(name, "yf")) { src = d.yf; n = nf; }
   else if (!strcmp(name, "zc")) { src = d.zc; n = qp->nW; }
@@ -692,12 +701,18 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
 
 // test hook: "persist_fault" = n makes the next n persistent launches wait for a workgroup that does not exist (exercises
 // the give-up path); "persist_off" reads (value < 0) or sets whether the solver has fallen back to the three-launch
-// pipeline.  Returns the value in effect, or SCP_ERR_INVALID.
+// pipeline; "persist_host_lists" = 1: the host builds the incidence lists and the row values before every persistent launch
+// and the kernel loads its slice of them, instead of building its own tables (SCP_PERSIST_HOST_LISTS=1 in the environment:
+// every QP object starts with it set).  Returns the value in effect, or SCP_ERR_INVALID.
 extern "C" int scp_qp_debug_set(scp_qp* qp, const char* key, int value) {
   if (!qp || !key) return SCP_ERR_INVALID;
   if (!strcmp(key, "persist_fault")) {
     if (value >= 0) qp->persist_fault = value;
     return qp->persist_fault;
+  }
+  if (!strcmp(key, "persist_host_lists")) {
+    if (value >= 0) qp->persist_host_lists = value != 0;
+    return qp->persist_host_lists ? 1 : 0;
   }
   if (!strcmp(key, "persist_off")) {
     if (value >= 0) qp->persist_off = value != 0;

@@ -695,7 +695,8 @@ int scp_qp_qp0_iterations(scp_qp* qp, int nit, double* dy_out) {
 }
 
 int scp_qp_cg1_prepare(scp_qp* qp) {
-  if (qp->dv.carried) return SCP_OK;
+  if (qp->dv.carried)  // (a persistent kernel with its own entry tables left the row values per row)
+    return qp->dv.vals_by_row ? scp_qp_rows_values_to_entries(qp) : SCP_OK;
   QP_CHECK(scp_qp_exact_qx(qp, true));
   QP_CHECK(scp_qp_rows_first_values(qp, scp_qp_qx(qp)));
   qp_on_cg1_prepared(qp);

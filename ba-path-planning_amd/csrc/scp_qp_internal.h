@@ -72,6 +72,8 @@ struct QpDev {
   double* gval2;  // [2 cap]   row vectors of a termination check: yc ...
   double* gval3;  // [2 cap]   ... and delta-yc (gval keeps the pipeline's values across a check)
   int *pos_i, *pos_j;  // [cap] entry positions of row n
+  double* grow;        // [cap] row values per ROW: what a persistent kernel that built its own entry tables leaves at its exit
+  int* own_code;       // [SCP_PERSIST_MAX_WG + 1][SCP_PERSIST_CAP_MAX] the sorted entry codes of each of its workgroups
   double* kkt_pool;  // scp_kkt_slots(K) cache slots of the rho-dependent blocks
   unsigned long long* sync_words;  // SCP_SYNC_WORDS: give-up word of the persistent kernel, scratch
   unsigned long long* cells;       // [K][N][D][2] tagged granules: S0 p cells published by the persistent kernel
@@ -86,7 +88,10 @@ struct QpDerived {
   bool qx = false;          // the S0 x half of HQ and the F x slab are exact for x
   int qx_half = 0;          // which half of HQ holds S0 x: 0 -> rows [K, 2K), 1 -> [0, K) (swapped by every single step)
   double vals_rho_c = 0.0;  // > 0: the small install built lists and row values with the latest rows, at this column rho
-  bool carried = false;     // the single-step pipeline's carried state (S0 x, F x, row values gval) matches (x, zc, yc, rho)
+  bool carried = false;     // the single-step pipeline's carried state (S0 x, F x, row values) matches (x, zc, yc, rho)
+  // (with carried) where the row values are: false -> gval, per entry of the incidence lists; true -> grow, per row, left by a
+  // persistent kernel that built its own entry tables (gval is stale then, and so are the lists unless `lists` says otherwise)
+  bool vals_by_row = false;
 };
 
 struct scp_qp {
@@ -122,6 +127,7 @@ struct scp_qp {
                                      // unprojected z = A x0 of a reset: their first step of a QP takes z = v (y = 0 then)
   int persist_variant;               // of the latest persistent launch: 0 = 8 (4 in 3-D) agents per workgroup, 1 = lean, 16
   int persist_fault;                 // test hook: the next n persistent launches wait for a workgroup that does not exist
+  bool persist_host_lists;           // test hook: the host builds lists and row values for every persistent launch
   bool persist_off;                  // a launch gave up (workgroups not co-resident): three-launch pipeline until the next
                                      // scp_qp_reset / scp_qp_set_problem re-arms the persistent path
   bool persist_skip_solve;           // the CUs for a persistent launch were not free: this scp_qp_solve call stays on the
@@ -194,6 +200,8 @@ int scp_qp_rows_gather(scp_qp* qp, const double* Q);
 // the lists (when stale) and the first row values g = (rho_c zc - yc) - rho_c eta.d(S0 x) of the single-step pipeline,
 // Qx = S0 x exact: nothing, one workgroup's launch, or scp_qp_csr_ensure + one row launch (for scp_qp_cg1_prepare)
 int scp_qp_rows_first_values(scp_qp* qp, const double* Qx);
+// the carried row values from grow (per row) into gval (per entry), the lists built when stale: scp_qp_csr_ensure + one launch
+int scp_qp_rows_values_to_entries(scp_qp* qp);
 // the row vectors of a fused termination check into the entry arrays: gval2 = yc and, with_dy, gval3 = delta-yc
 int scp_qp_rows_check_values(scp_qp* qp, bool with_dy);
 // small problems: working rows [nW, nW + n) recomputed from the linearisation point (scp_qp_add_rows_at) AND the incidence
@@ -227,6 +235,8 @@ constexpr int SCP_SYNC_WORDS = 16;  // u64: give-up word | scratch
 // Workgroups of a persistent launch: at most one per CU (all resident), and the exchange buffers below are sized for
 // exactly this many (+1: the fault-injection hook announces one workgroup more than it launches).
 constexpr int SCP_PERSIST_MAX_WG = 256;
+// No kernel's entry tables hold more rows than this: 160 KiB of LDS over the smallest entry (68 B, lean kernel in 2-D)
+constexpr int SCP_PERSIST_CAP_MAX = 2432;
 constexpr int SCP_GPART_WORDS = 2 * (SCP_PERSIST_MAX_WG + 1) * 4;  // two buffers x workgroups x two doubles as granule pairs
 constexpr int SCP_GCHECK_WORDS = (SCP_PERSIST_MAX_WG + 1) * 9 * 2;  // nine check results per workgroup as granule pairs
 bool scp_qp_persist_eligible(const scp_qp* qp);
@@ -260,11 +270,17 @@ inline void qp_on_fused_check(scp_qp* qp) { qp->dv.qx = true; }  // (S0 x and F 
 inline void qp_on_cg1_step(scp_qp* qp) { qp->dv.qx = false; qp->dv.qx_half ^= 1; }
 // a persistent launch ended: its last check left S0 x and F x exact.  After a give-up a workgroup may still have written
 // back (the kernel's exit decision closes that window but cannot exclude it): the carried slabs may not match x / z / y.
-inline void qp_on_persist_exit(scp_qp* qp, int code) {
+// own_lists: the kernel built its own entry tables and row values and left the values per row -- gval (and the lists, where
+// nobody has built them) do not belong to this state; whoever needs them goes through scp_qp_cg1_prepare.
+inline void qp_on_persist_exit(scp_qp* qp, int code, bool own_lists) {
   qp->dv.qx = code != SCP_PERSIST_GAVE_UP;
   if (code == SCP_PERSIST_GAVE_UP) qp->dv.carried = false;
+  else if (own_lists) qp->dv.carried = qp->dv.vals_by_row = true;
 }
 // what the rebuilds made (the iterations after scp_qp_cg1_prepare carry its row values on)
 inline void qp_on_qx_built(scp_qp* qp, bool with_fx) { qp->dv.qx_half = 0; qp->dv.qx = with_fx; }
 inline void qp_on_lists_built(scp_qp* qp) { qp->dv.lists = true; }
-inline void qp_on_cg1_prepared(scp_qp* qp) { qp->dv.lists = qp->dv.carried = true; qp->dv.vals_rho_c = 0.0; }
+inline void qp_on_cg1_prepared(scp_qp* qp) {
+  qp->dv.lists = qp->dv.carried = true; qp->dv.vals_by_row = false; qp->dv.vals_rho_c = 0.0;
+}
+inline void qp_on_vals_to_entries(scp_qp* qp) { qp->dv.vals_by_row = false; }  // (scp_qp_rows_values_to_entries)

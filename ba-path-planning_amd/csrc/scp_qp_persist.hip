@@ -99,13 +99,21 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
 
   // ---- entries of this block of agents (contiguous in the agent-major incidence lists) --------------------------
   const int a1 = min(a0 + APB, N);
-  const int ebase = A.cell_ptr[cell_of(0, a0, K)];
-  const int ne = A.cell_ptr[cell_of(0, a1, K)] - ebase;
-  if (entries_overflow<APB>(A)) return;
+  // (own_lists: built here from the raw rows, with the r tile, gp and e_pp as scratch; else the slice of the host's lists)
+  int ebase0 = 0, ne;
+  if (A.own_lists) {
+    ne = build_entry_tables<APB, NT>(A, a0, a1, cptr, e_code, (int*)e_pp, (int*)Rt, (int*)gp);
+    if (ne < 0) return;
+  } else {
+    ebase0 = A.cell_ptr[cell_of(0, a0, K)];
+    ne = A.cell_ptr[cell_of(0, a1, K)] - ebase0;
+    if (entries_overflow<APB>(A)) return;
+    for (int i = threadIdx.x; i <= (a1 - a0) * K; i += NT) cptr[i] = A.cell_ptr[cell_of(0, a0, K) + i] - ebase0;
+  }
   if (threadIdx.x == 0) fail_s = 0;
-  for (int i = threadIdx.x; i <= (a1 - a0) * K; i += NT) cptr[i] = A.cell_ptr[cell_of(0, a0, K) + i] - ebase;
   for (int e = threadIdx.x; e < ne; e += NT) {
-    const int code = A.ent_code[ebase + e];
+    const bool own_lists = A.own_lists != 0;
+    const int code = own_lists ? e_code[e] : A.ent_code[ebase0 + e];
     const int n = code >> 1, side = code & 1;
     const int wi = A.w_i[n], wj = A.w_j[n], wk = A.w_k[n];
     const int own = side ? wj : wi, par = side ? wi : wj;
@@ -113,17 +121,21 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
     e_pad[e] = ((wk * N + par) * D) * 2;
     e_row[e] = n;
     const int64_t bo = (int64_t)wk * C + (int64_t)own * D, bp = (int64_t)wk * C + (int64_t)par * D;
+    double ax = 0.0;  // c . (S0 x_own - S0 x_partner): the ax of rows_value_kernel (c and the difference change sign together)
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const double eta = A.w_eta[(size_t)n * D + d];
-      e_c[(size_t)e * D + d] = side ? -eta : eta;
-      e_qo[(size_t)e * D + d] = A.Qx[bo + d];
-      e_qp[(size_t)e * D + d] = A.Qx[bp + d];
+      const double c = side ? -eta : eta, qo = A.Qx[bo + d], qp = A.Qx[bp + d];
+      e_c[(size_t)e * D + d] = c;
+      e_qo[(size_t)e * D + d] = qo;
+      e_qp[(size_t)e * D + d] = qp;
+      ax = __builtin_fma(c, qo - qp, ax);
     }
     e_l[e] = A.w_l[n];
-    e_z[e] = A.zc[n];
-    e_y[e] = A.yc[n];
-    e_g[e] = A.gval[ebase + e];
+    const double zc = A.zc[n], yc = A.yc[n];
+    e_z[e] = zc;
+    e_y[e] = yc;
+    e_g[e] = !own_lists ? A.gval[ebase0 + e] : (A.vals_carried ? A.grow[n] : first_row_value(rho_c, zc, yc, ax));
   }
   for (int i = threadIdx.x; i < CB * RSK; i += NT) Rt[i] = 0.0;  // columns beyond the block stay zero
 
@@ -528,11 +540,14 @@ __global__ __launch_bounds__(64 * persist_apb(D)) void cg1_persist_kernel(Persis
       A.Qx[g] = qx[d];
     }
   }
+  const bool own_lists = A.own_lists != 0;
+  const int ebase = own_lists ? 0 : A.cell_ptr[cell_of(0, a0, K)];
   for (int e = threadIdx.x; e < ne; e += NT) {
-    A.gval[ebase + e] = e_g[e];
+    if (!own_lists) A.gval[ebase + e] = e_g[e];
     if (!((e_code[e] >> 16) & 1)) {
       A.zc[e_row[e]] = e_z[e];
       A.yc[e_row[e]] = e_y[e];
+      if (own_lists) A.grow[e_row[e]] = e_g[e];  // both entries of a row hold the same bits
       if (with_dy) A.dyc[e_row[e]] = e_pp[(size_t)e * D];
     }
   }
@@ -613,7 +628,11 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   const int apb = pk.apb;
   const int nblk = (qp->N + apb - 1) / apb;
   *ran = 0;
-  QP_CHECK(scp_qp_cg1_prepare(qp));
+  // Lists and row values that exist (the small install's one launch) are loaded; otherwise the kernel builds its own entry
+  // tables and values from the raw rows and needs S0 x and F x only (test hook "persist_host_lists": the host builds them)
+  const bool own_lists = !qp->persist_host_lists && !qp->dv.lists && qp->nW < (1 << 29);  // (32-bit entry codes)
+  if (!own_lists) QP_CHECK(scp_qp_cg1_prepare(qp));
+  else if (!qp->dv.carried) QP_CHECK(scp_qp_exact_qx(qp, true));
   // Entry tables: the workgroup is alone on its CU anyway (228 VGPRs x 8 waves), so it simply takes all the LDS there is
   // -- no read-back of the largest block's entry count.  A block of agents with more incident rows than fit (> ~1300 at
   // K = 50) makes the kernel leave at once with EXIT_OVERFLOW; that working set then runs on the three-launch pipeline.
@@ -623,7 +642,7 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
     const size_t fixed = pk.lds_bytes(K, 0, nb, D, apb);
     const size_t budget_lds = 160 * 1024 - pk.static_lds;
     if (fixed + 64 * pk.entry_bytes > budget_lds) return SCP_OK;
-    qp->persist_cap = (int)((budget_lds - fixed) / pk.entry_bytes / 64 * 64);
+    qp->persist_cap = std::min((int)((budget_lds - fixed) / pk.entry_bytes / 64 * 64), SCP_PERSIST_CAP_MAX);
   }
   // test hook (scp_qp_debug_set "persist_fault"): expect one workgroup more than is launched, so that the all-gather can
   // never complete -- the bounded spins must time out, every workgroup must leave without writing state back, and the
@@ -679,6 +698,8 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
   a.give_up = (unsigned*)d.sync_words;
   a.cell_ptr = d.cell_ptr; a.ent_code = d.ent_code; a.w_k = d.w_k; a.w_i = d.w_i; a.w_j = d.w_j;
   a.w_eta = d.w_eta; a.w_l = d.w_l; a.zc = d.zc; a.yc = d.yc; a.dyc = d.dyc; a.gval = d.gval;
+  a.nW = (int)qp->nW; a.own_lists = own_lists ? 1 : 0; a.own_code = d.own_code; a.grow = d.grow;
+  a.vals_carried = own_lists && qp->dv.carried ? 1 : 0;  // (a relaunch in the same solve: rows and rho as they were)
   a.host_status = qp->h_persist_dev;
   a.host_scal = qp->h_scal_dev;
   a.host_flag = (u64*)(qp->h_scal_dev + SL_COUNT + SCP_RESID_CAP);
@@ -727,7 +748,7 @@ int scp_qp_cg1_persist(scp_qp* qp, int it0, int cad0, int* ran, int* code, int* 
     *ran = 0;
     return SCP_OK;
   }
-  qp_on_persist_exit(qp, *code);
+  qp_on_persist_exit(qp, *code, own_lists);
   if (*code == SCP_PERSIST_GAVE_UP) {
     ++qp->persist_gave_up_total;
   } else {

@@ -149,13 +149,22 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
 
   // ---- entries of this block of agents (contiguous in the agent-major incidence lists) --------------------------
   const int a1 = min(a0 + APB16, N);
-  const int ebase = A.cell_ptr[cell_of(0, a0, K)];
-  const int ne = A.cell_ptr[cell_of(0, a1, K)] - ebase;
-  if (entries_overflow<APB16>(A)) return;
+  // (own_lists: built here from the raw rows, with the r / p tiles, gp and e_s as scratch; else the slice of the host's lists)
+  int ebase0 = 0, ne;
+  if (A.own_lists) {
+    ne = build_entry_tables<APB16, NT16>(A, a0, a1, cptr, e_code, (int*)e_s, (int*)Rt, (int*)gp);
+    if (ne < 0) return;
+  } else {
+    ebase0 = A.cell_ptr[cell_of(0, a0, K)];
+    ne = A.cell_ptr[cell_of(0, a1, K)] - ebase0;
+    if (entries_overflow<APB16>(A)) return;
+    for (int i = threadIdx.x; i <= (a1 - a0) * K; i += NT16) cptr[i] = A.cell_ptr[cell_of(0, a0, K) + i] - ebase0;
+  }
   if (threadIdx.x == 0) fail_s = 0;
-  for (int i = threadIdx.x; i <= (a1 - a0) * K; i += NT16) cptr[i] = A.cell_ptr[cell_of(0, a0, K) + i] - ebase;
   for (int e = threadIdx.x; e < ne; e += NT16) {
-    const int code = A.ent_code[ebase + e];
+    const bool own_lists = A.own_lists != 0;
+    const int code = own_lists ? e_code[e] : A.ent_code[ebase0 + e];
+    if (own_lists) A.own_code[(size_t)blockIdx.x * cap + e] = code;  // (n per entry again at the exit)
     const int n = code >> 1, side = code & 1;
     const int wi = A.w_i[n], wj = A.w_j[n], wk = A.w_k[n];
     const int own = side ? wj : wi, par = side ? wi : wj;
@@ -171,9 +180,10 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
     }
     e_ax[e] = ax;
     e_l[e] = A.w_l[n];
-    e_z[e] = A.zc[n];
-    e_y[e] = A.yc[n];
-    e_g[e] = A.gval[ebase + e];
+    const double zc = A.zc[n], yc = A.yc[n];
+    e_z[e] = zc;
+    e_y[e] = yc;
+    e_g[e] = !own_lists ? A.gval[ebase0 + e] : (A.vals_carried ? A.grow[n] : first_row_value(rho_c, zc, yc, ax));
   }
   for (int i = threadIdx.x; i < NC16 * RSK; i += NT16) Rt[i] = 0.0;  // columns beyond the block stay zero
   for (int i = threadIdx.x; i < tK * nks * 64; i += NT16) {
@@ -696,12 +706,15 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
       A.Qx[g] = hh * (c2[d] - 0.5 * c1b);
     }
   }
+  const bool own_lists = A.own_lists != 0;
+  const int ebase = own_lists ? 0 : A.cell_ptr[cell_of(0, a0, K)];
   for (int e = threadIdx.x; e < ne; e += NT16) {
-    A.gval[ebase + e] = e_g[e];
+    if (!own_lists) A.gval[ebase + e] = e_g[e];
     if (!((e_code[e] >> 10) & 1)) {
-      const int n = A.ent_code[ebase + e] >> 1;
+      const int n = (own_lists ? A.own_code[(size_t)blockIdx.x * cap + e] : A.ent_code[ebase + e]) >> 1;
       A.zc[n] = e_z[e];
       A.yc[n] = e_y[e];
+      if (own_lists) A.grow[n] = e_g[e];  // both entries of a row hold the same bits
     }
   }
   PSTAMP(8);

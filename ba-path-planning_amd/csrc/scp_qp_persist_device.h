@@ -43,6 +43,15 @@ struct PersistArgs {
   const int *cell_ptr, *ent_code, *w_k, *w_i, *w_j;
   const double *w_eta, *w_l;
   double *zc, *yc, *dyc, *gval;
+  // Where the entry tables come from.  own_lists = 0: the host built the incidence lists and the row values (cell_ptr,
+  // ent_code, gval: the small install's single launch, or the "persist_host_lists" hook) and the kernel copies its slice.
+  // own_lists = 1: every workgroup derives its slice from the nW raw rows (build_entry_tables) and forms the row values
+  // from the S0 x cells it loads anyway -- or, vals_carried, takes the values an earlier launch of this solve left per
+  // row in `grow` -- and cell_ptr / ent_code / gval are neither read nor written.
+  int nW, own_lists, vals_carried;
+  int* own_code;  // [SCP_PERSIST_MAX_WG + 1][ent_cap]: the sorted codes 2 n + side of each workgroup, written at entry and read
+                  // again by the same workgroup at the exit (the lean kernels keep no row index in LDS)
+  double* grow;   // [nW] the row values at the exit, per row (from the side-0 entry)
   unsigned* host_status;  // mapped host words: [0] exit code (EXIT_*), [1] ADMM iterations done when the kernel left
   double* host_scal;      // mapped host array: the nine check results in the SL_* slots of scp_qp::h_scal
   u64* host_flag;         // mapped completion word, set to `seq` last
@@ -225,8 +234,17 @@ __device__ __forceinline__ unsigned check_decision(const PersistArgs& A, const d
 }
 
 // More incident rows around some block of APB agents than the LDS tables hold: EVERY workgroup finds that out by itself
-// (the largest block's count, a few loads) and leaves before anything is published -- nobody spins on anybody.  True: the
-// caller returns at once.
+// (the largest block's count) and leaves before anything is published -- nobody spins on anybody.  `over`: this thread
+// saw a block beyond the capacity.  True: the caller returns at once.
+__device__ __forceinline__ bool leave_on_overflow(const PersistArgs& A, bool over) {
+  if (!__syncthreads_or(over)) return false;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    __hip_atomic_store(A.host_status, (unsigned)EXIT_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+  return true;
+}
+// ... from the host-built lists: a few loads of cell_ptr
 template <int APB>
 __device__ __forceinline__ bool entries_overflow(const PersistArgs& A) {
   int worst = 0;
@@ -234,12 +252,113 @@ __device__ __forceinline__ bool entries_overflow(const PersistArgs& A) {
     const int b0 = b * APB, b1 = min(b0 + APB, A.N);
     worst = max(worst, A.cell_ptr[cell_of(0, b1, A.K)] - A.cell_ptr[cell_of(0, b0, A.K)]);
   }
-  if (!__syncthreads_or(worst > A.ent_cap)) return false;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    __hip_atomic_store(A.host_status, (unsigned)EXIT_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(A.host_flag, A.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  return leave_on_overflow(A, worst > A.ent_cap);
+}
+
+// The entry tables of the block of agents [a0, a1) straight from the raw working rows (PersistArgs::own_lists), with no
+// word exchanged between workgroups: the same block-relative cell offsets (cptr[(a1 - a0) K + 1]) and the same codes
+// 2 n + side in the same order as the slice of the global build (scp_qp_csr_ensure: cells in cell_of order, ascending
+// code inside a cell), and the entry count of EVERY block of the grid, so that the overflow decision is the one every
+// other workgroup takes.  One pass over the nW rows (four rows in flight per thread): LDS atomic counts per block of the
+// grid and per own cell, the own hits appended unsorted; then, in LDS only, a scan of the cell counts (one wave), the
+// scatter into cell order and an insertion sort per cell.  Integer counts do not depend on the order of the atomics, and
+// the sort fixes the order inside a cell.  Temporaries, all free until the column state is loaded: hits [2 cap] (code,
+// cell), cur [(a1 - a0) K] fill cursors, blk_cnt [blocks of the grid].  Every loop is bounded by nW, the cell count or the
+// block's entry count.  Returns the block's entry count, or -1: some block overflows the tables, the caller returns.
+template <int APB, int NT>
+__device__ __forceinline__ int build_entry_tables(const PersistArgs& A, int a0, int a1, int* cptr, int* codes, int* hits,
+                                                  int* cur, int* blk_cnt) {
+  static_assert(APB <= 16 && (APB & (APB - 1)) == 0, "one wave scans 64 x 16 cells; blocks by shift");
+  const int K = A.K, nW = A.nW, cap = A.ent_cap, tid = threadIdx.x, me = blockIdx.x;
+  const int nb = (A.N + APB - 1) / APB, ncell = (a1 - a0) * K;
+  for (int i = tid; i <= ncell; i += NT) cptr[i] = 0;  // entry counts of the own cells first, offsets after the scan
+  for (int i = tid; i < ncell; i += NT) cur[i] = 0;
+  for (int i = tid; i < nb; i += NT) blk_cnt[i] = 0;
+  __syncthreads();
+  constexpr int U = 4;
+  for (int n0 = tid; n0 < nW; n0 += U * NT) {
+    int w[U][2];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int n = n0 + u * NT;
+      w[u][0] = n < nW ? A.w_i[n] : -1;
+      w[u][1] = n < nW ? A.w_j[n] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int n = n0 + u * NT;
+#pragma unroll
+      for (int side = 0; side < 2; ++side) {
+        const int ag = w[u][side];
+        if (ag < 0) continue;
+        if (ag / APB != me) {
+          atomicAdd(&blk_cnt[ag / APB], 1);
+        } else {
+          const int at = atomicAdd(&blk_cnt[me], 1);
+          const int cell = (ag - a0) * K + A.w_k[n];
+          atomicAdd(&cptr[cell], 1);
+          if (at < cap) {  // (beyond: every workgroup leaves below)
+            hits[2 * at] = 2 * n + side;
+            hits[2 * at + 1] = cell;
+          }
+        }
+      }
+    }
   }
-  return true;
+  __syncthreads();
+  int worst = 0;
+  for (int b = tid; b < nb; b += NT) worst = max(worst, blk_cnt[b]);
+  if (leave_on_overflow(A, worst > cap)) return -1;
+  const int ne = blk_cnt[me];
+  if (tid < 64) {  // exclusive scan of the cell counts: 16 consecutive cells per lane (at most 16 agents x 64 time steps)
+    constexpr int SC = 16;
+    int v[SC], tot = 0;
+#pragma unroll
+    for (int e = 0; e < SC; ++e) {
+      v[e] = SC * tid + e < ncell ? cptr[SC * tid + e] : 0;
+      tot += v[e];
+    }
+    int incl = tot;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(incl, o);
+      if (tid >= o) incl += t;
+    }
+    int run = incl - tot;
+#pragma unroll
+    for (int e = 0; e < SC; ++e) {
+      if (SC * tid + e < ncell) cptr[SC * tid + e] = run;
+      run += v[e];
+    }
+    if (tid == 63) cptr[ncell] = run;
+  }
+  __syncthreads();
+  for (int t = tid; t < ne; t += NT) {
+    const int cell = hits[2 * t + 1];
+    codes[cptr[cell] + atomicAdd(&cur[cell], 1)] = hits[2 * t];
+  }
+  __syncthreads();
+  for (int c = tid; c < ncell; c += NT) {  // ascending code inside every cell, as csr_sort_kernel leaves it
+    const int b = cptr[c], e = cptr[c + 1];
+    for (int i = b + 1; i < e; ++i) {
+      const int v = codes[i];
+      int j = i - 1;
+      while (j >= b && codes[j] > v) {
+        codes[j + 1] = codes[j];
+        --j;
+      }
+      codes[j + 1] = v;
+    }
+  }
+  __syncthreads();
+  return ne;
+}
+
+// The first row value of the single-step pipeline, g = (rho_c z_c - y_c) - rho_c ax with ax = c . (S0 x_own - S0 x_partner)
+// summed from 0 in axis order: the two fused multiply-adds rows_value_kernel<D, true> compiles to, spelled out so that the
+// bits do not hang on how this translation unit is contracted.
+__device__ __forceinline__ double first_row_value(double rho_c, double zc, double yc, double ax) {
+  return __builtin_fma(-rho_c, ax, __builtin_fma(rho_c, zc, -yc));
 }
 
 // The exit decision is collective: a workgroup that timed out has raised the give-up word BEFORE the cell or partial it

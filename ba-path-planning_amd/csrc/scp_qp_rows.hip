@@ -465,6 +465,15 @@ int scp_qp_csr_scatter(scp_qp* qp, int mode, const double* vec) {
   return launch_gather(qp);
 }
 
+int scp_qp_rows_values_to_entries(scp_qp* qp) {
+  const QpDev& d = qp->d;
+  QP_CHECK(scp_qp_csr_ensure(qp));
+  QP_CHECK(qp_launch(qp, csr_rowval_kernel, grid1(qp->nW), dim3(256), 0, qp->nW, 2, 0.0, d.zc, d.yc, d.grow, d.pos_i, d.pos_j,
+                     d.gval, nullptr, nullptr));
+  qp_on_vals_to_entries(qp);
+  return SCP_OK;
+}
+
 int scp_qp_rows_check_values(scp_qp* qp, bool with_dy) {
   const QpDev& d = qp->d;
   return qp_launch(qp, csr_rowval_kernel, grid1(qp->nW), dim3(256), 0, qp->nW, 1, 0.0, d.zc, d.yc, nullptr, d.pos_i, d.pos_j,
