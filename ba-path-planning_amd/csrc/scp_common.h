@@ -57,6 +57,9 @@ struct scp_ctx {
   unsigned long long* sep_n_solved;  // inside it: segments of the latest scp_check_separation that reached the quartic
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;
+  void* clr_ws;                   // device workspace of scp_clearance_profile (records, bounds, partials; grown on demand)
+  size_t clr_ws_bytes;
+  unsigned long long* clr_n_solved;  // inside it: segments of the latest scp_clearance_profile that reached the quartic
 };
 
 static inline int scp_fail(scp_ctx* ctx, int code, const char* fmt, ...) {

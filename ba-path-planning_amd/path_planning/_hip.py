@@ -155,6 +155,16 @@ class Conflict(C.Structure):
 CONFLICT_DTYPE = np.dtype([("row", np.uint64), ("min_dist", np.float64), ("t_min", np.float64), ("t_enter", np.float64),
                            ("t_exit", np.float64), ("pieces", np.uint32), ("reserved", np.uint32)])
 
+
+class Clearance(C.Structure):
+    """struct scp_clearance (scp_clearance_profile): the closest approach of one vehicle or of one time step"""
+    _fields_ = [("min_dist", C.c_double), ("t_min", C.c_double), ("row", C.c_uint64), ("sample_min_dist", C.c_double),
+                ("n_violating", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+CLEARANCE_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("row", np.uint64),
+                            ("sample_min_dist", np.float64), ("n_violating", np.uint64), ("reserved", np.uint64)])
+
 NO_ROW = 2**64 - 1  # UINT64_MAX: "no such row" in the stats of the pairwise passes
 
 ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
@@ -164,6 +174,7 @@ EXPORTS = [
     "scp_ctx_last_pair_ms", "scp_ctx_set_option",
     "scp_kinematics", "scp_fixed_bounds", "scp_linearize_pairs", "scp_select_pairs", "scp_check_avoidance", "scp_qp_add_rows_at",
     "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
+    "scp_clearance_profile", "scp_ctx_last_clearance_solved",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
     "scp_qp_reset", "scp_qp_set_rho", "scp_qp_add_rows", "scp_qp_solve", "scp_qp_clone_state", "scp_qp_get_solution",
@@ -218,6 +229,8 @@ def load_library():
     lib.scp_check_separation.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp]
     lib.scp_ctx_last_separation_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_list_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, i64, vp]
+    lib.scp_clearance_profile.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp]
+    lib.scp_ctx_last_clearance_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_collision_violations_at.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_gather_rows.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]
@@ -419,6 +432,24 @@ class Context:
                 return out[: n * CONFLICT_DTYPE.itemsize].cpu().numpy().view(CONFLICT_DTYPE).copy()
             cap = n
         raise HipError(SCP_ERR_CAPACITY, f"list_conflicts: {n} records after a repetition sized for {cap}")
+
+    def clearance_profile(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None):
+        """scp_clearance_profile over the pair range [q_begin, q_end): the closest approach of every vehicle and of every
+        time step, as two numpy structured arrays (CLEARANCE_DTYPE) of length N and K -- synchronises."""
+        torch = _torch()
+        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        size = CLEARANCE_DTYPE.itemsize
+        out = torch.empty((N + K) * size, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_clearance_profile(self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(),
+                                                  acc.data_ptr(), out.data_ptr(), out.data_ptr() + N * size))
+        both = out.cpu().numpy().view(CLEARANCE_DTYPE)
+        return both[:N].copy(), both[N:].copy()
+
+    def last_clearance_solved(self):
+        """segments of the latest clearance_profile that needed the quartic's minimum"""
+        n = C.c_uint64()
+        self.check(self.lib.scp_ctx_last_clearance_solved(self.h, C.byref(n)))
+        return int(n.value)
 
     def last_separation_solved(self):
         """segments of the latest check_separation that needed the quartic's minimum (the rest: one comparison)"""

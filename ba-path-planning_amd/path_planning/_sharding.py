@@ -198,9 +198,12 @@ class Shard:
         dist.broadcast(t, src=src, group=self.group)
         return [int(v) for v in t.tolist()]
 
-    def all_min(self, value: float) -> float:
+    def all_min(self, value):
+        """min over ranks of a float, or element-wise of a float64 array (every rank passes the same length)"""
         if self.alone:
             return value
+        if not isinstance(value, (int, float)):
+            return self._all_reduce_array(value, torch.float64, dist.ReduceOp.MIN)
         t = torch.tensor([value], dtype=torch.float64, device=self._dev())
         dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
         return float(t.item())
@@ -221,10 +224,13 @@ class Shard:
         dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
         return int(t.item())
 
-    def all_sum_int(self, value: int) -> int:
-        """sum over ranks of a non-negative integer (counts of violating segments; the sum must stay below 2^63)."""
+    def all_sum_int(self, value):
+        """sum over ranks of a non-negative integer (counts of violating segments; the sum must stay below 2^63), or
+        element-wise of an integer array, which keeps its dtype (every rank passes the same length)."""
         if self.alone:
-            return int(value)
+            return value if hasattr(value, "dtype") else int(value)
+        if hasattr(value, "dtype"):
+            return self._all_reduce_array(value.astype("int64"), torch.int64, dist.ReduceOp.SUM).astype(value.dtype)
         t = torch.tensor([int(value)], dtype=torch.int64, device=self._dev())
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return int(t.item())
@@ -240,6 +246,37 @@ class Shard:
         best_row = self.all_min_int(int(row) if value == best else none)
         mine = value == best and min(int(row), none) == best_row
         return best, best_row, self.all_min(extra if mine else float("inf"))
+
+    def all_argmin_arrays(self, min_dist, row, t):
+        """Element-wise over ranks: the lexicographically smallest (min_dist, row) pair and the `t` of the rank that holds it
+        (the clearance profiles: per vehicle / per step minimum distance, its row id and the time within the segment).
+        min_dist, t: float64 arrays, row: uint64 array (UINT64_MAX: none), the same length on every rank.  The values travel
+        as they are -- floats as float64, rows as their 64 bits -- and are compared on the host; with one rank: the inputs."""
+        if self.alone:
+            return min_dist, row, t
+        import numpy as np
+
+        n = len(min_dist)
+        vals = torch.from_numpy(np.stack([np.asarray(min_dist, np.float64), np.asarray(t, np.float64)])).to(self._dev())
+        rows = torch.from_numpy(np.ascontiguousarray(row, np.uint64).view(np.int64).copy()).to(self._dev())
+        all_vals = torch.empty(self.world * 2 * n, dtype=torch.float64, device=vals.device)
+        all_rows = torch.empty(self.world * n, dtype=torch.int64, device=vals.device)
+        dist.all_gather_into_tensor(all_vals, vals.reshape(-1).contiguous(), group=self.group)
+        dist.all_gather_into_tensor(all_rows, rows, group=self.group)
+        v = all_vals.cpu().numpy().reshape(self.world, 2, n)
+        r = all_rows.cpu().numpy().view(np.uint64).reshape(self.world, n)
+        m_out, r_out, t_out = v[0, 0].copy(), r[0].copy(), v[0, 1].copy()
+        for g in range(1, self.world):
+            better = (v[g, 0] < m_out) | ((v[g, 0] == m_out) & (r[g] < r_out))
+            m_out, r_out, t_out = np.where(better, v[g, 0], m_out), np.where(better, r[g], r_out), np.where(better, v[g, 1], t_out)
+        return m_out, r_out, t_out
+
+    def _all_reduce_array(self, arr, dtype, op):
+        import numpy as np
+
+        t = torch.from_numpy(np.ascontiguousarray(arr)).to(dtype).to(self._dev())
+        dist.all_reduce(t, op=op, group=self.group)
+        return t.cpu().numpy()
 
     def _dev(self):
         if dist.get_backend(self.group) == "nccl":

@@ -35,6 +35,9 @@ def build_parser():
     p.add_argument("--list-conflicts", action="store_true",
                    help="--continuous-check, and one more line per between-sample conflict: the two vehicles, when they are "
                         "closer than the minimum distance - 0.01 m, and how close they come")
+    p.add_argument("--clearance", action="store_true",
+                   help="--continuous-check, and one more line: the most exposed vehicle (smallest distance to any other over "
+                        "the whole flight) and how many vehicles are in a conflict; with --save-prefix also <prefix>_clearance.pdf")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -90,9 +93,9 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
-        if args.continuous_check or args.list_conflicts:
-            rep = (solver.validate_solution(continuous=True, conflicts=True) if args.list_conflicts
-                   else solver.validate_solution(continuous=True))
+        if args.continuous_check or args.list_conflicts or args.clearance:
+            extras = {k: True for k, on in (("conflicts", args.list_conflicts), ("clearance", args.clearance)) if on}
+            rep = solver.validate_solution(continuous=True, **extras)
             ca = rep["closest_approach"]
             if ca is None:
                 print("Continuous-time check: no pair of vehicles")
@@ -104,6 +107,15 @@ def main(argv=None):
                 print(f"  conflict: vehicles {w['vehicles'][0]} and {w['vehicles'][1]} from t = {w['t_start']:.4f} s to "
                       f"t = {w['t_end']:.4f} s, minimum distance {w['min_distance']:.4f} m at t = {w['t_min_distance']:.4f} s"
                       + (" (hull of separate stretches)" if w["pieces"] > 1 else ""))
+            me = rep.get("most_exposed_vehicle")
+            if me is not None:
+                n_conf = int((rep["vehicle_clearance"]["n_violating_segments"] > 0).sum())
+                print(f"Clearance: most exposed vehicle {me['vehicle']} comes within {me['distance']:.4f} m of vehicle "
+                      f"{me['partner']} at t = {me['time']:.4f} s; {n_conf} of {n_vehicles} vehicles in conflict")
+            if args.clearance and args.save_prefix:
+                from ..viz.plot_trajectories import plot_clearance
+
+                plot_clearance(solver, f"{args.save_prefix}_clearance.pdf")
 
         if not args.no_plots:
             pre = args.save_prefix

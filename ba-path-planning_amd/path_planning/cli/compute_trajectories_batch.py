@@ -134,15 +134,20 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
         if cfg.get("validate", False):
             record["min_pair_distance"] = float(solver.validate_solution()["min_pair_distance"])
         listing = cfg.get("list_conflicts", False)
-        if cfg.get("validate_continuous", False) or listing:
-            rep = (solver.validate_solution(continuous=True, conflicts=True) if listing
-                   else solver.validate_solution(continuous=True))
+        profiling = cfg.get("clearance", False)
+        if cfg.get("validate_continuous", False) or listing or profiling:
+            extras = {k: True for k, on in (("conflicts", listing), ("clearance", profiling)) if on}
+            rep = solver.validate_solution(continuous=True, **extras)
             if cfg.get("validate_continuous", False):
                 record["min_pair_distance_continuous"] = float(rep["min_pair_distance_continuous"])
                 record["n_violating_segments"] = int(rep["n_violating_segments"])
             if listing:
                 record["conflicts"] = [dict(w, vehicles=list(w["vehicles"])) for w in rep["conflicts"]]
                 record["n_conflicts"] = int(rep["n_conflicts"])
+            if profiling:
+                record["clearance_per_vehicle"] = [float(x) for x in rep["vehicle_clearance"]["min_distance"]]
+                record["clearance_per_step"] = [float(x) for x in rep["step_clearance"]["min_distance"]]
+                record["n_vehicles_in_conflict"] = int((rep["vehicle_clearance"]["n_violating_segments"] > 0).sum())
         if save_path is not None:
             np.savez_compressed(save_path, initial_positions=np.asarray(init_pos), final_positions=np.asarray(final_pos),
                                 space_dims=np.asarray(space, dtype=float), **solver.trajectories)
@@ -214,6 +219,10 @@ def build_parser():
     p.add_argument("--list-conflicts", action="store_true",
                    help="add every between-sample conflict to every record: conflicts (one entry per pair and stretch of time "
                         "below R - 0.01: vehicles, t_start, t_end, duration, min_distance, ...) and n_conflicts")
+    p.add_argument("--clearance", action="store_true",
+                   help="add the clearance profiles to every record: clearance_per_vehicle (every vehicle's smallest distance to "
+                        "any other over the whole flight), clearance_per_step (the fleet's smallest distance within every time "
+                        "step) and n_vehicles_in_conflict")
     p.add_argument("--warmup", type=int, default=0,
                    help="untimed solves per worker (stream) before the clock starts: the first solve of a worker builds its "
                         "solver object and loads the kernels (~0.1 s); with it the scenarios/s line is the steady-state rate")
@@ -251,6 +260,7 @@ def main(argv=None):
     cfg["validate"] = bool(args.validate)
     cfg["validate_continuous"] = bool(args.continuous_check)
     cfg["list_conflicts"] = bool(args.list_conflicts)
+    cfg["clearance"] = bool(args.clearance)
     cfg["polish"] = bool(args.polish)
     cfg["carry_rho"] = bool(args.carry_rho)
     many = args.streams > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1

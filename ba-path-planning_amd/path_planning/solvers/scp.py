@@ -26,7 +26,7 @@ import numpy as np
 
 from .. import _hip
 from .._sharding import Shard
-from .conflicts import conflict_windows
+from .conflicts import conflict_windows, pairs_from_index
 
 # The reference's callers build a NEW solver object per scenario (compute_trajectories_batch.py:103-117).  Here an object owns a
 # library context and a native solver (device workspace, pinned host words, the K x K blocks cached per rho): ~0.7 ms to
@@ -732,7 +732,7 @@ class SCP:
     # ------------------------------------------------------------------------------------------------
     # post-solve validation: one device pass over all pairs + the fixed rows on the host copy
     # ------------------------------------------------------------------------------------------------
-    def validate_solution(self, continuous=False, conflicts=False):
+    def validate_solution(self, continuous=False, conflicts=False, clearance=False):
         """Feasibility report of the stored trajectories: minimum pair distance over all stored samples and its
         first violation of R - 0.01 (device reduction, generalises scp.py:597-615), worst violation of every bound
         the reference imposes (scp.py:182-257) and of the final-state equalities (state K).
@@ -744,9 +744,19 @@ class SCP:
 
         conflicts=True (with continuous=True) lists every between-sample conflict: ``conflicts``, one dictionary per pair and
         contiguous stretch of time below R - 0.01 (conflicts.conflict_windows: vehicles, t_start, t_end, duration,
-        min_distance, t_min_distance, first_timestep, n_segments, pieces), sorted by start time, and ``n_conflicts``."""
+        min_distance, t_min_distance, first_timestep, n_segments, pieces), sorted by start time, and ``n_conflicts``.
+
+        clearance=True (with continuous=True) adds the clearance profiles (scp_clearance_profile): ``vehicle_clearance``, a
+        dictionary of length-N arrays -- every vehicle's closest approach over the whole flight: ``min_distance``, ``time``
+        (seconds from the start), ``timestep``, ``partner``, ``sample_min_distance`` (at the samples only) and
+        ``n_violating_segments``; ``step_clearance``, a dictionary of length-K arrays -- the fleet's closest approach within
+        every segment: ``min_distance``, ``time``, ``vehicles`` (K x 2), ``sample_min_distance``, ``n_violating_segments``; and
+        ``most_exposed_vehicle``: ``{"vehicle", "partner", "time", "distance"}`` of the smallest vehicle clearance (None
+        without a pair).  A vehicle or step without a pair has min_distance inf, time nan and partner / vehicles -1."""
         if conflicts and not continuous:
             raise ValueError("conflicts=True lists the conflicts of the continuous-time check: it needs continuous=True")
+        if clearance and not continuous:
+            raise ValueError("clearance=True profiles the continuous-time check: it needs continuous=True")
         if self.trajectories is None:
             raise ValueError("Trajectories not generated yet")
         N, K, D, h = self.N, self.K, self.D, self.h
@@ -783,7 +793,40 @@ class SCP:
             mine = c.list_conflicts(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)
             report["conflicts"] = conflict_windows(self.shard.allgather_records(mine), N, K, h)
             report["n_conflicts"] = len(report["conflicts"])
+        if clearance:
+            report.update(self._clearance_profiles(p, v, a, q0, q1))
         return report
+
+    def _clearance_profiles(self, p, v, a, q0, q1):
+        """The clearance part of validate_solution: one device pass (scp_clearance_profile) over this rank's pair range,
+        combined entry by entry over the ranks (lexicographic minimum of (distance, row), minimum, integer sum)."""
+        N, K, D, h = self.N, self.K, self.D, self.h
+        c = self._ctx
+        pairs = self.shard.pairs
+        out = {}
+        for name, e in zip(("vehicle_clearance", "step_clearance"),
+                           c.clearance_profile(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)):
+            dist, row, t = self.shard.all_argmin_arrays(e["min_dist"], e["row"], e["t_min"])
+            some = row != np.uint64(_hip.NO_ROW)
+            r = np.where(some, row, 0).astype(np.int64)
+            k, q = np.divmod(r, max(pairs, 1))
+            i, j = pairs_from_index(q, N) if pairs else (np.zeros_like(q), np.zeros_like(q))
+            prof = {"min_distance": dist, "time": np.where(some, k * h + t, np.nan)}
+            if name == "vehicle_clearance":
+                prof["timestep"] = np.where(some, k, -1)
+                prof["partner"] = np.where(some, np.where(i == np.arange(N), j, i), -1)
+            else:
+                prof["vehicles"] = np.where(some[:, None], np.stack([i, j], axis=1), -1)
+            prof["sample_min_distance"] = self.shard.all_min(e["sample_min_dist"])
+            prof["n_violating_segments"] = self.shard.all_sum_int(e["n_violating"].astype(np.int64))
+            out[name] = prof
+        vc = out["vehicle_clearance"]
+        out["most_exposed_vehicle"] = None
+        if pairs:
+            best = int(np.argmin(vc["min_distance"]))  # the closest approach of the continuous-time check; of its two vehicles the first
+            out["most_exposed_vehicle"] = {"vehicle": best, "partner": int(vc["partner"][best]), "time": float(vc["time"][best]),
+                                           "distance": float(vc["min_distance"][best])}
+        return out
 
     def _continuous_separation(self, p, v, a, q0, q1):
         """The continuous-time part of validate_solution: between two samples a vehicle flies p + t v + t^2/2 a (the

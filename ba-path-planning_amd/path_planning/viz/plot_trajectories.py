@@ -62,3 +62,34 @@ def plot_time_snapshots(solver, num_snapshots=5, save_path=None):
     if save_path:
         fig.savefig(save_path, bbox_inches="tight")
     return fig, axes
+
+
+def plot_clearance(solver, save_path="clearance.pdf"):
+    """The clearance profiles of validate_solution(continuous=True, clearance=True): left, the fleet's minimum distance over
+    the horizon, at the samples and over the whole segments, against R and the tolerated R - 0.01; right, the vehicles'
+    clearances in ascending order."""
+    import matplotlib.pyplot as plt
+
+    rep = solver.validate_solution(continuous=True, clearance=True)
+    sc, vc = rep["step_clearance"], rep["vehicle_clearance"]
+    t = solver.h * np.arange(solver.K)
+    fig, (ax, bx) = plt.subplots(1, 2, figsize=(13, 4.5))
+    ax.step(t, sc["sample_min_distance"], where="post", color="tab:gray", lw=1.0, label="at the samples")
+    ax.step(t, sc["min_distance"], where="post", color="tab:blue", lw=1.4, label="over the segments")
+    order = np.argsort(vc["min_distance"], kind="stable")
+    bx.plot(np.arange(solver.N), vc["sample_min_distance"][order], ".", color="tab:gray", ms=3, label="at the samples")
+    bx.plot(np.arange(solver.N), vc["min_distance"][order], "-", color="tab:blue", lw=1.4, label="over the segments")
+    for a in (ax, bx):
+        a.axhline(solver.R, color="tab:green", lw=0.8, ls="--", label=f"R = {solver.R} m")
+        a.axhline(solver.R - 0.01, color="tab:red", lw=0.8, ls=":", label="R - 0.01 m")
+        a.set_ylabel("minimum distance [m]")
+        a.legend(fontsize=8)
+    ax.set_xlabel("t [s]")
+    ax.set_title("fleet clearance per time step")
+    bx.set_xlabel("vehicles, by clearance")
+    n_conf = int((vc["n_violating_segments"] > 0).sum())
+    bx.set_title(f"clearance per vehicle ({n_conf} of {solver.N} in conflict)")
+    if save_path:
+        fig.savefig(save_path, bbox_inches="tight")
+    plt.close(fig)
+    return rep

@@ -242,6 +242,38 @@ int scp_list_conflicts(scp_ctx* ctx, int N, int K, int D, double h, double R, in
                        const double* pos, const double* vel, const double* acc, scp_conflict* out, int64_t capacity,
                        uint64_t* n_found);
 
+/* ---- clearance profiles: the closest approach of every vehicle and of every time step -------------------------------------
+ * A purely additive part of ABI version 7: one struct and two functions, nothing else changes.
+ * The K * (q_end - q_begin) segment minima of scp_check_separation, reduced along the other two axes:
+ *   per_vehicle[i] covers every row (k, q) of the pair range whose pair contains vehicle i (its margin, against whom, when);
+ *   per_step[k]    covers the rows k*pairs + q, q in [q_begin, q_end) (the fleet's minimum distance over the horizon).
+ * The arithmetic per segment is scp_check_separation's on the same bits: the lexicographic minimum of (min_dist, row) over the
+ * vehicles, and over the steps, is that call's (min_dist, argmin_row) with its argmin_t; the n_violating of the steps sum to
+ * its n_violating, those of the vehicles to twice that; the smallest sample_min_dist is its sample_min_dist; an entry with
+ * n_violating > 0 carries the (min_dist, row, t_min) of the smallest scp_list_conflicts record that involves it.
+ * An entry that covers no row (an empty range, N = 1, a vehicle without a pair in the shard) is
+ * {+inf, 0, UINT64_MAX, +inf, 0, 0}.  Both arrays are DEVICE memory; one of them may be NULL (that profile is not written),
+ * both NULL is SCP_ERR_INVALID.  The result is deterministic and does not depend on how a pair range is cut: over disjoint
+ * shards the entry-wise lexicographic minimum of (min_dist, row) with that shard's t_min, the entry-wise minimum of
+ * sample_min_dist and the entry-wise sum of n_violating are bit for bit those of the full range.  Unlike the check, a segment
+ * is excluded without minimising its quartic only if its distance provably exceeds max(R - 0.01, the smallest sampled
+ * distance of vehicle i, of vehicle j, of step k): more segments reach the quartic (scp_ctx_last_clearance_solved).
+ * Argument checks, error codes, stream and timing behaviour as scp_check_separation (scp_ctx_last_pair_ms: all kernels of
+ * the call). */
+typedef struct scp_clearance {
+  double min_dist;          /* smallest segment distance sqrt(max(min f, 0)) over the rows this entry covers; +inf: none */
+  double t_min;             /* where in [0, h] of that row's segment it is attained */
+  uint64_t row;             /* k*pairs + q of that segment; bitwise equal minima: the smallest row; UINT64_MAX: none */
+  double sample_min_dist;   /* smallest distance at the samples (t = 0) of the same rows, as scp_check_avoidance computes it */
+  uint64_t n_violating;     /* segments among them whose distance is < R - 0.01 (the test of scp_check_separation) */
+  uint64_t reserved;        /* 0 */
+} scp_clearance;
+int scp_clearance_profile(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                          const double* pos, const double* vel, const double* acc,
+                          scp_clearance* per_vehicle /* [N] or NULL */, scp_clearance* per_step /* [K] or NULL */);
+/* Segments of the latest scp_clearance_profile of this ctx whose quartic was minimised; a cost figure.  Synchronises. */
+int scp_ctx_last_clearance_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
+
 /* ---- constraint generation for the joint QP (a6): full pass over the linearised rows ------------------
  * For every local row not yet marked in sel_bitmap: if (A_col x)_r < l_r - feas_tol, mark it and append its
  * global id to new_rows.  (A_col x)_r = eta_r . ((pos_i - c_i) - (pos_j - c_j))[k], c = p0 + k h v0,

@@ -1,7 +1,7 @@
 """Device time of the continuous-time separation check (scp_check_separation) next to the sampled check
 (scp_check_avoidance) on the same trajectories, and the share of segments that reached the quartic.
 
-    python tools/separation_times.py [--reps 30] [--warmup 5] [--skip-solves] [--list]
+    python tools/separation_times.py [--reps 30] [--warmup 5] [--skip-solves] [--list] [--clearance]
 
 Shapes: 1024 x 50 x 2, 4096 x 50 x 2, 1024 x 50 x 3.  Data: (a) the grid-swap scenario of bench.py, solved trajectories
 (QP#0 + SCP iterations, max 15); (b) random kinematically consistent trajectories in a 20^D box (|v| <= 2, |a| <= 15 per
@@ -11,7 +11,11 @@ median, min and max over the repetitions after the warm-up.
 --list adds the conflict list (scp_list_conflicts) on the same trajectories, alternating with the check in one loop, and a
 small shape (128 x 50 x 2).  Its sort is not timed by itself: the call is repeated with capacity 0, which runs the same
 pass and the same (then empty) sort launches but stores and sorts nothing, and the difference of the medians is reported
-as the share of storing, sorting and gathering the records."""
+as the share of storing, sorting and gathering the records.
+
+--clearance adds the clearance profile (scp_clearance_profile) on the same trajectories, alternating with the check in one
+loop: device time of all its kernels, and the share of segments that reached the quartic for both -- the profile excludes a
+segment against the bounds of its two vehicles and its step, the check against one bound for the whole call."""
 import argparse
 import os
 import sys
@@ -90,12 +94,37 @@ def measure_listing(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
           f"{(f[0]-z[0])*1e3:.1f} us = {100.0*(f[0]-z[0])/f[0]:.1f} % of the list   records {n} (capacity {cap})", flush=True)
 
 
+def measure_clearance(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
+    t_chk, t_clr = [], []
+    for r in range(warmup + reps):
+        st = ctx.check_separation(N, K, D, h, R, pos, vel, acc)
+        a = ctx.last_pair_ms()
+        veh, step = ctx.clearance_profile(N, K, D, h, R, pos, vel, acc)
+        b = ctx.last_pair_ms()
+        if r >= warmup:
+            t_chk.append(a)
+            t_clr.append(b)
+    solved_clr = ctx.last_clearance_solved()
+    ctx.check_separation(N, K, D, h, R, pos, vel, acc)
+    solved_chk = ctx.last_separation_solved()
+    seg = K * N * (N - 1) // 2
+    assert step["min_dist"].min() == veh["min_dist"].min() == st["min_dist"] and int(step["n_violating"].sum()) == st["n_violating"]
+    q = lambda x: (float(np.median(x)), float(np.min(x)), float(np.max(x)))  # noqa: E731
+    k, c = q(t_chk), q(t_clr)
+    print(f"{label:28s} {N:5d} x {K} x {D}  check {k[0]*1e3:8.1f} us (min {k[1]*1e3:.1f}, max {k[2]*1e3:.1f})   "
+          f"clearance profile {c[0]*1e3:8.1f} us (min {c[1]*1e3:.1f}, max {c[2]*1e3:.1f})   profile / check {c[0]/k[0]:.2f}   "
+          f"quartic: check {solved_chk} of {seg} segments ({100.0*solved_chk/seg:.3f} %), profile {solved_clr} "
+          f"({100.0*solved_clr/seg:.3f} %)   vehicles in conflict {int((veh['n_violating'] > 0).sum())} of {N}, smallest "
+          f"clearance {veh['min_dist'].min():.4f}, median {float(np.median(veh['min_dist'])):.4f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-solves", action="store_true")
     ap.add_argument("--list", action="store_true", help="also time scp_list_conflicts, and add the shape 128 x 50 x 2")
+    ap.add_argument("--clearance", action="store_true", help="also time scp_clearance_profile beside the check")
     args = ap.parse_args()
     from path_planning import _hip
     from path_planning.scenarios.position_generator import generate_grid_swap
@@ -110,6 +139,8 @@ def main():
         measure(ctx, N, K, D, h, R, pos, vel, a, args.reps, args.warmup, "random, 20^D box")
         if args.list:
             measure_listing(ctx, N, K, D, h, R, pos, vel, a, args.reps, args.warmup, "random, 20^D box")
+        if args.clearance:
+            measure_clearance(ctx, N, K, D, h, R, pos, vel, a, args.reps, args.warmup, "random, 20^D box")
         if args.skip_solves:
             continue
         g0, gf, space = generate_grid_swap(N, seed=1000 * N, dim=D)
@@ -123,6 +154,9 @@ def main():
         if args.list:
             measure_listing(ctx, N, K, D, h, R, *dev, args.reps, args.warmup,
                             f"grid-swap solved ({s.last_info['n_iterations']} it.)")
+        if args.clearance:
+            measure_clearance(ctx, N, K, D, h, R, *dev, args.reps, args.warmup,
+                              f"grid-swap solved ({s.last_info['n_iterations']} it.)")
         del s
     ctx.close()
 
