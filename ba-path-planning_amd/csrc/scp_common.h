@@ -60,6 +60,8 @@ struct scp_ctx {
   void* clr_ws;                   // device workspace of scp_clearance_profile (records, bounds, partials; grown on demand)
   size_t clr_ws_bytes;
   unsigned long long* clr_n_solved;  // inside it: segments of the latest scp_clearance_profile that reached the quartic
+  void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)
+  size_t asg_ws_bytes;
 };
 
 static inline int scp_fail(scp_ctx* ctx, int code, const char* fmt, ...) {

@@ -81,6 +81,7 @@ extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
   if (ctx->gen_ws) (void)hipFree(ctx->gen_ws);
   if (ctx->sep_ws) (void)hipFree(ctx->sep_ws);
   if (ctx->clr_ws) (void)hipFree(ctx->clr_ws);
+  if (ctx->asg_ws) (void)hipFree(ctx->asg_ws);
   if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
   (void)hipHostFree(ctx->h_scratch);
   (void)hipHostFree(ctx->h_mirror);

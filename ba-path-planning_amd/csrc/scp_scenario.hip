@@ -10,6 +10,7 @@
 //   gen_finish_kernel   one workgroup per scenario: space box and scp_gen_stats
 // No floating-point atomics; no grid-wide barrier (the host loop syncs once per sweep on a mapped 4-byte word).
 #include "scp_common.h"
+#include "scp_line_device.h"
 
 #include <cmath>
 #include <vector>
@@ -45,29 +46,6 @@ __device__ inline double gen_coord(int cell, double pitch, double jitter, uint64
   const double u = (double)(h >> 11) * 0x1.0p-53;
   const double j = (2.0 * u - 1.0) * jitter;
   return (double)cell * pitch + j;
-}
-
-// squared closest approach of two straight-line motions in the plane: r0 = a_i - a_j, g = g_i - g_j
-// (straight_line_min_distance's arithmetic without the sqrt; x terms before y terms)
-__device__ inline double gen_d2(double r0x, double r0y, double gx, double gy) {
-#pragma clang fp contract(off)
-  const double drx = gx - r0x, dry = gy - r0y;
-  const double den = drx * drx + dry * dry;
-  double s = -(r0x * drx + r0y * dry) / (den > 0.0 ? den : 1.0);
-  s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
-  const double cx = r0x + s * drx, cy = r0y + s * dry;
-  return cx * cx + cy * cy;
-}
-
-// the same in 3-D (z terms last): equal to gen_d2 bit for bit when both agents share a layer (their z terms are 0)
-__device__ inline double gen_d2_3(double r0x, double r0y, double r0z, double gx, double gy, double gz) {
-#pragma clang fp contract(off)
-  const double drx = gx - r0x, dry = gy - r0y, drz = gz - r0z;
-  const double den = drx * drx + dry * dry + drz * drz;
-  double s = -(r0x * drx + r0y * dry + r0z * drz) / (den > 0.0 ? den : 1.0);
-  s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
-  const double cx = r0x + s * drx, cy = r0y + s * dry, cz = r0z + s * drz;
-  return cx * cx + cy * cy + cz * cz;
 }
 
 // pick order of two candidates: acceptable (d2 >= thr) before not; among acceptable the lower index; otherwise the larger

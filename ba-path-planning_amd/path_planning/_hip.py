@@ -165,6 +165,26 @@ class Clearance(C.Structure):
 CLEARANCE_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("row", np.uint64),
                             ("sample_min_dist", np.float64), ("n_violating", np.uint64), ("reserved", np.uint64)])
 
+
+class AssignStats(C.Structure):
+    """struct scp_assign_stats (scp_assign_goals; one per scenario, a DEVICE array)"""
+    _fields_ = [("cost_q", C.c_int64), ("cost_q_identity", C.c_int64), ("quantum", C.c_double), ("rounds", C.c_int64),
+                ("bids", C.c_int64), ("phases", C.c_int32), ("status", C.c_int32)]
+
+
+ASSIGN_STATS_DTYPE = np.dtype([("cost_q", np.int64), ("cost_q_identity", np.int64), ("quantum", np.float64),
+                               ("rounds", np.int64), ("bids", np.int64), ("phases", np.int32), ("status", np.int32)])
+
+
+class LineStats(C.Structure):
+    """struct scp_line_stats (scp_straight_line_check; one per scenario, a DEVICE array)"""
+    _fields_ = [("min_approach", C.c_double), ("arg_i", C.c_int32), ("arg_j", C.c_int32), ("n_close", C.c_int64),
+                ("n_opposed", C.c_int64)]
+
+
+LINE_STATS_DTYPE = np.dtype([("min_approach", np.float64), ("arg_i", np.int32), ("arg_j", np.int32), ("n_close", np.int64),
+                             ("n_opposed", np.int64)])
+
 NO_ROW = 2**64 - 1  # UINT64_MAX: "no such row" in the stats of the pairwise passes
 
 ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
@@ -182,6 +202,7 @@ EXPORTS = [
     "scp_solve_default_options", "scp_solver_create", "scp_solver_destroy", "scp_solver_update_settings", "scp_solver_solve",
     "scp_solver_step", "scp_solver_shard_begin", "scp_solver_shard_rows", "scp_solver_shard_qp", "scp_solver_shard_violations",
     "scp_solver_shard_round_done", "scp_solver_shard_end", "scp_gen_default_params", "scp_generate_grid_swap",
+    "scp_assign_goals", "scp_straight_line_check",
 ]
 
 
@@ -274,6 +295,8 @@ def load_library():
     lib.scp_gen_default_params.argtypes = [C.POINTER(GenParams)]
     lib.scp_gen_default_params.restype = None
     lib.scp_generate_grid_swap.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_uint64), C.POINTER(GenParams), vp, vp, vp, vp]
+    lib.scp_assign_goals.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+    lib.scp_straight_line_check.argtypes = [vp, i32, i32, i32, vp, vp, vp, f64, vp]
     _LIB, _LIB_PATH = lib, path
     return lib
 
@@ -479,6 +502,51 @@ class Context:
                                                    stats.data_ptr()))
         st = stats.cpu().numpy().view(GEN_STATS_DTYPE)
         return init, goal, space, st
+
+    def _scenario_points(self, start, goal):
+        """start / goal as contiguous float64 device tensors of one shape (B, N, D) (a single scenario (N, D) becomes B = 1)"""
+        torch = _torch()
+        out = []
+        for a in (start, goal):
+            t = a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))
+            t = t.to(device=self.tdev, dtype=torch.float64)
+            out.append((t[None] if t.dim() == 2 else t).contiguous())
+        if out[0].dim() != 3 or out[0].shape != out[1].shape:
+            raise ValueError(f"start {tuple(out[0].shape)} and goal {tuple(out[1].shape)} must both be (B, N, D) or (N, D)")
+        return out[0], out[1]
+
+    def assign_goals(self, start, goal, max_rounds_per_phase=0, want_prices=False):
+        """scp_assign_goals: the assignment of goals to interchangeable vehicles that minimises the sum of squared start-goal
+        distances, for B scenarios in one launch.  start / goal: (B, N, D) device tensors or arrays.  Returns goal_of
+        (B, N) int32 device tensor (vehicle i flies to goal[goal_of[i]]), the stats as a numpy structured array
+        (ASSIGN_STATS_DTYPE) of B entries and the auction's prices ((B, N) int64 device tensor, or None).  Synchronises."""
+        torch = _torch()
+        s, g = self._scenario_points(start, goal)
+        B, N, D = (int(v) for v in s.shape)
+        goal_of = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int32, device=self.tdev)
+        prices = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int64, device=self.tdev) if want_prices else None
+        stats = torch.empty(max(B, 1) * ASSIGN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_assign_goals(self.h, B, N, D, s.data_ptr(), g.data_ptr(), goal_of.data_ptr(),
+                                             prices.data_ptr() if want_prices else None, int(max_rounds_per_phase),
+                                             stats.data_ptr()))
+        return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
+
+    def straight_line_check(self, start, goal, goal_of=None, min_sep=0.0):
+        """scp_straight_line_check: closest approach, close pairs and opposed pairs of the equal-time straight-line motions
+        start_i -> goal[goal_of[i]] (goal_of None: the identity) of B scenarios, as a numpy structured array
+        (LINE_STATS_DTYPE) of B entries.  Synchronises."""
+        torch = _torch()
+        s, g = self._scenario_points(start, goal)
+        B, N, D = (int(v) for v in s.shape)
+        gof = None
+        if goal_of is not None:
+            gof = goal_of if torch.is_tensor(goal_of) else torch.as_tensor(np.ascontiguousarray(goal_of, dtype=np.int32))
+            gof = gof.to(device=self.tdev, dtype=torch.int32).reshape(B, N).contiguous()
+        stats = torch.empty(max(B, 1) * LINE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_straight_line_check(self.h, B, N, D, s.data_ptr(), g.data_ptr(),
+                                                    gof.data_ptr() if gof is not None else None, float(min_sep),
+                                                    stats.data_ptr()))
+        return stats.cpu().numpy().view(LINE_STATS_DTYPE)
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

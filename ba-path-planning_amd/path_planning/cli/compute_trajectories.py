@@ -38,6 +38,10 @@ def build_parser():
     p.add_argument("--clearance", action="store_true",
                    help="--continuous-check, and one more line: the most exposed vehicle (smallest distance to any other over "
                         "the whole flight) and how many vehicles are in a conflict; with --save-prefix also <prefix>_clearance.pdf")
+    p.add_argument("--assign-goals", action="store_true",
+                   help="interchangeable vehicles: before the solve, pair vehicles and goals so that the sum of squared "
+                        "start-goal distances is minimal (no head-on swaps), and print one line with cost, straight-line "
+                        "minimum approach and opposed pairs before and after")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -83,6 +87,11 @@ def main(argv=None):
         print(f"Successfully generated positions for {n_vehicles} vehicles")
         solver.set_initial_states(np.asarray(initial_positions))
         solver.set_final_states(np.asarray(final_positions))
+        if args.assign_goals:
+            from ..scenarios.assignment import describe
+
+            solver.assign_goals()
+            print(describe(solver.assignment_info))
 
         print("Generating trajectories...")
         start_time = time.time()

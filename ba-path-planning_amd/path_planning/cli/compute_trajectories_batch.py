@@ -94,6 +94,14 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
             solver.set_space_dims(space)
         solver.set_initial_states(init_pos)
         solver.set_final_states(final_pos)
+        assign_ms = None
+        if cfg.get("assign_goals", False):
+            from ..scenarios.assignment import describe
+
+            t_a = time.perf_counter()
+            solver.assign_goals()
+            assign_ms = (time.perf_counter() - t_a) * 1e3
+            print(f"  N={N} seed={seed}: {describe(solver.assignment_info)}")
         t0 = time.perf_counter()
         _ = solver.generate_trajectories(max_iterations=cfg["max_iterations"])
         iters = solver.last_info.get("n_iterations")
@@ -112,6 +120,10 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
         "seed": seed,
         "scp_iterations": iters,
     }
+    if cfg.get("assign_goals", False) and getattr(solver, "goal_assignment", None) is not None:
+        # (only with --assign-goals: without it the record is what it always was)
+        record["goal_assignment"] = [int(v) for v in solver.goal_assignment]
+        record["assign_ms"] = assign_ms
     if status == "success":
         # additions to the reference record: per-iteration wall time, ADMM iterations and final
         # residuals of every QP (QP#0 first), relative steps, convergence flag, minimum pair distance of the result
@@ -223,6 +235,10 @@ def build_parser():
                    help="add the clearance profiles to every record: clearance_per_vehicle (every vehicle's smallest distance to "
                         "any other over the whole flight), clearance_per_step (the fleet's smallest distance within every time "
                         "step) and n_vehicles_in_conflict")
+    p.add_argument("--assign-goals", action="store_true",
+                   help="interchangeable vehicles: pair vehicles and goals of every scenario so that the sum of squared "
+                        "start-goal distances is minimal before it is solved; prints one line per scenario (cost, straight-line "
+                        "minimum approach, opposed pairs, before -> after) and adds goal_assignment and assign_ms to its record")
     p.add_argument("--warmup", type=int, default=0,
                    help="untimed solves per worker (stream) before the clock starts: the first solve of a worker builds its "
                         "solver object and loads the kernels (~0.1 s); with it the scenarios/s line is the steady-state rate")
@@ -262,6 +278,8 @@ def main(argv=None):
     cfg["list_conflicts"] = bool(args.list_conflicts)
     cfg["clearance"] = bool(args.clearance)
     cfg["polish"] = bool(args.polish)
+    if args.assign_goals:  # (the key exists only with the flag: the JSON's config is otherwise unchanged)
+        cfg["assign_goals"] = True
     cfg["carry_rho"] = bool(args.carry_rho)
     many = args.streams > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
     cfg["kernel_timing"] = bool(args.kernel_timing) if args.kernel_timing is not None else not many

@@ -110,6 +110,9 @@ class SCP:
         self.initial_velocities = None
         self.final_positions = None
         self.final_velocities = None
+        self._final_given = None  # final states in the order given to set_final_states, once assign_goals has permuted them
+        self.goal_assignment = None
+        self.assignment_info = None
         self.pos_min = np.array(space_dims[: self.D])
         self.pos_max = np.array(space_dims[self.D:])
         self.vel_min = -2
@@ -231,6 +234,40 @@ class SCP:
             f"expected={self.D * self.N}"
         )
         self._dev.pop("p0", None)
+        self._final_given = None  # (assign_goals keeps the order given here)
+        self.goal_assignment = None
+        self.assignment_info = None
+
+    def assign_goals(self, min_sep=None):
+        """Interchangeable vehicles: re-pair vehicles and goals so that the sum of squared start-goal distances is minimal
+        (scp_assign_goals).  Call it after set_initial_states and set_final_states; the final positions AND velocities are
+        permuted, so vehicle i then flies to the goal given as number ``goal_assignment[i]``.  ``goal_assignment`` always
+        refers to the order handed to set_final_states: a second call recomputes from those originals, it does not compose.
+        ``assignment_info`` holds the auction's statistics and the straight-line checks before / after (min_sep, default the
+        minimum distance, is their "close" threshold).  Returns goal_assignment."""
+        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS
+
+        if self.initial_positions is None or self.final_positions is None:
+            raise ValueError("assign_goals needs both set_initial_states and set_final_states first")
+        if self._final_given is None:
+            self._final_given = (self.final_positions.copy(), self.final_velocities.copy())
+        pf, vf = (a.reshape(self.N, self.D) for a in self._final_given)
+        start = self.initial_positions.reshape(1, self.N, self.D)
+        sep = float(self.R if min_sep is None else min_sep)
+        goal_of, st, _ = self._ctx.assign_goals(start, pf[None])
+        before = self._ctx.straight_line_check(start, pf[None], None, sep)
+        after = self._ctx.straight_line_check(start, pf[None], goal_of, sep)
+        info = {k: st[k][0].item() for k in _ASSIGN_KEYS}
+        info["line_before"] = {k: before[k][0].item() for k in _LINE_KEYS}
+        info["line_after"] = {k: after[k][0].item() for k in _LINE_KEYS}
+        perm = goal_of[0].cpu().numpy().astype(np.int64)
+        self.final_positions = pf[perm].flatten()
+        self.final_velocities = vf[perm].flatten()
+        self._dev.pop("p0", None)
+        self.trajectories = None
+        self.goal_assignment = perm
+        self.assignment_info = info
+        return perm
 
     # ------------------------------------------------------------------------------------------------
     # device-side setup

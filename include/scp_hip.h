@@ -506,6 +506,65 @@ int scp_generate_grid_swap(scp_ctx* ctx, int B, int N, int D, const uint64_t* se
                            double* init /* [B][N][D] */, double* goal /* [B][N][D] */, double* space /* [B][2D] */,
                            scp_gen_stats* stats /* [B] */);
 
+/* ---- goal assignment for interchangeable vehicles: batched exact auction ------------------------------------------------
+ * A purely additive part of ABI version 7: two structs and two functions, nothing else changes.
+ * For each of B scenarios: the bijection goal_of (vehicle i flies to goal[goal_of[i]]) that minimises the sum of the squared
+ * start-goal distances, exactly on costs quantised per scenario.  Integer arithmetic after the quantisation, so a CPU
+ * restatement (tests/assignment_ref.py) agrees bit for bit.  Such an assignment has (s_i - s_j).(g_i - g_j) >= 0 for every pair
+ * (exchange argument), so no two equal-time straight-line motions are opposed: head-on swaps cannot occur.
+ *
+ * Quantisation (per scenario; every product rounded, no contraction; coordinates d ascending).
+ *   span_d = max - min over all 2N points;  Bd = sum_d span_d * span_d;  Bd = m 2^e with m in [0.5, 1) (frexp), s = 31 - e
+ *   (s = 0 if Bd == 0);  d2_ij = sum_d (start_i[d] - goal_j[d])^2;  c_ij = (int64) floor(ldexp(d2_ij, s)), which is below 2^31
+ *   because d2 <= Bd by the monotonicity of rounding;  a_ij = -(N + 1) c_ij;  quantum = ldexp(1, -s)  (m^2 per unit of c).
+ *
+ * Auction (Jacobi forward auction with epsilon scaling; prices p_j int64, starting at 0).
+ *   eps_0 = max(1, ((N + 1) floor(ldexp(Bd, s))) / 2); the next eps is max(1, eps / 4) (integer division); the phase with
+ *   eps = 1 is the last.  A phase starts with every person unassigned and keeps the prices of the previous phase.  In a round
+ *   EVERY unassigned person i computes v_ij = a_ij - p_j over all j, j1 = argmax (lowest j on ties), w1 = v_ij1, w2 = the
+ *   maximum over j != j1, and bids p_j1 + (w1 - w2) + eps for goal j1.  Every goal that received bids takes the highest
+ *   (lowest i on ties): its price becomes that bid, its previous owner becomes unassigned.  The phase ends when nobody is
+ *   unassigned.  N = 1: the identity, 0 phases.
+ * Consequences: the costs are integers scaled by N + 1 and the last eps is 1, so goal_of is EXACTLY optimal for c (in m^2:
+ * sum d2 within N quantum of the true optimum); a_{i,goal_of[i]} - p_{goal_of[i]} >= max_j (a_ij - p_j) - 1 with the returned
+ * prices; hence c_{i,gi} + c_{j,gj} <= c_{i,gj} + c_{j,gi} for all pairs; prices stay below 2^55.
+ *
+ * Guard.  max_rounds_per_phase <= 0 means 256 N + 4096 (about 50 x the longest phase observed, ~5 N).  A scenario whose phase
+ * is not finished after that many rounds gets status = 1, goal_of = the identity and cost_q = cost_q_identity (phases, rounds,
+ * bids and prices as they stood when it stopped); the call still returns SCP_OK.
+ *
+ * One workgroup per scenario in one launch: prices, owners and the bid table in LDS, one wave per bidding person; no
+ * workgroup waits for another.  Supported: B >= 1, 1 <= N <= 4096, D in {2, 3}, finite coordinates whose range does not
+ * overflow; anything else returns SCP_ERR_INVALID (for the coordinates: after the launch, outputs then undefined).
+ * start / goal [B][N][D], goal_of [B][N], prices [B][N] (or NULL) and stats [B] are DEVICE pointers.  Enqueued on the ctx's
+ * stream; synchronises. */
+typedef struct scp_assign_stats {  /* DEVICE, one per scenario, 48 bytes */
+  int64_t cost_q;           /* sum_i c[i][goal_of[i]] */
+  int64_t cost_q_identity;  /* sum_i c[i][i] */
+  double quantum;           /* 2^-s, m^2 */
+  int64_t rounds, bids;     /* over all phases; bids = persons that bid, summed over the rounds */
+  int32_t phases, status;   /* 0 ok, 1 round limit */
+} scp_assign_stats;
+int scp_assign_goals(scp_ctx* ctx, int B, int N, int D, const double* start /* [B][N][D] */, const double* goal /* [B][N][D] */,
+                     int32_t* goal_of /* [B][N] */, int64_t* prices /* [B][N] or NULL */, int64_t max_rounds_per_phase,
+                     scp_assign_stats* stats /* [B] */);
+
+/* Straight-line check: one pass per scenario over the pairs i < j of the motions start_i -> goal[goal_of[i]] (goal_of NULL:
+ * the identity).  d^2 is the squared closest approach of the "Block draw" rule above (the generator's device function, so a
+ * grid-swap-device scenario's min_approach is scp_gen_stats.min_approach bit for bit), with r0 = s_i - s_j and
+ * g = g_i - g_j; in 3-D the z terms come last.  A pair is opposed if sum_d r0[d] * g[d] < 0 (d ascending, no contraction),
+ * close if d^2 < min_sep * min_sep.  Deterministic.  Supported: B >= 1, 1 <= N <= 65536, D in {2, 3}, finite min_sep >= 0,
+ * goal_of entries in [0, N); anything else returns SCP_ERR_INVALID (for the entries: after the launch).  All pointers DEVICE;
+ * stream and synchronisation as scp_assign_goals. */
+typedef struct scp_line_stats {  /* DEVICE, one per scenario, 32 bytes */
+  double min_approach;  /* sqrt(min d^2); +inf for N = 1 */
+  int32_t arg_i, arg_j; /* the pair that attains it, the lowest (i, j) on ties; -1, -1 for N = 1 */
+  int64_t n_close;      /* pairs with d^2 < min_sep^2 */
+  int64_t n_opposed;    /* pairs with (s_i - s_j).(g_i - g_j) < 0 */
+} scp_line_stats;
+int scp_straight_line_check(scp_ctx* ctx, int B, int N, int D, const double* start, const double* goal,
+                            const int32_t* goal_of /* [B][N] or NULL */, double min_sep, scp_line_stats* stats /* [B] */);
+
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
 int scp_gemm_f64(scp_ctx* ctx, int use_mfma, int R, int M, int C, double alpha, const double* A,
