@@ -1,8 +1,8 @@
 // Clearance profile (scp_clearance_profile, include/scp_hip.h): the K x pairs quartic minimisation of scp_check_separation,
 // reduced along the other two axes -- for every VEHICLE the closest approach over all partners and segments, for every time
 // STEP the closest approach over all pairs --, plus per entry the sampled minimum and the number of violating segments.
-// The per-segment arithmetic is the check's, on the same operand bits (scp_separation_device.h): staging record, tiling,
-// quartic, lexicographic fold.
+// The per-segment arithmetic is the check's, on the same operand bits, and so are the tile scaffold and the host path around the
+// kernels (scp_separation_device.h).
 //
 // What differs is the exclusion test.  The check drops a segment whose distance provably exceeds ONE bound T = max(R - 0.01,
 // an upper bound of the call's minimum); a segment far above the global minimum can still be vehicle i's closest approach, so
@@ -59,41 +59,17 @@ struct ClrArgs {
   unsigned long long* n_solved;  // segments that reached the quartic
 };
 
-// The tile range tests of sep_pass_kernel, as functions.  (The check keeps its inline text: called through these functions its
-// instruction stream changes -- nine instructions fewer --, and that stream is pinned.)
-// Does the tile with the corner (i0, j0) hold a pair of [q_begin, q_end)?  Rows of the triangle are contiguous in q, so the
-// tile's own range decides.
-__device__ inline bool tile_live(int i0, int j0, int N, int64_t q_begin, int64_t q_end) {
-  const int i_last = min(i0 + SEP_TILE, N - 1) - 1;  // last vehicle that can be an `i` (i < j <= N - 1)
-  const int j_lo = max(j0, i0 + 1), j_hi = min(j0 + SEP_TILE, N) - 1;
-  bool live = i_last >= i0 && j_hi >= j_lo && j_hi > i0;
-  if (live) {
-    const int64_t q_min = tri_off(i0, N) + (j_lo - i0 - 1);
-    const int64_t q_max = tri_off(i_last, N) + (j_hi - i_last - 1);
-    live = q_max >= q_begin && q_min < q_end;
-  }
-  return live;
-}
-
-// A thread's j (fixed: j0 + lane) and its 16 i's (i0 + wave + 4 s): bit s says that the pair exists and lies in the range
-__device__ inline unsigned int tile_valid_mask(int i0, int j0, int wave, int lane, int N, int64_t q_begin, int64_t q_end) {
-  const int j = j0 + lane;
-  unsigned int valid = 0;
-  for (int s = 0; s < SEP_STEPS; ++s) {
-    const int i = i0 + wave + 4 * s;
-    if (i < j && j < N) {
-      const int64_t q = tri_off(i, N) + (j - i - 1);
-      if (q >= q_begin && q < q_end) valid |= 1u << s;
-    }
-  }
-  return valid;
-}
-
 __device__ inline ClrEntry clr_empty() { return ClrEntry{SEP_INF, SEP_NO_ROW, 0.0, 0ULL}; }
 
 __device__ inline void clr_fold(ClrEntry& x, const ClrEntry& o) {
   fold_min(x.m, x.row, x.t, o.m, o.row, o.t);
   x.n_viol += o.n_viol;
+}
+
+// one segment's result (f's minimum m at t, its row) into an entry
+__device__ inline void clr_offer(ClrEntry& x, double m, unsigned long long row, double t, double thr) {
+  fold_min(x.m, x.row, x.t, m, row, t);
+  x.n_viol += sep_violates(m, thr) ? 1ULL : 0ULL;  // the test n_violating of the check counts, on the same bits
 }
 
 // an upper bound of the distance whose square has these bits (the rounding of the root stays below the 1e-15)
@@ -121,51 +97,24 @@ __global__ __launch_bounds__(SEP_THREADS) void clr_seed_kernel(ClrArgs a) {
   if (!tile_live(i0, j0, N, a.q_begin, a.q_end)) return;  // uniform over the workgroup
   const unsigned int valid = tile_valid_mask(i0, j0, wave, lane, N, a.q_begin, a.q_end);
 
-  constexpr int PER_THREAD = (2 * SEP_TILE * D + SEP_THREADS - 1) / SEP_THREADS;
-  double pre[PER_THREAD];
-  auto fetch = [&](int k) {
-#pragma unroll
-    for (int e = 0; e < PER_THREAD; ++e) {
-      const int x = tid + e * SEP_THREADS;
-      if (x < 2 * SEP_TILE * D) {
-        const int side = x / (SEP_TILE * D), y = x % (SEP_TILE * D);
-        const int v = min((side ? j0 : i0) + y / D, N - 1);
-        pre[e] = a.rec[((int64_t)k * N + v) * NC + y % D];
-      }
-    }
-  };
-  auto stash = [&]() {
-#pragma unroll
-    for (int e = 0; e < PER_THREAD; ++e) {
-      const int x = tid + e * SEP_THREADS;
-      if (x < 2 * SEP_TILE * D) {
-        const int side = x / (SEP_TILE * D), y = x % (SEP_TILE * D);
-        sp[y % D][side * SEP_TILE + y / D] = pre[e];
-      }
-    }
-  };
+  TileStage<NC, D> stage;  // positions only
   double run_i[SEP_STEPS];  // per i of this thread: the smallest d.d over the steps (folded over the lanes at the end)
 #pragma unroll
   for (int s = 0; s < SEP_STEPS; ++s) run_i[s] = SEP_INF;
   double run_j = SEP_INF;
-  fetch(k_begin);
+  stage.fetch(a.rec, k_begin, N, i0, j0, tid);
   for (int k = k_begin; k < k_end; ++k) {
     __syncthreads();  // (the previous step has read sp)
-    stash();
+    stage.stash(sp, tid);
     __syncthreads();
-    if (k + 1 < k_end) fetch(k + 1);
+    if (k + 1 < k_end) stage.fetch(a.rec, k + 1, N, i0, j0, tid);
     double pj[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) pj[d] = sp[d][SEP_TILE + lane];
     double ss_min = SEP_INF;
 #pragma unroll
     for (int s = 0; s < SEP_STEPS; ++s) {
-      double acc_ss = 0.0;
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        const double df = sp[d][wave + 4 * s] - pj[d];  // the operands and the order of pair_geom and of the pass: the same bits
-        acc_ss = fma(df, df, acc_ss);
-      }
+      const double acc_ss = tile_dd<D>(sp, wave + 4 * s, pj);
       const double ss = (valid >> s) & 1u ? acc_ss : SEP_INF;
       run_i[s] = fmin(run_i[s], ss);
       ss_min = fmin(ss_min, ss);
@@ -204,10 +153,7 @@ __global__ __launch_bounds__(SEP_THREADS) void clr_pass_kernel(ClrArgs a) {
   ClrEntry own = clr_empty();
   unsigned long long n_solved = 0;  // thread 0 only
 
-  auto row_of = [&](int k, unsigned int id) {
-    const int i = i0 + (int)(id >> 6), jj = j0 + (int)(id & 63);
-    return (unsigned long long)((int64_t)k * a.pairs + tri_off(i, N) + (jj - i - 1));
-  };
+  auto row_of = [&](int k, unsigned int id) { return tile_row(k, a.pairs, N, i0, j0, (int)(id >> 6), (int)(id & 63)); };
 
   if (tile_live(i0, j0, N, a.q_begin, a.q_end)) {
     const unsigned int valid = tile_valid_mask(i0, j0, wave, lane, N, a.q_begin, a.q_end);
@@ -215,38 +161,14 @@ __global__ __launch_bounds__(SEP_THREADS) void clr_pass_kernel(ClrArgs a) {
       const int v = (tid < SEP_TILE ? i0 : j0) + (tid & 63);
       ub[tid] = v < N ? clr_bound(a.u2_veh[v]) : SEP_INF;  // a vehicle without a row here: +inf, and no valid pair uses it
     }
-    // staging: 2 x 64 records of NC doubles, contiguous per side in the time-major array; vehicles beyond N - 1 repeat it
-    // (their pairs are not valid)
-    constexpr int PER_THREAD = (2 * SEP_TILE * NC + SEP_THREADS - 1) / SEP_THREADS;
-    double pre[PER_THREAD];
-    auto fetch = [&](int k) {
-#pragma unroll
-      for (int e = 0; e < PER_THREAD; ++e) {
-        const int x = tid + e * SEP_THREADS;
-        if (x < 2 * SEP_TILE * NC) {
-          const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
-          const int v = min((side ? j0 : i0) + y / NC, N - 1);
-          pre[e] = a.rec[((int64_t)k * N + v) * NC + y % NC];
-        }
-      }
-    };
-    auto stash = [&]() {
-#pragma unroll
-      for (int e = 0; e < PER_THREAD; ++e) {
-        const int x = tid + e * SEP_THREADS;
-        if (x < 2 * SEP_TILE * NC) {
-          const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
-          sm[y % NC][side * SEP_TILE + y / NC] = pre[e];
-        }
-      }
-    };
-    fetch(k_begin);
+    TileStage<NC, NC> stage;
+    stage.fetch(a.rec, k_begin, N, i0, j0, tid);
     for (int k = k_begin; k < k_end; ++k) {
       __syncthreads();  // (the previous step's phase B has read sm, the queue and the results)
-      stash();
+      stage.stash(sm, tid);
       if (tid == 0) q_count = 0;
       __syncthreads();
-      if (k + 1 < k_end) fetch(k + 1);  // in flight during this step's arithmetic
+      if (k + 1 < k_end) stage.fetch(a.rec, k + 1, N, i0, j0, tid);  // in flight during this step's arithmetic
 
       // ---- phase A ------------------------------------------------------------------------------------------------
       double pj[D];
@@ -257,12 +179,7 @@ __global__ __launch_bounds__(SEP_THREADS) void clr_pass_kernel(ClrArgs a) {
 #pragma unroll
       for (int s = 0; s < SEP_STEPS; ++s) {
         const int il = wave + 4 * s;
-        double ss = 0.0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const double df = sm[d][il] - pj[d];  // the operands and the order of pair_geom: the same bits
-          ss = fma(df, df, ss);
-        }
+        const double ss = tile_dd<D>(sm, il, pj);
         if (!((valid >> s) & 1u)) continue;
         const double u = fmax(ub[il], u_jk);  // the largest of the three entries' bounds
         // sampled minimum per entry, as pair_geom computes it (within an ulp of sqrt(ss)): only a pair within 1e-12 of an
@@ -296,9 +213,8 @@ __global__ __launch_bounds__(SEP_THREADS) void clr_pass_kernel(ClrArgs a) {
         if (e < n_q) {
           const unsigned int id = queue[e];
           const int il = id >> 6, jl = id & 63;
-          SEP_TILE_QUARTIC(q, sm, il, jl);
           double m, t;
-          quartic_min(q, a.h, m, t);
+          quartic_min(tile_quartic<D>(sm, il, jl), a.h, m, t);
           res_m[tid] = m;
           res_t[tid] = t;
           res_id[tid] = (unsigned short)id;
@@ -308,26 +224,14 @@ __global__ __launch_bounds__(SEP_THREADS) void clr_pass_kernel(ClrArgs a) {
         if (wave < 2) {  // the owners of the vehicles: every result of the round that names mine
           for (unsigned int r = 0; r < n_r; ++r) {
             const unsigned int id = res_id[r];
-            if ((int)(wave == 0 ? id >> 6 : id & 63) == lane) {
-              const double m = res_m[r];
-              fold_min(own.m, own.row, own.t, m, row_of(k, id), res_t[r]);
-              own.n_viol += sqrt(fmax(m, 0.0)) < a.thr ? 1ULL : 0ULL;  // the test n_violating of the check counts, on the same bits
-            }
+            if ((int)(wave == 0 ? id >> 6 : id & 63) == lane) clr_offer(own, res_m[r], row_of(k, id), res_t[r], a.thr);
           }
         } else if (wave == 2) {  // the owner of the step: all results, strided over the lanes, then folded over the wave
           ClrEntry p = clr_empty();
-          for (unsigned int r = lane; r < n_r; r += 64) {
-            const double m = res_m[r];
-            fold_min(p.m, p.row, p.t, m, row_of(k, res_id[r]), res_t[r]);
-            p.n_viol += sqrt(fmax(m, 0.0)) < a.thr ? 1ULL : 0ULL;
-          }
+          for (unsigned int r = lane; r < n_r; r += 64) clr_offer(p, res_m[r], row_of(k, res_id[r]), res_t[r], a.thr);
+          wave_fold_min(p.m, p.row, p.t);
 #pragma unroll
-          for (int s = 32; s >= 1; s >>= 1) {
-            const double m2 = __shfl_xor(p.m, s, 64), t2 = __shfl_xor(p.t, s, 64);
-            const unsigned long long r2 = __shfl_xor(p.row, s, 64);
-            fold_min(p.m, p.row, p.t, m2, r2, t2);
-            p.n_viol += __shfl_xor(p.n_viol, s, 64);
-          }
+          for (int s = 32; s >= 1; s >>= 1) p.n_viol += __shfl_xor(p.n_viol, s, 64);
           clr_fold(own, p);
         }
         if (base + SEP_THREADS < n_q) __syncthreads();  // (the next round overwrites the results)
@@ -412,72 +316,48 @@ extern "C" int scp_clearance_profile(scp_ctx* ctx, int N, int K, int D, double h
                                      const double* pos, const double* vel, const double* acc, scp_clearance* per_vehicle,
                                      scp_clearance* per_step) {
   if (!ctx) return SCP_ERR_INVALID;
-  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  SCP_REQUIRE(ctx, pos && vel && acc, "clearance_profile: null pointer");
   SCP_REQUIRE(ctx, per_vehicle || per_step, "clearance_profile: both outputs are null");
-  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "clearance_profile: bad time step h=%g", h);
-  const int NC = 3 * D + 1;
-  const SepPlan plan = sep_plan(ctx, N, K, q_begin, q_end);
-  SCP_REQUIRE(ctx, plan.n_tiles < ((int64_t)1 << 31), "clearance_profile: %lld tiles exceed grid.x; shard the pair range",
-              (long long)plan.n_tiles);
-  const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
   const int64_t n_bounds = 2 * ((int64_t)N + K);  // U2_vehicle, U2_step, sample_vehicle, sample_step
-  const size_t bound_bytes = ((size_t)(n_bounds + 1) * sizeof(unsigned long long) + 63) & ~(size_t)63;  // + the solved count
-  const size_t veh_bytes = (size_t)plan.n_chunks * (size_t)plan.n_tiles * 2 * SEP_TILE * sizeof(ClrEntry);
-  const size_t step_bytes = (size_t)K * (size_t)plan.n_tiles * sizeof(ClrEntry);
-  ctx->clr_n_solved = nullptr;  // growing the workspace frees its place
-  rc = scp_ctx_ensure_bytes(ctx, &ctx->clr_ws, &ctx->clr_ws_bytes, rec_bytes + bound_bytes + veh_bytes + step_bytes + 64);
+  const size_t bound_bytes = ((size_t)n_bounds * sizeof(unsigned long long) + 63) & ~(size_t)63;
+  auto veh_bytes = [](const SepPlan& p) { return (size_t)p.n_chunks * (size_t)p.n_tiles * 2 * SEP_TILE * sizeof(ClrEntry); };
+  SepCall c;
+  int rc = sep_begin(ctx, "clearance_profile", N, K, D, h, q_begin, q_end, pos, vel, acc, [&](const SepPlan& p) {
+    return bound_bytes + veh_bytes(p) + (size_t)K * (size_t)p.n_tiles * sizeof(ClrEntry);
+  }, &c);
   if (rc) return rc;
+  const SepPlan& plan = c.plan;
 
   ClrArgs a{};
   a.N = N; a.K = K; a.D = D; a.kc = plan.kc;
   a.h = h; a.thr = R - 0.01;
   a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  double* rec = (double*)ctx->clr_ws;
-  a.rec = rec;
+  a.rec = c.rec;
   a.tile0 = plan.tile0; a.n_tiles = plan.n_tiles; a.nt = plan.nt;
-  unsigned long long* bounds = (unsigned long long*)((char*)ctx->clr_ws + rec_bytes);
+  unsigned long long* bounds = (unsigned long long*)c.extra;
   a.u2_veh = bounds;
   a.u2_step = bounds + N;
   a.s_veh = bounds + N + K;
   a.s_step = bounds + 2 * (int64_t)N + K;
-  a.n_solved = bounds + n_bounds;
-  a.part_veh = (ClrEntry*)((char*)bounds + bound_bytes);
-  a.part_step = (ClrEntry*)((char*)a.part_veh + veh_bytes);
+  a.n_solved = ctx->solved + SEP_SOLVED_PROFILE;
+  a.part_veh = (ClrEntry*)(c.extra + bound_bytes);
+  a.part_step = (ClrEntry*)((char*)a.part_veh + veh_bytes(plan));
 
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
   hipLaunchKernelGGL(clr_init_kernel, dim3(scp_cdiv(n_bounds, 256)), dim3(256), 0, ctx->stream, bounds, n_bounds, a.n_solved);
   if (plan.n_tiles > 0) {
-    hipLaunchKernelGGL(sep_prep_kernel, dim3(scp_cdiv((int64_t)N * K, 256)), dim3(256), 0, ctx->stream, N, K, D, h, pos, vel,
-                       acc, rec);
-    const dim3 grid((unsigned)plan.n_tiles, (unsigned)plan.n_chunks);
-    if (D == 2) {
-      hipLaunchKernelGGL(clr_seed_kernel<2>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-      hipLaunchKernelGGL(clr_pass_kernel<2>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-    } else {
-      hipLaunchKernelGGL(clr_seed_kernel<3>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-      hipLaunchKernelGGL(clr_pass_kernel<3>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-    }
-    SCP_HIP_CHECK(ctx, hipGetLastError());
+    sep_launch_tiles(ctx, plan, D, clr_seed_kernel<2>, clr_seed_kernel<3>, a);
+    sep_launch_tiles(ctx, plan, D, clr_pass_kernel<2>, clr_pass_kernel<3>, a);
   }
   if (per_vehicle)
     hipLaunchKernelGGL(clr_finish_vehicle_kernel, dim3(plan.nt), dim3(CLR_FINISH_SLICES * 64), 0, ctx->stream, a, plan.n_chunks,
                        plan.t_lo, plan.t_hi, per_vehicle);
   if (per_step) hipLaunchKernelGGL(clr_finish_step_kernel, dim3(K), dim3(SEP_THREADS), 0, ctx->stream, a, per_step);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
-  ctx->pair_timed = ctx->timing != 0;
-  ctx->pair_ran = true;
-  ctx->clr_n_solved = a.n_solved;
+  rc = sep_end(ctx);
+  if (rc) return rc;
+  ctx->solved_ran[SEP_SOLVED_PROFILE] = true;
   return SCP_OK;
 }
 
 // segments of the latest scp_clearance_profile of this ctx that reached the quartic (developer figure; synchronises)
 extern "C" int scp_ctx_last_clearance_solved(scp_ctx* ctx, uint64_t* n) {
-  if (!ctx || !n) return SCP_ERR_INVALID;
-  SCP_REQUIRE(ctx, ctx->clr_n_solved, "clearance_profile has not run yet");
-  SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  SCP_HIP_CHECK(ctx, hipMemcpy(n, ctx->clr_n_solved, sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return SCP_OK;
+  return sep_read_solved(ctx, SEP_SOLVED_PROFILE, "clearance_profile", n);
 }

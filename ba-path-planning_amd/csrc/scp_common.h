@@ -46,20 +46,20 @@ struct scp_ctx {
   unsigned long long* wg_part;    // [SCP_SMALL_MAX_WG][4] per-workgroup partials of a small-problem pairwise pass
   uint32_t* wg_rows;              // [workgroups][8192] per-workgroup sub-lists of its marked rows (grown on demand)
   size_t wg_rows_bytes;
-  unsigned* d_ticket;             // its last-workgroup-done counter (zero between launches)
+  unsigned* d_ticket;             // its last-workgroup-done counter (zero between launches): word 0 of a 64-byte block of
+                                  // device words that lives as long as the ctx ([1], [2]: the QP's tickets; [12, 16): `solved`)
   int timing;                     // HIP events around the pairwise kernels and the QP solves (scp_ctx_set_option; default on)
   int small_pass;                 // one-launch pairwise passes for small problems (scp_ctx_set_option; default on)
   unsigned long long rel_seq;     // of the latest scp_rel_step (completion word: h_scratch[64]; partials: h_scratch[0..64))
   void* gen_ws;                   // device workspace of scp_generate_grid_swap (grown on demand)
   size_t gen_ws_bytes;
-  void* sep_ws;                   // device workspace of scp_check_separation (time-major records + partials; grown on demand)
-  size_t sep_ws_bytes;
-  unsigned long long* sep_n_solved;  // inside it: segments of the latest scp_check_separation that reached the quartic
+  void* sep_ws;                   // device workspace of the continuous-time passes: scp_check_separation, scp_list_conflicts,
+  size_t sep_ws_bytes;            // scp_clearance_profile (time-major records + each call's own arrays; grown on demand)
+  unsigned long long* solved;     // [2] segments of the latest check / of the latest profile that reached the quartic (in
+                                  // the d_ticket block: a workspace that grows frees its old place, these words stay)
+  bool solved_ran[2];             // that call has run on this ctx
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;
-  void* clr_ws;                   // device workspace of scp_clearance_profile (records, bounds, partials; grown on demand)
-  size_t clr_ws_bytes;
-  unsigned long long* clr_n_solved;  // inside it: segments of the latest scp_clearance_profile that reached the quartic
   void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)
   size_t asg_ws_bytes;
 };

@@ -44,6 +44,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
     delete ctx;
     return SCP_ERR_HIP;
   }
+  ctx->solved = (unsigned long long*)(ctx->d_ticket + 12);  // the last 16 of its 64 bytes
   *out = ctx;
   return SCP_OK;
 }
@@ -80,7 +81,6 @@ extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
   if (ctx->tm_scratch) (void)hipFree(ctx->tm_scratch);
   if (ctx->gen_ws) (void)hipFree(ctx->gen_ws);
   if (ctx->sep_ws) (void)hipFree(ctx->sep_ws);
-  if (ctx->clr_ws) (void)hipFree(ctx->clr_ws);
   if (ctx->asg_ws) (void)hipFree(ctx->asg_ws);
   if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
   (void)hipHostFree(ctx->h_scratch);

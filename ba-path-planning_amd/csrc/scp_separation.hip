@@ -23,8 +23,9 @@
 // segment, one scp_conflict record (appended through a device counter), and sep_sort_* / sep_gather_kernel put the records
 // into ascending row order -- the keys are unique, so the sorted list depends neither on scheduling nor on the cut.
 //
-// The staging record, the tiling, the quartic and the lexicographic fold are scp_separation_device.h's: the clearance profile
-// (scp_clearance.hip) runs the same arithmetic on the same bits.
+// The tile scaffold (staging, range tests, sampled d.d, quartic, violation test, row id, lexicographic fold) and the host path
+// around the kernels (SepCall) are scp_separation_device.h's: the clearance profile (scp_clearance.hip) runs the same
+// arithmetic on the same bits.
 #include "scp_separation_device.h"
 
 namespace {
@@ -40,6 +41,16 @@ struct SepPartial {
   unsigned long long n_solved;   // segments that reached the quartic (reported by tools/separation_times.py)
   unsigned long long pad;
 };
+
+__device__ inline SepPartial sep_empty() { return SepPartial{SEP_INF, SEP_NO_ROW, 0.0, SEP_NO_ROW, 0, SEP_INF, 0, 0}; }
+
+__device__ inline void sep_fold(SepPartial& x, const SepPartial& o) {
+  fold_min(x.m, x.row, x.t, o.m, o.row, o.t);
+  x.first = o.first < x.first ? o.first : x.first;
+  x.n_viol += o.n_viol;
+  x.n_solved += o.n_solved;
+  x.sample = fmin(x.sample, o.sample);
+}
 
 // Where the LIST instantiation of the pass keeps its records
 struct SepList {
@@ -153,60 +164,17 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
   double best_m = SEP_INF, best_t = 0.0, min_ss = SEP_INF, min_raw = SEP_INF;
   unsigned long long best_row = SEP_NO_ROW, first = SEP_NO_ROW, n_viol = 0, n_solved = 0;
 
-  // the tile's pairs in [q_begin, q_end): rows of the triangle are contiguous in q, so the tile's own range decides
-  const int i_last = min(i0 + SEP_TILE, N - 1) - 1;  // last vehicle that can be an `i` (i < j <= N - 1)
-  const int j_lo = max(j0, i0 + 1), j_hi = min(j0 + SEP_TILE, N) - 1;
-  bool live = i_last >= i0 && j_hi >= j_lo && j_hi > i0;
-  if (live) {
-    const int64_t q_min = tri_off(i0, N) + (j_lo - i0 - 1);
-    const int64_t q_max = tri_off(i_last, N) + (j_hi - i_last - 1);
-    live = q_max >= a.q_begin && q_min < a.q_end;
-  }
-
-  if (live) {
-    // this thread's j (fixed) and its 16 i's: validity and row offset of each pair, once
-    const int j = j0 + lane;
-    unsigned int valid = 0;
-    for (int s = 0; s < SEP_STEPS; ++s) {
-      const int i = i0 + wave + 4 * s;
-      if (i < j && j < N) {
-        const int64_t q = tri_off(i, N) + (j - i - 1);
-        if (q >= a.q_begin && q < a.q_end) valid |= 1u << s;
-      }
-    }
-    // staging: 2 x 64 records of NC doubles, contiguous per side in the time-major array; vehicles beyond N - 1 repeat it
-    // (their pairs are not valid)
-    constexpr int PER_THREAD = (2 * SEP_TILE * NC + SEP_THREADS - 1) / SEP_THREADS;
-    double pre[PER_THREAD];
-    auto fetch = [&](int k) {
-#pragma unroll
-      for (int e = 0; e < PER_THREAD; ++e) {
-        const int x = tid + e * SEP_THREADS;
-        if (x < 2 * SEP_TILE * NC) {
-          const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
-          const int v = min((side ? j0 : i0) + y / NC, N - 1);
-          pre[e] = a.rec[((int64_t)k * N + v) * NC + y % NC];
-        }
-      }
-    };
-    auto stash = [&]() {
-#pragma unroll
-      for (int e = 0; e < PER_THREAD; ++e) {
-        const int x = tid + e * SEP_THREADS;
-        if (x < 2 * SEP_TILE * NC) {
-          const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
-          sm[y % NC][side * SEP_TILE + y / NC] = pre[e];
-        }
-      }
-    };
+  if (tile_live(i0, j0, N, a.q_begin, a.q_end)) {
+    const unsigned int valid = tile_valid_mask(i0, j0, wave, lane, N, a.q_begin, a.q_end);
+    TileStage<NC, NC> stage;
     double ub = SEP_INF;  // an upper bound of this call's minimum distance: the smallest sampled distance this wave has seen
-    fetch(k_begin);
+    stage.fetch(a.rec, k_begin, N, i0, j0, tid);
     for (int k = k_begin; k < k_end; ++k) {
       __syncthreads();  // (the previous step's phase B has read sm and the queue)
-      stash();
+      stage.stash(sm, tid);
       if (tid == 0) q_count = 0;
       __syncthreads();
-      if (k + 1 < k_end) fetch(k + 1);  // in flight during this step's arithmetic
+      if (k + 1 < k_end) stage.fetch(a.rec, k + 1, N, i0, j0, tid);  // in flight during this step's arithmetic
 
       // ---- phase A ------------------------------------------------------------------------------------------------
       double pj[D];
@@ -217,13 +185,7 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
       double ss_min = SEP_INF;
 #pragma unroll
       for (int s = 0; s < SEP_STEPS; ++s) {
-        const int il = wave + 4 * s;
-        double acc_ss = 0.0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const double df = sm[d][il] - pj[d];  // the operands and the order of pair_geom: the same bits
-          acc_ss = fma(df, df, acc_ss);
-        }
+        const double acc_ss = tile_dd<D>(sm, wave + 4 * s, pj);
         ss[s] = (valid >> s) & 1u ? acc_ss : SEP_INF;
         ss_min = fmin(ss_min, ss[s]);
       }
@@ -264,14 +226,12 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
       const unsigned int n_q = q_count;
       for (unsigned int e = tid; e < n_q; e += SEP_THREADS) {
         const int il = queue[e] >> 6, jl = queue[e] & 63;
-        const int i = i0 + il, jj = j0 + jl;
-        SEP_TILE_QUARTIC(q, sm, il, jl);
+        const Quartic q = tile_quartic<D>(sm, il, jl);
         double m, t;
         quartic_min(q, a.h, m, t);
-        const unsigned long long row =
-            (unsigned long long)((int64_t)k * a.pairs + tri_off(i, N) + (jj - i - 1));
+        const unsigned long long row = tile_row(k, a.pairs, N, i0, j0, il, jl);
         if constexpr (LIST) {
-          if (sqrt(fmax(m, 0.0)) < a.thr) {  // the test n_violating counts, on the same bits
+          if (sep_violates(m, a.thr)) {  // the test n_violating counts, on the same bits
             double t_in, t_out;
             unsigned int pieces;
             quartic_window(q, a.h, a.thr * a.thr, t, t_in, t_out, pieces);
@@ -280,7 +240,7 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
           }
         } else {
           fold_min(best_m, best_row, best_t, m, row, t);
-          if (sqrt(fmax(m, 0.0)) < a.thr) {
+          if (sep_violates(m, a.thr)) {
             ++n_viol;
             first = row < first ? row : first;
           }
@@ -292,11 +252,9 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
 
   if constexpr (LIST) return;
   // ---- workgroup reduction: wave shuffles, then the four wave results through LDS ---------------------------------------
+  wave_fold_min(best_m, best_row, best_t);
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) {
-    const double m2 = __shfl_xor(best_m, s, 64), t2 = __shfl_xor(best_t, s, 64);
-    const unsigned long long r2 = __shfl_xor(best_row, s, 64);
-    fold_min(best_m, best_row, best_t, m2, r2, t2);
     const unsigned long long f2 = __shfl_xor(first, s, 64);
     first = f2 < first ? f2 : first;
     n_viol += __shfl_xor(n_viol, s, 64);
@@ -307,13 +265,7 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_pass_kernel(SepArgs a) {
   __syncthreads();
   if (tid == 0) {
     SepPartial p = red[0];
-    for (int w = 1; w < SEP_THREADS / 64; ++w) {
-      fold_min(p.m, p.row, p.t, red[w].m, red[w].row, red[w].t);
-      p.first = red[w].first < p.first ? red[w].first : p.first;
-      p.n_viol += red[w].n_viol;
-      p.n_solved += red[w].n_solved;
-      p.sample = fmin(p.sample, red[w].sample);
-    }
+    for (int w = 1; w < SEP_THREADS / 64; ++w) sep_fold(p, red[w]);
     a.part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = p;
   }
 }
@@ -323,27 +275,15 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_finish_kernel(const SepPartia
                                                                  scp_separation_stats* __restrict__ stats,
                                                                  unsigned long long* __restrict__ n_solved_out) {
   __shared__ SepPartial red[SEP_THREADS];
-  SepPartial p{SEP_INF, SEP_NO_ROW, 0.0, SEP_NO_ROW, 0, SEP_INF, 0, 0};
+  SepPartial p = sep_empty();
   for (int64_t e = threadIdx.x; e < n; e += SEP_THREADS) {
     const SepPartial o = part[e];
-    fold_min(p.m, p.row, p.t, o.m, o.row, o.t);
-    p.first = o.first < p.first ? o.first : p.first;
-    p.n_viol += o.n_viol;
-    p.n_solved += o.n_solved;
-    p.sample = fmin(p.sample, o.sample);
+    sep_fold(p, o);
   }
   red[threadIdx.x] = p;
   __syncthreads();
   for (int s = SEP_THREADS / 2; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      SepPartial& x = red[threadIdx.x];
-      const SepPartial& o = red[threadIdx.x + s];
-      fold_min(x.m, x.row, x.t, o.m, o.row, o.t);
-      x.first = o.first < x.first ? o.first : x.first;
-      x.n_viol += o.n_viol;
-      x.n_solved += o.n_solved;
-      x.sample = fmin(x.sample, o.sample);
-    }
+    if ((int)threadIdx.x < s) sep_fold(red[threadIdx.x], red[threadIdx.x + s]);
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -456,14 +396,18 @@ __global__ __launch_bounds__(SEP_THREADS) void sep_gather_kernel(const scp_confl
   if (e < n) out[e] = raw[idx[e]];
 }
 
-SepArgs sep_args(int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end, const SepPlan& p, const double* rec,
-                 SepPartial* part) {
+SepArgs sep_args(int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end, const SepCall& c, SepPartial* part) {
   SepArgs a{};
-  a.N = N; a.K = K; a.D = D; a.kc = p.kc;
+  a.N = N; a.K = K; a.D = D; a.kc = c.plan.kc;
   a.h = h; a.thr = R - 0.01;
   a.q_begin = q_begin; a.q_end = q_end; a.pairs = scp_pairs(N);
-  a.rec = rec; a.part = part; a.tile0 = p.tile0; a.nt = p.nt;
+  a.rec = c.rec; a.part = part; a.tile0 = c.plan.tile0; a.nt = c.plan.nt;
   return a;
+}
+
+template <bool LIST>
+void sep_launch_pass(scp_ctx* ctx, const SepCall& c, const SepArgs& a) {
+  sep_launch_tiles(ctx, c.plan, a.D, sep_pass_kernel<2, LIST>, sep_pass_kernel<3, LIST>, a);
 }
 
 }  // namespace
@@ -471,49 +415,25 @@ SepArgs sep_args(int N, int K, int D, double h, double R, int64_t q_begin, int64
 extern "C" int scp_check_separation(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
                                     const double* pos, const double* vel, const double* acc, scp_separation_stats* stats) {
   if (!ctx) return SCP_ERR_INVALID;
-  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  SCP_REQUIRE(ctx, stats, "check_separation: null pointer");
+  SepCall c;
+  auto n_part = [](const SepPlan& p) { return p.n_tiles * p.n_chunks; };
+  int rc = sep_begin(ctx, "check_separation", N, K, D, h, q_begin, q_end, pos, vel, acc,
+                     [&](const SepPlan& p) { return (size_t)std::max<int64_t>(n_part(p), 1) * sizeof(SepPartial); }, &c);
   if (rc) return rc;
-  SCP_REQUIRE(ctx, pos && vel && acc && stats, "check_separation: null pointer");
-  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "check_separation: bad time step h=%g", h);
-  const int NC = 3 * D + 1;
-  const SepPlan plan = sep_plan(ctx, N, K, q_begin, q_end);
-  SCP_REQUIRE(ctx, plan.n_tiles < ((int64_t)1 << 31), "check_separation: %lld tiles exceed grid.x; shard the pair range",
-              (long long)plan.n_tiles);
-  const int64_t n_part = plan.n_tiles * plan.n_chunks;
-  const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
-  rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes,
-                            rec_bytes + (size_t)std::max<int64_t>(n_part, 1) * sizeof(SepPartial) + 64);
+  SepPartial* part = (SepPartial*)c.extra;
+  if (c.plan.n_tiles > 0) sep_launch_pass<false>(ctx, c, sep_args(N, K, D, h, R, q_begin, q_end, c, part));
+  hipLaunchKernelGGL(sep_finish_kernel, dim3(1), dim3(SEP_THREADS), 0, ctx->stream, part, n_part(c.plan), stats,
+                     ctx->solved + SEP_SOLVED_CHECK);
+  rc = sep_end(ctx);
   if (rc) return rc;
-  double* rec = (double*)ctx->sep_ws;
-  SepPartial* part = (SepPartial*)((char*)ctx->sep_ws + rec_bytes);
-  unsigned long long* n_solved = (unsigned long long*)(part + std::max<int64_t>(n_part, 1));
-
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
-  if (n_part > 0) {
-    hipLaunchKernelGGL(sep_prep_kernel, dim3(scp_cdiv((int64_t)N * K, 256)), dim3(256), 0, ctx->stream, N, K, D, h, pos, vel,
-                       acc, rec);
-    const SepArgs a = sep_args(N, K, D, h, R, q_begin, q_end, plan, rec, part);
-    const dim3 grid((unsigned)plan.n_tiles, (unsigned)plan.n_chunks);
-    if (D == 2) hipLaunchKernelGGL(sep_pass_kernel<2>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-    else hipLaunchKernelGGL(sep_pass_kernel<3>, grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-    SCP_HIP_CHECK(ctx, hipGetLastError());
-  }
-  hipLaunchKernelGGL(sep_finish_kernel, dim3(1), dim3(SEP_THREADS), 0, ctx->stream, part, n_part, stats, n_solved);
-  SCP_HIP_CHECK(ctx, hipGetLastError());
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
-  ctx->pair_timed = ctx->timing != 0;
-  ctx->pair_ran = true;
-  ctx->sep_n_solved = n_solved;
+  ctx->solved_ran[SEP_SOLVED_CHECK] = true;
   return SCP_OK;
 }
 
 // segments of the latest scp_check_separation of this ctx that reached the quartic (developer figure; synchronises)
 extern "C" int scp_ctx_last_separation_solved(scp_ctx* ctx, uint64_t* n) {
-  if (!ctx || !n) return SCP_ERR_INVALID;
-  SCP_REQUIRE(ctx, ctx->sep_n_solved, "check_separation has not run yet");
-  SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  SCP_HIP_CHECK(ctx, hipMemcpy(n, ctx->sep_n_solved, sizeof(uint64_t), hipMemcpyDeviceToHost));
-  return SCP_OK;
+  return sep_read_solved(ctx, SEP_SOLVED_CHECK, "check_separation", n);
 }
 
 // The violating segments of the pair range, one record each, in ascending row order (include/scp_hip.h)
@@ -521,42 +441,27 @@ extern "C" int scp_list_conflicts(scp_ctx* ctx, int N, int K, int D, double h, d
                                   const double* pos, const double* vel, const double* acc, scp_conflict* out, int64_t capacity,
                                   uint64_t* n_found) {
   if (!ctx) return SCP_ERR_INVALID;
-  int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
-  if (rc) return rc;
-  SCP_REQUIRE(ctx, pos && vel && acc && n_found, "list_conflicts: null pointer");
-  SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "list_conflicts: bad time step h=%g", h);
+  SCP_REQUIRE(ctx, n_found, "list_conflicts: null pointer");
   SCP_REQUIRE(ctx, capacity >= 0 && capacity <= ((int64_t)1 << 30), "list_conflicts: bad capacity %lld", (long long)capacity);
   SCP_REQUIRE(ctx, out || capacity == 0, "list_conflicts: null list of capacity %lld", (long long)capacity);
-  const int NC = 3 * D + 1;
-  const SepPlan plan = sep_plan(ctx, N, K, q_begin, q_end);
-  SCP_REQUIRE(ctx, plan.n_tiles < ((int64_t)1 << 31), "list_conflicts: %lld tiles exceed grid.x; shard the pair range",
-              (long long)plan.n_tiles);
   int64_t span = SORT_CHUNK;  // sort_span(capacity)
   while (span < capacity) span <<= 1;
-  const size_t rec_bytes = ((size_t)N * K * NC * sizeof(double) + 63) & ~(size_t)63;
   const size_t raw_bytes = ((size_t)capacity * sizeof(scp_conflict) + 63) & ~(size_t)63;
-  // the workspace is shared with scp_check_separation: growing it frees the place of that call's solved count
-  ctx->sep_n_solved = nullptr;
-  rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes,
-                            rec_bytes + raw_bytes + (size_t)span * (sizeof(unsigned long long) + sizeof(unsigned int)) + 64);
+  SepCall c;
+  int rc = sep_begin(ctx, "list_conflicts", N, K, D, h, q_begin, q_end, pos, vel, acc, [&](const SepPlan&) {
+    return raw_bytes + (size_t)span * (sizeof(unsigned long long) + sizeof(unsigned int));
+  }, &c);
   if (rc) return rc;
-  double* rec = (double*)ctx->sep_ws;
-  scp_conflict* raw = (scp_conflict*)((char*)ctx->sep_ws + rec_bytes);
-  unsigned long long* keys = (unsigned long long*)((char*)raw + raw_bytes);
+  scp_conflict* raw = (scp_conflict*)c.extra;
+  unsigned long long* keys = (unsigned long long*)(c.extra + raw_bytes);
   unsigned int* idx = (unsigned int*)(keys + span);
   unsigned long long* count = (unsigned long long*)n_found;
 
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, ctx->stream));
   SCP_HIP_CHECK(ctx, hipMemsetAsync(count, 0, sizeof(unsigned long long), ctx->stream));
-  if (plan.n_tiles > 0) {
-    hipLaunchKernelGGL(sep_prep_kernel, dim3(scp_cdiv((int64_t)N * K, 256)), dim3(256), 0, ctx->stream, N, K, D, h, pos, vel,
-                       acc, rec);
-    SepArgs a = sep_args(N, K, D, h, R, q_begin, q_end, plan, rec, nullptr);
+  if (c.plan.n_tiles > 0) {
+    SepArgs a = sep_args(N, K, D, h, R, q_begin, q_end, c, nullptr);
     a.list = SepList{raw, count, capacity};
-    const dim3 grid((unsigned)plan.n_tiles, (unsigned)plan.n_chunks);
-    if (D == 2) hipLaunchKernelGGL((sep_pass_kernel<2, true>), grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((sep_pass_kernel<3, true>), grid, dim3(SEP_THREADS), 0, ctx->stream, a);
-    SCP_HIP_CHECK(ctx, hipGetLastError());
+    sep_launch_pass<true>(ctx, c, a);
     if (capacity > 0) {
       const dim3 chunks((unsigned)(span / SORT_CHUNK)), halves((unsigned)scp_cdiv(span / 2, SEP_THREADS));
       hipLaunchKernelGGL(sep_sort_local_kernel, chunks, dim3(SEP_THREADS), 0, ctx->stream, raw, count, capacity, keys, idx,
@@ -570,11 +475,7 @@ extern "C" int scp_list_conflicts(scp_ctx* ctx, int N, int K, int D, double h, d
       }
       hipLaunchKernelGGL(sep_gather_kernel, dim3((unsigned)scp_cdiv(capacity, SEP_THREADS)), dim3(SEP_THREADS), 0, ctx->stream,
                          raw, count, capacity, idx, out);
-      SCP_HIP_CHECK(ctx, hipGetLastError());
     }
   }
-  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, ctx->stream));
-  ctx->pair_timed = ctx->timing != 0;
-  ctx->pair_ran = true;
-  return SCP_OK;
+  return sep_end(ctx);
 }

@@ -426,15 +426,19 @@ class Context:
                                                 self.stats.data_ptr()))
         return self.read_stats()
 
+    def _trajectory_args(self, N, K, D, h, R, pos, vel, acc, q_begin, q_end):
+        """the arguments every continuous-time pass begins with; the default pair range is all pairs"""
+        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        return self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(), acc.data_ptr()
+
     def check_separation(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None):
         """scp_check_separation over the pair range [q_begin, q_end): the continuous-time minimum distance of the trajectories
         pos / vel / acc ([N][K][D] device tensors).  Returns the stats as a dictionary -- synchronises."""
         torch = _torch()
-        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        args = self._trajectory_args(N, K, D, h, R, pos, vel, acc, q_begin, q_end)
         if getattr(self, "sep_stats", None) is None:
             self.sep_stats = torch.zeros(C.sizeof(SeparationStats) // 8, dtype=torch.float64, device=self.tdev)
-        self.check(self.lib.scp_check_separation(self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(),
-                                                 acc.data_ptr(), self.sep_stats.data_ptr()))
+        self.check(self.lib.scp_check_separation(*args, self.sep_stats.data_ptr()))
         st = SeparationStats.from_buffer_copy(self.sep_stats.cpu().numpy().tobytes())
         return {f: getattr(st, f) for f, _ in SeparationStats._fields_}
 
@@ -443,13 +447,12 @@ class Context:
         below R - 0.01, as a numpy structured array (CONFLICT_DTYPE) in ascending row order.  The list is sized here: `capacity`
         records (default 1024) and, if more were found, ONE repetition with exactly that many -- synchronises."""
         torch = _torch()
-        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        args = self._trajectory_args(N, K, D, h, R, pos, vel, acc, q_begin, q_end)
         cap = 1024 if capacity is None else int(capacity)
         n_found = torch.zeros(1, dtype=torch.int64, device=self.tdev)
         for _ in range(2):
             out = torch.empty(max(cap, 1) * CONFLICT_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
-            self.check(self.lib.scp_list_conflicts(self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(),
-                                                   acc.data_ptr(), out.data_ptr(), cap, n_found.data_ptr()))
+            self.check(self.lib.scp_list_conflicts(*args, out.data_ptr(), cap, n_found.data_ptr()))
             n = int(n_found.item())
             if n <= cap:
                 return out[: n * CONFLICT_DTYPE.itemsize].cpu().numpy().view(CONFLICT_DTYPE).copy()
@@ -460,11 +463,10 @@ class Context:
         """scp_clearance_profile over the pair range [q_begin, q_end): the closest approach of every vehicle and of every
         time step, as two numpy structured arrays (CLEARANCE_DTYPE) of length N and K -- synchronises."""
         torch = _torch()
-        q_end = N * (N - 1) // 2 if q_end is None else q_end
+        args = self._trajectory_args(N, K, D, h, R, pos, vel, acc, q_begin, q_end)
         size = CLEARANCE_DTYPE.itemsize
         out = torch.empty((N + K) * size, dtype=torch.uint8, device=self.tdev)
-        self.check(self.lib.scp_clearance_profile(self.h, N, K, D, h, R, q_begin, q_end, pos.data_ptr(), vel.data_ptr(),
-                                                  acc.data_ptr(), out.data_ptr(), out.data_ptr() + N * size))
+        self.check(self.lib.scp_clearance_profile(*args, out.data_ptr(), out.data_ptr() + N * size))
         both = out.cpu().numpy().view(CLEARANCE_DTYPE)
         return both[:N].copy(), both[N:].copy()
 

@@ -799,7 +799,9 @@ class SCP:
         N, K, D, h = self.N, self.K, self.D, self.h
         a, v, p = (self.trajectories[k] for k in ("accelerations", "velocities", "positions"))
         q0, q1 = self.shard.pair_range()
-        min_dist, first, _, _ = self._ctx.check_avoidance(N, K, D, self.R, self._ctx.tensor(p), q0, q1)
+        c = self._ctx
+        dev = (c.tensor(p), c.tensor(v), c.tensor(a)) if continuous else (c.tensor(p),)  # one upload for every pass below
+        min_dist, first, _, _ = c.check_avoidance(N, K, D, self.R, dev[0], q0, q1)
         min_dist = self.shard.all_min(min_dist)
         first = self.shard.all_min_int(first)
         pf = self.final_positions.reshape(N, D)
@@ -824,25 +826,24 @@ class SCP:
             report["first_violation"] = {"timestep": int(k), "vehicles": (i, j),
                                          "distance": float(np.linalg.norm(p[i, k] - p[j, k]))}
         if continuous:
-            report.update(self._continuous_separation(p, v, a, q0, q1))
+            report.update(self._continuous_separation(p, v, a, dev, q0, q1))
         if conflicts:
-            c = self._ctx
-            mine = c.list_conflicts(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)
+            mine = c.list_conflicts(N, K, D, h, self.R, *dev, q0, q1)
             report["conflicts"] = conflict_windows(self.shard.allgather_records(mine), N, K, h)
             report["n_conflicts"] = len(report["conflicts"])
         if clearance:
-            report.update(self._clearance_profiles(p, v, a, q0, q1))
+            report.update(self._clearance_profiles(dev, q0, q1))
         return report
 
-    def _clearance_profiles(self, p, v, a, q0, q1):
-        """The clearance part of validate_solution: one device pass (scp_clearance_profile) over this rank's pair range,
-        combined entry by entry over the ranks (lexicographic minimum of (distance, row), minimum, integer sum)."""
+    def _clearance_profiles(self, dev, q0, q1):
+        """The clearance part of validate_solution: one device pass (scp_clearance_profile) over this rank's pair range of the
+        device tensors dev = (positions, velocities, accelerations), combined entry by entry over the ranks (lexicographic
+        minimum of (distance, row), minimum, integer sum)."""
         N, K, D, h = self.N, self.K, self.D, self.h
-        c = self._ctx
         pairs = self.shard.pairs
         out = {}
         for name, e in zip(("vehicle_clearance", "step_clearance"),
-                           c.clearance_profile(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)):
+                           self._ctx.clearance_profile(N, K, D, h, self.R, *dev, q0, q1)):
             dist, row, t = self.shard.all_argmin_arrays(e["min_dist"], e["row"], e["t_min"])
             some = row != np.uint64(_hip.NO_ROW)
             r = np.where(some, row, 0).astype(np.int64)
@@ -865,13 +866,13 @@ class SCP:
                                            "distance": float(vc["min_distance"][best])}
         return out
 
-    def _continuous_separation(self, p, v, a, q0, q1):
+    def _continuous_separation(self, p, v, a, dev, q0, q1):
         """The continuous-time part of validate_solution: between two samples a vehicle flies p + t v + t^2/2 a (the
         kinematics of the stored trajectories), so two vehicles can pass each other inside a segment while every sampled
-        distance is fine.  One device pass (scp_check_separation) over this rank's pair range, combined over the ranks."""
+        distance is fine.  One device pass (scp_check_separation) over this rank's pair range of the device tensors dev (the
+        host arrays p, v, a uploaded), combined over the ranks."""
         N, K, D, h = self.N, self.K, self.D, self.h
-        c = self._ctx
-        st = c.check_separation(N, K, D, h, self.R, c.tensor(p), c.tensor(v), c.tensor(a), q0, q1)
+        st = self._ctx.check_separation(N, K, D, h, self.R, *dev, q0, q1)
         min_dist, row, t = self.shard.all_argmin(st["min_dist"], st["argmin_row"], st["argmin_t"])
         first = self.shard.all_min_int(st["first_violation"])
         n_viol = self.shard.all_sum_int(st["n_violating"])

@@ -307,6 +307,40 @@ def test_shards_merge_to_the_full_profile(ctx):
     assert rc == 0 and s_only.tobytes() == step.tobytes() and not untouched.view(np.uint8).any()
 
 
+def test_solved_counts_outlive_the_other_passes():
+    """the two cost figures belong to the context, not to a workspace: each getter reports its own call's latest run whatever
+    ran in between -- the other passes, a list call, a profile that grows the shared workspace -- and SCP_ERR_STATE only on a
+    context on which that call never ran"""
+    from path_planning import _hip
+
+    c = _hip.Context(0)
+    try:
+        for getter in (c.last_separation_solved, c.last_clearance_solved):
+            with pytest.raises(_hip.HipError) as err:
+                getter()
+            assert err.value.code == -4  # SCP_ERR_STATE
+        (pos, vel, acc), _, _ = random_case(c, 65, 7, 2, 17)
+        R = 0.8
+        c.check_separation(65, 7, 2, H, R, pos, vel, acc)
+        n_check = c.last_separation_solved()
+        with pytest.raises(_hip.HipError) as err:
+            c.last_clearance_solved()
+        assert err.value.code == -4
+        c.clearance_profile(65, 7, 2, H, R, pos, vel, acc)
+        n_profile = c.last_clearance_solved()
+        print(f"solved: check {n_check}, profile {n_profile} of {7 * 65 * 64 // 2} segments")
+        assert 0 < n_check <= 7 * 65 * 64 // 2 and 0 < n_profile <= 7 * 65 * 64 // 2
+        c.check_separation(65, 7, 2, H, R, pos, vel, acc)
+        c.list_conflicts(65, 7, 2, H, R, pos, vel, acc, capacity=0)
+        c.clearance_profile(65, 7, 2, H, R, pos, vel, acc)
+        assert (c.last_separation_solved(), c.last_clearance_solved()) == (n_check, n_profile)
+        big, _, _ = random_case(c, 130, 9, 3, 21)
+        c.clearance_profile(130, 9, 3, H, R, *big)  # grows the shared workspace
+        assert c.last_separation_solved() == n_check and 0 < c.last_clearance_solved() <= 9 * 130 * 129 // 2
+    finally:
+        c.close()
+
+
 # ---- 6. argument errors -----------------------------------------------------------------------------------------------------------
 def test_argument_errors(ctx):
     import torch

@@ -6,7 +6,7 @@
 Shapes: 1024 x 50 x 2, 4096 x 50 x 2, 1024 x 50 x 3.  Data: (a) the grid-swap scenario of bench.py, solved trajectories
 (QP#0 + SCP iterations, max 15); (b) random kinematically consistent trajectories in a 20^D box (|v| <= 2, |a| <= 15 per
 axis).  Times are HIP events around each call's kernels (scp_ctx_last_pair_ms), the two passes alternating in one process:
-median, min and max over the repetitions after the warm-up.
+median, min, quartiles and max over the repetitions after the warm-up.
 
 --list adds the conflict list (scp_list_conflicts) on the same trajectories, alternating with the check in one loop, and a
 small shape (128 x 50 x 2).  Its sort is not timed by itself: the call is repeated with capacity 0, which runs the same
@@ -40,6 +40,15 @@ def random_case(N, K, D, seed, h=0.2, side=20.0):
     return p0, v0, acc
 
 
+def q(x):
+    """median, min, max of the timed calls in ms; fmt() prints them in us with the quartiles"""
+    return float(np.median(x)), float(np.min(x)), float(np.max(x)), float(np.percentile(x, 25)), float(np.percentile(x, 75))
+
+
+def fmt(s):
+    return f"{s[0]*1e3:8.1f} us (min {s[1]*1e3:.1f}, p25 {s[3]*1e3:.1f}, p75 {s[4]*1e3:.1f}, max {s[2]*1e3:.1f})"
+
+
 def measure(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
     t_sep, t_chk = [], []
     for r in range(warmup + reps):
@@ -53,10 +62,9 @@ def measure(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
     ctx.check_separation(N, K, D, h, R, pos, vel, acc)
     solved = ctx.last_separation_solved()
     seg = K * N * (N - 1) // 2
-    q = lambda x: (float(np.median(x)), float(np.min(x)), float(np.max(x)))  # noqa: E731
     s, c = q(t_sep), q(t_chk)
-    print(f"{label:28s} {N:5d} x {K} x {D}  separation {s[0]*1e3:8.1f} us (min {s[1]*1e3:.1f}, max {s[2]*1e3:.1f})   "
-          f"sampled check {c[0]*1e3:8.1f} us (min {c[1]*1e3:.1f}, max {c[2]*1e3:.1f})   ratio {s[0]/c[0]:.2f}   "
+    print(f"{label:28s} {N:5d} x {K} x {D}  separation {fmt(s)}   "
+          f"sampled check {fmt(c)}   ratio {s[0]/c[0]:.2f}   "
           f"quartic: {solved} of {seg} segments ({100.0*solved/seg:.3f} %)   min distance continuous {st['min_dist']:.4f} "
           f"sampled {st['sample_min_dist']:.4f} violating {st['n_violating']}", flush=True)
 
@@ -86,11 +94,9 @@ def measure_listing(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
             t_chk.append(a)
             t_full.append(b)
             t_none.append(c)
-    q = lambda x: (float(np.median(x)), float(np.min(x)), float(np.max(x)))  # noqa: E731
     k, f, z = q(t_chk), q(t_full), q(t_none)
-    print(f"{label:28s} {N:5d} x {K} x {D}  check {k[0]*1e3:8.1f} us (min {k[1]*1e3:.1f}, max {k[2]*1e3:.1f})   "
-          f"list {f[0]*1e3:8.1f} us (min {f[1]*1e3:.1f}, max {f[2]*1e3:.1f})   list, capacity 0 {z[0]*1e3:8.1f} us "
-          f"(min {z[1]*1e3:.1f}, max {z[2]*1e3:.1f})   list / check {f[0]/k[0]:.2f}   store + sort + gather "
+    print(f"{label:28s} {N:5d} x {K} x {D}  check {fmt(k)}   "
+          f"list {fmt(f)}   list, capacity 0 {fmt(z)}   list / check {f[0]/k[0]:.2f}   store + sort + gather "
           f"{(f[0]-z[0])*1e3:.1f} us = {100.0*(f[0]-z[0])/f[0]:.1f} % of the list   records {n} (capacity {cap})", flush=True)
 
 
@@ -109,10 +115,9 @@ def measure_clearance(ctx, N, K, D, h, R, pos, vel, acc, reps, warmup, label):
     solved_chk = ctx.last_separation_solved()
     seg = K * N * (N - 1) // 2
     assert step["min_dist"].min() == veh["min_dist"].min() == st["min_dist"] and int(step["n_violating"].sum()) == st["n_violating"]
-    q = lambda x: (float(np.median(x)), float(np.min(x)), float(np.max(x)))  # noqa: E731
     k, c = q(t_chk), q(t_clr)
-    print(f"{label:28s} {N:5d} x {K} x {D}  check {k[0]*1e3:8.1f} us (min {k[1]*1e3:.1f}, max {k[2]*1e3:.1f})   "
-          f"clearance profile {c[0]*1e3:8.1f} us (min {c[1]*1e3:.1f}, max {c[2]*1e3:.1f})   profile / check {c[0]/k[0]:.2f}   "
+    print(f"{label:28s} {N:5d} x {K} x {D}  check {fmt(k)}   "
+          f"clearance profile {fmt(c)}   profile / check {c[0]/k[0]:.2f}   "
           f"quartic: check {solved_chk} of {seg} segments ({100.0*solved_chk/seg:.3f} %), profile {solved_clr} "
           f"({100.0*solved_clr/seg:.3f} %)   vehicles in conflict {int((veh['n_violating'] > 0).sum())} of {N}, smallest "
           f"clearance {veh['min_dist'].min():.4f}, median {float(np.median(veh['min_dist'])):.4f}", flush=True)
