@@ -47,7 +47,8 @@ struct scp_ctx {
   uint32_t* wg_rows;              // [workgroups][8192] per-workgroup sub-lists of its marked rows (grown on demand)
   size_t wg_rows_bytes;
   unsigned* d_ticket;             // its last-workgroup-done counter (zero between launches): word 0 of a 64-byte block of
-                                  // device words that lives as long as the ctx ([1], [2]: the QP's tickets; [12, 16): `solved`)
+                                  // device words that lives as long as the ctx ([1], [2]: the QP's tickets; [3]: the
+                                  // violations pass's "not finite" word; [12, 16): `solved`)
   int timing;                     // HIP events around the pairwise kernels and the QP solves (scp_ctx_set_option; default on)
   int small_pass;                 // one-launch pairwise passes for small problems (scp_ctx_set_option; default on)
   unsigned long long rel_seq;     // of the latest scp_rel_step (completion word: h_scratch[64]; partials: h_scratch[0..64))
@@ -62,6 +63,10 @@ struct scp_ctx {
   int* d_gen_flag;
   void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)
   size_t asg_ws_bytes;
+  int near_pass;                  // near form of the recomputing violations pass: 0 off, 1 auto, 2 force (scp_ctx_set_near_pass)
+  unsigned near_call_no;          // number of the latest recomputing violations pass (what its prep kernel leaves in
+                                  // d_ticket[3] when a staged value is not finite)
+  unsigned long long near_ran, near_fell_back;  // near passes of this ctx / those followed by the exhaustive pass
 };
 
 static inline int scp_fail(scp_ctx* ctx, int code, const char* fmt, ...) {
@@ -104,6 +109,32 @@ hipError_t scp_raise_lds_limit(int device, const void* kernel, size_t bytes);
 // ~20 us, then poll every ~20 us from a sleep, for many solver threads on few cores (compute-trajectories-batch).
 // Returns false after `timeout_s` seconds.
 bool scp_wait_host_word(volatile unsigned long long* word, unsigned long long seq, int timeout_s);
+
+// ---- the near form of the recomputing violations pass (scp_near.hip; chosen and followed up in scp_kernels.hip: pair_pass) ----
+// Rows whose bound  R - dist + |dP_i| + |dP_j|  lies below -SCP_NEAR_TAU are not examined.  The bound is a sum of four
+// numbers of the arena's size (<= 1e2): its fp64 rounding, the inflation of |dP| and the squared comparison included, stays
+// below 1e-12.  1e-6 is six orders above that and still six below the distances that decide anything (R ~ 1, feas_tol
+// 1e-6 .. 1e-4): at 1024 x 50 the examined rows are 6 445 of 26 188 800.  The caller trusts a near pass whose maximum is at
+// least -SCP_NEAR_TAU / 2: every unexamined row is then smaller than the maximum and, being negative, not violated.
+constexpr double SCP_NEAR_TAU = 1e-6;
+constexpr double SCP_NEAR_MAX_ABS = 1e100;  // staged values beyond this count as not finite (their squares must not overflow)
+struct ScpNearArgs {
+  int N, K, D;
+  double R, feas_tol;
+  int64_t q_begin, q_end;
+  const double* P_tm;      // [K][N][D] linearisation point, time-major
+  const double* dP_tm;     // [K][N][D] P_new - P_prev
+  const uint32_t* bitmap;  // working-set membership
+  uint32_t* mark;          // scratch map the violated rows outside the working set are marked in
+  scp_pair_stats* stats;   // max_violation (initialised by the prep kernel)
+  const unsigned* unbounded;  // == call_no: a staged value of this call was not finite, nothing is examined
+  unsigned call_no;
+};
+inline unsigned* scp_near_unbounded_word(scp_ctx* ctx) { return ctx->d_ticket + 3; }
+// the tables of one time step fit the LDS of a workgroup; *lds_bytes: their size
+bool scp_near_fits(int N, int D, size_t* lds_bytes);
+// the near kernel, between the two events scp_ctx_last_pair_ms reads
+int scp_launch_near_violations(scp_ctx* ctx, const ScpNearArgs& a, size_t lds_bytes);
 
 // shape / pair-range validation shared by every pairwise pass (scp_kernels.hip)
 int scp_check_pair_range(scp_ctx* ctx, int N, int K, int D, int64_t q_begin, int64_t q_end);

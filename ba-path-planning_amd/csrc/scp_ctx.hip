@@ -29,6 +29,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
   ctx->stream = (hipStream_t)hip_stream;
   ctx->timing = 1;
   ctx->small_pass = getenv("SCP_NO_SMALL_PASS") ? 0 : 1;  // (developer switch; scp_ctx_set_option at run time)
+  ctx->near_pass = 1;  // auto (scp_ctx_set_near_pass)
   if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->n_cu = 0;
   if (hipMalloc(&ctx->d_scratch, 72 * sizeof(double)) != hipSuccess ||
       hipMemset(ctx->d_scratch, 0, 72 * sizeof(double)) != hipSuccess ||  // ([64]: ticket counter of scp_rel_step)

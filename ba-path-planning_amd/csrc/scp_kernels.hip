@@ -956,11 +956,14 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_pass_kernel(PairArgs a) {
 #endif
 }
 
-// [N][K][D] -> time-major P_prev and dP = P_new - P_prev (MODE_VIOL_RECOMPUTE)
+// [N][K][D] -> time-major P_prev and dP = P_new - P_prev (MODE_VIOL_RECOMPUTE).  A staged value that is not finite (or so
+// large that its square is not: SCP_NEAR_MAX_ABS) leaves this call's number in *unbounded: the near form of the pass
+// (scp_near.hip) then marks nothing and the caller takes the exhaustive pass.  The word is never reset: calls are numbered.
 __global__ __launch_bounds__(256) void pair_prep_delta_kernel(int N, int K, int D, const double* __restrict__ pos_prev,
                                                                const double* __restrict__ pos_new,
                                                                double* __restrict__ P_tm, double* __restrict__ dP_tm,
-                                                               scp_pair_stats* __restrict__ stats) {
+                                                               scp_pair_stats* __restrict__ stats,
+                                                               unsigned* __restrict__ unbounded, unsigned call_no) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t C = (int64_t)N * D;
   if (t == 0) pair_stats_init(stats);
@@ -970,8 +973,11 @@ __global__ __launch_bounds__(256) void pair_prep_delta_kernel(int N, int K, int 
   const int i = c / D, d = c % D;
   const int64_t g = ((int64_t)i * K + k) * D + d;
   const double pp = pos_prev[g];
+  const double dp = pos_new[g] - pp;
   P_tm[t] = pp;
-  dP_tm[t] = pos_new[g] - pp;
+  dP_tm[t] = dp;
+  if (!(fabs(pp) <= SCP_NEAR_MAX_ABS) || !(fabs(dp) <= SCP_NEAR_MAX_ABS))
+    __hip_atomic_store(unbounded, call_no, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -1246,13 +1252,12 @@ static int split_linearize_items(scp_ctx* ctx, PairArgs& a, PairKernel kern, siz
   return SCP_OK;
 }
 
-// The pass of a large problem: a prep kernel (time-major slices, the stats' initial values, the cleared map of a REPLACE
-// pass), then the pass kernel; the compaction follows in pair_pass.  pos, p0, v0: the pass's positions in the reference
-// layout and the initial states; MODE_VIOL_RECOMPUTE: pos = the linearisation point, p0 = the new positions (v0 unused).
-static int launch_large_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
-                             const double* v0) {
+// The prep kernel of a multi-launch pass: time-major slices (a.P_tm, a.Q_tm), the stats' initial values, the cleared map of a
+// REPLACE pass.  pos, p0, v0: the pass's positions in the reference layout and the initial states; MODE_VIOL_RECOMPUTE:
+// pos = the linearisation point, p0 = the new positions (v0 unused).
+static int launch_pass_prep(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
+                            const double* v0) {
   const int N = a.N, K = a.K, D = a.D;
-  const int64_t nq = a.q_end - a.q_begin;
   ctx->last_pass_small = false;
   const size_t slice = ((size_t)N * K * D + 1) & ~(size_t)1;  // keep the second array 16-byte aligned
   const int rc = scp_ctx_ensure_bytes(ctx, (void**)&ctx->tm_scratch, &ctx->tm_bytes, 2 * slice * sizeof(double));
@@ -1261,13 +1266,27 @@ static int launch_large_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMark
   double* Q_tm = (mode != MODE_CHECK && mode != MODE_SELECT) ? ctx->tm_scratch + slice : nullptr;
   const dim3 prep_grid(scp_cdiv((int64_t)N * K * D, 256));
   const bool clear = marks.kind == PassMarks::REPLACE;
-  if (mode == MODE_VIOL_RECOMPUTE)
-    hipLaunchKernelGGL(pair_prep_delta_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, pos, p0, P_tm, Q_tm, a.stats);
-  else
+  if (mode == MODE_VIOL_RECOMPUTE) {
+    if (++ctx->near_call_no == 0u) ctx->near_call_no = 1u;  // (0 is the word's initial value)
+    hipLaunchKernelGGL(pair_prep_delta_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, pos, p0, P_tm, Q_tm, a.stats,
+                       scp_near_unbounded_word(ctx), ctx->near_call_no);
+  } else {
     hipLaunchKernelGGL(pair_prep_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, a.h, pos, p0, v0, P_tm, Q_tm,
                        a.stats, clear ? marks.bitmap : nullptr, clear ? a.words : (int64_t)0);
+  }
+  SCP_HIP_CHECK(ctx, hipGetLastError());
   a.P_tm = P_tm;
   a.Q_tm = Q_tm;
+  return SCP_OK;
+}
+
+// The pass of a large problem: the prep kernel, then the pass kernel; the compaction follows in pair_pass.
+static int launch_large_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
+                             const double* v0) {
+  const int N = a.N, K = a.K, D = a.D;
+  const int64_t nq = a.q_end - a.q_begin;
+  const int rc_prep = launch_pass_prep(ctx, mode, a, marks, pos, p0, v0);
+  if (rc_prep) return rc_prep;
   if (nq <= 0) return SCP_OK;
   const size_t slice_bytes = (size_t)N * D * sizeof(double);
   const bool two_slices = mode == MODE_LINEARIZE || mode == MODE_VIOL_RECOMPUTE;  // (the second one PAIR_LDS_Q_OFF doubles in)
@@ -1300,8 +1319,32 @@ static int pair_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks
   const char* abl = getenv("SCP_PAIR_ABLATE");
   a.ablate = abl ? atoi(abl) : 0;
 #endif
-  if (pair_mode_has_small(mode) && small_pass_ok(ctx, a.N, a.K, a.D, a.q_end - a.q_begin, small_pass_slices(mode, a)))
+  const bool small = pair_mode_has_small(mode) && small_pass_ok(ctx, a.N, a.K, a.D, a.q_end - a.q_begin, small_pass_slices(mode, a));
+  // The near form of the recomputing violations pass (scp_near.hip): only the pairs close enough to be violated.  Its
+  // result is the exhaustive pass's, bit for bit, as long as some examined row is close to active; the stats the caller is
+  // about to read anyway tell (the unexamined rows lie below -SCP_NEAR_TAU), and otherwise the exhaustive pass runs after
+  // all -- from an untouched working set: every examined row was negative, nothing was marked.
+  size_t near_lds = 0;
+  if (mode == MODE_VIOL_RECOMPUTE && marks.kind == PassMarks::MERGE && !a.x_tm && ctx->near_pass != 0 &&
+      (!small || ctx->near_pass == 2) && a.q_end > a.q_begin && a.margin >= 0.0 && a.R > 0.0 && scp_near_fits(a.N, a.D, &near_lds)) {
+    int rc = launch_pass_prep(ctx, mode, a, marks, pos, p0, v0);
+    if (rc) return rc;
+    const ScpNearArgs na{a.N, a.K, a.D, a.R, a.margin, a.q_begin, a.q_end, a.P_tm, a.Q_tm, a.bitmap, a.mark, a.stats,
+                         scp_near_unbounded_word(ctx), ctx->near_call_no};
+    rc = scp_launch_near_violations(ctx, na, near_lds);
+    if (rc) return rc;
+    rc = launch_compaction(ctx, a.mark, a.words, a.q_end - a.q_begin, a.q_begin, a.pairs, marks.rows, marks.cap, marks.bitmap,
+                           a.stats);
+    if (rc) return rc;
+    scp_pair_stats st;
+    rc = scp_ctx_wait_stats(ctx, &st);
+    if (rc) return rc;
+    ++ctx->near_ran;
+    if (st.max_violation >= -0.5 * SCP_NEAR_TAU) return SCP_OK;
+    ++ctx->near_fell_back;  // (also: a staged value was not finite -- the kernel left the initial -inf)
+  } else if (small) {
     return launch_small_pass(ctx, mode, a, marks, pos, p0);
+  }
   const int rc = launch_large_pass(ctx, mode, a, marks, pos, p0, v0);
   if (rc || marks.kind == PassMarks::NONE) return rc;
   // (the marks of a MERGE pass are the bits of the scratch map; merging them into the working-set bitmap also clears it)
@@ -1430,6 +1473,7 @@ int scp_violations_from_solution(scp_ctx* ctx, int N, int K, int D, double R, do
   int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
   if (rc) return rc;
   const int64_t nq = q_end - q_begin;
+  if (ctx->near_pass == 2) return SCP_OK;  // (forced near form: the caller's three calls reach it)
   if (!small_pass_ok(ctx, N, K, D, nq, 2)) return SCP_OK;
   if (!spec_bitmap || !small_pass_ok(ctx, N, K, D, nq, 3)) spec_rows = nullptr;  // (no LDS for the third slice: no speculation)
   PairArgs a = pair_args(N, K, D, R, h, q_begin, q_end, stats);

@@ -191,7 +191,7 @@ ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (ch
 
 EXPORTS = [
     "scp_set_host_wait", "scp_abi_version", "scp_ctx_create", "scp_ctx_destroy", "scp_last_error", "scp_ctx_synchronize",
-    "scp_ctx_last_pair_ms", "scp_ctx_set_option",
+    "scp_ctx_last_pair_ms", "scp_ctx_set_option", "scp_ctx_set_near_pass", "scp_ctx_near_pass_counts", "scp_ctx_peek_scratch_map",
     "scp_kinematics", "scp_fixed_bounds", "scp_linearize_pairs", "scp_select_pairs", "scp_check_avoidance", "scp_qp_add_rows_at",
     "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
     "scp_clearance_profile", "scp_ctx_last_clearance_solved",
@@ -235,6 +235,9 @@ def load_library():
     lib.scp_ctx_set_option.argtypes = [vp, C.c_char_p, i32]
     lib.scp_ctx_set_option.restype = i32
     lib.scp_set_host_wait.restype = None
+    lib.scp_ctx_set_near_pass.argtypes = [vp, i32]
+    lib.scp_ctx_near_pass_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.scp_ctx_peek_scratch_map.argtypes = [vp, vp, i64]
     lib.scp_ctx_create.argtypes = [i32, vp, C.POINTER(vp)]
     lib.scp_ctx_destroy.argtypes = [vp]
     lib.scp_ctx_destroy.restype = None
@@ -363,6 +366,26 @@ class Context:
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
+
+    def set_near_pass(self, mode):
+        """scp_ctx_set_near_pass: the near form of the recomputing violations pass -- 0 off, 1 auto (default: large problems),
+        2 force (small problems too).  Results never depend on it."""
+        self.check(self.lib.scp_ctx_set_near_pass(self.h, int(mode)))
+        self.options_changed = True
+
+    def near_pass_counts(self):
+        """(near passes run on this context, how many of them were followed by the exhaustive pass)"""
+        n, f = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.scp_ctx_near_pass_counts(self.h, C.byref(n), C.byref(f)))
+        return int(n.value), int(f.value)
+
+    def peek_scratch_map(self, words):
+        """test hook: the first `words` words of the violations passes' scratch bitmap (numpy uint32) -- synchronises"""
+        out = np.empty(int(words), dtype=np.uint32)
+        if out.size == 0:
+            return out
+        self.check(self.lib.scp_ctx_peek_scratch_map(self.h, out.ctypes.data_as(C.c_void_p), int(words)))
+        return out
 
     def set_timing(self, on):
         self.set_option("kernel_timing", 1 if on else 0)

@@ -152,6 +152,16 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     from the [N][K][D] arrays, reduction, sorted row list and host-visible stats in the pass kernel's last workgroup.
  *     0: prep kernel + pass + compaction launches as for large problems. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
+/* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
+ * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
+ * finite -- the results are the exhaustive pass's, bit for bit.  mode 0: never; 1 (default): for problems too large for
+ * the one-launch passes, when feas_tol >= 0 and a time step's tables fit the LDS; 2: wherever it can run, small problems
+ * included (tests, A/B runs). */
+int scp_ctx_set_near_pass(scp_ctx* ctx, int mode);
+/* Near passes this ctx has run, and how many of them were followed by the exhaustive pass. */
+int scp_ctx_near_pass_counts(scp_ctx* ctx, uint64_t* n_near /* [host] */, uint64_t* n_fell_back /* [host] */);
+/* Test hook: the first `words` words of the scratch bitmap of the violations passes (all zero between calls).  Synchronises. */
+int scp_ctx_peek_scratch_map(scp_ctx* ctx, uint32_t* out /* [host] */, int64_t words);
 
 /* ---- a4 / a7: SCP._compute_positions_velocities (scp.py:371-397),
  *               SCP._accelerations_to_positions_velocities (scp.py:559-595) ---------------------------

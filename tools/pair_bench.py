@@ -1,4 +1,4 @@
-"""Developer tool: run only the pairwise passes (linearize, violations, check) a few times at a given size --
+"""Developer tool: run only the pairwise passes (linearize, select, violations exhaustive and near, check) a few times at a given size --
 the target of `rocprofv3 --pmc` runs (HBM traffic, stall breakdown).  Not part of the product path."""
 import argparse
 import os
@@ -38,11 +38,18 @@ def main():
         ms = pp.last_linearize_ms
         print(f"select     {ms*1e3:8.1f} us  {pp.rows/ms/1e6:8.1f} G rows/s  sel={rows.numel()} min={md:.4f}")
     rows, md, fv = pp.linearize(pos_t, p0_t, v0_t, a.margin)  # (the violations pass works on the bitmap of a linearisation)
-    for r in range(a.reps):
-        pp.bitmap.zero_()
-        new, mv = pp.violations(pos_t, p0_t, v0_t, 1e-6)
-        ms = pp.last_violations_ms
-        print(f"violations {ms*1e3:8.1f} us  {pp.rows*bytes_row/ms/1e6:8.1f} GB/s  new={new.numel()} maxv={mv:.3e}")
+    # the recomputing violations pass: exhaustive (every row), then its near form (only the pairs close enough to be
+    # violated; the time is the near kernel's -- or the exhaustive kernel's when the pass fell back to it)
+    for mode, name in ((0, "violations"), (1, "viol. near")):
+        ctx.set_near_pass(mode)
+        for r in range(a.reps):
+            pp.bitmap.zero_()
+            n0, f0 = ctx.near_pass_counts()
+            new, mv = pp.violations(pos_t, p0_t, v0_t, 1e-6)
+            ms = pp.last_violations_ms
+            n1, f1 = ctx.near_pass_counts()
+            print(f"{name} {ms*1e3:8.1f} us  {pp.rows/ms/1e6:8.1f} G rows/s  new={new.numel()} maxv={mv:.3e}"
+                  f"  near={n1 - n0} fell_back={f1 - f0}")
     for r in range(a.reps):
         ctx.check_avoidance(N, K, D, 0.8, pos_t)
         print(f"check      {ctx.last_pair_ms()*1e3:8.1f} us")
