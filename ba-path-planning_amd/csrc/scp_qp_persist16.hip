@@ -61,6 +61,11 @@ constexpr int AB_STRIDE = 32;  // per-agent bound table: 8 groups of 4 doubles
 // like H_f^{-1}) next to p = H_f^{-1} r and publish the cells straight from the accumulators, before any prefix scan.  (<2, 16>
 // would have the waves too, but not the registers or the LDS; <3, 8> has none.)
 constexpr bool t_on_mfma(int D, int APB) { return 4 * nct_of(D, APB) < APB && APB <= 8; }
+// K slices of the MFMA phase whose operand loads are in flight together (4 registers each).  <2, 16> takes none: at 128
+// registers every form of the ring, even one slot deep, spills two registers more than the plain loop (65).  Eight-agent
+// kernels at 1024 x 50: 2, 3 and 4 slots measure within 0.1 us per step of each other, 5 and 8 slower again
+// (DESIGN.md 3.3).
+constexpr int mfma_slices(int D, int APB) { return APB > 8 ? 1 : 4; }
 // entry tables, doubles per incident row: signed eta [D], l, z, y, g, c . (S0 x_own - S0 x_partner), c . (S0 p_own - S0 p_partner)
 constexpr int ent_doubles(int D) { return D + 6; }
 
@@ -99,6 +104,7 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   constexpr int NCT = nct_of(D, APB16);        // column tiles of the MFMA phase
   constexpr int NC16 = 16 * NCT;               // tile columns (D APB16 of them in use)
   constexpr bool TQ = t_on_mfma(D, APB16);     // S0 p = T r on the matrix waves the column tiles leave idle
+  constexpr int MU = mfma_slices(D, APB16);    // K slices per batch of operand loads
   extern __shared__ __attribute__((aligned(16))) double lds[];
   __shared__ double red[NCHK][APB16];
   __shared__ double cert_s[3][APB16];  // per wave: |dy|, support value, |A^T dy| of the batch's last step (fixed rows)
@@ -263,6 +269,19 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
   u64* my_cell = A.cells + ((size_t)((int64_t)min(k, K - 1) * N + (aok ? agent : 0)) * D) * 2;
   double* my_pt = Pt + (size_t)(wave * D) * RSK + k;   // + d RSK: this lane's slot of column (agent, d)
   double* my_rt = Rt + (size_t)(wave * D) * RSK + k;
+  // TQ, the waves that form T r: which of this lane's four accumulator rows (tile 16 + lk + 4 q of column li) belong to a
+  // cell with rows, i.e. get published -- cptr does not change during a launch, so the step's epilogue looks nothing up
+  unsigned pub_rows = 0;
+  if constexpr (TQ) {
+    const int li = lane & 15, al = li / D;
+    if (wave >= 4 * NCT && wave < 4 * NCT + 4 && li < D * APB16 && a0 + al < N) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = (wave & 3) * 16 + (lane >> 4) + 4 * q;
+        if (row < K && cptr[al * K + row + 1] > cptr[al * K + row]) pub_rows |= 1u << q;
+      }
+    }
+  }
 
   PSTAMP(0);
   bool ok = true;
@@ -290,6 +309,8 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
       double g[D];
 #pragma unroll
       for (int d = 0; d < D; ++d) g[d] = 0.0;
+      // (one entry per trip: with the loads of 2 - 4 entries in flight per wait -- indices clamped or lanes masked -- the
+      // clamps and selects cost more VALU time at two waves per SIMD than the round trips they save)
       for (int e = c0; e < c1e; ++e) {
         const double ge = e_g[e];
 #pragma unroll
@@ -329,26 +350,57 @@ __global__ __launch_bounds__(64 * APB16) void cg1_persist16_kernel(PersistArgs A
       const int tile = wave & 3, ct = tw ? 0 : wave >> 2;
       const double* Mt = (tw ? Tl : Ml) + (size_t)tile * nks * 64 + lane;
       const double* Bt = Rt + (size_t)(ct * 16 + li) * RSK;
+      // K slices s = 0 ... nks - 1 into the one accumulator, in that order.  The operands go through a ring of MU slots: the
+      // loads of slice s + MU are issued as soon as the MFMA of slice s has taken its slot's operands, so MU slices' loads
+      // are in flight while the MFMAs issue and an MFMA waits for the matrix pipe, not for its own LDS round trip.  Slice
+      // indices are clamped (every load is in bounds, whatever it is used for); B beyond the horizon is an exact 0.0 by a
+      // select (pad_col(K) < 4 nks for some K: no padding to rely on).
+      auto load_slice = [&](int s, double& a, double& b) {  // (b: as loaded; the select is mfma_slice's, after the wait)
+        s = min(s, nks - 1);
+        a = Mt[(size_t)s * 64];
+        b = Bt[min(4 * s + lk, K - 1)];
+      };
+      auto mfma_slice = [&](int s, double a, double b, double4_t c) {
+        return __builtin_amdgcn_mfma_f64_16x16x4f64(a, 4 * s + lk < K ? b : 0.0, c, 0, 0, 0);
+      };
       double4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-      for (int s = 0; s < nks; ++s) {
-        const int kk = 4 * s + lk;
-        const double b = kk < K ? Bt[kk] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Mt[(size_t)s * 64], b, acc, 0, 0, 0);
+      if constexpr (MU > 1) {
+        double am[MU], bm[MU];
+#pragma unroll
+        for (int u = 0; u < MU; ++u) load_slice(u, am[u], bm[u]);
+        int s0 = 0;
+        for (; s0 + MU <= nks; s0 += MU) {
+#pragma unroll
+          for (int u = 0; u < MU; ++u) {
+            acc = mfma_slice(s0 + u, am[u], bm[u], acc);
+            load_slice(s0 + MU + u, am[u], bm[u]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < MU - 1; ++u)  // the last nks mod MU slices (nks is uniform: scalar branches)
+          if (s0 + u < nks) acc = mfma_slice(s0 + u, am[u], bm[u], acc);
+      } else {  // (<2, 16>, no ring: one slice at a time, each MFMA behind its own loads)
+        for (int s = 0; s < nks; ++s) {
+          const int kk = 4 * s + lk;
+          const double b = kk < K ? Bt[kk] : 0.0;
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Mt[(size_t)s * 64], b, acc, 0, 0, 0);
+        }
       }
       if (TQ && tw) {
-        // column li = (local agent al, axis d); row = time step.  The row loop reads the very bits that are published.
+        // column li = (local agent al, axis d); row = time step.  The row loop reads the very bits that are published:
+        // the hand-off the partner workgroups wait for goes first, the tile writes after it.
         const int al = li / D, d = li % D;
-        const bool col_ok = li < D * APB16 && a0 + al < N;
         double* Ot = Qt + (size_t)li * RSK;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int row = tile * 16 + lk + 4 * q;
-          if (row < K) {
-            Ot[row] = acc[q];
-            if (col_ok && cptr[al * K + row + 1] > cptr[al * K + row])  // cells with rows only
-              st_granules(A.cells + ((size_t)((int64_t)row * N + a0 + al) * D + d) * 2, tag, acc[q]);
-          }
+          if ((pub_rows >> q) & 1u)  // cells with rows only
+            st_granules(A.cells + ((size_t)((int64_t)row * N + a0 + al) * D + d) * 2, tag, acc[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = tile * 16 + lk + 4 * q;
+          if (row < K) Ot[row] = acc[q];
         }
       } else {
         double* Ot = Pt + (size_t)(ct * 16 + li) * RSK;
