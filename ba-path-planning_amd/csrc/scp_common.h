@@ -51,6 +51,8 @@ struct scp_ctx {
                                   // violations pass's "not finite" word; [12, 16): `solved`)
   int timing;                     // HIP events around the pairwise kernels and the QP solves (scp_ctx_set_option; default on)
   int small_pass;                 // one-launch pairwise passes for small problems (scp_ctx_set_option; default on)
+  int fused_step_prep;            // large problems: the prep launch of a pass derives the positions it stages from the
+                                  // accelerations / the QP's solution itself (scp_ctx_set_option; default on)
   unsigned long long rel_seq;     // of the latest scp_rel_step (completion word: h_scratch[64]; partials: h_scratch[0..64))
   void* gen_ws;                   // device workspace of scp_generate_grid_swap (grown on demand)
   size_t gen_ws_bytes;
@@ -149,7 +151,15 @@ int scp_violations_from_solution(scp_ctx* ctx, int N, int K, int D, double R, do
                                  double* pos_out, double feas_tol, int64_t* new_rows, int64_t new_cap, uint32_t* sel_bitmap,
                                  scp_pair_stats* stats, const double* rel_prev /* [N][K][D] or NULL */,
                                  int64_t* spec_rows /* or NULL: + the selection around the new positions */, int64_t spec_cap,
-                                 uint32_t* spec_bitmap, double spec_margin, bool* fused);
+                                 uint32_t* spec_bitmap, double spec_margin, int* form);
+// ... *form: nothing was launched | the one-launch pass of a small problem (stats, relative-step sums and the speculative
+// selection in the mirror) | the multi-launch pass with a prep launch that derived x_out / pos_out ("fused_step_prep")
+enum { SCP_FROM_SOLUTION_NONE = 0, SCP_FROM_SOLUTION_SMALL = 1, SCP_FROM_SOLUTION_LARGE = 2 };
+// scp_kinematics(acc) -> pos_out + scp_linearize_pairs (eta_out != NULL) / scp_select_pairs at pos_out with one prep launch
+// for both, where the pass runs as several launches ("fused_step_prep"; scp_kernels.hip)
+int scp_pairs_from_acc(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end, const double* acc,
+                       const double* p0, const double* v0, double* pos_out, double* eta_out, double* l_out, double margin,
+                       int64_t* sel_rows, int64_t sel_cap, uint32_t* sel_bitmap, scp_pair_stats* stats, bool* fused);
 // scp_rel_step's numbers from the sums that pass left in the mirror (after its stats have arrived)  (scp_ctx.hip)
 void scp_ctx_mirror_rel(scp_ctx* ctx, int64_t n, double* out);
 // scp_qp_get_solution + scp_kinematics + scp_check_avoidance + scp_select_pairs of a small problem in one launch
@@ -160,6 +170,9 @@ int scp_select_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double
 // scp_kinematics + a copy of `acc` to acc_copy in the same launch (scp_traj.hip)
 int scp_launch_kinematics_copy(scp_ctx* ctx, int N, int K, int D, double h, const double* acc, const double* p0,
                                const double* v0, double* pos_out, double* vel_out, double* acc_copy);
+// scp_rel_step(a_new, a_prev) + a copy of a_new to copy_out (NULL: none) in the same launch (scp_traj.hip); copy_out must not
+// overlap a_prev
+int scp_launch_rel_step_copy(scp_ctx* ctx, int64_t n, const double* a_new, const double* a_prev, double* out, double* copy_out);
 // the QP's current iterate in its own layout ([K][N D], device pointer)
 const double* scp_qp_solution_tm(const scp_qp* qp);
 

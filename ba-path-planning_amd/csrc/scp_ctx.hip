@@ -29,6 +29,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
   ctx->stream = (hipStream_t)hip_stream;
   ctx->timing = 1;
   ctx->small_pass = getenv("SCP_NO_SMALL_PASS") ? 0 : 1;  // (developer switch; scp_ctx_set_option at run time)
+  ctx->fused_step_prep = 1;
   ctx->near_pass = 1;  // auto (scp_ctx_set_near_pass)
   if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->n_cu = 0;
   if (hipMalloc(&ctx->d_scratch, 72 * sizeof(double)) != hipSuccess ||
@@ -55,6 +56,9 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
 // the pass times read 0, solve_ms becomes the host's wall clock around the solve (the host waits for its result anyway).
 // "single_launch_passes": the one-launch form of the pairwise passes of small problems (pair_pass_kernel<.., SMALL>); 0:
 // prep kernel + pass + compaction as for large problems (same results; tests compare the two).
+// "fused_step_prep": where a pass runs as several launches, its prep launch derives the positions it stages -- from the
+// accelerations at the start of a step, from the QP's time-major solution in a round -- instead of following a layout change
+// and a kinematics launch; 0: those launches run as before (same results; tests/test_step_prep_gpu.py compares the two).
 extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   if (!ctx || !key) return SCP_ERR_INVALID;
   if (strcmp(key, "kernel_timing") == 0) {
@@ -64,6 +68,10 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   }
   if (strcmp(key, "single_launch_passes") == 0) {
     ctx->small_pass = value ? 1 : 0;
+    return SCP_OK;
+  }
+  if (strcmp(key, "fused_step_prep") == 0) {
+    ctx->fused_step_prep = value ? 1 : 0;
     return SCP_OK;
   }
   return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: unknown key '%s'", key);

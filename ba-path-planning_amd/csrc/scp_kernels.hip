@@ -96,6 +96,26 @@ struct PairArgs {
   unsigned long long seq;
 };
 
+// The per-element bodies of the prep kernels: ONE definition each for the kernels that re-stage existing position arrays
+// (pair_prep_kernel, pair_prep_delta_kernel) and for the kernel that derives the positions in the same launch
+// (pass_prep_from_acc_kernel).
+// position p of (k, c) -> time-major P and Q = P - (p0 + (k h) v0) (either output may be NULL)
+__device__ inline void prep_point(double p, const double* __restrict__ p0, const double* __restrict__ v0, int c, int k,
+                                  double h, int64_t t, double* __restrict__ P_tm, double* __restrict__ Q_tm) {
+  if (P_tm) P_tm[t] = p;
+  if (Q_tm) Q_tm[t] = p - free_motion(p0[c], v0[c], k, h);
+}
+// previous and new position of (k, c) -> time-major P_prev and dP = P_new - P_prev; a value that is not finite (or so large
+// that its square is not: SCP_NEAR_MAX_ABS) leaves this call's number in *unbounded
+__device__ inline void prep_delta(double pp, double pn, int64_t t, double* __restrict__ P_tm, double* __restrict__ dP_tm,
+                                  unsigned* __restrict__ unbounded, unsigned call_no) {
+  const double dp = pn - pp;
+  P_tm[t] = pp;
+  dP_tm[t] = dp;
+  if (!(fabs(pp) <= SCP_NEAR_MAX_ABS) || !(fabs(dp) <= SCP_NEAR_MAX_ABS))
+    __hip_atomic_store(unbounded, call_no, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // [N][K][D] -> time-major P and Q = P - (p0 + (k h) v0) (either output may be NULL); also clears the bitmap the pass
 // is about to mark (linearize), so that no memset launch is needed
 __global__ __launch_bounds__(256) void pair_prep_kernel(int N, int K, int D, double h, const double* __restrict__ pos,
@@ -111,9 +131,7 @@ __global__ __launch_bounds__(256) void pair_prep_kernel(int N, int K, int D, dou
   const int k = (int)(t / C);
   const int c = (int)(t % C);
   const int i = c / D, d = c % D;
-  const double p = pos[((int64_t)i * K + k) * D + d];
-  if (P_tm) P_tm[t] = p;
-  if (Q_tm) Q_tm[t] = p - free_motion(p0[c], v0[c], k, h);
+  prep_point(pos[((int64_t)i * K + k) * D + d], p0, v0, c, k, h, t, P_tm, Q_tm);
 }
 
 // lexicographic pairs (i, j), i < j: row i + 1 of the triangle starts at j = i + 2.
@@ -972,12 +990,63 @@ __global__ __launch_bounds__(256) void pair_prep_delta_kernel(int N, int K, int 
   const int c = (int)(t % C);
   const int i = c / D, d = c % D;
   const int64_t g = ((int64_t)i * K + k) * D + d;
-  const double pp = pos_prev[g];
-  const double dp = pos_new[g] - pp;
-  P_tm[t] = pp;
-  dP_tm[t] = dp;
-  if (!(fabs(pp) <= SCP_NEAR_MAX_ABS) || !(fabs(dp) <= SCP_NEAR_MAX_ABS))
-    __hip_atomic_store(unbounded, call_no, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  prep_delta(pos_prev[g], pos_new[g], t, P_tm, dP_tm, unbounded, call_no);
+}
+
+// The prep of a pass whose positions do not exist yet: they are the kinematics of `acc`, and ONE launch integrates them
+// (kin_point: the bits of kinematics_kernel), leaves them in the reference layout (pos_out) and stages the pass's slices.
+//   FROM_TM  (violations pass of a round): acc = the QP's solution in its own time-major layout, read with stride C; one
+//            thread per time-major element.  Replaces from_time_major_kernel (x_out), kinematics_kernel (pos_out) and
+//            pair_prep_delta_kernel (P_tm = pos_prev, Q_tm = pos_out - pos_prev, the not-finite word).
+//   !FROM_TM (linearise / select at the start of a step): acc = the linearisation point's accelerations [N][K][D]; one
+//            thread per element of that layout, as kinematics_kernel.  Replaces kinematics_kernel and pair_prep_kernel
+//            (P_tm, Q_tm or NULL, the cleared map of the REPLACE pass).
+// Either way thread 0 initialises the stats.  Element-local: no thread reads what another one writes.
+struct PrepFromAcc {
+  int N, K, D;
+  double h;
+  const double* acc;
+  const double *p0, *v0;
+  double* pos_out;
+  double *P_tm, *Q_tm;
+  scp_pair_stats* stats;
+  const double* pos_prev;  // FROM_TM: [N][K][D] the linearisation point
+  double* x_out;           //          [N][K][D] copy of acc
+  unsigned* unbounded;
+  unsigned call_no;
+  uint32_t* clear_map;     // !FROM_TM
+  int64_t clear_words;
+};
+template <bool FROM_TM>
+__global__ __launch_bounds__(256) void pass_prep_from_acc_kernel(PrepFromAcc a) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int K = a.K, D = a.D;
+  const int64_t C = (int64_t)a.N * D;
+  if (e == 0) pair_stats_init(a.stats);
+  if (!FROM_TM)
+    for (int64_t w = e; w < a.clear_words; w += (int64_t)gridDim.x * 256) a.clear_map[w] = 0u;
+  if (e >= C * K) return;
+  int i, k, d;
+  if (FROM_TM) {
+    k = (int)(e / C);
+    const int c = (int)(e % C);
+    i = c / D, d = c % D;
+  } else {
+    d = (int)(e % D);
+    k = (int)((e / D) % K);
+    i = (int)(e / ((int64_t)D * K));
+  }
+  const int c = i * D + d;
+  const int64_t g = ((int64_t)i * K + k) * D + d, t = (int64_t)k * C + c;
+  double p, v;
+  kin_point(FROM_TM ? a.acc + c : a.acc + (int64_t)i * K * D + d, FROM_TM ? C : (int64_t)D, k, a.h, a.p0[c], a.v0[c], p, v);
+  a.pos_out[g] = p;
+  if (FROM_TM) {
+    a.x_out[g] = a.acc[t];
+    prep_delta(a.pos_prev[g], p, t, a.P_tm, a.Q_tm, a.unbounded, a.call_no);
+  } else {
+    prep_point(p, a.p0, a.v0, c, k, a.h, t, a.P_tm, a.Q_tm);
+  }
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -1255,8 +1324,12 @@ static int split_linearize_items(scp_ctx* ctx, PairArgs& a, PairKernel kern, siz
 // The prep kernel of a multi-launch pass: time-major slices (a.P_tm, a.Q_tm), the stats' initial values, the cleared map of a
 // REPLACE pass.  pos, p0, v0: the pass's positions in the reference layout and the initial states; MODE_VIOL_RECOMPUTE:
 // pos = the linearisation point, p0 = the new positions (v0 unused).
+// Where the positions are still to be derived, pass_prep_from_acc_kernel does that in the same launch: a.x_tm set
+// (MODE_VIOL_RECOMPUTE: the new positions, left in a.x_out / a.pos_out; a.x_tm is cleared -- from here on the pass is the
+// plain one on those arrays), or acc_ref set (linearise / select: the positions of the accelerations acc_ref, left in
+// a.pos_out; a.p0, a.v0, a.h: the kinematics' inputs).
 static int launch_pass_prep(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
-                            const double* v0) {
+                            const double* v0, const double* acc_ref = nullptr) {
   const int N = a.N, K = a.K, D = a.D;
   ctx->last_pass_small = false;
   const size_t slice = ((size_t)N * K * D + 1) & ~(size_t)1;  // keep the second array 16-byte aligned
@@ -1268,8 +1341,19 @@ static int launch_pass_prep(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks
   const bool clear = marks.kind == PassMarks::REPLACE;
   if (mode == MODE_VIOL_RECOMPUTE) {
     if (++ctx->near_call_no == 0u) ctx->near_call_no = 1u;  // (0 is the word's initial value)
-    hipLaunchKernelGGL(pair_prep_delta_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, pos, p0, P_tm, Q_tm, a.stats,
-                       scp_near_unbounded_word(ctx), ctx->near_call_no);
+    if (a.x_tm) {
+      const PrepFromAcc f{N, K, D, a.h, a.x_tm, a.p0, a.v0, a.pos_out, P_tm, Q_tm, a.stats, pos, a.x_out,
+                          scp_near_unbounded_word(ctx), ctx->near_call_no, nullptr, 0};
+      hipLaunchKernelGGL(pass_prep_from_acc_kernel<true>, prep_grid, dim3(256), 0, ctx->stream, f);
+      a.x_tm = nullptr;
+    } else {
+      hipLaunchKernelGGL(pair_prep_delta_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, pos, p0, P_tm, Q_tm, a.stats,
+                         scp_near_unbounded_word(ctx), ctx->near_call_no);
+    }
+  } else if (acc_ref) {
+    const PrepFromAcc f{N, K, D, a.h, acc_ref, a.p0, a.v0, a.pos_out, P_tm, Q_tm, a.stats, nullptr, nullptr, nullptr, 0u,
+                        clear ? marks.bitmap : nullptr, clear ? a.words : (int64_t)0};
+    hipLaunchKernelGGL(pass_prep_from_acc_kernel<false>, prep_grid, dim3(256), 0, ctx->stream, f);
   } else {
     hipLaunchKernelGGL(pair_prep_kernel, prep_grid, dim3(256), 0, ctx->stream, N, K, D, a.h, pos, p0, v0, P_tm, Q_tm,
                        a.stats, clear ? marks.bitmap : nullptr, clear ? a.words : (int64_t)0);
@@ -1282,10 +1366,10 @@ static int launch_pass_prep(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks
 
 // The pass of a large problem: the prep kernel, then the pass kernel; the compaction follows in pair_pass.
 static int launch_large_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
-                             const double* v0) {
+                             const double* v0, const double* acc_ref) {
   const int N = a.N, K = a.K, D = a.D;
   const int64_t nq = a.q_end - a.q_begin;
-  const int rc_prep = launch_pass_prep(ctx, mode, a, marks, pos, p0, v0);
+  const int rc_prep = launch_pass_prep(ctx, mode, a, marks, pos, p0, v0, acc_ref);
   if (rc_prep) return rc_prep;
   if (nq <= 0) return SCP_OK;
   const size_t slice_bytes = (size_t)N * D * sizeof(double);
@@ -1306,9 +1390,11 @@ static int launch_large_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMark
 }
 
 // Every pairwise pass: as one launch when the problem is small and the mode has that form (ctx->last_pass_small tells),
-// otherwise prep kernel, pass kernel and the compaction of its marks.
+// otherwise prep kernel, pass kernel and the compaction of its marks.  acc_ref: a large linearise / select pass whose
+// positions the prep kernel derives itself (launch_pass_prep); a.x_tm of a large violations pass likewise -- its first prep
+// launch leaves the new positions in a.pos_out, which is what a second one (the exhaustive pass after the near form) stages.
 static int pair_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks, const double* pos, const double* p0,
-                     const double* v0) {
+                     const double* v0, const double* acc_ref = nullptr) {
   if (marks.kind != PassMarks::NONE) {
     const int rc = ensure_cmp(ctx, a.words);
     if (rc) return rc;
@@ -1319,13 +1405,15 @@ static int pair_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks
   const char* abl = getenv("SCP_PAIR_ABLATE");
   a.ablate = abl ? atoi(abl) : 0;
 #endif
-  const bool small = pair_mode_has_small(mode) && small_pass_ok(ctx, a.N, a.K, a.D, a.q_end - a.q_begin, small_pass_slices(mode, a));
+  const bool small = !acc_ref && pair_mode_has_small(mode) &&
+                     small_pass_ok(ctx, a.N, a.K, a.D, a.q_end - a.q_begin, small_pass_slices(mode, a));
+  if (mode == MODE_VIOL_RECOMPUTE && a.x_tm) p0 = a.pos_out;  // (the new positions, once a prep launch has derived them)
   // The near form of the recomputing violations pass (scp_near.hip): only the pairs close enough to be violated.  Its
   // result is the exhaustive pass's, bit for bit, as long as some examined row is close to active; the stats the caller is
   // about to read anyway tell (the unexamined rows lie below -SCP_NEAR_TAU), and otherwise the exhaustive pass runs after
   // all -- from an untouched working set: every examined row was negative, nothing was marked.
   size_t near_lds = 0;
-  if (mode == MODE_VIOL_RECOMPUTE && marks.kind == PassMarks::MERGE && !a.x_tm && ctx->near_pass != 0 &&
+  if (mode == MODE_VIOL_RECOMPUTE && marks.kind == PassMarks::MERGE && ctx->near_pass != 0 &&
       (!small || ctx->near_pass == 2) && a.q_end > a.q_begin && a.margin >= 0.0 && a.R > 0.0 && scp_near_fits(a.N, a.D, &near_lds)) {
     int rc = launch_pass_prep(ctx, mode, a, marks, pos, p0, v0);
     if (rc) return rc;
@@ -1345,7 +1433,7 @@ static int pair_pass(scp_ctx* ctx, int mode, PairArgs& a, const PassMarks& marks
   } else if (small) {
     return launch_small_pass(ctx, mode, a, marks, pos, p0);
   }
-  const int rc = launch_large_pass(ctx, mode, a, marks, pos, p0, v0);
+  const int rc = launch_large_pass(ctx, mode, a, marks, pos, p0, v0, acc_ref);
   if (rc || marks.kind == PassMarks::NONE) return rc;
   // (the marks of a MERGE pass are the bits of the scratch map; merging them into the working-set bitmap also clears it)
   return launch_compaction(ctx, a.mark, a.words, a.q_end - a.q_begin, a.q_begin, a.pairs, marks.rows, marks.cap,
@@ -1462,31 +1550,66 @@ extern "C" int scp_collision_violations_at(scp_ctx* ctx, int N, int K, int D, do
 
 // internal (scp_common.h): scp_qp_get_solution + scp_kinematics + scp_collision_violations_at of a SMALL problem in ONE
 // launch -- the pass derives the new positions from the QP's time-major solution x_tm itself and leaves them (pos_out) and
-// the solution in the reference layout (x_out) behind; bit-identical to the three calls.  *fused = false: not a small
-// problem, nothing was launched.
+// the solution in the reference layout (x_out) behind; bit-identical to the three calls.  *form = SCP_FROM_SOLUTION_SMALL.
+// A LARGE problem (or the forced near form) with the ctx's "fused_step_prep" on: the same three calls' results from the
+// prep launch of the multi-launch pass (pass_prep_from_acc_kernel<true>), near form and its exhaustive fall-back included;
+// x_out and pos_out exist afterwards, but no relative-step sums and no speculative selection:
+// *form = SCP_FROM_SOLUTION_LARGE.  *form = SCP_FROM_SOLUTION_NONE: nothing was launched.
 int scp_violations_from_solution(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end,
                                  const double* pos_prev, const double* x_tm, const double* p0, const double* v0, double* x_out,
                                  double* pos_out, double feas_tol, int64_t* new_rows, int64_t new_cap, uint32_t* sel_bitmap,
                                  scp_pair_stats* stats, const double* rel_prev, int64_t* spec_rows, int64_t spec_cap,
-                                 uint32_t* spec_bitmap, double spec_margin, bool* fused) {
-  *fused = false;
+                                 uint32_t* spec_bitmap, double spec_margin, int* form) {
+  *form = SCP_FROM_SOLUTION_NONE;
   int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
   if (rc) return rc;
   const int64_t nq = q_end - q_begin;
-  if (ctx->near_pass == 2) return SCP_OK;  // (forced near form: the caller's three calls reach it)
-  if (!small_pass_ok(ctx, N, K, D, nq, 2)) return SCP_OK;
-  if (!spec_bitmap || !small_pass_ok(ctx, N, K, D, nq, 3)) spec_rows = nullptr;  // (no LDS for the third slice: no speculation)
+  // (forced near form: the multi-launch pass reaches it)
+  const bool small = ctx->near_pass != 2 && small_pass_ok(ctx, N, K, D, nq, 2);
+  if (!small && (!ctx->fused_step_prep || nq <= 0)) return SCP_OK;
   PairArgs a = pair_args(N, K, D, R, h, q_begin, q_end, stats);
   a.margin = feas_tol;
   a.x_tm = x_tm; a.p0 = p0; a.v0 = v0; a.x_out = x_out; a.pos_out = pos_out;
+  if (!small) {
+    rc = pair_pass(ctx, MODE_VIOL_RECOMPUTE, a, {PassMarks::MERGE, new_rows, new_cap, sel_bitmap}, pos_prev, nullptr, nullptr);
+    if (rc) return rc;
+    *form = SCP_FROM_SOLUTION_LARGE;
+    return SCP_OK;
+  }
+  if (!spec_bitmap || !small_pass_ok(ctx, N, K, D, nq, 3)) spec_rows = nullptr;  // (no LDS for the third slice: no speculation)
   a.rel_prev = rel_prev;
   a.rel_blocks = rel_step_blocks((int64_t)N * K * D);
   a.spec_rows = spec_rows; a.spec_cap = spec_cap; a.spec_bitmap = spec_bitmap; a.spec_margin = spec_margin;
   rc = pair_pass(ctx, MODE_VIOL_RECOMPUTE, a, {PassMarks::MERGE, new_rows, new_cap, sel_bitmap}, pos_prev, nullptr, nullptr);
   if (rc) return rc;
   if (!ctx->last_pass_small) return scp_fail(ctx, SCP_ERR_STATE, "violations_from_solution: the small-problem pass did not run");
-  *fused = true;
+  *form = SCP_FROM_SOLUTION_SMALL;
   return SCP_OK;
+}
+
+// internal (scp_common.h): scp_kinematics(acc) -> pos_out followed by scp_linearize_pairs (eta_out != NULL) or
+// scp_select_pairs (eta_out == NULL) at pos_out, for a pass that runs as several launches: the prep launch integrates the
+// positions itself (pass_prep_from_acc_kernel<false>) instead of re-staging an array the launch before it wrote.
+// Bit-identical to the two calls.  *fused = false: nothing was launched (the ctx's "fused_step_prep" is off, the pair range
+// is empty, or the pass has a one-launch form at this size) -- the caller makes the two calls.
+int scp_pairs_from_acc(scp_ctx* ctx, int N, int K, int D, double R, double h, int64_t q_begin, int64_t q_end, const double* acc,
+                       const double* p0, const double* v0, double* pos_out, double* eta_out, double* l_out, double margin,
+                       int64_t* sel_rows, int64_t sel_cap, uint32_t* sel_bitmap, scp_pair_stats* stats, bool* fused) {
+  *fused = false;
+  const int rc = scp_check_pair_range(ctx, N, K, D, q_begin, q_end);
+  if (rc) return rc;
+  const int mode = eta_out ? MODE_LINEARIZE : MODE_SELECT;
+  if (!ctx->fused_step_prep || q_end <= q_begin) return SCP_OK;
+  if (pair_mode_has_small(mode) && small_pass_ok(ctx, N, K, D, q_end - q_begin, 1)) return SCP_OK;
+  SCP_REQUIRE(ctx, acc && p0 && v0 && pos_out && sel_bitmap && stats && (sel_rows || sel_cap == 0) && (!eta_out || l_out),
+              "pairs_from_acc: null pointer");
+  SCP_REQUIRE(ctx, ((uintptr_t)eta_out % 16 == 0) && ((uintptr_t)l_out % 16 == 0), "pairs_from_acc: eta/l must be 16-byte aligned");
+  PairArgs a = pair_args(N, K, D, R, h, q_begin, q_end, stats);
+  a.eta = eta_out; a.l = l_out; a.margin = margin;
+  a.p0 = p0; a.v0 = v0; a.pos_out = pos_out;
+  *fused = true;
+  return pair_pass(ctx, mode, a, {PassMarks::REPLACE, sel_rows, sel_cap, sel_bitmap}, pos_out, eta_out ? p0 : nullptr,
+                   eta_out ? v0 : nullptr, acc);
 }
 
 // internal (scp_common.h): scp_qp_get_solution + scp_kinematics + scp_check_avoidance + scp_select_pairs of a SMALL problem

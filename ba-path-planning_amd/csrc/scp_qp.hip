@@ -42,6 +42,17 @@ __global__ __launch_bounds__(256) void qp_reset_kernel(int N, int K, int D, int 
   qp_reset_body<false>(threadIdx.x, true, reset_xs, N, K, D, Rf, x0, F, S0, x, zf, fx, Qx, yf);
 }
 
+// ... and the same outputs from a (column tile) x (row slab) grid that fills the chip (scp_reset_device.h): the reset's
+// default form wherever its LDS tile fits ("reset_form" of scp_qp_debug_set: 0 = the kernel above)
+__global__ __launch_bounds__(256) void qp_reset_tiled_kernel(int N, int K, int D, int Rf, const double* __restrict__ x0,
+                                                              const double* __restrict__ F, const double* __restrict__ S0,
+                                                              double* __restrict__ x, double* __restrict__ zf,
+                                                              double* __restrict__ fx, double* __restrict__ Qx,
+                                                              double* __restrict__ yf) {
+  extern __shared__ double reset_tile[];  // [K][RESET_TILE] x tile | [RESET_SLAB][K] rows of F | S0
+  qp_reset_tiled_body(reset_tile, N, K, D, Rf, x0, F, S0, x, zf, fx, Qx, yf);
+}
+
 // ----------------------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------------------
@@ -200,6 +211,7 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
   qp->steps_since_reset = 0;
   memset(qp->lim, 0, sizeof(qp->lim));
   qp->persist_fault = 0;
+  qp->reset_form = 1;
   {  // (the environment sets the hook's starting value: the QP objects inside scp_solver have no handle of their own)
     const char* e = getenv("SCP_PERSIST_HOST_LISTS");
     qp->persist_host_lists = e && atoi(e) != 0;
@@ -317,9 +329,15 @@ static int reset_impl(scp_qp* qp, const double* x0, int64_t n, const int64_t* ro
     // (the install launch did the reset too)
   } else if (one_launch) {
     // z = A x (primal warm start, scp.py:443), y = 0 and the single-step pipeline's carried F x, S0 x in one launch
-    QP_CHECK(qp_launch(qp, qp_reset_kernel, dim3(scp_cdiv(qp->C, RESET_COLS)), dim3(256),
-                       (size_t)qp->K * RESET_COLS * sizeof(double), qp->N, qp->K, qp->D, qp->Rf, x0, d.F, d.S0, d.x, d.zf, d.fx,
-                       d.HQ + nx, d.yf));
+    const size_t tiled_lds = qp_reset_tiled_lds_bytes(qp->K);
+    if (qp->reset_form == 1 && tiled_lds <= 64 * 1024)
+      QP_CHECK(qp_launch(qp, qp_reset_tiled_kernel,
+                         dim3((unsigned)scp_cdiv(qp->C, RESET_TILE), (unsigned)scp_cdiv(qp->Rf + qp->K, RESET_SLAB)), dim3(256),
+                         tiled_lds, qp->N, qp->K, qp->D, qp->Rf, x0, d.F, d.S0, d.x, d.zf, d.fx, d.HQ + nx, d.yf));
+    else
+      QP_CHECK(qp_launch(qp, qp_reset_kernel, dim3(scp_cdiv(qp->C, RESET_COLS)), dim3(256),
+                         (size_t)qp->K * RESET_COLS * sizeof(double), qp->N, qp->K, qp->D, qp->Rf, x0, d.F, d.S0, d.x, d.zf,
+                         d.fx, d.HQ + nx, d.yf));
   } else {
     if (x0) QP_CHECK(scp_launch_to_time_major(ctx, qp->N, qp->K, qp->D, x0, d.x));
     else SCP_HIP_CHECK(ctx, hipMemsetAsync(d.x, 0, nx * sizeof(double), ctx->stream));
@@ -703,7 +721,8 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
 // the give-up path); "persist_off" reads (value < 0) or sets whether the solver has fallen back to the three-launch
 // pipeline; "persist_host_lists" = 1: the host builds the incidence lists and the row values before every persistent launch
 // and the kernel loads its slice of them, instead of building its own tables (SCP_PERSIST_HOST_LISTS=1 in the environment:
-// every QP object starts with it set).  Returns the value in effect, or SCP_ERR_INVALID.
+// every QP object starts with it set); "reset_form" = 0: scp_qp_reset's one-launch form runs as the 16-column kernel
+// (qp_reset_kernel), 1 (default): as the tiled kernel where its LDS fits.  Returns the value in effect, or SCP_ERR_INVALID.
 extern "C" int scp_qp_debug_set(scp_qp* qp, const char* key, int value) {
   if (!qp || !key) return SCP_ERR_INVALID;
   if (!strcmp(key, "persist_fault")) {
@@ -713,6 +732,10 @@ extern "C" int scp_qp_debug_set(scp_qp* qp, const char* key, int value) {
   if (!strcmp(key, "persist_host_lists")) {
     if (value >= 0) qp->persist_host_lists = value != 0;
     return qp->persist_host_lists ? 1 : 0;
+  }
+  if (!strcmp(key, "reset_form")) {
+    if (value >= 0) qp->reset_form = value != 0 ? 1 : 0;
+    return qp->reset_form;
   }
   if (!strcmp(key, "persist_off")) {
     if (value >= 0) qp->persist_off = value != 0;

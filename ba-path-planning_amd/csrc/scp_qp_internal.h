@@ -128,6 +128,7 @@ struct scp_qp {
   int persist_variant;               // of the latest persistent launch: 0 = 8 (4 in 3-D) agents per workgroup, 1 = lean, 16
   int persist_fault;                 // test hook: the next n persistent launches wait for a workgroup that does not exist
   bool persist_host_lists;           // test hook: the host builds lists and row values for every persistent launch
+  int reset_form;                    // scp_qp_reset's one-launch kernel: 1 = tiled over the whole chip (default), 0 = 16-column
   bool persist_off;                  // a launch gave up (workgroups not co-resident): three-launch pipeline until the next
                                      // scp_qp_reset / scp_qp_set_problem re-arms the persistent path
   bool persist_skip_solve;           // the CUs for a persistent launch were not free: this scp_qp_solve call stays on the

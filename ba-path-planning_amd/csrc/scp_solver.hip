@@ -73,6 +73,8 @@ struct scp_solver {
   int64_t* sel2;        // the speculative selection's list and bitmap (allocated on first use, swapped in when accepted)
   int64_t sel2_cap;
   uint32_t* bitmap2;
+  bool pos_pending;  // a step has begun and s->pos_a (the positions of its acc_in) is still to be computed: step_linearize does
+                     // it, inside the prep launch of its pass where that pass runs as several launches
   double rho_start;  // > 0: the joint QP of the next step starts at this rho (options.carry_rho), else at settings.rho
   struct StepState* step;  // the SCP iteration in flight (phases of solve_joint_qp / of the sharded entry points)
 };
@@ -192,7 +194,8 @@ struct StepGuard {  // (for the callers that run all phases inside one function)
 };
 
 // phase 1 -- _add_collision_constraints (scp.py:453-557) over the pair range [q_begin, q_end): linearise around `acc_in`,
-// whose positions the caller holds in s->pos_a; the selected rows are s->sel[0, *n_sel) (global ids, ascending)
+// whose positions the caller holds in s->pos_a (s->pos_pending: they are computed here, by the pass's own prep launch where
+// it has one); the selected rows are s->sel[0, *n_sel) (global ids, ascending)
 int step_linearize(scp_solver* s, StepState& t, const double* acc_in, const double* limits, const double* space,
                    const double* p0, const double* v0, const double* pf, const double* vf, const scp_solve_options* o,
                    double eps, int64_t q_begin, int64_t q_end, scp_qp_record* rec, int64_t* n_sel) {
@@ -215,17 +218,28 @@ int step_linearize(scp_solver* s, StepState& t, const double* acc_in, const doub
   if (!t.row_free) SV_CHECK(ensure_row_planes(s));
   const bool spec = s->spec_valid && t.row_free && q_begin == 0 && q_end == s->pairs && s->spec_margin == o->working_set_margin;
   s->spec_valid = false;
+  bool enqueued = false;  // the pass is in the stream already: the kinematics and its prep were one launch (large problems)
+  if (s->pos_pending) {
+    s->pos_pending = false;
+    if (!spec)
+      SV_CHECK(scp_pairs_from_acc(ctx, N, K, D, s->R, s->h, q_begin, q_end, acc_in, p0, v0, s->pos_a,
+                                  t.row_free ? nullptr : s->eta, t.row_free ? nullptr : s->l, o->working_set_margin, s->sel,
+                                  s->sel_cap, s->bitmap, s->stats, &enqueued));
+    if (!enqueued) SV_CHECK(scp_kinematics(ctx, N, K, D, s->h, acc_in, p0, v0, s->pos_a, nullptr));
+  }
   if (spec) {  // (the pass that produced s->pos_a also selected around it: same list, same bitmap)
     *n_sel = s->spec_n;
     return SCP_OK;
   }
-  for (;;) {
-    if (t.row_free)
+  for (;; enqueued = false) {  // (a repeat with a longer list finds s->pos_a in place and makes the public call)
+    if (enqueued) {
+    } else if (t.row_free) {
       SV_CHECK(scp_select_pairs(ctx, N, K, D, s->R, q_begin, q_end, s->pos_a, o->working_set_margin, s->sel, s->sel_cap,
                                 s->bitmap, s->stats));
-    else
+    } else {
       SV_CHECK(scp_linearize_pairs(ctx, N, K, D, s->R, s->h, q_begin, q_end, s->pos_a, p0, v0, s->eta, s->l,
                                    o->working_set_margin, s->sel, s->sel_cap, s->bitmap, s->stats));
+    }
     if (q_end <= q_begin) {  // an empty shard: nothing ran, nothing was published
       *n_sel = 0;
       return SCP_OK;
@@ -298,7 +312,7 @@ int step_violations(scp_solver* s, StepState& t, int64_t* n_new) {
   }
   for (;;) {
     if (t.solution_pending) {
-      bool fused = false;
+      int form = SCP_FROM_SOLUTION_NONE;
       const bool spec = s->want_spec && t.row_free && t.q_begin == 0 && t.q_end == s->pairs;
       if (spec && !s->sel2) {  // (first use: the second list / bitmap of the speculative selection)
         const size_t words = (size_t)std::max<int64_t>((s->rows + 31) / 32, 1);
@@ -309,9 +323,15 @@ int step_violations(scp_solver* s, StepState& t, int64_t* n_new) {
       SV_CHECK(scp_violations_from_solution(ctx, s->N, s->K, s->D, s->R, s->h, t.q_begin, t.q_end, s->pos_a,
                                             scp_qp_solution_tm(s->qp), t.p0, t.v0, s->x, s->pos_b, t.o.feasibility_tol,
                                             s->sel, s->sel_cap, s->bitmap, s->stats, t.acc_in, spec ? s->sel2 : nullptr,
-                                            s->sel2_cap, s->bitmap2, t.o.working_set_margin, &fused));
+                                            s->sel2_cap, s->bitmap2, t.o.working_set_margin, &form));
       t.solution_pending = false;  // (s->x and s->pos_b exist from here on, also for a repeat with a longer list)
-      if (fused) {
+      if (form == SCP_FROM_SOLUTION_LARGE) {  // (the multi-launch pass, s->x / s->pos_b from its prep launch: stats only)
+        SV_CHECK(read_stats(s, true));
+        if ((int64_t)s->h_stats->n_selected <= s->sel_cap) break;
+        SV_CHECK(grow_sel(s, (int64_t)s->h_stats->n_selected));
+        continue;
+      }
+      if (form == SCP_FROM_SOLUTION_SMALL) {
         SV_CHECK(read_stats(s, true));
         scp_ctx_mirror_rel(ctx, (int64_t)s->N * s->K * s->D, t.rel);
         t.rel_ready = true;
@@ -385,6 +405,13 @@ int solve_joint_qp(scp_solver* s, const double* acc_in, const double* limits, co
   }
   step_finish(s, t, rec);
   return SCP_OK;
+}
+
+// the end of a step: rel = scp_rel_step(s->x, acc_in), and s->x handed out in acc_out by the SAME launch -- the kernel reads
+// every element of s->x anyway, and the host's wait for its sums is the step's last wait (no copy launch, no stream drain:
+// acc_out is ordered on the ctx stream like any kernel's output)
+int rel_step_out(scp_solver* s, const double* acc_in, double* acc_out, double* rel) {
+  return scp_launch_rel_step_copy(s->ctx, (int64_t)s->N * s->K * s->D, s->x, acc_in, rel, acc_out);
 }
 
 }  // namespace
@@ -480,6 +507,7 @@ extern "C" int scp_solver_solve(scp_solver* s, const double* limits, const doubl
   const double t_start = now_s();
   s->spec_valid = false;
   s->want_spec = true;
+  s->pos_pending = false;
 
   // a2 + a3: bounds, QP#0 (scp.py:137-138, :323-369)
   SV_CHECK(scp_qp_set_problem(s->qp, limits, space, p0, v0, pf, vf));
@@ -615,14 +643,17 @@ extern "C" int scp_solver_step(scp_solver* s, const double* limits, const double
   s->spec_valid = false;
   s->want_spec = false;
   SV_CHECK(scp_qp_set_problem(s->qp, limits, space, p0, v0, pf, vf));
-  SV_CHECK(scp_kinematics(ctx, N, K, D, s->h, acc_in, p0, v0, s->pos_a, nullptr));
+  s->pos_pending = true;  // (s->pos_a = the positions of acc_in: step_linearize)
   SV_CHECK(solve_joint_qp(s, acc_in, limits, space, p0, v0, pf, vf, o, 0.0, rec));
   double rel[3];
-  if (s->step->rel_ready) memcpy(rel, s->step->rel, sizeof(rel));
-  else SV_CHECK(scp_rel_step(ctx, (int64_t)N * K * D, s->x, acc_in, rel));  // scp.py:157-159
+  if (s->step->rel_ready) {  // (left behind by the last violations pass: small problems)
+    memcpy(rel, s->step->rel, sizeof(rel));
+    SV_HIP(hipMemcpyAsync(acc_out, s->x, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
+    SV_HIP(hipStreamSynchronize(ctx->stream));
+  } else {
+    SV_CHECK(rel_step_out(s, acc_in, acc_out, rel));  // scp.py:157-159
+  }
   rec->rel_step = rel[2];
-  SV_HIP(hipMemcpyAsync(acc_out, s->x, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
   rec->time_sec = now_s() - t0;
   return SCP_OK;
 }
@@ -661,8 +692,7 @@ extern "C" int scp_solver_shard_begin(scp_solver* s, const double* limits, const
   SV_CHECK(scp_qp_set_problem(s->qp, limits, space, p0, v0, pf, vf));
   if (pos_in)
     SV_HIP(hipMemcpyAsync(s->pos_a, pos_in, (size_t)N * K * D * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  else
-    SV_CHECK(scp_kinematics(ctx, N, K, D, s->h, acc_in, p0, v0, s->pos_a, nullptr));
+  s->pos_pending = !pos_in;  // (NULL: s->pos_a = the positions of acc_in, computed by step_linearize)
   int64_t n = 0;
   int rc = step_linearize(s, t, acc_in, limits, space, p0, v0, pf, vf, o, 0.0, q_begin, q_end, rec, &n);
   memcpy(t.lim_copy, lim, sizeof(lim));  // (step_linearize re-initialised the state)
@@ -728,14 +758,11 @@ extern "C" int scp_solver_shard_end(scp_solver* s, double* acc_out, scp_qp_recor
   if (!t.active) return scp_fail(ctx, SCP_ERR_STATE, "solver_shard_end: no step in flight");
   SCP_REQUIRE(ctx, acc_out && rec, "solver_shard_end: null pointer");
   StepGuard guard{s, t};
-  const size_t nbytes = (size_t)s->N * s->K * s->D * sizeof(double);
   double rel[3];
-  SV_CHECK(scp_rel_step(ctx, (int64_t)s->N * s->K * s->D, s->x, t.acc_in, rel));  // scp.py:157-159
+  SV_CHECK(rel_step_out(s, t.acc_in, acc_out, rel));  // scp.py:157-159
   const double t0 = t.t0;
   step_finish(s, t, rec);
   rec->rel_step = rel[2];
-  SV_HIP(hipMemcpyAsync(acc_out, s->x, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
-  SV_HIP(hipStreamSynchronize(ctx->stream));
   rec->time_sec = now_s() - t0;
   return SCP_OK;
 }

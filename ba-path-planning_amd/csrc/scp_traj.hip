@@ -231,17 +231,37 @@ int scp_launch_bounds_time_major(scp_ctx* ctx, int N, int K, int D, double h, co
 // ----------------------------------------------------------------------------------------------------
 // partial[2 b], partial[2 b + 1] = block b's sums; the partials live in mapped host memory and the LAST block to finish
 // (a ticket counter in device memory, at most 32 tickets) raises the completion word, so the host needs neither a copy
-// launch nor a stream drain to read them.
+// launch nor a stream drain to read them.  copy_out (or NULL): a[] is also handed out there, as kinematics_kernel hands out
+// its accelerations -- the loop visits every element anyway, and the step's result needs no copy launch of its own.
 __global__ __launch_bounds__(256) void rel_step_partial_kernel(int64_t n, const double* __restrict__ a,
                                                                 const double* __restrict__ b,
+                                                                double* __restrict__ copy_out,
                                                                 double* __restrict__ partial,
                                                                 unsigned* __restrict__ ticket,
                                                                 unsigned long long* __restrict__ done,
                                                                 unsigned long long seq) {
   __shared__ double s0[4], s1[4];
   double d2 = 0.0, b2 = 0.0;
-  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
-    rel_accum(a[t], b[t], d2, b2);
+  // (four elements' loads in flight before the first is used; the sums take them in the order of the plain loop)
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (; t + 3 * stride < n; t += 4 * stride) {
+    double av[4], bv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      av[u] = a[t + u * stride];
+      bv[u] = b[t + u * stride];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (copy_out) copy_out[t + u * stride] = av[u];
+      rel_accum(av[u], bv[u], d2, b2);
+    }
+  }
+  for (; t < n; t += stride) {
+    const double at = a[t];
+    if (copy_out) copy_out[t] = at;
+    rel_accum(at, b[t], d2, b2);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -268,13 +288,13 @@ __global__ __launch_bounds__(256) void rel_step_partial_kernel(int64_t n, const 
   }
 }
 
-extern "C" int scp_rel_step(scp_ctx* ctx, int64_t n, const double* a_new, const double* a_prev, double* out) {
-  if (!ctx) return SCP_ERR_INVALID;
-  SCP_REQUIRE(ctx, n > 0 && a_new && a_prev && out, "rel_step: bad arguments");
+// scp_rel_step + a copy of a_new to copy_out (or NULL: none) in the same launch (scp_common.h).  The copy is stream-ordered
+// like any kernel's output; the host's wait below returns once every workgroup has drawn its ticket.
+int scp_launch_rel_step_copy(scp_ctx* ctx, int64_t n, const double* a_new, const double* a_prev, double* out, double* copy_out) {
   const int blocks = rel_step_blocks(n);
   // the (at most 64) partial sums go straight to the mapped host scratch: no copy launch
   const unsigned long long seq = ++ctx->rel_seq;
-  hipLaunchKernelGGL(rel_step_partial_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n, a_new, a_prev,
+  hipLaunchKernelGGL(rel_step_partial_kernel, dim3(blocks), dim3(256), 0, ctx->stream, n, a_new, a_prev, copy_out,
                      ctx->h_scratch_dev, (unsigned*)(ctx->d_scratch + 64), (unsigned long long*)(ctx->h_scratch_dev + 64), seq);
   SCP_HIP_CHECK(ctx, hipGetLastError());
   {
@@ -291,4 +311,10 @@ extern "C" int scp_rel_step(scp_ctx* ctx, int64_t n, const double* a_new, const 
   out[1] = std::sqrt(b2);
   out[2] = out[0] / out[1];
   return SCP_OK;
+}
+
+extern "C" int scp_rel_step(scp_ctx* ctx, int64_t n, const double* a_new, const double* a_prev, double* out) {
+  if (!ctx) return SCP_ERR_INVALID;
+  SCP_REQUIRE(ctx, n > 0 && a_new && a_prev && out, "rel_step: bad arguments");
+  return scp_launch_rel_step_copy(ctx, n, a_new, a_prev, out, nullptr);
 }

@@ -362,7 +362,8 @@ class Context:
     def set_option(self, key, value):
         """scp_ctx_set_option: "kernel_timing" (HIP events around the pairwise kernels and QP solves; 0 saves ~25 queue packets
         per complete solve, the kernel times in the records then read 0 and solve_ms is host wall clock),
-        "single_launch_passes" (one-launch pairwise passes for small problems)"""
+        "single_launch_passes" (one-launch pairwise passes for small problems), "fused_step_prep" (large problems: the prep
+        launch of a pass derives the positions it stages itself; results never depend on it)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True

@@ -150,7 +150,10 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     (compute-trajectories-batch), where every packet of a stream costs dispatch latency.
  *   "single_launch_passes" (default 1): pairwise passes of small problems (<= 2 M collision rows) run as ONE launch -- staging
  *     from the [N][K][D] arrays, reduction, sorted row list and host-visible stats in the pass kernel's last workgroup.
- *     0: prep kernel + pass + compaction launches as for large problems. */
+ *     0: prep kernel + pass + compaction launches as for large problems.
+ *   "fused_step_prep" (default 1): where a pass runs as several launches, its prep launch derives the positions it stages --
+ *     from acc_in at the start of scp_solver_step, from the QP's time-major solution in every round -- instead of following
+ *     a layout change and a kinematics launch.  0: those launches run separately. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -418,7 +421,8 @@ int scp_solver_solve(scp_solver* s, const double* limits, const double* space, c
 /* ONE SCP iteration (the loop body scp.py:152-166 without the convergence decision): linearise around acc_in, joint QP with
  * exact constraint generation, relative step -> *rec [host] (rel_step, time_sec, linearize_ms ... filled), acc_out = the new
  * accelerations ([N][K][D] device, may alias nothing).  Same calls in the same order as one pass of scp_solver_solve's loop;
- * bench.py times this call.  Synchronises the stream before returning. */
+ * bench.py times this call.  The host waits for the relative step; acc_out is written by that kernel and is ordered on the
+ * ctx stream like any kernel's output (small problems, whose last pass computes the relative step, copy and drain). */
 int scp_solver_step(scp_solver* s, const double* limits, const double* space, const double* p0, const double* v0,
                     const double* pf, const double* vf, const scp_solve_options* o, const double* acc_in, double* acc_out,
                     scp_qp_record* rec);
@@ -590,7 +594,9 @@ int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t cap, int64_t*
  * (value < 0) or set whether the solver has fallen back; "persist_host_lists" = 1: the host builds the incidence lists and
  * the row values before every persistent launch and the kernel loads its slice, instead of building its own entry tables
  * (tests/test_persist_lists_gpu.py; the QP objects inside scp_solver take the starting value from SCP_PERSIST_HOST_LISTS
- * in the environment).  Returns the value in effect. */
+ * in the environment); "reset_form": 1 (default) = scp_qp_reset's one-launch form runs as the tiled kernel that fills the
+ * chip wherever its LDS tile fits, 0 = as the 16-column kernel (same bits; tests/test_reset_forms_gpu.py).  Returns the
+ * value in effect. */
 int scp_qp_debug_set(scp_qp* qp, const char* key, int value);
 
 #ifdef __cplusplus

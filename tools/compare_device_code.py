@@ -128,6 +128,14 @@ def main():
               f"{'same' if same_m else 'DIFFERENT ' + str(bm)} |")
     extra = sorted(set(B) - set(P))
     print(f"\nonly in the branch: {', '.join('`' + dm[n] + '`' for n in extra) if extra else 'none'}")
+    kernels = [n for n in extra if B[n][3] is not None]
+    if kernels:  # the resources of the kernels the branch adds
+        print("\n| new kernel | file | instr. | VGPR | SGPR | scratch B | LDS B | spills s/v |")
+        print("|---|---|---|---|---|---|---|---|")
+        for n in kernels:
+            bf, _, bn, bm = B[n]
+            print(f"| `{dm[n]}` | {bf} | {bn} | {bm['vgpr']} | {bm['sgpr']} | {bm['scratch']} | {bm['lds']} | "
+                  f"{bm['sgpr_spill']}/{bm['vgpr_spill']} |")
     print(f"\n{len(P)} parent functions compared, {bad} differences")
     return 1 if bad else 0
 
