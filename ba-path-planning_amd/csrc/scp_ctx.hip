@@ -47,6 +47,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
     return SCP_ERR_HIP;
   }
   ctx->solved = (unsigned long long*)(ctx->d_ticket + 12);  // the last 16 of its 64 bytes
+  ctx->delay_solved = (unsigned long long*)(ctx->d_ticket + 10);  // the 8 before them
   *out = ctx;
   return SCP_OK;
 }
@@ -59,6 +60,8 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
 // "fused_step_prep": where a pass runs as several launches, its prep launch derives the positions it stages -- from the
 // accelerations at the start of a step, from the QP's time-major solution in a round -- instead of following a layout change
 // and a kinematics launch; 0: those launches run as before (same results; tests/test_step_prep_gpu.py compares the two).
+// "delay_lag_chunk" / "delay_time_chunk": lags / global segments per workgroup of scp_delay_margins; 0 (default): the call
+// chooses (same results; tests/test_delay_gpu.py compares forced chunks with the call's own).
 extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   if (!ctx || !key) return SCP_ERR_INVALID;
   if (strcmp(key, "kernel_timing") == 0) {
@@ -72,6 +75,11 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   }
   if (strcmp(key, "fused_step_prep") == 0) {
     ctx->fused_step_prep = value ? 1 : 0;
+    return SCP_OK;
+  }
+  if (strcmp(key, "delay_lag_chunk") == 0 || strcmp(key, "delay_time_chunk") == 0) {
+    if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
+    (key[6] == 'l' ? ctx->delay_lag_chunk : ctx->delay_time_chunk) = value;
     return SCP_OK;
   }
   return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: unknown key '%s'", key);

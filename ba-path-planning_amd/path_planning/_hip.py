@@ -166,6 +166,18 @@ CLEARANCE_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("r
                             ("sample_min_dist", np.float64), ("n_violating", np.uint64), ("reserved", np.uint64)])
 
 
+class DelayMargin(C.Structure):
+    """struct scp_delay_margin (scp_delay_margins): the closest approach of one vehicle started s steps late"""
+    _fields_ = [("min_dist", C.c_double), ("t_min", C.c_double), ("partner", C.c_uint32), ("segment", C.c_uint32),
+                ("n_violating", C.c_uint64)]
+
+
+DELAY_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("partner", np.uint32), ("segment", np.uint32),
+                        ("n_violating", np.uint64)])
+
+NO_INDEX = 2**32 - 1  # UINT32_MAX: "none" in the partner / segment of a delay margin
+
+
 class AssignStats(C.Structure):
     """struct scp_assign_stats (scp_assign_goals; one per scenario, a DEVICE array)"""
     _fields_ = [("cost_q", C.c_int64), ("cost_q_identity", C.c_int64), ("quantum", C.c_double), ("rounds", C.c_int64),
@@ -195,6 +207,7 @@ EXPORTS = [
     "scp_kinematics", "scp_fixed_bounds", "scp_linearize_pairs", "scp_select_pairs", "scp_check_avoidance", "scp_qp_add_rows_at",
     "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
     "scp_clearance_profile", "scp_ctx_last_clearance_solved",
+    "scp_delay_margins", "scp_ctx_last_delay_solved",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
     "scp_qp_reset", "scp_qp_set_rho", "scp_qp_add_rows", "scp_qp_solve", "scp_qp_clone_state", "scp_qp_get_solution",
@@ -255,6 +268,8 @@ def load_library():
     lib.scp_list_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, i64, vp]
     lib.scp_clearance_profile.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp]
     lib.scp_ctx_last_clearance_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.scp_delay_margins.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
+    lib.scp_ctx_last_delay_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_collision_violations_at.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_gather_rows.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]
@@ -498,6 +513,25 @@ class Context:
         """segments of the latest clearance_profile that needed the quartic's minimum"""
         n = C.c_uint64()
         self.check(self.lib.scp_ctx_last_clearance_solved(self.h, C.byref(n)))
+        return int(n.value)
+
+    def delay_margins(self, N, K, D, h, R, pos, vel, acc, max_lag, a_begin=0, a_end=None):
+        """scp_delay_margins for the vehicles [a_begin, a_end) and the lags 0 .. max_lag: the clearance of every vehicle
+        started s steps late, as a numpy structured array (DELAY_DTYPE) of shape (a_end - a_begin, max_lag + 1) --
+        synchronises."""
+        torch = _torch()
+        a_end = N if a_end is None else a_end
+        shape = (max(a_end - a_begin, 0), max(max_lag, 0) + 1)
+        out = torch.empty(max(shape[0] * shape[1], 1) * DELAY_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_delay_margins(self.h, N, K, D, h, R, a_begin, a_end, max_lag, pos.data_ptr(), vel.data_ptr(),
+                                              acc.data_ptr(), out.data_ptr()))
+        n = shape[0] * shape[1] * DELAY_DTYPE.itemsize
+        return out[:n].cpu().numpy().view(DELAY_DTYPE).reshape(shape).copy()
+
+    def last_delay_solved(self):
+        """segments of the latest delay_margins that needed the quartic's minimum"""
+        n = C.c_uint64()
+        self.check(self.lib.scp_ctx_last_delay_solved(self.h, C.byref(n)))
         return int(n.value)
 
     def last_separation_solved(self):

@@ -38,6 +38,10 @@ def build_parser():
     p.add_argument("--clearance", action="store_true",
                    help="--continuous-check, and one more line: the most exposed vehicle (smallest distance to any other over "
                         "the whole flight) and how many vehicles are in a conflict; with --save-prefix also <prefix>_clearance.pdf")
+    p.add_argument("--delay-tolerance", type=int, default=None, metavar="STEPS",
+                   help="--continuous-check, and one more line: the vehicle that tolerates the smallest late start (alone, in "
+                        "whole time steps up to STEPS) before it comes closer than the minimum distance - 0.01 m to anybody, "
+                        "who limits it and where; with --save-prefix also <prefix>_delay.pdf")
     p.add_argument("--assign-goals", action="store_true",
                    help="interchangeable vehicles: before the solve, pair vehicles and goals so that the sum of squared "
                         "start-goal distances is minimal (no head-on swaps), and print one line with cost, straight-line "
@@ -102,8 +106,10 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
-        if args.continuous_check or args.list_conflicts or args.clearance:
+        if args.continuous_check or args.list_conflicts or args.clearance or args.delay_tolerance is not None:
             extras = {k: True for k, on in (("conflicts", args.list_conflicts), ("clearance", args.clearance)) if on}
+            if args.delay_tolerance is not None:
+                extras["delay"] = args.delay_tolerance
             rep = solver.validate_solution(continuous=True, **extras)
             ca = rep["closest_approach"]
             if ca is None:
@@ -125,6 +131,23 @@ def main(argv=None):
                 from ..viz.plot_trajectories import plot_clearance
 
                 plot_clearance(solver, f"{args.save_prefix}_clearance.pdf")
+            if args.delay_tolerance is not None:
+                lt = rep["least_tolerant_vehicle"]
+                if lt is None:
+                    print("Delay tolerance: no pair of vehicles")
+                elif lt["steps"] >= args.delay_tolerance:
+                    print(f"Delay tolerance: every vehicle may start {lt['steps']} steps ({lt['seconds']:.2f} s) late; least "
+                          f"tolerant vehicle {lt['vehicle']} then still keeps {lt['distance']:.4f} m from vehicle "
+                          f"{lt['partner']} at t = {lt['time']:.4f} s")
+                else:
+                    late = (f"may start {lt['steps']} steps ({lt['seconds']:.2f} s) late" if lt["steps"] >= 0
+                            else "is in conflict on schedule")
+                    print(f"Delay tolerance: least tolerant vehicle {lt['vehicle']} {late}; one step more and it comes within "
+                          f"{lt['distance']:.4f} m of vehicle {lt['partner']} at t = {lt['time']:.4f} s")
+                if args.save_prefix:
+                    from ..viz.plot_trajectories import plot_delay_margin
+
+                    plot_delay_margin(solver, args.delay_tolerance, f"{args.save_prefix}_delay.pdf")
 
         if not args.no_plots:
             pre = args.save_prefix

@@ -160,6 +160,10 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
                 record["clearance_per_vehicle"] = [float(x) for x in rep["vehicle_clearance"]["min_distance"]]
                 record["clearance_per_step"] = [float(x) for x in rep["step_clearance"]["min_distance"]]
                 record["n_vehicles_in_conflict"] = int((rep["vehicle_clearance"]["n_violating_segments"] > 0).sum())
+        if cfg.get("delay_tolerance") is not None:
+            steps = solver.validate_solution(continuous=True, delay=int(cfg["delay_tolerance"]))["delay_tolerance"]["steps"]
+            record["delay_tolerance_steps"] = [int(x) for x in steps]
+            record["min_delay_tolerance_steps"] = int(steps.min())
         if save_path is not None:
             np.savez_compressed(save_path, initial_positions=np.asarray(init_pos), final_positions=np.asarray(final_pos),
                                 space_dims=np.asarray(space, dtype=float), **solver.trajectories)
@@ -235,6 +239,10 @@ def build_parser():
                    help="add the clearance profiles to every record: clearance_per_vehicle (every vehicle's smallest distance to "
                         "any other over the whole flight), clearance_per_step (the fleet's smallest distance within every time "
                         "step) and n_vehicles_in_conflict")
+    p.add_argument("--delay-tolerance", type=int, default=None, metavar="STEPS",
+                   help="add the delay tolerance to every record: delay_tolerance_steps (per vehicle, the largest late start in "
+                        "whole time steps up to STEPS, of that vehicle alone, that keeps every segment at R - 0.01 or more; -1: "
+                        "in conflict on schedule) and min_delay_tolerance_steps")
     p.add_argument("--assign-goals", action="store_true",
                    help="interchangeable vehicles: pair vehicles and goals of every scenario so that the sum of squared "
                         "start-goal distances is minimal before it is solved; prints one line per scenario (cost, straight-line "
@@ -280,6 +288,8 @@ def main(argv=None):
     cfg["polish"] = bool(args.polish)
     if args.assign_goals:  # (the key exists only with the flag: the JSON's config is otherwise unchanged)
         cfg["assign_goals"] = True
+    if args.delay_tolerance is not None:  # (likewise)
+        cfg["delay_tolerance"] = int(args.delay_tolerance)
     cfg["carry_rho"] = bool(args.carry_rho)
     many = args.streams > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
     cfg["kernel_timing"] = bool(args.kernel_timing) if args.kernel_timing is not None else not many
@@ -365,6 +375,9 @@ def main(argv=None):
         res["trial_index"] = trial
         if job in scenario_ok:
             res["scenario_ok"] = scenario_ok[job]
+        for key in ("delay_tolerance_steps", "min_delay_tolerance_steps"):  # (--delay-tolerance: the record's last fields)
+            if key in res:
+                res[key] = res.pop(key)
         status_str = "OK" if res["status"] == "success" else f"ERR ({res['error']})"
         print(f"  [rank {rank}] N={N} trial {trial+1:02d}/{cfg['trials_per_N']}  time = {res['time_sec']:.3f}s  [{status_str}]")
         return res

@@ -61,6 +61,17 @@ def clear_native_pool():
 atexit.register(clear_native_pool)
 
 
+def gather_delay_blocks(shard, mine, a0):
+    """The ranks' blocks of delay margins (DELAY_DTYPE, (vehicles of the rank, S + 1), the rank's first vehicle a0) concatenated
+    in vehicle order, flat: the records travel through Shard.allgather_records under the row id a (S + 1) + s, as their bytes."""
+    lags = mine.shape[1]
+    rec = np.empty(mine.size, dtype=[("row", np.uint64)] + _hip.DELAY_DTYPE.descr)
+    rec["row"] = a0 * lags + np.arange(mine.size)
+    for f in _hip.DELAY_DTYPE.names:
+        rec[f] = mine.reshape(-1)[f]
+    return shard.allgather_records(rec)[list(_hip.DELAY_DTYPE.names)]
+
+
 class SCP:
     def __init__(
         self,
@@ -769,7 +780,7 @@ class SCP:
     # ------------------------------------------------------------------------------------------------
     # post-solve validation: one device pass over all pairs + the fixed rows on the host copy
     # ------------------------------------------------------------------------------------------------
-    def validate_solution(self, continuous=False, conflicts=False, clearance=False):
+    def validate_solution(self, continuous=False, conflicts=False, clearance=False, delay=None):
         """Feasibility report of the stored trajectories: minimum pair distance over all stored samples and its
         first violation of R - 0.01 (device reduction, generalises scp.py:597-615), worst violation of every bound
         the reference imposes (scp.py:182-257) and of the final-state equalities (state K).
@@ -789,11 +800,26 @@ class SCP:
         ``n_violating_segments``; ``step_clearance``, a dictionary of length-K arrays -- the fleet's closest approach within
         every segment: ``min_distance``, ``time``, ``vehicles`` (K x 2), ``sample_min_distance``, ``n_violating_segments``; and
         ``most_exposed_vehicle``: ``{"vehicle", "partner", "time", "distance"}`` of the smallest vehicle clearance (None
-        without a pair).  A vehicle or step without a pair has min_distance inf, time nan and partner / vehicles -1."""
+        without a pair).  A vehicle or step without a pair has min_distance inf, time nan and partner / vehicles -1.
+
+        delay=S (an int, 0 <= S <= K, with continuous=True) adds the delay margins (scp_delay_margins): how close every vehicle
+        comes to anybody if it ALONE starts s = 0 .. S steps late (held at its start, everybody else on schedule and parked at
+        the goal afterwards).  ``delay_margin``: a dictionary of N x (S + 1) arrays ``min_distance``, ``time`` (seconds from
+        the start; nan without a pair), ``partner`` (-1 without a pair) and ``n_violating_segments``; ``delay_tolerance``: a
+        dictionary of length-N arrays ``steps`` (the largest s <= S such that the lags 0 .. s are all free of violating
+        segments; -1 if lag 0 already violates), ``seconds`` (steps * h) and ``limited_by`` (the partner at lag steps + 1, -1
+        where steps = S); ``least_tolerant_vehicle``: ``{"vehicle", "steps", "seconds", "partner", "time", "distance"}`` of
+        the smallest ``steps`` (ties: the lowest index; partner, time and distance are those of lag steps + 1, or of lag S
+        where steps = S; None without a pair)."""
         if conflicts and not continuous:
             raise ValueError("conflicts=True lists the conflicts of the continuous-time check: it needs continuous=True")
         if clearance and not continuous:
             raise ValueError("clearance=True profiles the continuous-time check: it needs continuous=True")
+        if delay is not None:
+            if not continuous:
+                raise ValueError("delay=S delays the vehicles of the continuous-time check: it needs continuous=True")
+            if isinstance(delay, bool) or not isinstance(delay, (int, np.integer)) or not 0 <= delay <= self.K:
+                raise ValueError(f"delay={delay!r}: the largest delay is a whole number of steps in [0, K = {self.K}]")
         if self.trajectories is None:
             raise ValueError("Trajectories not generated yet")
         N, K, D, h = self.N, self.K, self.D, self.h
@@ -833,7 +859,34 @@ class SCP:
             report["n_conflicts"] = len(report["conflicts"])
         if clearance:
             report.update(self._clearance_profiles(dev, q0, q1))
+        if delay is not None:
+            report.update(self._delay_margins(dev, int(delay)))
         return report
+
+    def _delay_margins(self, dev, S):
+        """The delay part of validate_solution: one device pass (scp_delay_margins) over this rank's vehicles of the device
+        tensors dev = (positions, velocities, accelerations); the ranks' blocks are concatenated, nothing is merged."""
+        N, K, D, h = self.N, self.K, self.D, self.h
+        a0, a1 = self.shard.agent_range()
+        mine = self._ctx.delay_margins(N, K, D, h, self.R, *dev, S, a0, a1)
+        e = gather_delay_blocks(self.shard, mine, a0).reshape(N, S + 1)
+        some = e["partner"] != np.uint32(_hip.NO_INDEX)
+        n_viol = e["n_violating"].astype(np.int64)
+        partner = np.where(some, e["partner"].astype(np.int64), -1)
+        margin = {"min_distance": e["min_dist"].copy(),
+                  "time": np.where(some, np.where(some, e["segment"], 0).astype(np.float64) * h + e["t_min"], np.nan),
+                  "partner": partner, "n_violating_segments": n_viol}
+        bad = n_viol > 0
+        steps = np.where(bad.any(axis=1), bad.argmax(axis=1), S + 1).astype(np.int64) - 1  # the first violating lag, less one
+        at = np.minimum(steps + 1, S)  # the lag that limits the vehicle (lag S where nothing does)
+        idx = np.arange(N)
+        tolerance = {"steps": steps, "seconds": steps * h, "limited_by": np.where(steps < S, partner[idx, at], -1)}
+        least = None
+        if N > 1:
+            v = int(np.argmin(steps))  # ties: the lowest index
+            least = {"vehicle": v, "steps": int(steps[v]), "seconds": float(steps[v] * h), "partner": int(partner[v, at[v]]),
+                     "time": float(margin["time"][v, at[v]]), "distance": float(margin["min_distance"][v, at[v]])}
+        return {"delay_margin": margin, "delay_tolerance": tolerance, "least_tolerant_vehicle": least}
 
     def _clearance_profiles(self, dev, q0, q1):
         """The clearance part of validate_solution: one device pass (scp_clearance_profile) over this rank's pair range of the

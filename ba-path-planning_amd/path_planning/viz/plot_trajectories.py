@@ -93,3 +93,30 @@ def plot_clearance(solver, save_path="clearance.pdf"):
         fig.savefig(save_path, bbox_inches="tight")
     plt.close(fig)
     return rep
+
+
+def plot_delay_margin(solver, max_lag, save_path="delay.pdf"):
+    """The delay margins of validate_solution(continuous=True, delay=max_lag): one curve per vehicle, its smallest distance to
+    anybody over the delay of its start (that vehicle alone, in seconds), against the tolerated R - 0.01; the least tolerant
+    vehicle is drawn on top."""
+    import matplotlib.pyplot as plt
+
+    rep = solver.validate_solution(continuous=True, delay=max_lag)
+    dist = rep["delay_margin"]["min_distance"]
+    lag = solver.h * np.arange(dist.shape[1])
+    fig, ax = plt.subplots(figsize=(7.5, 4.5))
+    for v in range(solver.N):
+        ax.plot(lag, dist[v], "-", color="tab:blue", lw=0.7, alpha=0.5, marker=".", ms=3)
+    lt = rep["least_tolerant_vehicle"]
+    if lt is not None:
+        ax.plot(lag, dist[lt["vehicle"]], "-", color="tab:orange", lw=1.6, marker=".", ms=4,
+                label=f"vehicle {lt['vehicle']}: {lt['steps']} steps")
+    ax.axhline(solver.R - 0.01, color="tab:red", lw=0.8, ls=":", label="R - 0.01 m")
+    ax.set_xlabel("delay of the vehicle's start [s]")
+    ax.set_ylabel("minimum distance to anybody [m]")
+    ax.set_title(f"delay margin per vehicle ({solver.N} vehicles, up to {max_lag} steps)")
+    ax.legend(fontsize=8)
+    if save_path:
+        fig.savefig(save_path, bbox_inches="tight")
+    plt.close(fig)
+    return rep

@@ -153,7 +153,9 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     0: prep kernel + pass + compaction launches as for large problems.
  *   "fused_step_prep" (default 1): where a pass runs as several launches, its prep launch derives the positions it stages --
  *     from acc_in at the start of scp_solver_step, from the QP's time-major solution in every round -- instead of following
- *     a layout change and a kinematics launch.  0: those launches run separately. */
+ *     a layout change and a kinematics launch.  0: those launches run separately.
+ *   "delay_lag_chunk", "delay_time_chunk" (default 0: chosen by the call): the lags / the global segments one workgroup of
+ *     scp_delay_margins covers; developer switches for tests and measurements. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -286,6 +288,50 @@ int scp_clearance_profile(scp_ctx* ctx, int N, int K, int D, double h, double R,
                           scp_clearance* per_vehicle /* [N] or NULL */, scp_clearance* per_step /* [K] or NULL */);
 /* Segments of the latest scp_clearance_profile of this ctx whose quartic was minimised; a cost figure.  Synchronises. */
 int scp_ctx_last_clearance_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
+
+/* ---- delay margins: the clearance of every vehicle against a late start ------------------------------------------------------
+ * A purely additive part of ABI version 7: one struct and two functions, nothing else changes.
+ * pos, vel, acc are [N][K][D] as scp_check_separation takes them.  Every vehicle i has K + 2 RECORDS (position, velocity,
+ * acceleration), r = -1 .. K:
+ *   r = -1        held at the start:    (p_i[0], 0, 0);
+ *   r = 0 .. K-1  the stored segment:   (p_i[r], v_i[r], a_i[r]);
+ *   r = K         parked at the goal:   (pK_i, 0, 0),  pK = p[K-1] + (h*v[K-1] + (0.5*h*h)*a[K-1]), every product and every sum
+ *                 rounded on its own (no contraction), so that numpy reproduces the bits of pK.
+ * DELAY s of vehicle a, s = 0 .. max_lag: a alone starts s steps late -- it is held at its start for s steps, then flies its
+ * stored plan; everybody else flies on schedule and parks at the goal afterwards.  The comparison covers the global segments
+ * g = 0 .. K+s-1; in segment g vehicle a uses record g - s (-1 while g < s) and a vehicle b != a record min(g, K).  The segment
+ * distance is that of the other continuous-time passes, sqrt(max(min_{t in [0, h]} f(t), 0)), f the quartic of the two records'
+ * differences (the arithmetic per segment is scp_check_separation's).
+ * ENTRY (a, s), out[(a - a_begin) * (max_lag + 1) + s], reduces over all b != a and all g: min_dist, t_min, segment (the
+ * global g) and partner (b) are those of the lexicographic minimum of (min f, g, b) -- bitwise equal minima go to the
+ * smallest (g, b) --; n_violating counts the (b, g) whose segment distance is < R - 0.01 (the test of scp_check_separation).
+ * An entry without a pair (N = 1) is {+inf, 0, UINT32_MAX, UINT32_MAX, 0}.  Two consequences:
+ *   lag 0 is the clearance profile: entry (a, 0) has the min_dist, t_min and n_violating of scp_clearance_profile's
+ *     per_vehicle[a] over the full pair range, bit for bit, and (segment, partner) is that entry's row decoded (the order
+ *     (g, b) is the row order k*pairs + q restricted to vehicle a; the quartic's coefficients are products of two
+ *     differences, so they carry the same bits whichever vehicle is subtracted from which);
+ *   a delay is a shifted fleet: on arrays of horizon K + s in which vehicle a has s held records followed by its plan and
+ *     everybody else the plan followed by s parked records, scp_clearance_profile's per_vehicle[a] is entry (a, s) bit for bit.
+ * Ranges: 0 <= a_begin <= a_end <= N (an empty range writes nothing and returns SCP_OK), 0 <= max_lag <= K.  The result is
+ * deterministic (no floating-point atomics) and does not depend on how the vehicle range is cut: the entries of disjoint
+ * ranges, concatenated, are the bytes of the full call -- the vehicle range is the multi-rank cut, nothing has to be merged.
+ * A segment is excluded without minimising its quartic only if its distance provably exceeds max(R - 0.01, the smallest
+ * distance entry (a, s) has so far); results never depend on what was excluded (scp_ctx_last_delay_solved).  `out` is DEVICE
+ * memory.  Argument checks, error codes, stream and timing behaviour as scp_clearance_profile (scp_ctx_last_pair_ms: all
+ * kernels of the call).  scp_ctx_set_option "delay_lag_chunk" / "delay_time_chunk" (default 0: chosen by the call) fix the
+ * lags / global segments a workgroup covers; developer switches, results never depend on them. */
+typedef struct scp_delay_margin {   /* 32 bytes */
+  double   min_dist;    /* smallest segment distance of vehicle a, started s steps late, to anybody; +inf: no pair */
+  double   t_min;       /* where in [0, h] of that segment */
+  uint32_t partner;     /* against whom; UINT32_MAX: none */
+  uint32_t segment;     /* global segment g in [0, K + s); UINT32_MAX: none */
+  uint64_t n_violating; /* (partner, segment) combinations below R - 0.01 */
+} scp_delay_margin;
+int scp_delay_margins(scp_ctx* ctx, int N, int K, int D, double h, double R, int a_begin, int a_end, int max_lag,
+                      const double* pos, const double* vel, const double* acc,
+                      scp_delay_margin* out /* DEVICE, [a_end - a_begin][max_lag + 1] */);
+/* Segments of the latest scp_delay_margins of this ctx whose quartic was minimised; a cost figure.  Synchronises. */
+int scp_ctx_last_delay_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
 
 /* ---- constraint generation for the joint QP (a6): full pass over the linearised rows ------------------
  * For every local row not yet marked in sel_bitmap: if (A_col x)_r < l_r - feas_tol, mark it and append its
