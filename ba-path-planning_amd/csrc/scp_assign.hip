@@ -15,6 +15,7 @@
 //   line_finish_kernel  one wave per scenario folds its partials in the same order relation
 // No workgroup waits for another one; every loop is bounded by a count (rounds by the guard, phases by the halving of eps).
 #include "scp_common.h"
+#include "scp_assign_device.h"
 #include "scp_line_device.h"
 
 #include <climits>
@@ -24,24 +25,6 @@ namespace {
 
 constexpr int ASG_MAXN = 4096;
 constexpr int LINE_TILE = 256;
-
-// c_ij of the rule: floor(ldexp(d2, s)) with d2 summed in coordinate order, every product rounded
-__device__ inline long long asg_cost(const double* __restrict__ a, const double* __restrict__ g, int D, int sh) {
-#pragma clang fp contract(off)
-  const double dx = a[0] - g[0], dy = a[1] - g[1];
-  double d2 = dx * dx + dy * dy;
-  if (D == 3) {
-    const double dz = a[2] - g[2];
-    d2 = d2 + dz * dz;
-  }
-  return (long long)ldexp(d2, sh);  // (non-negative and below 2^31: the conversion truncates = floor)
-}
-
-__device__ inline long long asg_wave_sum(long long v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const double* __restrict__ start,
                                                            const double* __restrict__ goal, int32_t* __restrict__ goal_of,
@@ -422,15 +405,6 @@ __global__ __launch_bounds__(64) void line_finish_kernel(int ntri, const LinePar
     st.n_opposed = (int64_t)opposed;
     stats[b] = st;
   }
-}
-
-// the mapped host word the kernels raise on unusable input (shared with the generator's sweep flag: calls do not overlap)
-int asg_host_flag(scp_ctx* ctx) {
-  if (!ctx->h_gen_flag) {
-    SCP_HIP_CHECK(ctx, hipHostMalloc((void**)&ctx->h_gen_flag, 64, hipHostMallocMapped));
-    SCP_HIP_CHECK(ctx, hipHostGetDevicePointer((void**)&ctx->d_gen_flag, ctx->h_gen_flag, 0));
-  }
-  return SCP_OK;
 }
 
 }  // namespace

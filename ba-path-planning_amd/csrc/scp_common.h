@@ -69,6 +69,12 @@ struct scp_ctx {
   int* d_gen_flag;
   void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)
   size_t asg_ws_bytes;
+  void* asgw_ws;                  // device workspace of scp_assign_goals_wide (per-scenario auction state + control blocks;
+  size_t asgw_ws_bytes;           // grown on demand)
+  int asgw_min_bidders;           // its rounds with at least this many bidders run on the whole chip; 0: chosen by the call
+  int asgw_prices_in_lds;         // its narrow runs keep the prices in LDS: -1 auto, 0 never, 1 where they fit
+  int asgw_control_threads;       // threads of its control workgroup: 0 chosen by the call (256 up to N = 512, else 1024)
+                                  // (scp_ctx_set_option; developer switches, results never depend on them)
   int near_pass;                  // near form of the recomputing violations pass: 0 off, 1 auto, 2 force (scp_ctx_set_near_pass)
   unsigned near_call_no;          // number of the latest recomputing violations pass (what its prep kernel leaves in
                                   // d_ticket[3] when a staged value is not finite)

@@ -31,6 +31,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
   ctx->small_pass = getenv("SCP_NO_SMALL_PASS") ? 0 : 1;  // (developer switch; scp_ctx_set_option at run time)
   ctx->fused_step_prep = 1;
   ctx->near_pass = 1;  // auto (scp_ctx_set_near_pass)
+  ctx->asgw_prices_in_lds = -1;  // auto
   if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->n_cu = 0;
   if (hipMalloc(&ctx->d_scratch, 72 * sizeof(double)) != hipSuccess ||
       hipMemset(ctx->d_scratch, 0, 72 * sizeof(double)) != hipSuccess ||  // ([64]: ticket counter of scp_rel_step)
@@ -62,6 +63,11 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
 // and a kinematics launch; 0: those launches run as before (same results; tests/test_step_prep_gpu.py compares the two).
 // "delay_lag_chunk" / "delay_time_chunk": lags / global segments per workgroup of scp_delay_margins; 0 (default): the call
 // chooses (same results; tests/test_delay_gpu.py compares forced chunks with the call's own).
+// "assign_wide_min_bidders" / "assign_wide_prices_in_lds" / "assign_wide_control_threads": scp_assign_goals_wide's three
+// size-dependent forks -- the bidder count from which a round runs on the whole chip (0: the call chooses; 1: every round;
+// >= N: none), where its narrow runs keep the prices (-1 auto, 0 global memory, 1 LDS where 8 N bytes fit) and the threads
+// of its control workgroup (0: 256 up to N = 512, else 1024; or either number); same results
+// (tests/test_assignment_wide_gpu.py compares them).
 extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   if (!ctx || !key) return SCP_ERR_INVALID;
   if (strcmp(key, "kernel_timing") == 0) {
@@ -82,6 +88,22 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
     (key[6] == 'l' ? ctx->delay_lag_chunk : ctx->delay_time_chunk) = value;
     return SCP_OK;
   }
+  if (strcmp(key, "assign_wide_min_bidders") == 0) {
+    if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
+    ctx->asgw_min_bidders = value;
+    return SCP_OK;
+  }
+  if (strcmp(key, "assign_wide_prices_in_lds") == 0) {
+    if (value < -1 || value > 1) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need -1, 0 or 1)", key, value);
+    ctx->asgw_prices_in_lds = value;
+    return SCP_OK;
+  }
+  if (strcmp(key, "assign_wide_control_threads") == 0) {
+    if (value != 0 && value != 256 && value != 1024)
+      return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0, 256 or 1024)", key, value);
+    ctx->asgw_control_threads = value;
+    return SCP_OK;
+  }
   return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: unknown key '%s'", key);
 }
 
@@ -99,6 +121,7 @@ extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
   if (ctx->gen_ws) (void)hipFree(ctx->gen_ws);
   if (ctx->sep_ws) (void)hipFree(ctx->sep_ws);
   if (ctx->asg_ws) (void)hipFree(ctx->asg_ws);
+  if (ctx->asgw_ws) (void)hipFree(ctx->asgw_ws);
   if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
   (void)hipHostFree(ctx->h_scratch);
   (void)hipHostFree(ctx->h_mirror);

@@ -215,7 +215,7 @@ EXPORTS = [
     "scp_solve_default_options", "scp_solver_create", "scp_solver_destroy", "scp_solver_update_settings", "scp_solver_solve",
     "scp_solver_step", "scp_solver_shard_begin", "scp_solver_shard_rows", "scp_solver_shard_qp", "scp_solver_shard_violations",
     "scp_solver_shard_round_done", "scp_solver_shard_end", "scp_gen_default_params", "scp_generate_grid_swap",
-    "scp_assign_goals", "scp_straight_line_check",
+    "scp_assign_goals", "scp_straight_line_check", "scp_assign_goals_wide",
 ]
 
 
@@ -314,6 +314,7 @@ def load_library():
     lib.scp_gen_default_params.restype = None
     lib.scp_generate_grid_swap.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_uint64), C.POINTER(GenParams), vp, vp, vp, vp]
     lib.scp_assign_goals.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+    lib.scp_assign_goals_wide.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
     lib.scp_straight_line_check.argtypes = [vp, i32, i32, i32, vp, vp, vp, f64, vp]
     _LIB, _LIB_PATH = lib, path
     return lib
@@ -378,7 +379,9 @@ class Context:
         """scp_ctx_set_option: "kernel_timing" (HIP events around the pairwise kernels and QP solves; 0 saves ~25 queue packets
         per complete solve, the kernel times in the records then read 0 and solve_ms is host wall clock),
         "single_launch_passes" (one-launch pairwise passes for small problems), "fused_step_prep" (large problems: the prep
-        launch of a pass derives the positions it stages itself; results never depend on it)"""
+        launch of a pass derives the positions it stages itself; results never depend on it), "assign_wide_min_bidders" /
+        "assign_wide_prices_in_lds" / "assign_wide_control_threads" (the three forks of assign_goals_wide; results never
+        depend on them)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
@@ -580,15 +583,22 @@ class Context:
         distances, for B scenarios in one launch.  start / goal: (B, N, D) device tensors or arrays.  Returns goal_of
         (B, N) int32 device tensor (vehicle i flies to goal[goal_of[i]]), the stats as a numpy structured array
         (ASSIGN_STATS_DTYPE) of B entries and the auction's prices ((B, N) int64 device tensor, or None).  Synchronises."""
+        return self._assign_goals(self.lib.scp_assign_goals, start, goal, max_rounds_per_phase, want_prices)
+
+    def assign_goals_wide(self, start, goal, max_rounds_per_phase=0, want_prices=False):
+        """scp_assign_goals_wide: assign_goals for N up to 65536 -- the same rule and the same bytes, the auction's state in
+        global memory and the rounds with many bidders on the whole GPU.  Arguments and returns as assign_goals."""
+        return self._assign_goals(self.lib.scp_assign_goals_wide, start, goal, max_rounds_per_phase, want_prices)
+
+    def _assign_goals(self, fn, start, goal, max_rounds_per_phase, want_prices):
         torch = _torch()
         s, g = self._scenario_points(start, goal)
         B, N, D = (int(v) for v in s.shape)
         goal_of = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int32, device=self.tdev)
         prices = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int64, device=self.tdev) if want_prices else None
         stats = torch.empty(max(B, 1) * ASSIGN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
-        self.check(self.lib.scp_assign_goals(self.h, B, N, D, s.data_ptr(), g.data_ptr(), goal_of.data_ptr(),
-                                             prices.data_ptr() if want_prices else None, int(max_rounds_per_phase),
-                                             stats.data_ptr()))
+        self.check(fn(self.h, B, N, D, s.data_ptr(), g.data_ptr(), goal_of.data_ptr(),
+                      prices.data_ptr() if want_prices else None, int(max_rounds_per_phase), stats.data_ptr()))
         return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
 
     def straight_line_check(self, start, goal, goal_of=None, min_sep=0.0):

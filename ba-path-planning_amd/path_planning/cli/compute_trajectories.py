@@ -46,6 +46,9 @@ def build_parser():
                    help="interchangeable vehicles: before the solve, pair vehicles and goals so that the sum of squared "
                         "start-goal distances is minimal (no head-on swaps), and print one line with cost, straight-line "
                         "minimum approach and opposed pairs before and after")
+    p.add_argument("--assign-method", choices=("auto", "single", "wide"), default="auto",
+                   help="--assign-goals through the one-workgroup auction (single, up to 4096 vehicles), the whole-GPU one (wide, "
+                        "up to 65536) or whichever fits (auto); the assignment is the same")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -94,7 +97,7 @@ def main(argv=None):
         if args.assign_goals:
             from ..scenarios.assignment import describe
 
-            solver.assign_goals()
+            solver.assign_goals(method=args.assign_method)
             print(describe(solver.assignment_info))
 
         print("Generating trajectories...")

@@ -99,7 +99,7 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
             from ..scenarios.assignment import describe
 
             t_a = time.perf_counter()
-            solver.assign_goals()
+            solver.assign_goals(method=cfg.get("assign_method", "auto"))
             assign_ms = (time.perf_counter() - t_a) * 1e3
             print(f"  N={N} seed={seed}: {describe(solver.assignment_info)}")
         t0 = time.perf_counter()
@@ -247,6 +247,9 @@ def build_parser():
                    help="interchangeable vehicles: pair vehicles and goals of every scenario so that the sum of squared "
                         "start-goal distances is minimal before it is solved; prints one line per scenario (cost, straight-line "
                         "minimum approach, opposed pairs, before -> after) and adds goal_assignment and assign_ms to its record")
+    p.add_argument("--assign-method", choices=("auto", "single", "wide"), default="auto",
+                   help="--assign-goals through the one-workgroup auction (single, up to 4096 vehicles), the whole-GPU one (wide, "
+                        "up to 65536) or whichever fits (auto); the assignment is the same")
     p.add_argument("--warmup", type=int, default=0,
                    help="untimed solves per worker (stream) before the clock starts: the first solve of a worker builds its "
                         "solver object and loads the kernels (~0.1 s); with it the scenarios/s line is the steady-state rate")
@@ -288,6 +291,8 @@ def main(argv=None):
     cfg["polish"] = bool(args.polish)
     if args.assign_goals:  # (the key exists only with the flag: the JSON's config is otherwise unchanged)
         cfg["assign_goals"] = True
+        if args.assign_method != "auto":  # (likewise)
+            cfg["assign_method"] = args.assign_method
     if args.delay_tolerance is not None:  # (likewise)
         cfg["delay_tolerance"] = int(args.delay_tolerance)
     cfg["carry_rho"] = bool(args.carry_rho)

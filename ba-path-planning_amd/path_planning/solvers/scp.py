@@ -249,15 +249,19 @@ class SCP:
         self.goal_assignment = None
         self.assignment_info = None
 
-    def assign_goals(self, min_sep=None):
+    def assign_goals(self, min_sep=None, method="auto"):
         """Interchangeable vehicles: re-pair vehicles and goals so that the sum of squared start-goal distances is minimal
         (scp_assign_goals).  Call it after set_initial_states and set_final_states; the final positions AND velocities are
         permuted, so vehicle i then flies to the goal given as number ``goal_assignment[i]``.  ``goal_assignment`` always
         refers to the order handed to set_final_states: a second call recomputes from those originals, it does not compose.
         ``assignment_info`` holds the auction's statistics and the straight-line checks before / after (min_sep, default the
-        minimum distance, is their "close" threshold).  Returns goal_assignment."""
-        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS
+        minimum distance, is their "close" threshold).  ``method``: "single" (scp_assign_goals, up to 4096 vehicles), "wide"
+        (scp_assign_goals_wide, up to 65536) or "auto" (wide from 1024 vehicles, where it is faster); the result does not
+        depend on it.  Returns
+        goal_assignment."""
+        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS, assign_method
 
+        assign = assign_method(self._ctx, method, self.N)
         if self.initial_positions is None or self.final_positions is None:
             raise ValueError("assign_goals needs both set_initial_states and set_final_states first")
         if self._final_given is None:
@@ -265,7 +269,7 @@ class SCP:
         pf, vf = (a.reshape(self.N, self.D) for a in self._final_given)
         start = self.initial_positions.reshape(1, self.N, self.D)
         sep = float(self.R if min_sep is None else min_sep)
-        goal_of, st, _ = self._ctx.assign_goals(start, pf[None])
+        goal_of, st, _ = assign(start, pf[None])
         before = self._ctx.straight_line_check(start, pf[None], None, sep)
         after = self._ctx.straight_line_check(start, pf[None], goal_of, sep)
         info = {k: st[k][0].item() for k in _ASSIGN_KEYS}

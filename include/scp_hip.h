@@ -609,6 +609,35 @@ int scp_assign_goals(scp_ctx* ctx, int B, int N, int D, const double* start /* [
                      int32_t* goal_of /* [B][N] */, int64_t* prices /* [B][N] or NULL */, int64_t max_rounds_per_phase,
                      scp_assign_stats* stats /* [B] */);
 
+/* The same rule with the state in global memory and, for the rounds in which many persons bid, the whole GPU behind one
+ * scenario (a further additive part of ABI version 7: this one function).  Arguments, outputs, the rule (quantisation,
+ * auction, guard, status 0 / 1, the behaviour on unusable coordinates), stream and synchronisation are scp_assign_goals's;
+ * supported: B >= 1, 1 <= N <= 65536, D in {2, 3}.  For every input both functions accept, goal_of, prices and every field of
+ * stats (rounds, bids and phases included) are the same bytes; for every N they are those of tests/assignment_ref.py.
+ *
+ * Price bound for this range.  Let C = (N + 1) 2^31 (so |a_ij| < C).  A goal that received a bid in a phase stays owned until
+ * the phase ends, and the phase ends once every goal is owned.  So in every round but a phase's last, each bidder i with
+ * target j1 finds a goal j0 != j1 that has received no bid in this phase (if only one such goal is left and somebody bids
+ * for it, the round is the last).  j0 is still at its price p0_j0 of the phase's start, and w2 >= a_ij0 - p0_j0 gives
+ * bid = a_ij1 - w2 + eps <= (a_ij1 - a_ij0) + p0_j0 + eps < C + P0 + eps (P0: the highest price at the phase's start).  In
+ * the last round w2 >= a_ij - p_j for any j != j1 at its current price, so a bid stays below C + eps + the highest current
+ * price.  So a phase raises the highest price by less than 2 (C + eps).  eps_0 <= C / 2 < 2^47 reaches 1 after at
+ * most 24 divisions by 4, so there are at most 25 phases, and the sum of their eps is at most (4/3) eps_0 + 25.  Hence
+ *   prices <= 50 C + (4/3) C + 50 < 52 (N + 1) 2^31, which is below 2^53 at N = 65536 (and below 2^49 at N = 4096);
+ * v_ij = a_ij - p_j and every bid then stay within +-2^54: every intermediate fits int64 with nine bits to spare.
+ * (tests/test_assignment_wide_cpu.py checks the bound on the reference's prices.)
+ *
+ * Rounds with few bidders run in one workgroup per scenario, round after round in one launch; rounds with many run as three
+ * launches whose grids cover (scenario, bidder); DESIGN.md section 3.8 has the launch sequence.  No workgroup waits for
+ * another.  Developer switches (scp_ctx_set_option; results never depend on them): "assign_wide_min_bidders" (0: chosen by the
+ * call; otherwise rounds with at least that many bidders take the three launches: 1 = every round, a value >= N = none),
+ * "assign_wide_prices_in_lds" (-1 auto, 0: the one-workgroup rounds read the prices from global memory, 1: from LDS where
+ * 8 N bytes fit, N <= 16384), "assign_wide_control_threads" (0: 256 threads in the one workgroup up to N = 512 and 1024
+ * beyond; 256 or 1024: that many). */
+int scp_assign_goals_wide(scp_ctx* ctx, int B, int N, int D, const double* start /* [B][N][D] */,
+                          const double* goal /* [B][N][D] */, int32_t* goal_of /* [B][N] */, int64_t* prices /* [B][N] or NULL */,
+                          int64_t max_rounds_per_phase, scp_assign_stats* stats /* [B] */);
+
 /* Straight-line check: one pass per scenario over the pairs i < j of the motions start_i -> goal[goal_of[i]] (goal_of NULL:
  * the identity).  d^2 is the squared closest approach of the "Block draw" rule above (the generator's device function, so a
  * grid-swap-device scenario's min_approach is scp_gen_stats.min_approach bit for bit), with r0 = s_i - s_j and

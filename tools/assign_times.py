@@ -6,7 +6,8 @@ Beside each B = 1 row scipy's linear_sum_assignment on the same quantised costs 
 (otherwise the row says so); its optimum must equal cost_q.
 Rows "solve": SCP iterations and wall time of generate_trajectories on grid-swap scenarios (host generator) of 128 and 1024
 agents, with the given pairing and after SCP.assign_goals (T = 10 s, h = 0.2 s, R = 0.8 m, the batch CLI's configuration).
-usage: python tools/assign_times.py [--reps 3] [--out FILE] [--skip-solves]"""
+--wide: only the rows "assign-wide" (see wide_rows): scp_assign_goals against scp_assign_goals_wide, and wide alone beyond 4096.
+usage: python tools/assign_times.py [--reps 3] [--out FILE] [--skip-solves] [--wide]"""
 import argparse
 import json
 import os
@@ -39,11 +40,51 @@ def scenarios(kind, N, B):
     return init.cpu().numpy(), goal.cpu().numpy()
 
 
+def wide_rows(ctx, emit, reps):
+    """Rows "assign-wide": scp_assign_goals and scp_assign_goals_wide on the same scenarios, alternating in one loop (the
+    best of `reps` each, after one untimed call each), their outputs compared byte for byte; beyond 4096 vehicles wide alone
+    (uniform and grid-swap-device points at 16384, a jittered grid with 1/16 of its goals permuted at 16384 and 65536)."""
+    import assignment_wide_cases
+
+    def timed(fn, start, goal):
+        t0 = time.perf_counter()
+        out = fn(start, goal, want_prices=True)
+        return time.perf_counter() - t0, out
+
+    shapes = [(kind, N, B) for N, B in ((128, 1), (1024, 1), (4096, 1), (128, 4096)) for kind in ("uniform", "grid-swap-device")]
+    shapes += [("jittered-grid", 16384, 1), ("jittered-grid", 65536, 1), ("grid-swap-device", 16384, 1), ("uniform", 16384, 1)]
+    for kind, N, B in shapes:
+        if kind == "jittered-grid":
+            pts = [x[None] for x in assignment_wide_cases.jittered_grid(N, 11, swaps=N // 16)]
+        else:
+            pts = scenarios(kind, N, B)
+        start, goal = (ctx.tensor(x) for x in pts)
+        methods = {"wide": ctx.assign_goals_wide}
+        if N <= 4096:
+            methods["single"] = ctx.assign_goals
+        first = {m: timed(fn, start, goal) for m, fn in methods.items()}  # untimed: code objects, LDS limit, workspace
+        n = reps if max(t for t, _ in first.values()) < 5.0 else 1
+        best = {m: float("inf") for m in methods}
+        for _ in range(n):
+            for m, fn in methods.items():
+                best[m] = min(best[m], timed(fn, start, goal)[0])
+        st = first["wide"][1][1]
+        row = {"row": "assign-wide", "points": kind, "N": N, "B": B, "reps": n, "wide_ms": best["wide"] * 1e3,
+               "phases_max": int(st["phases"].max()), "rounds_max": int(st["rounds"].max()), "bids_max": int(st["bids"].max()),
+               "status_nonzero": int((st["status"] != 0).sum())}
+        if "single" in methods:
+            (g1, s1, p1), (g2, s2, p2) = first["single"][1], first["wide"][1]
+            row.update(single_ms=best["single"] * 1e3, single_over_wide=best["single"] / best["wide"],
+                       same_bytes=bool((g1 == g2).all().item() and (p1 == p2).all().item() and s1.tobytes() == s2.tobytes()))
+        emit(row)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-solves", action="store_true")
+    ap.add_argument("--wide", action="store_true", help="only the rows that compare scp_assign_goals_wide with scp_assign_goals")
     a = ap.parse_args()
     lines = []
 
@@ -53,6 +94,14 @@ def main():
         lines.append(s)
 
     ctx = _context(0)
+    if a.wide:
+        wide_rows(ctx, emit, a.reps)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("# python tools/assign_times.py --wide --out ...  (MI355X, one GPU; single and wide alternate in one loop: "
+                        "best of `reps` calls each after one untimed call each, host clock around the synchronising call)\n")
+                f.write("\n".join(lines) + "\n")
+        return
     for N, B in ((128, 1), (128, 4096), (1024, 1), (4096, 1)):
         for kind in ("uniform", "grid-swap-device"):
             start, goal = (ctx.tensor(x) for x in scenarios(kind, N, B))
