@@ -156,6 +156,15 @@ CONFLICT_DTYPE = np.dtype([("row", np.uint64), ("min_dist", np.float64), ("t_min
                            ("t_exit", np.float64), ("pieces", np.uint32), ("reserved", np.uint32)])
 
 
+class Hold(C.Structure):
+    """struct scp_hold (scp_update_holds / scp_apply_holds): a fixed separating half-plane in place of one collision row"""
+    _fields_ = [("row", C.c_uint64), ("eta", C.c_double * 3), ("margin", C.c_double), ("reserved", C.c_uint64)]
+
+
+HOLD_DTYPE = np.dtype([("row", np.uint64), ("eta", np.float64, (3,)), ("margin", np.float64), ("reserved", np.uint64)])
+HOLD_MAX_TABLE = 1 << 20  # SCP_HOLD_MAX_TABLE
+
+
 class Clearance(C.Structure):
     """struct scp_clearance (scp_clearance_profile): the closest approach of one vehicle or of one time step"""
     _fields_ = [("min_dist", C.c_double), ("t_min", C.c_double), ("row", C.c_uint64), ("sample_min_dist", C.c_double),
@@ -208,6 +217,7 @@ EXPORTS = [
     "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
     "scp_clearance_profile", "scp_ctx_last_clearance_solved",
     "scp_delay_margins", "scp_ctx_last_delay_solved",
+    "scp_update_holds", "scp_apply_holds",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
     "scp_qp_reset", "scp_qp_set_rho", "scp_qp_add_rows", "scp_qp_solve", "scp_qp_clone_state", "scp_qp_get_solution",
@@ -270,6 +280,8 @@ def load_library():
     lib.scp_ctx_last_clearance_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_delay_margins.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
     lib.scp_ctx_last_delay_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.scp_update_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp]
+    lib.scp_apply_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_collision_violations_at.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]
     lib.scp_gather_rows.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]
@@ -501,6 +513,52 @@ class Context:
             cap = n
         raise HipError(SCP_ERR_CAPACITY, f"list_conflicts: {n} records after a repetition sized for {cap}")
 
+    def hold_table(self, holds=None, capacity=None):
+        """A device table for update_holds / apply_holds: (uint8 tensor of `capacity` scp_hold records, int64 count tensor)
+        holding the records `holds` (a HOLD_DTYPE array sorted by row; None: empty)."""
+        torch = _torch()
+        holds = np.zeros(0, dtype=HOLD_DTYPE) if holds is None else np.ascontiguousarray(holds, dtype=HOLD_DTYPE)
+        cap = max(int(holds.size if capacity is None else capacity), holds.size, 1)
+        table = torch.zeros(cap * HOLD_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        if holds.size:
+            table[: holds.nbytes] = torch.from_numpy(holds.view(np.uint8).copy()).to(self.tdev)
+        return table, torch.full((1,), int(holds.size), dtype=torch.int64, device=self.tdev)
+
+    def read_holds(self, table, n):
+        """the first n records of a device table as a numpy structured array (HOLD_DTYPE) -- synchronises"""
+        n = int(n.item()) if hasattr(n, "item") else int(n)
+        return table[: n * HOLD_DTYPE.itemsize].cpu().numpy().view(HOLD_DTYPE).copy()
+
+    def update_holds(self, N, K, D, h, R, pos, vel, acc, conflicts, table, n_holds, pad, q_begin=0, q_end=None, grow=True):
+        """scp_update_holds: one repair pass's update of a table of holds from a conflict list.  `conflicts`: a CONFLICT_DTYPE
+        array in ascending row order (what list_conflicts returns); `table`, `n_holds`: as hold_table makes them.  Returns (table, n_holds, needed): the table after the update and the number of records it
+        needs.  If that exceeds the table's capacity the table is unchanged and, with grow=True, the call is repeated ONCE
+        on a copy with room for `needed` records (the returned table is then a new tensor); grow=False returns the unchanged
+        table with n_holds restored -- synchronises."""
+        torch = _torch()
+        args = self._trajectory_args(N, K, D, h, R, pos, vel, acc, q_begin, q_end)
+        rec = np.ascontiguousarray(conflicts, dtype=CONFLICT_DTYPE)
+        c_dev = torch.zeros(max(rec.nbytes, 1), dtype=torch.uint8, device=self.tdev)
+        if rec.size:
+            c_dev[: rec.nbytes] = torch.from_numpy(rec.view(np.uint8).copy()).to(self.tdev)
+        c_n = torch.full((1,), int(rec.size), dtype=torch.int64, device=self.tdev)
+        size = HOLD_DTYPE.itemsize
+        before = int(n_holds.item())
+        for _ in range(2):
+            cap = table.numel() // size
+            self.check(self.lib.scp_update_holds(*args, c_dev.data_ptr(), c_n.data_ptr(), float(pad), table.data_ptr(), cap,
+                                                 n_holds.data_ptr()))
+            needed = int(n_holds.item())
+            if needed <= cap:
+                return table, n_holds, needed
+            n_holds.fill_(before)  # the table is as it was
+            if not grow:
+                return table, n_holds, needed
+            bigger = torch.zeros(needed * size, dtype=torch.uint8, device=self.tdev)
+            bigger[: before * size] = table[: before * size]
+            table = bigger
+        raise HipError(SCP_ERR_CAPACITY, f"update_holds: {needed} records after a repetition sized for {cap}")
+
     def clearance_profile(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None):
         """scp_clearance_profile over the pair range [q_begin, q_end): the closest approach of every vehicle and of every
         time step, as two numpy structured arrays (CLEARANCE_DTYPE) of length N and K -- synchronises."""
@@ -646,7 +704,7 @@ class PairPass:
         self.bitmap = torch.zeros(max((self.rows + 31) // 32, 1), dtype=torch.int32, device=ctx.tdev)
         self.sel_cap = int(sel_cap if sel_cap is not None else min(max(self.rows, 1), max(65536, 64 * N * K)))
         self.sel = torch.empty(self.sel_cap, dtype=torch.int64, device=ctx.tdev)
-        self.last_linearize_ms = self.last_violations_ms = 0.0
+        self.last_linearize_ms = self.last_violations_ms = self.last_holds_ms = 0.0
         self.pos_prev = None  # linearisation point of the stored rows (kept for the recomputing violations pass)
 
     def _alloc_planes(self):
@@ -728,6 +786,24 @@ class PairPass:
             # the list was too short: the library merged nothing into the working-set bitmap (n_selected > capacity), so
             # the pass is simply repeated with a longer list
             self._grow(n_sel)
+
+    def apply_holds(self, table, n, p0, v0):
+        """scp_apply_holds on the stored rows of the latest linearize(): the holds of this pair range overwrite their rows of
+        the planes and are marked in the working-set bitmap; returns the global ids (ascending) of those that were not marked
+        before.  table, n: a device table of holds and its count (Context.hold_table)."""
+        c = self.ctx
+        torch = _torch()
+        n_new = torch.zeros(1, dtype=torch.int64, device=c.tdev)
+        while True:
+            c.check(c.lib.scp_apply_holds(c.h, self.N, self.K, self.D, self.h, self.R, self.q_begin, self.q_end,
+                                          table.data_ptr(), n.data_ptr(), p0.data_ptr(), v0.data_ptr(), self.eta.data_ptr(),
+                                          self.l.data_ptr(), self.bitmap.data_ptr(), self.sel.data_ptr(), self.sel_cap,
+                                          n_new.data_ptr()))
+            found = int(n_new.item())
+            self.last_holds_ms = c.last_pair_ms()
+            if found <= self.sel_cap:
+                return self.sel[:found].clone()
+            self._grow(found)  # nothing was written: repeat with a longer list
 
     def gather(self, rows):
         c = self.ctx

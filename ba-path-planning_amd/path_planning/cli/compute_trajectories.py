@@ -42,6 +42,10 @@ def build_parser():
                    help="--continuous-check, and one more line: the vehicle that tolerates the smallest late start (alone, in "
                         "whole time steps up to STEPS) before it comes closer than the minimum distance - 0.01 m to anybody, "
                         "who limits it and where; with --save-prefix also <prefix>_delay.pdf")
+    p.add_argument("--repair-conflicts", type=int, nargs="?", const=6, default=None, metavar="PASSES",
+                   help="after the solve, remove the between-sample conflicts with holds (fixed separating half-planes on the "
+                        "two rows around every conflicting segment, at most PASSES passes, default 6) and print the report; "
+                        "the checks and plots then show the repaired trajectories")
     p.add_argument("--assign-goals", action="store_true",
                    help="interchangeable vehicles: before the solve, pair vehicles and goals so that the sum of squared "
                         "start-goal distances is minimal (no head-on swaps), and print one line with cost, straight-line "
@@ -109,6 +113,12 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
+        if args.repair_conflicts is not None:
+            rep = solver.repair_conflicts(max_passes=args.repair_conflicts)
+            counts = " -> ".join(str(n) for n in [rep["conflicts_before"]] + rep["conflicts_per_pass"])
+            print(f"Conflict repair: {counts} conflicting segments in {rep['passes']} passes ({rep['holds']} holds, stopped by "
+                  f"{rep['stopped_by']}), cost ratio {rep['cost_ratio']:.4f}, {rep['time_sec']:.3f} s"
+                  + ("" if rep["repaired"] else "; NOT repaired"))
         if args.continuous_check or args.list_conflicts or args.clearance or args.delay_tolerance is not None:
             extras = {k: True for k, on in (("conflicts", args.list_conflicts), ("clearance", args.clearance)) if on}
             if args.delay_tolerance is not None:

@@ -143,6 +143,12 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
             persist_gave_up=int(sum(int(q.get("persist_gave_up", 0)) for q in qps)),
             rho_switches_in_kernel=int(sum(int(q.get("rho_switches_in_kernel", 0)) for q in qps)),
         )
+        if cfg.get("repair_conflicts") is not None:
+            # (only with --repair-conflicts; what follows -- validation, the saved trajectories -- describes the repaired result)
+            rep = solver.repair_conflicts(max_passes=int(cfg["repair_conflicts"]))
+            record["conflicts_before"] = int(rep["conflicts_before"])
+            record["conflicts_after"] = int(rep["conflicts_per_pass"][-1] if rep["conflicts_per_pass"] else rep["conflicts_before"])
+            record["repair_passes"] = int(rep["passes"])
         if cfg.get("validate", False):
             record["min_pair_distance"] = float(solver.validate_solution()["min_pair_distance"])
         listing = cfg.get("list_conflicts", False)
@@ -243,6 +249,9 @@ def build_parser():
                    help="add the delay tolerance to every record: delay_tolerance_steps (per vehicle, the largest late start in "
                         "whole time steps up to STEPS, of that vehicle alone, that keeps every segment at R - 0.01 or more; -1: "
                         "in conflict on schedule) and min_delay_tolerance_steps")
+    p.add_argument("--repair-conflicts", type=int, nargs="?", const=6, default=None, metavar="PASSES",
+                   help="after every solve, remove the between-sample conflicts with holds (SCP.repair_conflicts, at most PASSES "
+                        "passes, default 6) and add conflicts_before, conflicts_after and repair_passes to its record")
     p.add_argument("--assign-goals", action="store_true",
                    help="interchangeable vehicles: pair vehicles and goals of every scenario so that the sum of squared "
                         "start-goal distances is minimal before it is solved; prints one line per scenario (cost, straight-line "
@@ -295,6 +304,8 @@ def main(argv=None):
             cfg["assign_method"] = args.assign_method
     if args.delay_tolerance is not None:  # (likewise)
         cfg["delay_tolerance"] = int(args.delay_tolerance)
+    if args.repair_conflicts is not None:  # (likewise)
+        cfg["repair_conflicts"] = int(args.repair_conflicts)
     cfg["carry_rho"] = bool(args.carry_rho)
     many = args.streams > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
     cfg["kernel_timing"] = bool(args.kernel_timing) if args.kernel_timing is not None else not many

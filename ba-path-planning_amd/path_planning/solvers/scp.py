@@ -191,6 +191,7 @@ class SCP:
         self._ctx.set_timing(self.kernel_timing)
         self._qp = None
         self._pairs = None
+        self._holds = None  # (device table, count) of repair_conflicts while one of its passes runs
         self._dev = {}
         self.last_info = {}
 
@@ -702,6 +703,14 @@ class SCP:
 
         prev_pos, _ = self._kinematics(acc, want_vel=False)
         rows, _, _ = pp.linearize(prev_pos, p0, v0, self.working_set_margin)
+        if self._holds is not None:
+            # repair_conflicts: the held rows of the planes become their fixed half-planes and all of them join the working set
+            # (marked in the bitmap, so no violations pass adds their own-direction form again)
+            import torch
+
+            held = pp.apply_holds(*self._holds, p0, v0)
+            if held.numel():
+                rows = torch.cat([rows, held]).sort().values
         w_eta, w_l = pp.gather(rows)
         rows, w_eta, w_l = self.shard.allgather_rows(rows, w_eta, w_l)
 
@@ -948,6 +957,85 @@ class SCP:
             m, t1 = segment_min_distance(p[i, k] - p[j, k], v[i, k] - v[j, k], a[i, k] - a[j, k], h)
             out["first_violation_continuous"] = {"timestep": k, "time": k * h + t1, "vehicles": (i, j), "distance": m}
         return out
+
+    # ------------------------------------------------------------------------------------------------
+    # repair of between-sample conflicts (not in the reference): holds, DESIGN.md section 3.7
+    # ------------------------------------------------------------------------------------------------
+    def repair_conflicts(self, max_passes=6, pad=0.02, max_iterations=15):
+        """Remove the between-sample conflicts of the stored trajectories (what validate_solution(continuous=True,
+        conflicts=True) lists) by HOLDS: for every conflicting segment the two collision rows at its ends are replaced by one
+        fixed half-plane eta . (p_i - p_j) >= R + margin, eta the direction of the closest approach, which keeps the pair
+        apart over the whole segment (include/scp_hip.h, scp_update_holds).  A PASS lists the conflicts, updates the table
+        of holds (a conflict that persists raises its margin by its shortfall + pad), re-runs the SCP loop from the stored
+        accelerations (at most max_iterations iterations, to the usual relative-step tolerance) and lists again.  Passes
+        repeat until no conflict is left, max_passes have run, or a QP of the pass ends with a status other than solved /
+        solved inaccurate -- then the trajectories from before that pass are kept.
+
+        Always the Python-driven, row-writing loop (the planes of all rows, 24 B per row, are allocated), whatever `native` /
+        `row_free` say; one rank only.  ``self.trajectories`` becomes the last accepted pass.  Returns (and stores in
+        ``last_info["repair"]``) a dictionary: ``conflicts_before`` and ``conflicts_per_pass`` (violating segments, the records
+        of scp_list_conflicts), ``passes``, ``holds``, ``repaired`` (no conflict left), ``stopped_by`` ("clean", "max_passes"
+        or "qp_status"), ``cost_ratio`` (sum of squared accelerations after / before), ``time_sec``; per pass also
+        ``iterations_per_pass``, ``admm_steps_per_pass``, ``update_holds_ms`` and ``apply_holds_ms`` (device time of the
+        table update and of the pass's last plane overwrite).  Without a conflict it returns at once with passes = 0 and
+        leaves the trajectories untouched."""
+        if self.trajectories is None:
+            raise ValueError("Trajectories not generated yet")
+        if self.shard.world != 1:
+            raise ValueError("repair_conflicts supports one rank only (world_size == 1)")
+        t_start = time.perf_counter()
+        N, K, D, h, c = self.N, self.K, self.D, self.h, self._ctx
+        p0, v0, pf, vf = self._states()
+        traj = self.trajectories
+        acc = c.tensor(traj["accelerations"])
+        dev = (c.tensor(traj["positions"]), c.tensor(traj["velocities"]), acc)
+        cost_before = float(np.sum(traj["accelerations"] ** 2))
+        found = c.list_conflicts(N, K, D, h, self.R, *dev)
+        info = {"conflicts_before": int(found.size), "conflicts_per_pass": [], "passes": 0, "holds": 0, "repaired": found.size == 0,
+                "stopped_by": "clean" if found.size == 0 else "max_passes", "cost_ratio": 1.0, "iterations_per_pass": [],
+                "admm_steps_per_pass": [], "update_holds_ms": [], "apply_holds_ms": []}
+        if found.size and max_passes > 0:
+            self._ensure_qp().set_problem(self._limits(), self._space(), p0, v0, pf, vf)
+            self._rho_start = 0.0
+            table, n_holds = c.hold_table(capacity=max(1024, 4 * found.size))
+        try:
+            while found.size and info["passes"] < max_passes:
+                table, n_holds, info["holds"] = c.update_holds(N, K, D, h, self.R, *dev, found, table, n_holds, pad)
+                info["update_holds_ms"].append(c.last_pair_ms())
+                self._holds = (table, n_holds)
+                x, iterations, steps, ok = acc, 0, 0, True
+                while iterations < max_iterations:
+                    new = self._solve_with_avoidance_constraints(x)
+                    iterations += 1
+                    steps += int(self._last_qp_info["iter"])
+                    ok = self._last_qp_info["status_val"] in (1, 2)
+                    if not ok:
+                        break
+                    _, _, rel = c.rel_step(new, x)
+                    x = new
+                    if rel <= self.convergence_tolerance:
+                        break
+                info["passes"] += 1
+                info["iterations_per_pass"].append(iterations)
+                info["admm_steps_per_pass"].append(steps)
+                info["apply_holds_ms"].append(float(self._pairs.last_holds_ms))
+                if not ok:
+                    info["stopped_by"] = "qp_status"
+                    break
+                pos, vel = self._kinematics(x)
+                acc, dev = x, (pos, vel, x)
+                found = c.list_conflicts(N, K, D, h, self.R, *dev)
+                info["conflicts_per_pass"].append(int(found.size))
+                self.trajectories = {"positions": pos.cpu().numpy(), "velocities": vel.cpu().numpy(),
+                                     "accelerations": x.cpu().numpy()}
+                if found.size == 0:
+                    info["repaired"], info["stopped_by"] = True, "clean"
+        finally:
+            self._holds = None
+        info["cost_ratio"] = float(np.sum(self.trajectories["accelerations"] ** 2)) / cost_before if cost_before > 0 else 1.0
+        info["time_sec"] = time.perf_counter() - t_start
+        self.last_info["repair"] = info
+        return info
 
     # ------------------------------------------------------------------------------------------------
     # visualisation passthroughs (scp.py:644-840): host-side matplotlib over the stored numpy trajectories

@@ -333,6 +333,53 @@ int scp_delay_margins(scp_ctx* ctx, int N, int K, int D, double h, double R, int
 /* Segments of the latest scp_delay_margins of this ctx whose quartic was minimised; a cost figure.  Synchronises. */
 int scp_ctx_last_delay_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
 
+/* ---- holds: repair between-sample conflicts with a separating half-plane per segment ------------------------------------------
+ * A purely additive part of ABI version 7: one struct and two functions, nothing else changes.
+ * A HOLD (row r = (k', q), unit vector e, margin c >= 0) replaces collision row r of the linearisation by the FIXED half-plane
+ *   e . (p_i[k'] - p_j[k']) >= R + c,   in the row form of scp_linearize_pairs:  eta_r = e,
+ *   l_r = (R + c) - e . ((p0_i - p0_j) + (k' h)(v0_i - v0_j)),
+ * which does not depend on the linearisation point.  If the rows k and k + 1 of a pair carry the same e with margin c,
+ * e . d(t) (d: the relative motion in segment k, a quadratic in t) is >= R + c at both ends of the segment, hence
+ * >= R + c - |e . (a_i - a_j)[k]| h^2 / 8 inside it, and |d(t)| >= e . d(t).
+ *
+ * scp_update_holds: one repair pass's table update.  Every record of scp_list_conflicts (row (k, q), min_dist, t_min) whose pair
+ * lies in [q_begin, q_end) yields, with the differences of pos / vel / acc[.][k] taken i minus j, every product and every sum
+ * rounded on its own (no contraction) and coordinates in ascending order:
+ *   t = t_min;  dm = dp + (t dv + ((0.5 t) t) da);  n = sqrt(sum_d dm_d^2);
+ *   n >= 1e-6: e = dm / n;  otherwise w = dv + t da and  2-D: e = (-w_1, w_0) / |w|;  3-D: e = (w x e_m) / |w x e_m| with m the
+ *   coordinate of the smallest |w_m| (the lowest on ties);  |w| < 1e-12: e = e_0;
+ *   the shortfall s = (R - min_dist) + pad.
+ * The record proposes (e, s) for row (k, q) and, if k + 1 < K, for row (k + 1, q).  Several proposals for one row: the largest
+ * s wins, ties go to the proposal of the smaller conflict row.  Then the merge into the table (sorted by row, unique rows): a
+ * row already held takes the new e and its margin becomes old + s; a new row enters with margin s.
+ * `conflicts` is a list as scp_list_conflicts leaves it (ascending rows), `table` has room for `capacity` records, *n_holds
+ * (in / out) of them are in use; all are DEVICE memory.  Capacity as scp_list_conflicts: if the result needs more than
+ * `capacity` records the table is left as it was, *n_holds receives the size needed and the call returns SCP_OK.
+ * Deterministic, no floating-point atomics.  The largest table (and the longest conflict list) is SCP_HOLD_MAX_TABLE records;
+ * beyond it the call returns SCP_ERR_CAPACITY.  Argument checks, stream and timing as scp_list_conflicts; the host reads the two
+ * counts first (drains the stream).
+ *
+ * scp_apply_holds: for every hold whose pair lies in [q_begin, q_end), e goes to the SoA planes `eta` and l_r (the formula
+ * above, no contraction) to `l` at the local row, as scp_linearize_pairs lays them out, and the row's bit is set in
+ * sel_bitmap; new_rows receives, in ascending order, the global ids of the holds whose bit was clear, *n_new (DEVICE) their
+ * number.  If *n_new > new_cap NOTHING is written at all (planes, bitmap, list): repeat the call with a longer list.  Every
+ * other entry of the planes and of the bitmap keeps its bits. */
+#define SCP_HOLD_MAX_TABLE (1 << 20)
+typedef struct scp_hold {   /* 48 bytes */
+  uint64_t row;       /* k' * pairs + q */
+  double eta[3];      /* the unit vector e; eta[2] = 0 in 2-D */
+  double margin;      /* c >= 0 */
+  uint64_t reserved;  /* 0 */
+} scp_hold;
+int scp_update_holds(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                     const double* pos, const double* vel, const double* acc, const scp_conflict* conflicts,
+                     const uint64_t* n_conflicts /* DEVICE */, double pad, scp_hold* table, int64_t capacity,
+                     uint64_t* n_holds /* DEVICE, in / out */);
+int scp_apply_holds(scp_ctx* ctx, int N, int K, int D, double h, double R, int64_t q_begin, int64_t q_end,
+                    const scp_hold* table, const uint64_t* n_holds /* DEVICE */, const double* p0, const double* v0,
+                    double* eta, double* l, uint32_t* sel_bitmap, int64_t* new_rows, int64_t new_cap,
+                    uint64_t* n_new /* DEVICE */);
+
 /* ---- constraint generation for the joint QP (a6): full pass over the linearised rows ------------------
  * For every local row not yet marked in sel_bitmap: if (A_col x)_r < l_r - feas_tol, mark it and append its
  * global id to new_rows.  (A_col x)_r = eta_r . ((pos_i - c_i) - (pos_j - c_j))[k], c = p0 + k h v0,
