@@ -48,7 +48,8 @@ struct scp_ctx {
   size_t wg_rows_bytes;
   unsigned* d_ticket;             // its last-workgroup-done counter (zero between launches): word 0 of a 64-byte block of
                                   // device words that lives as long as the ctx ([1], [2]: the QP's tickets; [3]: the
-                                  // violations pass's "not finite" word; [10, 12): `delay_solved`; [12, 16): `solved`)
+                                  // violations pass's "not finite" word; [8, 10): `lag_solved`; [10, 12): `delay_solved`;
+                                  // [12, 16): `solved`)
   int timing;                     // HIP events around the pairwise kernels and the QP solves (scp_ctx_set_option; default on)
   int small_pass;                 // one-launch pairwise passes for small problems (scp_ctx_set_option; default on)
   int fused_step_prep;            // large problems: the prep launch of a pass derives the positions it stages from the
@@ -57,7 +58,7 @@ struct scp_ctx {
   void* gen_ws;                   // device workspace of scp_generate_grid_swap (grown on demand)
   size_t gen_ws_bytes;
   void* sep_ws;                   // device workspace of the continuous-time passes: scp_check_separation, scp_list_conflicts,
-  size_t sep_ws_bytes;            // scp_clearance_profile, scp_delay_margins (time-major records + each call's own arrays; grown on demand)
+  size_t sep_ws_bytes;            // scp_clearance_profile, scp_delay_margins, scp_lag_conflicts (time-major records + each call's own arrays; grown on demand)
   unsigned long long* solved;     // [2] segments of the latest check / of the latest profile that reached the quartic (in
                                   // the d_ticket block: a workspace that grows frees its old place, these words stay)
   bool solved_ran[2];             // that call has run on this ctx
@@ -65,6 +66,9 @@ struct scp_ctx {
   bool delay_solved_ran;
   int delay_lag_chunk, delay_time_chunk;  // lags / global segments per workgroup of scp_delay_margins; 0: chosen by the call
                                   // (scp_ctx_set_option; developer switches, results never depend on them)
+  unsigned long long* lag_solved;  // the same figure of the latest scp_lag_conflicts (in the d_ticket block too)
+  bool lag_solved_ran;
+  int lagc_lag_chunk, lagc_time_chunk;  // the same two switches of scp_lag_conflicts
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;
   void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)

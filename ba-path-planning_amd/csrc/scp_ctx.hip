@@ -49,6 +49,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
   }
   ctx->solved = (unsigned long long*)(ctx->d_ticket + 12);  // the last 16 of its 64 bytes
   ctx->delay_solved = (unsigned long long*)(ctx->d_ticket + 10);  // the 8 before them
+  ctx->lag_solved = (unsigned long long*)(ctx->d_ticket + 8);     // and the 8 before those
   *out = ctx;
   return SCP_OK;
 }
@@ -63,6 +64,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
 // and a kinematics launch; 0: those launches run as before (same results; tests/test_step_prep_gpu.py compares the two).
 // "delay_lag_chunk" / "delay_time_chunk": lags / global segments per workgroup of scp_delay_margins; 0 (default): the call
 // chooses (same results; tests/test_delay_gpu.py compares forced chunks with the call's own).
+// "lagc_lag_chunk" / "lagc_time_chunk": the same two of scp_lag_conflicts (tests/test_stagger_gpu.py).
 // "assign_wide_min_bidders" / "assign_wide_prices_in_lds" / "assign_wide_control_threads": scp_assign_goals_wide's three
 // size-dependent forks -- the bidder count from which a round runs on the whole chip (0: the call chooses; 1: every round;
 // >= N: none), where its narrow runs keep the prices (-1 auto, 0 global memory, 1 LDS where 8 N bytes fit) and the threads
@@ -86,6 +88,11 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   if (strcmp(key, "delay_lag_chunk") == 0 || strcmp(key, "delay_time_chunk") == 0) {
     if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
     (key[6] == 'l' ? ctx->delay_lag_chunk : ctx->delay_time_chunk) = value;
+    return SCP_OK;
+  }
+  if (strcmp(key, "lagc_lag_chunk") == 0 || strcmp(key, "lagc_time_chunk") == 0) {
+    if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
+    (key[5] == 'l' ? ctx->lagc_lag_chunk : ctx->lagc_time_chunk) = value;
     return SCP_OK;
   }
   if (strcmp(key, "assign_wide_min_bidders") == 0) {

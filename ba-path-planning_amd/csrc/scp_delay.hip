@@ -5,9 +5,7 @@
 // violation test and the lexicographic fold are those of the other continuous-time passes (scp_separation_device.h), and entry
 // (a, 0) is scp_clearance_profile's per_vehicle[a] bit for bit.
 //
-// Records: K + 2 per vehicle, time major -- index 0: held at the start (p[0], 0, 0); 1 .. K: the stored segments; K + 1:
-// parked at the goal (pK, 0, 0).  In the global segment g of delay s vehicle a uses record index max(g - s, -1) + 1 and
-// every b != a index min(g, K) + 1: two contiguous copies per tile and segment.
+// Records and the two-sided tile fetch: scp_delay_device.h (shared with scp_lag_conflicts).
 //
 // Exclusion: a segment (a, s, b, g) is dropped without its quartic only if its distance provably exceeds
 // T = max(R - 0.01, U), U an upper bound of the FINAL minimum of entry (a, s): the smallest minimum the workgroup has computed
@@ -25,7 +23,7 @@
 //                      (f, g, b) lexicographically, an integer count --, so no reduction depends on an order.  One partial per
 //                      (segment chunk, b tile, vehicle, lag) goes to global memory;
 //   dly_finish_kernel  one thread per entry (a, s): the fold over the segment chunks and the b tiles -> scp_delay_margin.
-#include "scp_separation_device.h"
+#include "scp_delay_device.h"
 
 namespace {
 
@@ -52,56 +50,6 @@ __device__ inline DlyEntry dly_empty() { return DlyEntry{SEP_INF, SEP_NO_ROW, 0.
 
 // an upper bound of the distance whose square is m (the rounding of the root stays below the 1e-15)
 __device__ inline double dly_bound(double m) { return sqrt(fmax(m, 0.0)) * (1.0 + 1e-15); }
-
-// The staging records.  pK = p[K-1] + (h v[K-1] + (h^2/2) a[K-1]) with every product and every sum rounded on its own, so
-// that numpy reproduces its bits.
-__global__ __launch_bounds__(256) void dly_prep_kernel(int N, int K, int D, double h, const double* __restrict__ pos,
-                                                        const double* __restrict__ vel, const double* __restrict__ acc,
-                                                        double* __restrict__ rec, unsigned long long* __restrict__ n_solved) {
-#pragma clang fp contract(off)
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (record, i)
-  if (t == 0) *n_solved = 0ULL;
-  if (t >= (int64_t)N * (K + 2)) return;
-  const int r = (int)(t / N) - 1, i = (int)(t % N);  // r = -1: held, K: parked
-  const int k = r < 0 ? 0 : (r >= K ? K - 1 : r);
-  const int64_t src = ((int64_t)i * K + k) * D;
-  double* o = rec + t * (3 * D + 1);
-  const double hh2 = 0.5 * h * h;
-  double vv = 0.0, aa = 0.0;
-  for (int d = 0; d < D; ++d) {
-    double p = pos[src + d], v = vel[src + d], a = acc[src + d];
-    if (r >= K) {
-      const double hv = h * v, ha = hh2 * a;
-      const double step = hv + ha;
-      p = p + step;
-    }
-    if (r < 0 || r >= K) v = a = 0.0;
-    o[d] = p;
-    o[D + d] = v;
-    o[2 * D + d] = a;
-    vv = fma(v, v, vv);
-    aa = fma(a, a, aa);
-  }
-  // sep_prep_kernel's upper bound of h |v| + h^2/2 |a| (exactly 0 for a held or parked record)
-  o[3 * D] = (h * sqrt(vv) + hh2 * sqrt(aa)) * (1.0 + 1e-12);
-}
-
-// TileStage with a record index per side: the a side (planes [0, 64)) stages record ra, the b side ([64, 128)) record rb
-template <int NC>
-struct DlyStage : TileStage<NC, NC> {
-  using Base = TileStage<NC, NC>;
-  __device__ __forceinline__ void fetch2(const double* __restrict__ rec, int ra, int rb, int N, int a0, int b0, int tid) {
-#pragma unroll
-    for (int e = 0; e < Base::PER_THREAD; ++e) {
-      const int x = tid + e * SEP_THREADS;
-      if (x < Base::COUNT) {
-        const int side = x / (SEP_TILE * NC), y = x % (SEP_TILE * NC);
-        const int v = min((side ? b0 : a0) + y / NC, N - 1);
-        this->pre[e] = rec[((int64_t)(side ? rb : ra) * N + v) * NC + y % NC];
-      }
-    }
-  }
-};
 
 template <int D>
 __global__ __launch_bounds__(SEP_THREADS) void dly_pass_kernel(DlyArgs a) {
@@ -232,32 +180,6 @@ __global__ __launch_bounds__(256) void dly_finish_kernel(DlyArgs a, int n_gchunk
   out[e] = r;
 }
 
-// How a call covers its entries: tiles, lags per workgroup, global segments per workgroup
-struct DlyPlan {
-  int nta, ntb, lc, n_lchunks, gc, n_gchunks;
-  int64_t n_tiles;
-};
-
-inline DlyPlan dly_plan(const scp_ctx* ctx, int N, int K, int n_a, int S) {
-  DlyPlan p{};
-  p.nta = scp_cdiv(n_a, SEP_TILE);
-  p.ntb = scp_cdiv(N, SEP_TILE);
-  p.n_tiles = (int64_t)p.nta * p.ntb;
-  // ~8 workgroups per compute unit: first from the lags, then, where tiles x lags are still too few, from the segments (at
-  // least four per workgroup: each (lag, chunk) costs a partial per vehicle)
-  const int64_t want = 8 * (int64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
-  const int64_t tiles = std::max<int64_t>(p.n_tiles, 1);
-  const int64_t lch = std::min<int64_t>(S + 1, std::max<int64_t>(1, (want + tiles - 1) / tiles));
-  p.lc = ctx->delay_lag_chunk > 0 ? std::min(ctx->delay_lag_chunk, S + 1) : scp_cdiv(S + 1, lch);
-  p.n_lchunks = scp_cdiv(S + 1, p.lc);
-  const int G = K + S;
-  const int64_t wgs = tiles * p.n_lchunks;
-  const int64_t gch = std::min<int64_t>(G, std::max<int64_t>(1, (want + wgs - 1) / wgs));
-  p.gc = ctx->delay_time_chunk > 0 ? std::min(ctx->delay_time_chunk, G) : std::max(std::min(4, G), scp_cdiv(G, gch));
-  p.n_gchunks = scp_cdiv(G, p.gc);
-  return p;
-}
-
 }  // namespace
 
 extern "C" int scp_delay_margins(scp_ctx* ctx, int N, int K, int D, double h, double R, int a_begin, int a_end, int max_lag,
@@ -271,7 +193,7 @@ extern "C" int scp_delay_margins(scp_ctx* ctx, int N, int K, int D, double h, do
   SCP_REQUIRE(ctx, pos && vel && acc && out, "%s: null pointer", who);
   SCP_REQUIRE(ctx, h > 0.0 && h < SEP_INF, "%s: bad time step h=%g", who, h);
   const int n_a = a_end - a_begin;
-  const DlyPlan plan = dly_plan(ctx, N, K, n_a, max_lag);
+  const DlyPlan plan = dly_plan(ctx, N, K, n_a, max_lag, ctx->delay_lag_chunk, ctx->delay_time_chunk);
   SCP_REQUIRE(ctx, plan.n_tiles < ((int64_t)1 << 31) && plan.n_lchunks <= 65535 && plan.n_gchunks <= 65535,
               "%s: %lld tiles x %d lag chunks x %d segment chunks exceed the grid; shard the vehicle range", who,
               (long long)plan.n_tiles, plan.n_lchunks, plan.n_gchunks);

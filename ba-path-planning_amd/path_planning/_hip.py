@@ -187,6 +187,16 @@ DELAY_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("partn
 NO_INDEX = 2**32 - 1  # UINT32_MAX: "none" in the partner / segment of a delay margin
 
 
+class StartScheduleStats(C.Structure):
+    """struct scp_start_schedule_stats (scp_schedule_starts; DEVICE)"""
+    _fields_ = [("n_delayed", C.c_int32), ("n_unplaced", C.c_int32), ("max_delay", C.c_int32), ("first_unplaced", C.c_int32),
+                ("total_delay", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+MAX_LAG = 63          # scp_lag_conflicts / scp_schedule_starts: one bit per lag in a 64-bit word
+SCHEDULE_MAX_N = 16384  # scp_schedule_starts
+
+
 class AssignStats(C.Structure):
     """struct scp_assign_stats (scp_assign_goals; one per scenario, a DEVICE array)"""
     _fields_ = [("cost_q", C.c_int64), ("cost_q_identity", C.c_int64), ("quantum", C.c_double), ("rounds", C.c_int64),
@@ -217,6 +227,7 @@ EXPORTS = [
     "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
     "scp_clearance_profile", "scp_ctx_last_clearance_solved",
     "scp_delay_margins", "scp_ctx_last_delay_solved",
+    "scp_lag_conflicts", "scp_ctx_last_lag_solved", "scp_schedule_starts",
     "scp_update_holds", "scp_apply_holds",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
@@ -280,6 +291,9 @@ def load_library():
     lib.scp_ctx_last_clearance_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_delay_margins.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
     lib.scp_ctx_last_delay_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.scp_lag_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
+    lib.scp_ctx_last_lag_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.scp_schedule_starts.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.scp_update_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp]
     lib.scp_apply_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
@@ -393,7 +407,8 @@ class Context:
         "single_launch_passes" (one-launch pairwise passes for small problems), "fused_step_prep" (large problems: the prep
         launch of a pass derives the positions it stages itself; results never depend on it), "assign_wide_min_bidders" /
         "assign_wide_prices_in_lds" / "assign_wide_control_threads" (the three forks of assign_goals_wide; results never
-        depend on them)"""
+        depend on them), "delay_lag_chunk" / "delay_time_chunk" and "lagc_lag_chunk" / "lagc_time_chunk" (lags / global segments
+        per workgroup of delay_margins and of lag_conflicts, 0: chosen by the call; results never depend on them)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
@@ -594,6 +609,50 @@ class Context:
         n = C.c_uint64()
         self.check(self.lib.scp_ctx_last_delay_solved(self.h, C.byref(n)))
         return int(n.value)
+
+    def lag_conflicts(self, N, K, D, h, R, pos, vel, acc, max_lag, a_begin=0, a_end=None, device=False):
+        """scp_lag_conflicts for the vehicles [a_begin, a_end) and the lags 0 .. max_lag: bit s of mask[a - a_begin][b] says
+        that a, started s steps late, conflicts with b.  The words live in an int64 torch tensor used as raw 8-byte storage
+        (device=True returns that tensor, for schedule_starts); otherwise a numpy uint64 array of shape (a_end - a_begin, N) --
+        synchronises."""
+        torch = _torch()
+        a_end = N if a_end is None else a_end
+        rows = max(a_end - a_begin, 0)
+        out = torch.empty((max(rows, 1), max(N, 1)), dtype=torch.int64, device=self.tdev)  # (an empty range: still a pointer)
+        self.check(self.lib.scp_lag_conflicts(self.h, N, K, D, h, R, a_begin, a_end, max_lag, pos.data_ptr(), vel.data_ptr(),
+                                              acc.data_ptr(), out.data_ptr()))
+        out = out[:rows]
+        return out if device else out.cpu().numpy().view(np.uint64)
+
+    def last_lag_solved(self):
+        """segments of the latest lag_conflicts that needed the quartic's minimum"""
+        n = C.c_uint64()
+        self.check(self.lib.scp_ctx_last_lag_solved(self.h, C.byref(n)))
+        return int(n.value)
+
+    def schedule_starts(self, mask, max_lag, order=None):
+        """scp_schedule_starts: the greedy launch schedule of the (N, N) pair-lag masks (a numpy uint64 array or the int64
+        device tensor of lag_conflicts(device=True)), the vehicles taken in `order` (a permutation; None: 0 .. N-1).  Returns
+        the delays (numpy int32, -1: unplaced) and the stats as a dictionary -- synchronises."""
+        torch = _torch()
+        if not torch.is_tensor(mask):
+            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint64).view(np.int64))
+        mask = mask.to(device=self.tdev, dtype=torch.int64).contiguous()
+        if mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
+            raise ValueError(f"schedule_starts: the masks must be (N, N), not {tuple(mask.shape)}")
+        N = int(mask.shape[0])
+        od = None
+        if order is not None:
+            od = order if torch.is_tensor(order) else torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
+            od = od.to(device=self.tdev, dtype=torch.int32).reshape(-1).contiguous()
+            if od.numel() != N:
+                raise ValueError(f"schedule_starts: order has {od.numel()} entries for {N} vehicles")
+        delay = torch.empty(max(N, 1), dtype=torch.int32, device=self.tdev)
+        stats = torch.zeros(C.sizeof(StartScheduleStats), dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_schedule_starts(self.h, N, int(max_lag), mask.data_ptr(), od.data_ptr() if od is not None else None,
+                                                delay.data_ptr(), stats.data_ptr()))
+        st = StartScheduleStats.from_buffer_copy(stats.cpu().numpy().tobytes())
+        return delay[:N].cpu().numpy(), {f: int(getattr(st, f)) for f, _ in StartScheduleStats._fields_ if f != "reserved"}
 
     def last_separation_solved(self):
         """segments of the latest check_separation that needed the quartic's minimum (the rest: one comparison)"""

@@ -42,6 +42,10 @@ def build_parser():
                    help="--continuous-check, and one more line: the vehicle that tolerates the smallest late start (alone, in "
                         "whole time steps up to STEPS) before it comes closer than the minimum distance - 0.01 m to anybody, "
                         "who limits it and where; with --save-prefix also <prefix>_delay.pdf")
+    p.add_argument("--stagger-starts", type=int, default=None, metavar="STEPS",
+                   help="after the solve, look for late starts of at most STEPS whole time steps that remove the between-sample "
+                        "conflicts without changing a plan (pair-lag conflict masks and a greedy schedule by vehicle index) and "
+                        "print the summary and the delayed vehicles; the checks and plots still show the plans as solved")
     p.add_argument("--repair-conflicts", type=int, nargs="?", const=6, default=None, metavar="PASSES",
                    help="after the solve, remove the between-sample conflicts with holds (fixed separating half-planes on the "
                         "two rows around every conflicting segment, at most PASSES passes, default 6) and print the report; "
@@ -119,6 +123,15 @@ def main(argv=None):
             print(f"Conflict repair: {counts} conflicting segments in {rep['passes']} passes ({rep['holds']} holds, stopped by "
                   f"{rep['stopped_by']}), cost ratio {rep['cost_ratio']:.4f}, {rep['time_sec']:.3f} s"
                   + ("" if rep["repaired"] else "; NOT repaired"))
+        if args.stagger_starts is not None:
+            st = solver.stagger_starts(args.stagger_starts)
+            print(f"Staggered starts: {st['n_delayed']} of {n_vehicles} vehicles delayed by up to {st['max_delay']} steps "
+                  f"({st['max_delay'] * time_step:.2f} s; {st['total_delay']} steps in all), conflicting segments "
+                  f"{st['conflicts_before']} -> {st['conflicts_after']}, minimum distance {st['min_distance_after']:.4f} m over "
+                  f"{st['horizon_steps']} steps, {st['time_sec']:.3f} s"
+                  + ("" if st["scheduled"] else f"; {st['n_unplaced']} vehicles found NO delay"))
+            for v in np.nonzero(st["delays"] > 0)[0]:
+                print(f"  vehicle {v}: starts {st['delays'][v]} steps ({st['delays'][v] * time_step:.2f} s) late")
         if args.continuous_check or args.list_conflicts or args.clearance or args.delay_tolerance is not None:
             extras = {k: True for k, on in (("conflicts", args.list_conflicts), ("clearance", args.clearance)) if on}
             if args.delay_tolerance is not None:

@@ -170,6 +170,13 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
             steps = solver.validate_solution(continuous=True, delay=int(cfg["delay_tolerance"]))["delay_tolerance"]["steps"]
             record["delay_tolerance_steps"] = [int(x) for x in steps]
             record["min_delay_tolerance_steps"] = int(steps.min())
+        if cfg.get("stagger_starts") is not None:
+            # (only with --stagger-starts; the plans, and everything above, describe the fleet as solved)
+            st = solver.stagger_starts(int(cfg["stagger_starts"]))
+            record["stagger_max_delay"] = int(st["max_delay"])
+            record["stagger_n_delayed"] = int(st["n_delayed"])
+            record["stagger_n_unplaced"] = int(st["n_unplaced"])
+            record["stagger_conflicts_after"] = int(st["conflicts_after"])
         if save_path is not None:
             np.savez_compressed(save_path, initial_positions=np.asarray(init_pos), final_positions=np.asarray(final_pos),
                                 space_dims=np.asarray(space, dtype=float), **solver.trajectories)
@@ -249,6 +256,10 @@ def build_parser():
                    help="add the delay tolerance to every record: delay_tolerance_steps (per vehicle, the largest late start in "
                         "whole time steps up to STEPS, of that vehicle alone, that keeps every segment at R - 0.01 or more; -1: "
                         "in conflict on schedule) and min_delay_tolerance_steps")
+    p.add_argument("--stagger-starts", type=int, default=None, metavar="STEPS",
+                   help="after every solve, look for late starts of at most STEPS whole time steps that remove the between-sample "
+                        "conflicts without changing a plan (SCP.stagger_starts) and add stagger_max_delay, stagger_n_delayed, "
+                        "stagger_n_unplaced and stagger_conflicts_after to its record")
     p.add_argument("--repair-conflicts", type=int, nargs="?", const=6, default=None, metavar="PASSES",
                    help="after every solve, remove the between-sample conflicts with holds (SCP.repair_conflicts, at most PASSES "
                         "passes, default 6) and add conflicts_before, conflicts_after and repair_passes to its record")
@@ -304,6 +315,8 @@ def main(argv=None):
             cfg["assign_method"] = args.assign_method
     if args.delay_tolerance is not None:  # (likewise)
         cfg["delay_tolerance"] = int(args.delay_tolerance)
+    if args.stagger_starts is not None:  # (likewise)
+        cfg["stagger_starts"] = int(args.stagger_starts)
     if args.repair_conflicts is not None:  # (likewise)
         cfg["repair_conflicts"] = int(args.repair_conflicts)
     cfg["carry_rho"] = bool(args.carry_rho)
@@ -391,7 +404,9 @@ def main(argv=None):
         res["trial_index"] = trial
         if job in scenario_ok:
             res["scenario_ok"] = scenario_ok[job]
-        for key in ("delay_tolerance_steps", "min_delay_tolerance_steps"):  # (--delay-tolerance: the record's last fields)
+        # (--delay-tolerance, --stagger-starts: the record's last fields)
+        for key in ("delay_tolerance_steps", "min_delay_tolerance_steps", "stagger_max_delay", "stagger_n_delayed",
+                    "stagger_n_unplaced", "stagger_conflicts_after"):
             if key in res:
                 res[key] = res.pop(key)
         status_str = "OK" if res["status"] == "success" else f"ERR ({res['error']})"

@@ -27,6 +27,7 @@ import numpy as np
 from .. import _hip
 from .._sharding import Shard
 from .conflicts import conflict_windows, pairs_from_index
+from .stagger import staggered_fleet
 
 # The reference's callers build a NEW solver object per scenario (compute_trajectories_batch.py:103-117).  Here an object owns a
 # library context and a native solver (device workspace, pinned host words, the K x K blocks cached per rho): ~0.7 ms to
@@ -192,6 +193,7 @@ class SCP:
         self._qp = None
         self._pairs = None
         self._holds = None  # (device table, count) of repair_conflicts while one of its passes runs
+        self.staggered = None  # the fleet of the latest stagger_starts (its trajectories stay as they are)
         self._dev = {}
         self.last_info = {}
 
@@ -1035,6 +1037,61 @@ class SCP:
         info["cost_ratio"] = float(np.sum(self.trajectories["accelerations"] ** 2)) / cost_before if cost_before > 0 else 1.0
         info["time_sec"] = time.perf_counter() - t_start
         self.last_info["repair"] = info
+        return info
+
+    # ------------------------------------------------------------------------------------------------
+    # staggered starts (not in the reference): pair-lag masks and a greedy launch schedule, DESIGN.md section 3.7
+    # ------------------------------------------------------------------------------------------------
+    def stagger_starts(self, max_delay, order=None):
+        """Remove the between-sample conflicts of the stored trajectories WITHOUT changing a plan: some vehicles start a few
+        whole steps later, at most ``max_delay`` (an int in [0, min(K, 63)]).  One device pass computes, for every ordered pair
+        and every lag, whether the pair conflicts when the first vehicle starts that many steps after the second
+        (scp_lag_conflicts); a greedy schedule then takes the vehicles in ``order`` (a permutation of 0 .. N-1; None: by
+        index) and gives each the smallest delay that conflicts with nobody placed before it (scp_schedule_starts), -1 if
+        there is none -- such a vehicle is unplaced, flies undelayed and is reported.  No QP is solved, so this also serves
+        plans of ``generate_trajectories(max_iterations=0)`` and fleets whose joint QP fails.  One rank only.
+
+        ``self.trajectories`` is left untouched; the staggered fleet -- arrays (N, K + Dmax, D), Dmax the largest delay, every
+        vehicle held at its start before it leaves and parked at its goal after it has arrived -- is stored as
+        ``self.staggered`` ({"positions", "velocities", "accelerations", "delays"}) and judged by the continuous-time check.
+        Returns (and stores in ``last_info["stagger"]``) a dictionary: ``delays`` (int array, -1: unplaced), ``scheduled`` (every
+        vehicle placed), ``n_delayed``, ``n_unplaced``, ``max_delay``, ``total_delay``, ``conflicts_before`` /
+        ``conflicts_after`` (violating segments of the stored and of the staggered fleet, scp_check_separation),
+        ``min_distance_after``, ``horizon_steps`` (K + Dmax), ``lag_conflicts_ms`` / ``schedule_ms`` (device time of the two
+        calls) and ``time_sec``."""
+        if self.trajectories is None:
+            raise ValueError("Trajectories not generated yet")
+        if self.shard.world != 1:
+            raise ValueError("stagger_starts supports one rank only (world_size == 1)")
+        top = min(self.K, _hip.MAX_LAG)
+        if isinstance(max_delay, bool) or not isinstance(max_delay, (int, np.integer)) or not 0 <= max_delay <= top:
+            raise ValueError(f"max_delay={max_delay!r}: the largest delay is a whole number of steps in [0, min(K, 63) = {top}]")
+        if self.N > _hip.SCHEDULE_MAX_N:
+            raise ValueError(f"stagger_starts schedules at most {_hip.SCHEDULE_MAX_N} vehicles")
+        if order is not None:
+            order = np.asarray(order, dtype=np.int64).reshape(-1)
+            if order.size != self.N or not np.array_equal(np.sort(order), np.arange(self.N)):
+                raise ValueError("order must be a permutation of 0 .. N-1")
+        t_start = time.perf_counter()
+        N, K, D, h, c = self.N, self.K, self.D, self.h, self._ctx
+        S = int(max_delay)
+        host = tuple(self.trajectories[k] for k in ("positions", "velocities", "accelerations"))
+        dev = tuple(c.tensor(x) for x in host)
+        before = c.check_separation(N, K, D, h, self.R, *dev)
+        mask = c.lag_conflicts(N, K, D, h, self.R, *dev, S, device=True)
+        lag_ms = c.last_pair_ms()
+        delays, st = c.schedule_starts(mask, S, order)
+        schedule_ms = c.last_pair_ms()
+        pos, vel, acc = staggered_fleet(*host, h, delays)
+        horizon = pos.shape[1]
+        after = c.check_separation(N, horizon, D, h, self.R, c.tensor(pos), c.tensor(vel), c.tensor(acc))
+        self.staggered = {"positions": pos, "velocities": vel, "accelerations": acc, "delays": delays.astype(np.int64)}
+        info = {"delays": delays.astype(np.int64), "scheduled": st["n_unplaced"] == 0, "n_delayed": st["n_delayed"],
+                "n_unplaced": st["n_unplaced"], "max_delay": st["max_delay"], "total_delay": st["total_delay"],
+                "conflicts_before": int(before["n_violating"]), "conflicts_after": int(after["n_violating"]),
+                "min_distance_after": float(after["min_dist"]), "horizon_steps": int(horizon), "lag_conflicts_ms": lag_ms,
+                "schedule_ms": schedule_ms, "time_sec": time.perf_counter() - t_start}
+        self.last_info["stagger"] = info
         return info
 
     # ------------------------------------------------------------------------------------------------

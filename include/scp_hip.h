@@ -155,7 +155,8 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     from acc_in at the start of scp_solver_step, from the QP's time-major solution in every round -- instead of following
  *     a layout change and a kinematics launch.  0: those launches run separately.
  *   "delay_lag_chunk", "delay_time_chunk" (default 0: chosen by the call): the lags / the global segments one workgroup of
- *     scp_delay_margins covers; developer switches for tests and measurements. */
+ *     scp_delay_margins covers; developer switches for tests and measurements.
+ *   "lagc_lag_chunk", "lagc_time_chunk" (default 0: chosen by the call): the same two of scp_lag_conflicts. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -332,6 +333,54 @@ int scp_delay_margins(scp_ctx* ctx, int N, int K, int D, double h, double R, int
                       scp_delay_margin* out /* DEVICE, [a_end - a_begin][max_lag + 1] */);
 /* Segments of the latest scp_delay_margins of this ctx whose quartic was minimised; a cost figure.  Synchronises. */
 int scp_ctx_last_delay_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
+
+/* ---- staggered starts: pair-lag conflict masks and a greedy launch schedule ------------------------------------------------
+ * A purely additive part of ABI version 7: one struct and three functions, nothing else changes.
+ * The cheapest remedy for between-sample conflicts: every plan stays as it is and some vehicles start a few steps later.
+ * Records, lags, global segments, the segment distance sqrt(max(min f, 0)) and the threshold R - 0.01 are those of
+ * scp_delay_margins above; that call reduces over b, so it covers one late vehicle among punctual ones.  Here the same segment
+ * test is kept per ORDERED pair and per lag:
+ *   MASKS.  For a != b and s = 0 .. max_lag, bit s of mask[a][b] is set iff at least one global segment g in [0, K + s)
+ *     violates the threshold, the segment comparing record max(g - s, -1) of a with record min(g, K) of b -- exactly the (b, g)
+ *     entry (a, s) of scp_delay_margins counts in n_violating, decided on the same bits.  mask[a][a] = 0, bits above max_lag are
+ *     0, and bit 0 is symmetric (the quartic's coefficients carry the same bits whichever vehicle is subtracted from which).
+ *   ONLY THE RELATIVE LAG MATTERS.  If a starts d_a steps late and b d_b, d_a >= d_b, the segments before d_b compare two held
+ *     records (a constant: f(0) of the first segment that lag d_a - d_b examines), those after K + d_a two parked records (the
+ *     goal distance: the END of the last segment that lag examines, equal to it up to rounding), and in between lies the
+ *     situation of lag d_a - d_b of (a, b).  So the pair conflicts iff bit d_a - d_b of mask[a][b] is set (d_a < d_b: bit
+ *     d_b - d_a of mask[b][a]) -- unless a start or goal distance lies within rounding of the threshold.
+ *   SCHEDULE.  Vehicles are taken in the order order[0], order[1], ... (a permutation of 0 .. N-1; NULL: the identity).
+ *     Vehicle v gets the smallest d in [0, max_lag] that conflicts with no vehicle u PLACED before it: for d >= d_u bit d - d_u
+ *     of mask[v][u] must be clear, for d < d_u bit d_u - d of mask[u][v].  Without such a d, delay[v] = -1: v is unplaced and
+ *     takes no part in the later comparisons.  Integers only, deterministic; a fleet without lag-0 conflicts gets all zeros.
+ *   THE STAGGERED FLEET has the horizon K + Dmax, Dmax the largest delay; vehicle v uses record clamp(g - d_v, -1, K) in
+ *     segment g (unplaced vehicles: d = 0).  It is an ordinary input of scp_check_separation and scp_list_conflicts, which
+ *     judge the result.
+ * scp_lag_conflicts: arguments, argument checks, error codes, stream and timing behaviour as scp_delay_margins, plus
+ * max_lag <= 63 (so 0 <= max_lag <= min(K, 63)).  `mask` is DEVICE memory, row a - a_begin of N words per vehicle of the range;
+ * an empty range writes nothing; the rows of disjoint ranges, concatenated, are the bytes of the full call (the vehicle range
+ * is the multi-rank cut).  A segment is excluded without minimising its quartic only if its distance provably exceeds
+ * R - 0.01, and an (a, b, s) whose bit is set may skip its remaining segments; the mask never depends on either
+ * (scp_ctx_last_lag_solved).  Results are combined by integer ORs only and do not depend on how lags and segments are cut over
+ * workgroups: scp_ctx_set_option "lagc_lag_chunk" / "lagc_time_chunk" (default 0: chosen by the call) are developer switches.
+ * scp_schedule_starts: all pointers DEVICE; supported 1 <= N <= 16384, 0 <= max_lag <= 63; only bits 0 .. max_lag of a word
+ * are looked at.  One workgroup; the call synchronises (scp_ctx_last_pair_ms then reports its kernel).  An `order` that is no
+ * permutation returns SCP_ERR_INVALID after the launch; delay and stats are then undefined. */
+typedef struct scp_start_schedule_stats {   /* DEVICE, 48 bytes */
+  int32_t n_delayed;       /* vehicles with delay > 0 */
+  int32_t n_unplaced;      /* vehicles with delay = -1 */
+  int32_t max_delay;       /* the largest delay (0 if nobody is placed) */
+  int32_t first_unplaced;  /* the first vehicle, in schedule order, that found no delay; -1: none */
+  int64_t total_delay;     /* sum of the delays of the placed vehicles */
+  int64_t reserved[3];     /* 0 */
+} scp_start_schedule_stats;
+int scp_lag_conflicts(scp_ctx* ctx, int N, int K, int D, double h, double R, int a_begin, int a_end, int max_lag,
+                      const double* pos, const double* vel, const double* acc,
+                      uint64_t* mask /* DEVICE, [a_end - a_begin][N] */);
+/* Segments of the latest scp_lag_conflicts of this ctx whose quartic was minimised; a cost figure.  Synchronises. */
+int scp_ctx_last_lag_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
+int scp_schedule_starts(scp_ctx* ctx, int N, int max_lag, const uint64_t* mask /* [N][N] */,
+                        const int32_t* order /* [N] or NULL */, int32_t* delay /* [N] */, scp_start_schedule_stats* stats);
 
 /* ---- holds: repair between-sample conflicts with a separating half-plane per segment ------------------------------------------
  * A purely additive part of ABI version 7: one struct and two functions, nothing else changes.
