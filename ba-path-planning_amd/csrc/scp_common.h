@@ -48,7 +48,7 @@ struct scp_ctx {
   size_t wg_rows_bytes;
   unsigned* d_ticket;             // its last-workgroup-done counter (zero between launches): word 0 of a 64-byte block of
                                   // device words that lives as long as the ctx ([1], [2]: the QP's tickets; [3]: the
-                                  // violations pass's "not finite" word; [8, 10): `lag_solved`; [10, 12): `delay_solved`;
+                                  // violations pass's "not finite" word; [4, 8): the two words of scp_schedule_starts_batch; [8, 10): `lag_solved`; [10, 12): `delay_solved`;
                                   // [12, 16): `solved`)
   int timing;                     // HIP events around the pairwise kernels and the QP solves (scp_ctx_set_option; default on)
   int small_pass;                 // one-launch pairwise passes for small problems (scp_ctx_set_option; default on)
@@ -69,6 +69,9 @@ struct scp_ctx {
   unsigned long long* lag_solved;  // the same figure of the latest scp_lag_conflicts (in the d_ticket block too)
   bool lag_solved_ran;
   int lagc_lag_chunk, lagc_time_chunk;  // the same two switches of scp_lag_conflicts
+  int stg_batch_threads;          // threads per workgroup of scp_schedule_starts_batch: 0 chosen by the call, 256 or 1024
+  int stg_batch_transposed;       // it reads the masks' columns from a transposed copy it makes in sep_ws: -1 chosen by the
+                                  // call (from 16 candidates on), 0 never, 1 always
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;
   void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)

@@ -32,6 +32,7 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
   ctx->fused_step_prep = 1;
   ctx->near_pass = 1;  // auto (scp_ctx_set_near_pass)
   ctx->asgw_prices_in_lds = -1;  // auto
+  ctx->stg_batch_transposed = -1;  // auto
   if (hipDeviceGetAttribute(&ctx->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ctx->n_cu = 0;
   if (hipMalloc(&ctx->d_scratch, 72 * sizeof(double)) != hipSuccess ||
       hipMemset(ctx->d_scratch, 0, 72 * sizeof(double)) != hipSuccess ||  // ([64]: ticket counter of scp_rel_step)
@@ -65,6 +66,10 @@ extern "C" int scp_ctx_create(int device, void* hip_stream, scp_ctx** out) {
 // "delay_lag_chunk" / "delay_time_chunk": lags / global segments per workgroup of scp_delay_margins; 0 (default): the call
 // chooses (same results; tests/test_delay_gpu.py compares forced chunks with the call's own).
 // "lagc_lag_chunk" / "lagc_time_chunk": the same two of scp_lag_conflicts (tests/test_stagger_gpu.py).
+// "stg_batch_threads": threads per workgroup of scp_schedule_starts_batch, 0 (default): the call chooses by N, or 256 / 1024
+// (same results; tests/test_stagger_search_gpu.py compares the two).  "stg_batch_transposed": it reads the columns of the masks
+// from a transposed copy made per call in the workspace of the continuous-time passes (-1, default: from 16 candidates on; 0 never;
+// 1 always; same results, same test).
 // "assign_wide_min_bidders" / "assign_wide_prices_in_lds" / "assign_wide_control_threads": scp_assign_goals_wide's three
 // size-dependent forks -- the bidder count from which a round runs on the whole chip (0: the call chooses; 1: every round;
 // >= N: none), where its narrow runs keep the prices (-1 auto, 0 global memory, 1 LDS where 8 N bytes fit) and the threads
@@ -93,6 +98,17 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
   if (strcmp(key, "lagc_lag_chunk") == 0 || strcmp(key, "lagc_time_chunk") == 0) {
     if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
     (key[5] == 'l' ? ctx->lagc_lag_chunk : ctx->lagc_time_chunk) = value;
+    return SCP_OK;
+  }
+  if (strcmp(key, "stg_batch_threads") == 0) {
+    if (value != 0 && value != 256 && value != 1024)
+      return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0, 256 or 1024)", key, value);
+    ctx->stg_batch_threads = value;
+    return SCP_OK;
+  }
+  if (strcmp(key, "stg_batch_transposed") == 0) {
+    if (value < -1 || value > 1) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need -1, 0 or 1)", key, value);
+    ctx->stg_batch_transposed = value;
     return SCP_OK;
   }
   if (strcmp(key, "assign_wide_min_bidders") == 0) {

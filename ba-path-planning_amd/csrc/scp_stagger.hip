@@ -1,4 +1,4 @@
-// Staggered starts (scp_lag_conflicts, scp_schedule_starts; include/scp_hip.h): leave every plan as it is and start some
+// Staggered starts (scp_lag_conflicts, scp_schedule_starts, scp_schedule_starts_batch; include/scp_hip.h): leave every plan as it is and start some
 // vehicles a few steps later.
 //
 // The MASK pass keeps what scp_delay_margins reduces away: for every ORDERED pair (a, b) and every lag s = 0 .. S, bit s of
@@ -29,6 +29,12 @@
 // The OR is associative and commutative, so forbid[v] at step t is the reduction of the rule, and every thread reads the one
 // word forbid[v] and derives d itself: one barrier per step and no reduction tree.  An unplaced vehicle ORs nothing.  All
 // shifts go through shl64 / shr64, which shift in two halves: no shift count above 32 occurs.
+//
+// The order is the only free parameter of that rule.  The BATCH kernel (scp_schedule_starts_batch) runs the same steps for B
+// candidate orders at once, one workgroup of 256 or 1024 threads per candidate with its own forbid[] / pending[] in LDS; the
+// masks are read only and shared.  Thread 0 of every workgroup packs (n_unplaced, max_delay, total_delay, b) -- or total before
+// max -- into one word whose integer order is the key's lexicographic order and takes one atomicMin on a device word; the host
+// decodes the best candidate from it.  A second word takes the minimum over the candidates that are no permutation.
 #include "scp_assign_device.h"
 #include "scp_delay_device.h"
 
@@ -131,6 +137,7 @@ __global__ __launch_bounds__(SEP_THREADS) void lagc_pass_kernel(LagcArgs a) {
 
 // ---- the schedule ---------------------------------------------------------------------------------------------------------------
 constexpr int STG_MAXN = 16384;
+constexpr int STG_MAXB = 65535;  // candidates of one scp_schedule_starts_batch (16 bits of the key)
 constexpr int STG_THREADS = 1024;
 constexpr unsigned long long STG_ALL = 0xFFFFFFFFFFFFFFFFULL;
 
@@ -219,6 +226,122 @@ __global__ __launch_bounds__(STG_THREADS) void stg_schedule_kernel(int N, int S,
   }
 }
 
+// ---- the schedules of many orders ---------------------------------------------------------------------------------------------
+// The steps of stg_schedule_kernel for a workgroup of THREADS threads and an order that is given; LDS as there.  (Its own body:
+// with the steps in a function of both, stg_schedule_kernel no longer compiled to the instructions it had.)  Returns false
+// (uniform) and schedules nothing if `order` is no permutation; otherwise thread 0 holds the stats in `st` at the end.
+// mask_t: NULL, or the transposed masks (mask_t[v][w] = mask[w][v]): column v of a step is then read from a row.
+template <int THREADS>
+__device__ __forceinline__ bool stg_batch_one(int N, int S, const unsigned long long* __restrict__ mask,
+                                              const unsigned long long* __restrict__ mask_t,
+                                              const int32_t* __restrict__ order, int32_t* __restrict__ delay,
+                                              scp_start_schedule_stats& st) {
+  extern __shared__ unsigned long long stg_lds[];
+  unsigned long long* forbid = stg_lds;
+  unsigned int* pending = (unsigned int*)(stg_lds + N);
+  __shared__ int bad;
+  const int tid = threadIdx.x;
+  const int n_words = (N + 31) / 32;
+  const unsigned long long beyond = ~(shl64(1ULL, S + 1) - 1ULL);  // the delays above S: never allowed
+
+  // ---- `order` is a permutation: every entry in range, every vehicle named once -----------------------------------------------
+  if (tid == 0) bad = 0;
+  for (int x = tid; x < n_words; x += THREADS) pending[x] = 0u;
+  for (int w = tid; w < N; w += THREADS) forbid[w] = beyond;
+  __syncthreads();
+  for (int t = tid; t < N; t += THREADS) {
+    const int v = order[t];
+    if (v < 0 || v >= N) {
+      bad = 1;
+    } else {
+      const unsigned int bit = 1u << (v & 31);
+      if (atomicOr(&pending[v >> 5], bit) & bit) bad = 1;
+    }
+  }
+  __syncthreads();
+  if (bad) return false;  // (uniform) nothing is scheduled
+
+  int n_delayed = 0, n_unplaced = 0, max_delay = 0, first_unplaced = -1;  // thread 0 only
+  long long total = 0;
+  for (int t = 0; t < N; ++t) {
+    const int v = order[t];
+    const unsigned long long f = forbid[v];  // complete: the steps before this one ended with a barrier
+    const int d = f == STG_ALL ? -1 : __ffsll((long long)~f) - 1;
+    if (tid == 0) {
+      delay[v] = d;
+      pending[v >> 5] &= ~(1u << (v & 31));  // (read again only after the barrier: this step excludes v itself)
+      if (d < 0) {
+        ++n_unplaced;
+        if (first_unplaced < 0) first_unplaced = v;
+      } else {
+        n_delayed += d > 0;
+        max_delay = max(max_delay, d);
+        total += d;
+      }
+    }
+    if (d >= 0) {
+      const unsigned long long* column = mask_t ? mask_t + (int64_t)v * N : mask + v;  // mask[w][v] = column[w * stride]
+      const int64_t stride = mask_t ? 1 : N;
+      for (int w = tid; w < N; w += THREADS) {
+        if (w == v || !((pending[w >> 5] >> (w & 31)) & 1u)) continue;
+        const unsigned long long fw = forbid[w];
+        if (fw == STG_ALL) continue;  // nothing left to forbid
+        forbid[w] = fw | stg_forbidden(column[w * stride], mask[(int64_t)v * N + w], d);
+      }
+    }
+    __syncthreads();
+  }
+  st.n_delayed = n_delayed;
+  st.n_unplaced = n_unplaced;
+  st.max_delay = max_delay;
+  st.first_unplaced = first_unplaced;
+  st.total_delay = total;
+  st.reserved[0] = st.reserved[1] = st.reserved[2] = 0;
+  return true;
+}
+
+// The key of a candidate under an objective as ONE word whose integer order is the lexicographic order of the rule:
+// n_unplaced <= 2^14 (15 bits), max_delay <= 63 (6 bits), total_delay <= 63 * 16384 < 2^20 (20 bits), b < 2^16.
+__device__ __host__ inline unsigned long long stg_key(const scp_start_schedule_stats& st, int objective, unsigned int b) {
+  const unsigned long long u = (unsigned long long)st.n_unplaced, m = (unsigned long long)st.max_delay,
+                           t = (unsigned long long)st.total_delay;
+  return (u << 42) | (objective == 0 ? (m << 36) | (t << 16) : (t << 22) | (m << 16)) | b;
+}
+
+// out[c][r] = in[r][c] of N x N words: 64 x 64 tiles through LDS (a column of padding: the reads by column spread over the banks)
+__global__ __launch_bounds__(256) void stg_transpose_kernel(int N, const unsigned long long* __restrict__ in,
+                                                            unsigned long long* __restrict__ out) {
+  __shared__ unsigned long long tile[64][65];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+  for (int y = wave; y < 64; y += 4)
+    if (r0 + y < N && c0 + lane < N) tile[y][lane] = in[(int64_t)(r0 + y) * N + (c0 + lane)];
+  __syncthreads();
+  for (int y = wave; y < 64; y += 4)
+    if (c0 + y < N && r0 + lane < N) out[(int64_t)(c0 + y) * N + (r0 + lane)] = tile[lane][y];
+}
+
+// One workgroup per candidate order; no workgroup waits for another.  words[0]: the smallest key, words[1]: the lowest
+// candidate that is no permutation; both all ones at the launch.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void stg_batch_kernel(int N, int S, const unsigned long long* __restrict__ mask,
+                                                            const unsigned long long* __restrict__ mask_t,
+                                                            const int32_t* __restrict__ orders, int objective,
+                                                            int32_t* __restrict__ delay,
+                                                            scp_start_schedule_stats* __restrict__ stats,
+                                                            unsigned long long* __restrict__ words) {
+  const unsigned int b = blockIdx.x;
+  scp_start_schedule_stats st;
+  if (!stg_batch_one<THREADS>(N, S, mask, mask_t, orders + (int64_t)b * N, delay + (int64_t)b * N, st)) {
+    if (threadIdx.x == 0) atomicMin(words + 1, (unsigned long long)b);
+    return;
+  }
+  if (threadIdx.x == 0) {
+    stats[b] = st;
+    atomicMin(words, stg_key(st, objective, b));
+  }
+}
+
 }  // namespace
 
 extern "C" int scp_lag_conflicts(scp_ctx* ctx, int N, int K, int D, double h, double R, int a_begin, int a_end, int max_lag,
@@ -300,5 +423,57 @@ extern "C" int scp_schedule_starts(scp_ctx* ctx, int N, int max_lag, const uint6
   ctx->pair_timed = ctx->timing != 0;
   ctx->pair_ran = true;
   SCP_REQUIRE(ctx, *hflag == 0, "%s: order is not a permutation of 0 .. N-1", who);
+  return SCP_OK;
+}
+
+// B candidate orders on the same masks in one launch, one workgroup each, and the candidate with the smallest key.
+extern "C" int scp_schedule_starts_batch(scp_ctx* ctx, int N, int max_lag, const uint64_t* mask, int B, const int32_t* orders,
+                                         int objective, int32_t* delay, scp_start_schedule_stats* stats, int32_t* best) {
+  const char* who = "scp_schedule_starts_batch";
+  if (!ctx) return SCP_ERR_INVALID;
+  SCP_REQUIRE(ctx, mask && orders && delay && stats && best, "%s: null pointer", who);
+  SCP_REQUIRE(ctx, N >= 1 && N <= STG_MAXN, "%s: N = %d (need 1 <= N <= %d)", who, N, STG_MAXN);
+  SCP_REQUIRE(ctx, max_lag >= 0 && max_lag <= 63, "%s: max_lag = %d (need 0 <= max_lag <= 63)", who, max_lag);
+  SCP_REQUIRE(ctx, B >= 1 && B <= STG_MAXB, "%s: B = %d (need 1 <= B <= %d)", who, B, STG_MAXB);
+  SCP_REQUIRE(ctx, objective == 0 || objective == 1, "%s: objective = %d (need 0: makespan or 1: total)", who, objective);
+  SCP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (const int rc = asg_host_flag(ctx)) return rc;
+  // up to 256 vehicles no thread beyond the first 256 would have a vehicle, and a step's barrier spans 4 waves instead of 16
+  // (unmeasured); above, the loads of a step are what it waits for and 1024 threads issue them at once (at 1024 and 4096
+  // vehicles 256 threads take 1.5 and 1.1 times as long: profiles/stagger_search.txt)
+  const int threads = ctx->stg_batch_threads ? ctx->stg_batch_threads : (N <= 256 ? 256 : 1024);
+  const void* kernel = threads == 256 ? reinterpret_cast<const void*>(stg_batch_kernel<256>)
+                                      : reinterpret_cast<const void*>(stg_batch_kernel<1024>);
+  const size_t lds = sizeof(unsigned long long) * (size_t)N + sizeof(unsigned int) * (size_t)((N + 31) / 32);
+  if (lds > 48 * 1024) SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, kernel, lds));
+  // the transposed copy of the masks, in the workspace of the continuous-time passes: with it a step reads two rows instead of a
+  // row and a column.  From 16 candidates on the call is faster with it, its launch included (1024 vehicles: 0.87 against
+  // 1.19 ms at B = 16, 0.88 against 1.46 ms at B = 256; 4096: 8.8 against 13.8 ms and 9.7 against 38 ms); below 16: unmeasured
+  unsigned long long* mask_t = nullptr;
+  if (ctx->stg_batch_transposed < 0 ? B >= 16 : ctx->stg_batch_transposed) {
+    if (const int rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes, (size_t)N * N * sizeof(unsigned long long)))
+      return rc;
+    mask_t = (unsigned long long*)ctx->sep_ws;
+  }
+  hipStream_t st = ctx->stream;
+  unsigned long long* words = (unsigned long long*)(ctx->d_ticket + 4);       // [0]: smallest key, [1]: lowest bad candidate
+  unsigned long long* hwords = (unsigned long long*)(ctx->h_gen_flag + 4);    // their pinned host copy
+  const unsigned long long* mk = (const unsigned long long*)mask;
+  if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, st));
+  SCP_HIP_CHECK(ctx, hipMemsetAsync(words, 0xFF, 2 * sizeof(unsigned long long), st));
+  if (mask_t) stg_transpose_kernel<<<dim3(scp_cdiv(N, 64), scp_cdiv(N, 64)), 256, 0, st>>>(N, mk, mask_t);
+  if (threads == 256)
+    stg_batch_kernel<256><<<B, 256, lds, st>>>(N, max_lag, mk, mask_t, orders, objective, delay, stats, words);
+  else
+    stg_batch_kernel<1024><<<B, 1024, lds, st>>>(N, max_lag, mk, mask_t, orders, objective, delay, stats, words);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && ctx->timing) e = hipEventRecord(ctx->pair_ev1, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(hwords, words, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return scp_fail(ctx, SCP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  ctx->pair_timed = ctx->timing != 0;
+  ctx->pair_ran = true;
+  SCP_REQUIRE(ctx, hwords[1] == STG_ALL, "%s: candidate %llu is not a permutation of 0 .. N-1", who, hwords[1]);
+  *best = (int32_t)(hwords[0] & 0xFFFFULL);
   return SCP_OK;
 }

@@ -193,8 +193,13 @@ class StartScheduleStats(C.Structure):
                 ("total_delay", C.c_int64), ("reserved", C.c_int64 * 3)]
 
 
+START_SCHEDULE_STATS_DTYPE = np.dtype([("n_delayed", np.int32), ("n_unplaced", np.int32), ("max_delay", np.int32),
+                                       ("first_unplaced", np.int32), ("total_delay", np.int64), ("reserved", np.int64, (3,))])
+
 MAX_LAG = 63          # scp_lag_conflicts / scp_schedule_starts: one bit per lag in a 64-bit word
 SCHEDULE_MAX_N = 16384  # scp_schedule_starts
+SCHEDULE_MAX_BATCH = 65535  # candidates of one scp_schedule_starts_batch
+SCHEDULE_OBJECTIVES = {"makespan": 0, "total": 1}  # its `objective`
 
 
 class AssignStats(C.Structure):
@@ -227,7 +232,7 @@ EXPORTS = [
     "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
     "scp_clearance_profile", "scp_ctx_last_clearance_solved",
     "scp_delay_margins", "scp_ctx_last_delay_solved",
-    "scp_lag_conflicts", "scp_ctx_last_lag_solved", "scp_schedule_starts",
+    "scp_lag_conflicts", "scp_ctx_last_lag_solved", "scp_schedule_starts", "scp_schedule_starts_batch",
     "scp_update_holds", "scp_apply_holds",
     "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
     "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
@@ -294,6 +299,7 @@ def load_library():
     lib.scp_lag_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
     lib.scp_ctx_last_lag_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.scp_schedule_starts.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.scp_schedule_starts_batch.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(C.c_int32)]
     lib.scp_update_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp]
     lib.scp_apply_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
@@ -408,7 +414,10 @@ class Context:
         launch of a pass derives the positions it stages itself; results never depend on it), "assign_wide_min_bidders" /
         "assign_wide_prices_in_lds" / "assign_wide_control_threads" (the three forks of assign_goals_wide; results never
         depend on them), "delay_lag_chunk" / "delay_time_chunk" and "lagc_lag_chunk" / "lagc_time_chunk" (lags / global segments
-        per workgroup of delay_margins and of lag_conflicts, 0: chosen by the call; results never depend on them)"""
+        per workgroup of delay_margins and of lag_conflicts, 0: chosen by the call; results never depend on them),
+        "stg_batch_threads" (threads per workgroup of schedule_starts_batch: 0 chosen by the call, 256 or 1024; likewise),
+        "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
+        never, 1 always; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
@@ -653,6 +662,35 @@ class Context:
                                                 delay.data_ptr(), stats.data_ptr()))
         st = StartScheduleStats.from_buffer_copy(stats.cpu().numpy().tobytes())
         return delay[:N].cpu().numpy(), {f: int(getattr(st, f)) for f, _ in StartScheduleStats._fields_ if f != "reserved"}
+
+    def schedule_starts_batch(self, mask, max_lag, orders, objective="makespan"):
+        """scp_schedule_starts_batch: the greedy schedules of B candidate orders (array-like or device tensor of shape (B, N),
+        every row a permutation) on the same masks (as schedule_starts) in one launch.  Returns the delays (numpy int32 of
+        shape (B, N), -1: unplaced), the stats as a dictionary of length-B arrays (the fields of scp_start_schedule_stats) and
+        the candidate with the smallest key -- "makespan": (n_unplaced, max_delay, total_delay, b), "total": (n_unplaced,
+        total_delay, max_delay, b).  Synchronises."""
+        torch = _torch()
+        if objective not in SCHEDULE_OBJECTIVES:
+            raise ValueError(f"schedule_starts_batch: objective={objective!r} (need one of {sorted(SCHEDULE_OBJECTIVES)})")
+        if not torch.is_tensor(mask):
+            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint64).view(np.int64))
+        mask = mask.to(device=self.tdev, dtype=torch.int64).contiguous()
+        if mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
+            raise ValueError(f"schedule_starts_batch: the masks must be (N, N), not {tuple(mask.shape)}")
+        N = int(mask.shape[0])
+        od = orders if torch.is_tensor(orders) else torch.as_tensor(np.ascontiguousarray(orders, dtype=np.int32))
+        if od.dim() != 2 or od.shape[1] != N or od.shape[0] < 1:
+            raise ValueError(f"schedule_starts_batch: orders must be (B, {N}) with B >= 1, not {tuple(od.shape)}")
+        od = od.to(device=self.tdev, dtype=torch.int32).contiguous()
+        B = int(od.shape[0])
+        delay = torch.empty((B, max(N, 1)), dtype=torch.int32, device=self.tdev)
+        stats = torch.zeros(B * START_SCHEDULE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        best = C.c_int32(-1)
+        self.check(self.lib.scp_schedule_starts_batch(self.h, N, int(max_lag), mask.data_ptr(), B, od.data_ptr(),
+                                                      SCHEDULE_OBJECTIVES[objective], delay.data_ptr(), stats.data_ptr(),
+                                                      C.byref(best)))
+        st = stats.cpu().numpy().view(START_SCHEDULE_STATS_DTYPE)
+        return delay.cpu().numpy(), {f: st[f].copy() for f in START_SCHEDULE_STATS_DTYPE.names}, int(best.value)
 
     def last_separation_solved(self):
         """segments of the latest check_separation that needed the quartic's minimum (the rest: one comparison)"""

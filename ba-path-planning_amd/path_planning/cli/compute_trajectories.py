@@ -14,6 +14,30 @@ from ..scenarios.position_generator import generate_grid_swap, generate_position
 from ..solvers.scp import SCP
 
 
+def add_stagger_search_arguments(p):
+    """the four flags of the order search of --stagger-starts (shared with compute-trajectories-batch)"""
+    p.add_argument("--stagger-search", type=int, default=None, metavar="B",
+                   help="with --stagger-starts: schedule B candidate launch orders per round in one GPU launch (the given order, "
+                        "its reverse, random ones) and keep the best; never worse than the schedule by vehicle index")
+    p.add_argument("--stagger-rounds", type=int, default=None, metavar="R",
+                   help="with --stagger-search: R rounds (default 1); every round after the first derives its candidates from "
+                        "the best order so far")
+    p.add_argument("--stagger-seed", type=int, default=None, help="with --stagger-search: seed of the random orders (default 0)")
+    p.add_argument("--stagger-objective", choices=("makespan", "total"), default=None,
+                   help="with --stagger-search: after the fewest unplaced vehicles, prefer the smallest largest delay (makespan, "
+                        "default) or the smallest sum of delays (total)")
+
+
+def stagger_search_keywords(parser, args):
+    """the keywords of SCP.stagger_starts the four flags ask for; the flags are errors without --stagger-starts"""
+    given = {"search": args.stagger_search, "rounds": args.stagger_rounds, "seed": args.stagger_seed,
+             "objective": args.stagger_objective}
+    given = {k: v for k, v in given.items() if v is not None}
+    if given and args.stagger_starts is None:
+        parser.error("--stagger-" + next(iter(given)) + " needs --stagger-starts")
+    return given
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="compute-trajectories", description=__doc__.split("\n\n")[0])
     p.add_argument("--n-agents", type=int, default=10)
@@ -46,6 +70,7 @@ def build_parser():
                    help="after the solve, look for late starts of at most STEPS whole time steps that remove the between-sample "
                         "conflicts without changing a plan (pair-lag conflict masks and a greedy schedule by vehicle index) and "
                         "print the summary and the delayed vehicles; the checks and plots still show the plans as solved")
+    add_stagger_search_arguments(p)
     p.add_argument("--repair-conflicts", type=int, nargs="?", const=6, default=None, metavar="PASSES",
                    help="after the solve, remove the between-sample conflicts with holds (fixed separating half-planes on the "
                         "two rows around every conflicting segment, at most PASSES passes, default 6) and print the report; "
@@ -64,7 +89,9 @@ def build_parser():
 
 def main(argv=None):
     """Create collision-free trajectories for a set of initial and final positions."""
-    args = build_parser().parse_args([] if argv is None else argv)
+    parser = build_parser()
+    args = parser.parse_args([] if argv is None else argv)
+    stagger_search = stagger_search_keywords(parser, args)
     print("------ WOW Fleet Collision-Free 2D Trajectory Generation ------")
 
     n_vehicles = args.n_agents
@@ -124,12 +151,18 @@ def main(argv=None):
                   f"{rep['stopped_by']}), cost ratio {rep['cost_ratio']:.4f}, {rep['time_sec']:.3f} s"
                   + ("" if rep["repaired"] else "; NOT repaired"))
         if args.stagger_starts is not None:
-            st = solver.stagger_starts(args.stagger_starts)
+            st = solver.stagger_starts(args.stagger_starts, **stagger_search)
             print(f"Staggered starts: {st['n_delayed']} of {n_vehicles} vehicles delayed by up to {st['max_delay']} steps "
                   f"({st['max_delay'] * time_step:.2f} s; {st['total_delay']} steps in all), conflicting segments "
                   f"{st['conflicts_before']} -> {st['conflicts_after']}, minimum distance {st['min_distance_after']:.4f} m over "
                   f"{st['horizon_steps']} steps, {st['time_sec']:.3f} s"
                   + ("" if st["scheduled"] else f"; {st['n_unplaced']} vehicles found NO delay"))
+            if "search" in st:
+                se = st["search"]
+                print(f"  order search ({se['objective']}): {se['candidates']} candidates x {se['rounds_run']} rounds, best is "
+                      f"candidate {se['best_candidate']} of round {se['best_round']}; by vehicle index: "
+                      f"{se['baseline']['n_unplaced']} unplaced, largest delay {se['baseline']['max_delay']}, "
+                      f"{se['baseline']['total_delay']} steps in all" + ("" if se["improved"] else " (not improved)"))
             for v in np.nonzero(st["delays"] > 0)[0]:
                 print(f"  vehicle {v}: starts {st['delays'][v]} steps ({st['delays'][v] * time_step:.2f} s) late")
         if args.continuous_check or args.list_conflicts or args.clearance or args.delay_tolerance is not None:

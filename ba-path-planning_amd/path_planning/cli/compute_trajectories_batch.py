@@ -21,6 +21,7 @@ import numpy as np
 from ..scenarios.grid_swap_device import generate_grid_swap_batch, generate_grid_swap_device
 from ..scenarios.position_generator import generate_grid_swap, generate_positions
 from ..solvers.scp import SCP
+from .compute_trajectories import add_stagger_search_arguments, stagger_search_keywords
 
 # ---------------------------- Config (reference defaults, compute_trajectories_batch.py:14-24) -------------
 CONFIG = {
@@ -172,11 +173,16 @@ def run_single_trial(N, cfg, rng=None, seed=None, device=None, scenario=None, sa
             record["min_delay_tolerance_steps"] = int(steps.min())
         if cfg.get("stagger_starts") is not None:
             # (only with --stagger-starts; the plans, and everything above, describe the fleet as solved)
-            st = solver.stagger_starts(int(cfg["stagger_starts"]))
+            st = solver.stagger_starts(int(cfg["stagger_starts"]), **cfg.get("stagger_search", {}))
             record["stagger_max_delay"] = int(st["max_delay"])
             record["stagger_n_delayed"] = int(st["n_delayed"])
             record["stagger_n_unplaced"] = int(st["n_unplaced"])
             record["stagger_conflicts_after"] = int(st["conflicts_after"])
+            if "search" in cfg.get("stagger_search", {}):  # (only with --stagger-search; 0 candidates: the one order)
+                base = st["search"]["baseline"] if "search" in st else st
+                record["stagger_search_candidates"] = int(st["search"]["candidates"]) if "search" in st else 0
+                record["stagger_baseline_n_unplaced"] = int(base["n_unplaced"])
+                record["stagger_baseline_max_delay"] = int(base["max_delay"])
         if save_path is not None:
             np.savez_compressed(save_path, initial_positions=np.asarray(init_pos), final_positions=np.asarray(final_pos),
                                 space_dims=np.asarray(space, dtype=float), **solver.trajectories)
@@ -260,6 +266,7 @@ def build_parser():
                    help="after every solve, look for late starts of at most STEPS whole time steps that remove the between-sample "
                         "conflicts without changing a plan (SCP.stagger_starts) and add stagger_max_delay, stagger_n_delayed, "
                         "stagger_n_unplaced and stagger_conflicts_after to its record")
+    add_stagger_search_arguments(p)
     p.add_argument("--repair-conflicts", type=int, nargs="?", const=6, default=None, metavar="PASSES",
                    help="after every solve, remove the between-sample conflicts with holds (SCP.repair_conflicts, at most PASSES "
                         "passes, default 6) and add conflicts_before, conflicts_after and repair_passes to its record")
@@ -293,7 +300,9 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args([] if argv is None else argv)
+    parser = build_parser()
+    args = parser.parse_args([] if argv is None else argv)
+    stagger_search = stagger_search_keywords(parser, args)
     if args.streams > 1:
         # HIP maps streams onto 4 hardware queues by default and kernels of streams that share a queue run one after the
         # other -- a persistent QP kernel holds its queue for a millisecond.  Effective only before the runtime starts.
@@ -317,6 +326,8 @@ def main(argv=None):
         cfg["delay_tolerance"] = int(args.delay_tolerance)
     if args.stagger_starts is not None:  # (likewise)
         cfg["stagger_starts"] = int(args.stagger_starts)
+        if stagger_search:  # (likewise: --stagger-search, --stagger-rounds, --stagger-seed, --stagger-objective)
+            cfg["stagger_search"] = stagger_search
     if args.repair_conflicts is not None:  # (likewise)
         cfg["repair_conflicts"] = int(args.repair_conflicts)
     cfg["carry_rho"] = bool(args.carry_rho)
@@ -406,7 +417,8 @@ def main(argv=None):
             res["scenario_ok"] = scenario_ok[job]
         # (--delay-tolerance, --stagger-starts: the record's last fields)
         for key in ("delay_tolerance_steps", "min_delay_tolerance_steps", "stagger_max_delay", "stagger_n_delayed",
-                    "stagger_n_unplaced", "stagger_conflicts_after"):
+                    "stagger_n_unplaced", "stagger_conflicts_after", "stagger_search_candidates",
+                    "stagger_baseline_n_unplaced", "stagger_baseline_max_delay"):
             if key in res:
                 res[key] = res.pop(key)
         status_str = "OK" if res["status"] == "success" else f"ERR ({res['error']})"

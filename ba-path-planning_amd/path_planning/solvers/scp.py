@@ -27,7 +27,7 @@ import numpy as np
 from .. import _hip
 from .._sharding import Shard
 from .conflicts import conflict_windows, pairs_from_index
-from .stagger import staggered_fleet
+from .stagger import candidate_orders, refined_orders, schedule_key, staggered_fleet
 
 # The reference's callers build a NEW solver object per scenario (compute_trajectories_batch.py:103-117).  Here an object owns a
 # library context and a native solver (device workspace, pinned host words, the K x K blocks cached per rho): ~0.7 ms to
@@ -1042,7 +1042,7 @@ class SCP:
     # ------------------------------------------------------------------------------------------------
     # staggered starts (not in the reference): pair-lag masks and a greedy launch schedule, DESIGN.md section 3.7
     # ------------------------------------------------------------------------------------------------
-    def stagger_starts(self, max_delay, order=None):
+    def stagger_starts(self, max_delay, order=None, *, search=0, rounds=1, seed=0, objective="makespan"):
         """Remove the between-sample conflicts of the stored trajectories WITHOUT changing a plan: some vehicles start a few
         whole steps later, at most ``max_delay`` (an int in [0, min(K, 63)]).  One device pass computes, for every ordered pair
         and every lag, whether the pair conflicts when the first vehicle starts that many steps after the second
@@ -1058,7 +1058,18 @@ class SCP:
         vehicle placed), ``n_delayed``, ``n_unplaced``, ``max_delay``, ``total_delay``, ``conflicts_before`` /
         ``conflicts_after`` (violating segments of the stored and of the staggered fleet, scp_check_separation),
         ``min_distance_after``, ``horizon_steps`` (K + Dmax), ``lag_conflicts_ms`` / ``schedule_ms`` (device time of the two
-        calls) and ``time_sec``."""
+        calls) and ``time_sec``.
+
+        The greedy schedule depends on the order it takes the vehicles in.  ``search=B`` (an int in [1, 65535]; 0: the one order
+        above) schedules B candidate orders per round in one launch each (scp_schedule_starts_batch) and keeps the best under
+        ``objective`` -- "makespan": fewest unplaced vehicles, then the smallest largest delay, then the smallest total delay;
+        "total": fewest unplaced, then total, then largest.  Round 0 takes ``candidate_orders(N, B, default_rng(seed),
+        base=order)``, every later one of ``rounds`` takes ``refined_orders`` of the best so far; a later round replaces the
+        best only by a strictly smaller key, and the search stops when nobody is unplaced or delayed.  Candidate 0 of round 0 is
+        ``order`` itself, so the result is never worse than without the search.  The masks are computed once.  The info then
+        also has ``search``: ``candidates``, ``rounds_run``, ``best_round``, ``best_candidate``, ``best_order``, ``baseline``
+        (``n_unplaced`` / ``max_delay`` / ``total_delay`` / ``n_delayed`` of ``order``), ``improved`` and ``objective``;
+        ``schedule_ms`` is the sum over the rounds."""
         if self.trajectories is None:
             raise ValueError("Trajectories not generated yet")
         if self.shard.world != 1:
@@ -1072,6 +1083,12 @@ class SCP:
             order = np.asarray(order, dtype=np.int64).reshape(-1)
             if order.size != self.N or not np.array_equal(np.sort(order), np.arange(self.N)):
                 raise ValueError("order must be a permutation of 0 .. N-1")
+        if isinstance(search, bool) or not isinstance(search, (int, np.integer)) or not 0 <= search <= _hip.SCHEDULE_MAX_BATCH:
+            raise ValueError(f"search={search!r}: the candidate orders per round are an int in [0, {_hip.SCHEDULE_MAX_BATCH}]")
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or rounds < 1:
+            raise ValueError(f"rounds={rounds!r}: an int >= 1")
+        if objective not in _hip.SCHEDULE_OBJECTIVES:
+            raise ValueError(f"objective={objective!r}: one of {sorted(_hip.SCHEDULE_OBJECTIVES)}")
         t_start = time.perf_counter()
         N, K, D, h, c = self.N, self.K, self.D, self.h, self._ctx
         S = int(max_delay)
@@ -1080,8 +1097,11 @@ class SCP:
         before = c.check_separation(N, K, D, h, self.R, *dev)
         mask = c.lag_conflicts(N, K, D, h, self.R, *dev, S, device=True)
         lag_ms = c.last_pair_ms()
-        delays, st = c.schedule_starts(mask, S, order)
-        schedule_ms = c.last_pair_ms()
+        if search:
+            delays, st, schedule_ms, found = self._search_start_orders(mask, S, order, int(search), int(rounds), seed, objective)
+        else:
+            delays, st = c.schedule_starts(mask, S, order)
+            schedule_ms = c.last_pair_ms()
         pos, vel, acc = staggered_fleet(*host, h, delays)
         horizon = pos.shape[1]
         after = c.check_separation(N, horizon, D, h, self.R, c.tensor(pos), c.tensor(vel), c.tensor(acc))
@@ -1091,8 +1111,35 @@ class SCP:
                 "conflicts_before": int(before["n_violating"]), "conflicts_after": int(after["n_violating"]),
                 "min_distance_after": float(after["min_dist"]), "horizon_steps": int(horizon), "lag_conflicts_ms": lag_ms,
                 "schedule_ms": schedule_ms, "time_sec": time.perf_counter() - t_start}
+        if search:
+            info["search"] = found
         self.last_info["stagger"] = info
         return info
+
+    def _search_start_orders(self, mask, S, order, B, rounds, seed, objective):
+        """the order search of stagger_starts on the device masks: (delays, stats, device ms, the info's "search" entry)"""
+        c, N = self._ctx, self.N
+        rng = np.random.default_rng(seed)
+        fields = ("n_delayed", "n_unplaced", "max_delay", "first_unplaced", "total_delay")
+        best = None  # (key, order, delays, stats, round, candidate)
+        ms = 0.0
+        for r in range(rounds):
+            orders = candidate_orders(N, B, rng, base=order) if r == 0 else refined_orders(best[1], best[2], B, rng)
+            delays, stats, b = c.schedule_starts_batch(mask, S, orders, objective)
+            ms += c.last_pair_ms()
+            st = {f: int(stats[f][b]) for f in fields}
+            key = schedule_key(st["n_unplaced"], st["max_delay"], st["total_delay"], objective)
+            if r == 0:
+                baseline = {f: int(stats[f][0]) for f in ("n_unplaced", "max_delay", "total_delay", "n_delayed")}
+                base_key = schedule_key(baseline["n_unplaced"], baseline["max_delay"], baseline["total_delay"], objective)
+            if best is None or key < best[0]:
+                best = (key, orders[b].copy(), delays[b].copy(), st, r, b)
+            if best[0] == (0, 0, 0):
+                break
+        found = {"candidates": B, "rounds_run": r + 1, "best_round": best[4], "best_candidate": best[5],
+                 "best_order": best[1].astype(np.int64), "baseline": baseline, "improved": best[0] < base_key,
+                 "objective": objective}
+        return best[2], best[3], ms, found
 
     # ------------------------------------------------------------------------------------------------
     # visualisation passthroughs (scp.py:644-840): host-side matplotlib over the stored numpy trajectories

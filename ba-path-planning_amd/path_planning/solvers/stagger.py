@@ -31,3 +31,49 @@ def delays_satisfy_masks(mask, delays):
     a, b = np.nonzero((d[:, None] >= d[None, :]) & (d[:, None] >= 0) & (d[None, :] >= 0) & ~np.eye(d.size, dtype=bool))
     lag = (d[a] - d[b]).astype(np.uint64)
     return not ((mask[a, b] >> lag) & np.uint64(1)).any()
+
+
+def schedule_key(n_unplaced, max_delay, total_delay, objective):
+    """the key of scp_schedule_starts_batch without its trailing candidate index, as a tuple of Python integers"""
+    u, m, t = int(n_unplaced), int(max_delay), int(total_delay)
+    return (u, m, t) if objective == "makespan" else (u, t, m)
+
+
+def candidate_orders(N, B, rng, base=None):
+    """(B, N) int32 candidate orders of a first search round: row 0 is `base` (None: 0 .. N-1), row 1 its reverse, every further
+    row rng.permutation(N), drawn in sequence -- deterministic for a given numpy.random.Generator."""
+    base = np.arange(N, dtype=np.int32) if base is None else np.asarray(base, dtype=np.int32).reshape(N)
+    out = np.empty((B, N), dtype=np.int32)
+    out[0] = base
+    if B >= 2:
+        out[1] = base[::-1]
+    for b in range(2, B):
+        out[b] = rng.permutation(N)
+    return out
+
+
+def refined_orders(best_order, delays, B, rng):
+    """(B, N) int32 candidate orders derived from the best order so far and its delays (-1: unplaced); pos: the position of a
+    vehicle in best_order.  Row 0: best_order; row 1: the unplaced vehicles by pos, then the placed ones by pos; row 2: the
+    unplaced by pos, then the placed by ascending delay (ties by pos); row 3: the placed by descending delay (ties by pos), then
+    the unplaced by pos; every further row: best_order after max(1, N // 16) transpositions of the positions
+    rng.integers(0, N, 2), drawn in sequence.  B < 4: the first B rows."""
+    best = np.asarray(best_order, dtype=np.int32).reshape(-1)
+    N = best.size
+    d = np.asarray(delays, dtype=np.int64).reshape(N)[best]  # by position
+    pos = np.arange(N)
+    unplaced, placed = pos[d < 0], pos[d >= 0]
+    rows = [pos,
+            np.concatenate([unplaced, placed]),
+            np.concatenate([unplaced, placed[np.argsort(d[placed], kind="stable")]]),
+            np.concatenate([placed[np.argsort(-d[placed], kind="stable")], unplaced])]
+    out = np.empty((B, N), dtype=np.int32)
+    for b in range(min(B, 4)):
+        out[b] = best[rows[b]]
+    for b in range(4, B):
+        row = best.copy()
+        for _ in range(max(1, N // 16)):
+            i, j = (int(x) for x in rng.integers(0, N, 2))
+            row[i], row[j] = row[j], row[i]
+        out[b] = row
+    return out

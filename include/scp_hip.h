@@ -156,7 +156,12 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     a layout change and a kinematics launch.  0: those launches run separately.
  *   "delay_lag_chunk", "delay_time_chunk" (default 0: chosen by the call): the lags / the global segments one workgroup of
  *     scp_delay_margins covers; developer switches for tests and measurements.
- *   "lagc_lag_chunk", "lagc_time_chunk" (default 0: chosen by the call): the same two of scp_lag_conflicts. */
+ *   "lagc_lag_chunk", "lagc_time_chunk" (default 0: chosen by the call): the same two of scp_lag_conflicts.
+ *   "stg_batch_threads" (default 0: chosen by the call from N; or 256 or 1024): threads per workgroup of
+ *     scp_schedule_starts_batch; a developer switch.
+ *   "stg_batch_transposed" (default -1: chosen by the call, from 16 candidates on; 0 never; 1 always): scp_schedule_starts_batch
+ *     first writes a transposed copy of the masks (N^2 words in the context's workspace) and reads the masks' columns from
+ *     its rows; a developer switch. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -335,7 +340,7 @@ int scp_delay_margins(scp_ctx* ctx, int N, int K, int D, double h, double R, int
 int scp_ctx_last_delay_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
 
 /* ---- staggered starts: pair-lag conflict masks and a greedy launch schedule ------------------------------------------------
- * A purely additive part of ABI version 7: one struct and three functions, nothing else changes.
+ * A purely additive part of ABI version 7: one struct and four functions, nothing else changes.
  * The cheapest remedy for between-sample conflicts: every plan stays as it is and some vehicles start a few steps later.
  * Records, lags, global segments, the segment distance sqrt(max(min f, 0)) and the threshold R - 0.01 are those of
  * scp_delay_margins above; that call reduces over b, so it covers one late vehicle among punctual ones.  Here the same segment
@@ -381,6 +386,26 @@ int scp_lag_conflicts(scp_ctx* ctx, int N, int K, int D, double h, double R, int
 int scp_ctx_last_lag_solved(scp_ctx* ctx, uint64_t* n_solved /* [host] */);
 int scp_schedule_starts(scp_ctx* ctx, int N, int max_lag, const uint64_t* mask /* [N][N] */,
                         const int32_t* order /* [N] or NULL */, int32_t* delay /* [N] */, scp_start_schedule_stats* stats);
+/* scp_schedule_starts_batch (one more function of ABI version 7, nothing else changes): the order is the only free parameter
+ * of the SCHEDULE rule, so B candidate orders are scheduled on the same masks in ONE launch and the best is named.
+ *   RULE.  For every candidate b = 0 .. B-1, delay[b][.] and stats[b] are the bytes scp_schedule_starts(ctx, N, max_lag, mask,
+ *     orders + b N, ...) writes: every field, first_unplaced and the zeroed `reserved` included.  Integers only.
+ *   OBJECTIVE.  *best is the candidate with the smallest key, compared lexicographically:
+ *     objective 0 ("makespan"): (n_unplaced, max_delay, total_delay, b);   objective 1 ("total"): (n_unplaced, total_delay,
+ *     max_delay, b).  The trailing b sends ties to the lowest index.  (n_unplaced <= 2^14, max_delay <= 63,
+ *     total_delay < 2^20 and b < 2^16 pack into one 64-bit word whose integer minimum is the lexicographic one.)
+ * mask, orders, delay and stats are DEVICE memory, `best` is host memory; `orders` must not be NULL.  Supported: 1 <= N <= 16384,
+ * 0 <= max_lag <= 63, 1 <= B <= 65535, objective 0 or 1, non-null pointers; anything else returns SCP_ERR_INVALID with a
+ * message.  One workgroup per candidate, no workgroup waits for another, the masks are only read (from 16 candidates on the
+ * call first writes their transpose into N^2 words of the context's workspace, so that both reads of a step are rows).  Enqueued on the ctx
+ * stream; the call synchronises, and scp_ctx_last_pair_ms then reports its device time.  If a candidate is no permutation the
+ * call returns SCP_ERR_INVALID after the launch, the message names the lowest such candidate, delay / stats / *best are
+ * undefined and the context stays usable.  Results do not depend on the threads a workgroup runs with
+ * (scp_ctx_set_option "stg_batch_threads"). */
+int scp_schedule_starts_batch(scp_ctx* ctx, int N, int max_lag, const uint64_t* mask /* [N][N] DEVICE */,
+                              int B, const int32_t* orders /* [B][N] DEVICE, not NULL */, int objective,
+                              int32_t* delay /* [B][N] DEVICE */, scp_start_schedule_stats* stats /* [B] DEVICE */,
+                              int32_t* best /* [host] */);
 
 /* ---- holds: repair between-sample conflicts with a separating half-plane per segment ------------------------------------------
  * A purely additive part of ABI version 7: one struct and two functions, nothing else changes.
