@@ -205,6 +205,11 @@ int scp_launch_add_rows_at(scp_ctx* ctx, int N, int K, int D, int64_t base, int6
                            const double* pos_prev, const double* p0, const double* v0, double R, double h, const double* Qx,
                            int64_t* w_row, int* wk, int* wi, int* wj, double* weta, double* wl, double* zc, double* yc);
 
+// the launch of scp_qp_set_position_boxes: rows [3K-1, 4K-2) of lf / uf from the boxes lo / hi [N][K][D] by state; space6 =
+// {min_0 .. min_2, max_0 .. max_2} and states = [p0 | v0 | pf | vf] as scp_qp keeps them (scp_corridor.hip)
+int scp_launch_position_boxes(scp_ctx* ctx, int N, int K, int D, double h, const double* space6, const double* states,
+                              const double* lo, const double* hi, double* lf, double* uf);
+
 // ---- internal launchers (time-major device layout [K][C], C = N*D) --------------------------------
 // Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y   (row-major; A small and L2 resident)  (scp_gemm.hip)
 int scp_launch_gemm(scp_ctx* ctx, int use_mfma, int R, int M, int C, double alpha, const double* A,

@@ -200,6 +200,7 @@ extern "C" int scp_qp_create(scp_ctx* ctx, int N, int K, int D, double h, const 
   qp->row_cap = row_capacity;
   qp->nW = 0;
   qp->problem_set = qp->reset_done = false;
+  qp->has_boxes = false;
   qp->rho = s->rho;
   carve(qp->d, workspace, K, qp->C, row_capacity, D);
   scp_qp_kkt_init_slots(qp);
@@ -299,8 +300,19 @@ extern "C" int scp_qp_set_problem(scp_qp* qp, const double* limits, const double
     qp->space[3 + d] = d < qp->D ? space[qp->D + d] : 0.0;
   }
   qp->problem_set = true;
+  qp->has_boxes = false;  // (the launch above rewrote every bound)
   qp->reset_done = false;
   qp->persist_off = false;  // a give-up is a property of the moment (another kernel held the CUs), not of the object
+  return SCP_OK;
+}
+
+extern "C" int scp_qp_set_position_boxes(scp_qp* qp, const double* lo, const double* hi) {
+  if (!qp) return SCP_ERR_INVALID;
+  if (!lo && !hi) return SCP_OK;
+  SCP_REQUIRE(qp->ctx, lo && hi, "qp_set_position_boxes: lo and hi are both given or both NULL");
+  if (!qp->problem_set) return scp_fail(qp->ctx, SCP_ERR_STATE, "qp_set_position_boxes: call scp_qp_set_problem first");
+  QP_CHECK(scp_launch_position_boxes(qp->ctx, qp->N, qp->K, qp->D, qp->h, qp->space, qp->d.states, lo, hi, qp->d.lf, qp->d.uf));
+  qp->has_boxes = true;
   return SCP_OK;
 }
 
@@ -643,6 +655,7 @@ extern "C" int scp_qp_clone_state(scp_qp* dst, const scp_qp* src) {
   dst->rho = src->rho;
   dst->st = src->st;
   dst->problem_set = true;
+  dst->has_boxes = src->has_boxes;  // (lf / uf were copied)
   qp_on_x_set(dst, false);
   QP_CHECK(scp_qp_build_kkt(dst));
   dst->reset_done = true;
@@ -682,7 +695,8 @@ extern "C" int scp_qp_get_duals(scp_qp* qp, double* y_fixed, double* y_col) {
 
 // test hook: copy one internal array of the solver to `out` (device pointer, capacity `cap` doubles); *n_out [host] = its
 // length.  names: "fx" (carried F x, [4K-1][C]), "qx" (carried S0 x, [K][C]), "gval" (row value per incidence entry),
-// "zf", "yf" ([4K-1][C]), "zc", "yc" (per working row), "x" ([K][C]); "Hf", "Minv", "T" (K x K, row-major): the blocks of
+// "zf", "yf", "lf", "uf" ([4K-1][C]; lf / uf: the bounds of the fixed rows), "zc", "yc" (per working row), "x" ([K][C]);
+// "Hf", "Minv", "T" (K x K, row-major): the blocks of
 // the current rho (H_f, its inverse, T = S0 H_f^{-1}) in the active cache slot.
 extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t cap, int64_t* n_out) {
   if (!qp) return SCP_ERR_INVALID;
@@ -699,6 +713,8 @@ extern "C" int scp_qp_peek(scp_qp* qp, const char* name, double* out, int64_t ca
     src = d.gval; n = 2 * qp->nW;
   }
   else if (!strcmp(name, "zf")) { src = d.zf; n = nf; }
+  else if (!strcmp(name, "lf")) { src = d.lf; n = nf; }
+  else if (!strcmp(name, "uf")) { src = d.uf; n = nf; }
   else if (!strcmp(name, "yf")) { src = d.yf; n = nf; }
   else if (!strcmp(name, "zc")) { src = d.zc; n = qp->nW; }
   else if (!strcmp(name, "yc")) { src = d.yc; n = qp->nW; }

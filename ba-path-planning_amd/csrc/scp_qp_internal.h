@@ -102,6 +102,8 @@ struct scp_qp {
   scp_qp_settings st;
   int64_t row_cap, nW;
   bool problem_set, reset_done;
+  bool has_boxes;  // scp_qp_set_position_boxes has rewritten position rows of lf / uf since the latest scp_qp_set_problem: the
+                   // lean persistent kernels, which re-derive the bounds from space / states, do not run this QP
   QpDerived dv;
   double rho;
   QpDev d;

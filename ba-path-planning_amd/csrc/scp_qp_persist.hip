@@ -580,6 +580,9 @@ static int persist_variant_for(const scp_qp* qp) {
   const bool fits_old = (qp->N + apb - 1) / apb <= max_wg;
   const bool fits16 = qp->D == 2 && (qp->N + 15) / 16 <= max_wg;
   const bool fits8 = (qp->N + 7) / 8 <= max_wg;
+  // per-state position boxes live in lf / uf only: the lean kernels re-derive the bounds from space / states and would not
+  // see them, so such a QP runs the round-2 kernel or the three-launch pipeline, whatever settings.persistent asks for
+  if (qp->has_boxes) return fits_old ? 0 : -1;
   if (qp->st.persistent == 2 && fits16) return 1;
   if (qp->st.persistent == 3 && fits8) return 2;
   if (qp->st.persistent == 4 && fits_old) return 0;

@@ -77,6 +77,7 @@ struct scp_solver {
                      // it, inside the prep launch of its pass where that pass runs as several launches
   double rho_start;  // > 0: the joint QP of the next step starts at this rho (options.carry_rho), else at settings.rho
   struct StepState* step;  // the SCP iteration in flight (phases of solve_joint_qp / of the sharded entry points)
+  const double *box_lo, *box_hi;  // per-state position boxes [N][K][D] (scp_solver_set_position_boxes; NULL: none), kept by pointer
 };
 
 namespace {
@@ -126,6 +127,13 @@ int make_qp(scp_solver* s, int64_t cap, void** ws_out, scp_qp** qp_out) {
   return SCP_OK;
 }
 
+// the one way this file sets a QP's problem: the bounds, then the solver's position boxes (none: no further launch)
+int set_problem(scp_solver* s, scp_qp* qp, const double* limits, const double* space, const double* p0, const double* v0,
+                const double* pf, const double* vf) {
+  SV_CHECK(scp_qp_set_problem(qp, limits, space, p0, v0, pf, vf));
+  return scp_qp_set_position_boxes(qp, s->box_lo, s->box_hi);
+}
+
 // working set outgrew the capacity: continue in a larger workspace (keep_state: iterate, duals, rows, rho travel along)
 int grow_qp(scp_solver* s, int64_t need, bool keep_state, const double* limits, const double* space, const double* p0,
             const double* v0, const double* pf, const double* vf) {
@@ -134,7 +142,7 @@ int grow_qp(scp_solver* s, int64_t need, bool keep_state, const double* limits, 
   void* ws = nullptr;
   scp_qp* qp = nullptr;
   SV_CHECK(make_qp(s, cap, &ws, &qp));
-  int rc = keep_state ? scp_qp_clone_state(qp, s->qp) : scp_qp_set_problem(qp, limits, space, p0, v0, pf, vf);
+  int rc = keep_state ? scp_qp_clone_state(qp, s->qp) : set_problem(s, qp, limits, space, p0, v0, pf, vf);
   if (rc != SCP_OK) {
     scp_qp_destroy(qp);
     (void)hipFree(ws);
@@ -492,6 +500,14 @@ extern "C" int scp_solver_update_settings(scp_solver* s, const scp_qp_settings* 
   return rc;
 }
 
+extern "C" int scp_solver_set_position_boxes(scp_solver* s, const double* lo, const double* hi) {
+  if (!s) return SCP_ERR_INVALID;
+  SCP_REQUIRE(s->ctx, (lo != nullptr) == (hi != nullptr), "solver_set_position_boxes: lo and hi are both given or both NULL");
+  s->box_lo = lo;
+  s->box_hi = hi;
+  return SCP_OK;
+}
+
 extern "C" int scp_solver_solve(scp_solver* s, const double* limits, const double* space, const double* p0,
                                 const double* v0, const double* pf, const double* vf, const scp_solve_options* o,
                                 double* acc_out, double* pos_out, double* vel_out, scp_solve_result* res,
@@ -510,7 +526,7 @@ extern "C" int scp_solver_solve(scp_solver* s, const double* limits, const doubl
   s->pos_pending = false;
 
   // a2 + a3: bounds, QP#0 (scp.py:137-138, :323-369)
-  SV_CHECK(scp_qp_set_problem(s->qp, limits, space, p0, v0, pf, vf));
+  SV_CHECK(set_problem(s, s->qp, limits, space, p0, v0, pf, vf));
   scp_qp_settings st0 = s->st;
   st0.max_iter = o->max_iter0;
   SV_CHECK(scp_qp_update_settings(s->qp, &st0));
@@ -642,7 +658,7 @@ extern "C" int scp_solver_step(scp_solver* s, const double* limits, const double
   s->rho_start = 0.0;
   s->spec_valid = false;
   s->want_spec = false;
-  SV_CHECK(scp_qp_set_problem(s->qp, limits, space, p0, v0, pf, vf));
+  SV_CHECK(set_problem(s, s->qp, limits, space, p0, v0, pf, vf));
   s->pos_pending = true;  // (s->pos_a = the positions of acc_in: step_linearize)
   SV_CHECK(solve_joint_qp(s, acc_in, limits, space, p0, v0, pf, vf, o, 0.0, rec));
   double rel[3];
@@ -689,7 +705,7 @@ extern "C" int scp_solver_shard_begin(scp_solver* s, const double* limits, const
   double lim[6], spc[6];
   memcpy(lim, limits, sizeof(lim));
   memcpy(spc, space, 2 * D * sizeof(double));
-  SV_CHECK(scp_qp_set_problem(s->qp, limits, space, p0, v0, pf, vf));
+  SV_CHECK(set_problem(s, s->qp, limits, space, p0, v0, pf, vf));
   if (pos_in)
     SV_HIP(hipMemcpyAsync(s->pos_a, pos_in, (size_t)N * K * D * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   s->pos_pending = !pos_in;  // (NULL: s->pos_a = the positions of acc_in, computed by step_linearize)

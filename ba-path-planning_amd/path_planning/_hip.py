@@ -221,6 +221,33 @@ class LineStats(C.Structure):
 LINE_STATS_DTYPE = np.dtype([("min_approach", np.float64), ("arg_i", np.int32), ("arg_j", np.int32), ("n_close", np.int64),
                              ("n_opposed", np.int64)])
 
+class OccupancyGrid(C.Structure):
+    """struct scp_occupancy_grid (host): the geometry of an occupancy grid"""
+    _fields_ = [("origin", C.c_double * 3), ("cell", C.c_double), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
+class CorridorStats(C.Structure):
+    """struct scp_corridor_stats (scp_check_corridor; one per vehicle, a DEVICE array)"""
+    _fields_ = [("max_excess", C.c_double), ("segment", C.c_uint32), ("n_blocked", C.c_uint32), ("n_outside", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+CORRIDOR_STATS_DTYPE = np.dtype([("max_excess", np.float64), ("segment", np.uint32), ("n_blocked", np.uint32),
+                                 ("n_outside", np.uint64), ("reserved", np.uint64)])
+CORRIDOR_MAX_CELLS = 1 << 24  # scp_occupancy_prepare
+CORRIDOR_MAX_GROW = 1024      # scp_corridor_boxes
+
+
+def occupancy_grid(D, origin, cell, dims) -> OccupancyGrid:
+    """scp_occupancy_grid from origin (D,), the cell size and dims = (nx, ny[, nz])"""
+    g = OccupancyGrid()
+    for d in range(3):
+        g.origin[d] = float(origin[d]) if d < D else 0.0
+        g.dims[d] = int(dims[d]) if d < len(dims) else 1
+    g.cell = float(cell)
+    return g
+
+
 NO_ROW = 2**64 - 1  # UINT64_MAX: "no such row" in the stats of the pairwise passes
 
 ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
@@ -242,6 +269,8 @@ EXPORTS = [
     "scp_solver_step", "scp_solver_shard_begin", "scp_solver_shard_rows", "scp_solver_shard_qp", "scp_solver_shard_violations",
     "scp_solver_shard_round_done", "scp_solver_shard_end", "scp_gen_default_params", "scp_generate_grid_swap",
     "scp_assign_goals", "scp_straight_line_check", "scp_assign_goals_wide",
+    "scp_occupancy_prepare", "scp_corridor_boxes", "scp_corridor_state_boxes", "scp_qp_set_position_boxes",
+    "scp_solver_set_position_boxes", "scp_check_corridor",
 ]
 
 
@@ -348,6 +377,13 @@ def load_library():
     lib.scp_assign_goals.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
     lib.scp_assign_goals_wide.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
     lib.scp_straight_line_check.argtypes = [vp, i32, i32, i32, vp, vp, vp, f64, vp]
+    pg = C.POINTER(OccupancyGrid)
+    lib.scp_occupancy_prepare.argtypes = [vp, i32, pg, vp, vp]
+    lib.scp_corridor_boxes.argtypes = [vp, i32, i32, i32, pg, vp, vp, i32, vp, vp]
+    lib.scp_corridor_state_boxes.argtypes = [vp, i32, i32, i32, pg, vp, f64, vp, vp, vp]
+    lib.scp_qp_set_position_boxes.argtypes = [vp, vp, vp]
+    lib.scp_solver_set_position_boxes.argtypes = [vp, vp, vp]
+    lib.scp_check_corridor.argtypes = [vp, i32, i32, i32, f64, pg, vp, vp, vp, vp, f64, vp]
     _LIB, _LIB_PATH = lib, path
     return lib
 
@@ -773,6 +809,48 @@ class Context:
                                                     stats.data_ptr()))
         return stats.cpu().numpy().view(LINE_STATS_DTYPE)
 
+    # ---- static obstacles: occupancy grid, corridor boxes, the corridor check ------------------------------------------
+    def occupancy_prepare(self, D, grid: OccupancyGrid, occ):
+        """scp_occupancy_prepare: the summed table (int32 device tensor [nz][ny][nx]) of the occupancy grid `occ` (array or
+        uint8 device tensor [nz][ny][nx], nonzero = occupied).  Returns (occ on the device, sat)."""
+        torch = _torch()
+        if not torch.is_tensor(occ):
+            occ = torch.as_tensor(np.ascontiguousarray(np.asarray(occ) != 0, dtype=np.uint8))
+        occ = occ.to(device=self.tdev, dtype=torch.uint8).contiguous()
+        shape = (int(grid.dims[2]), int(grid.dims[1]), int(grid.dims[0]))
+        if tuple(occ.shape) != shape:
+            raise ValueError(f"occupancy grid of shape {tuple(occ.shape)}, the geometry says [nz][ny][nx] = {shape}")
+        sat = torch.empty(shape, dtype=torch.int32, device=self.tdev)
+        self.check(self.lib.scp_occupancy_prepare(self.h, int(D), C.byref(grid), occ.data_ptr(), sat.data_ptr()))
+        return occ, sat
+
+    def corridor_boxes(self, N, K, D, grid: OccupancyGrid, sat, ref, max_grow):
+        """scp_corridor_boxes: ref (N, K+1, D) device tensor -> (cells (N, K, 6) int32 device tensor, n_blocked int64 device
+        tensor of one word).  No host read."""
+        torch = _torch()
+        cells = torch.empty((N, K, 6), dtype=torch.int32, device=self.tdev)
+        n_blocked = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_corridor_boxes(self.h, N, K, D, C.byref(grid), sat.data_ptr(), ref.data_ptr(), int(max_grow),
+                                               cells.data_ptr(), n_blocked.data_ptr()))
+        return cells, n_blocked
+
+    def corridor_state_boxes(self, N, K, D, grid: OccupancyGrid, cells, shrink):
+        """scp_corridor_state_boxes: -> (lo, hi (N, K, D) device tensors by state, n_open int64 device tensor of one word)"""
+        torch = _torch()
+        lo, hi = self.empty(N, K, D), self.empty(N, K, D)
+        n_open = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_corridor_state_boxes(self.h, N, K, D, C.byref(grid), cells.data_ptr(), float(shrink),
+                                                     lo.data_ptr(), hi.data_ptr(), n_open.data_ptr()))
+        return lo, hi, n_open
+
+    def check_corridor(self, N, K, D, h, grid: OccupancyGrid, cells, pos, vel, acc, tol=0.0):
+        """scp_check_corridor: one record per vehicle as a numpy structured array (CORRIDOR_STATS_DTYPE) -- synchronises"""
+        torch = _torch()
+        out = torch.empty(max(N, 1) * CORRIDOR_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_check_corridor(self.h, N, K, D, float(h), C.byref(grid), cells.data_ptr(), pos.data_ptr(),
+                                               vel.data_ptr(), acc.data_ptr(), float(tol), out.data_ptr()))
+        return out.cpu().numpy().view(CORRIDOR_STATS_DTYPE)[:N].copy()
+
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape
         M2, Cc = X.shape
@@ -963,6 +1041,18 @@ class QP:
         self.ctx.check(self.ctx.lib.scp_qp_set_problem(self.h_qp, lp, sp, p0.data_ptr(), v0.data_ptr(), pf.data_ptr(),
                                                        vf.data_ptr()))
 
+    def set_position_boxes(self, lo, hi):
+        """scp_qp_set_position_boxes: per-(vehicle, state) position boxes lo / hi ((N, K, D) device tensors by state; both
+        None: a no-op) into the bounds of the position rows.  Call it after set_problem, which clears them."""
+        if (lo is None) != (hi is None):
+            raise ValueError("set_position_boxes: lo and hi are both given or both None")
+        if lo is not None:
+            for t in (lo, hi):
+                if tuple(t.shape) != (self.N, self.K, self.D) or not t.is_contiguous():
+                    raise ValueError(f"set_position_boxes: boxes are contiguous ({self.N}, {self.K}, {self.D}) tensors")
+        self.ctx.check(self.ctx.lib.scp_qp_set_position_boxes(self.h_qp, lo.data_ptr() if lo is not None else None,
+                                                              hi.data_ptr() if hi is not None else None))
+
     def reset(self, x0=None):
         self.ctx.check(self.ctx.lib.scp_qp_reset(self.h_qp, x0.data_ptr() if x0 is not None else None))
         self.n_rows = 0
@@ -1040,6 +1130,15 @@ class NativeSolver:
             self.close()
         except Exception:
             pass
+
+    def set_position_boxes(self, lo, hi):
+        """scp_solver_set_position_boxes: the solver applies lo / hi ((N, K, D) device tensors by state; both None: none)
+        after every scp_qp_set_problem it makes.  The tensors are kept alive here."""
+        if (lo is None) != (hi is None):
+            raise ValueError("set_position_boxes: lo and hi are both given or both None")
+        self._boxes = (lo, hi)
+        self.ctx.check(self.ctx.lib.scp_solver_set_position_boxes(self.h_solver, lo.data_ptr() if lo is not None else None,
+                                                                  hi.data_ptr() if hi is not None else None))
 
     def default_options(self, **kw) -> SolveOptions:
         o = SolveOptions()

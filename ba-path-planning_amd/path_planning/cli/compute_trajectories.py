@@ -82,9 +82,38 @@ def build_parser():
     p.add_argument("--assign-method", choices=("auto", "single", "wide"), default="auto",
                    help="--assign-goals through the one-workgroup auction (single, up to 4096 vehicles), the whole-GPU one (wide, "
                         "up to 65536) or whichever fits (auto); the assignment is the same")
+    p.add_argument("--obstacle-discs", nargs="+", default=None, metavar="X,Y[,Z],R",
+                   help="static obstacles: discs (spheres in 3-D) given as centre and radius; before the solve, safe flight "
+                        "corridors around the straight lines from start to goal become per-step position boxes of the QP, and "
+                        "after it one line says whether every segment stays inside its box")
+    p.add_argument("--corridor-cell", type=float, default=None, metavar="METRES",
+                   help="with --obstacle-discs: edge length of the occupancy grid's cells (default: a quarter of the minimum "
+                        "distance)")
+    p.add_argument("--corridor-grow", type=int, default=None, metavar="CELLS",
+                   help="with --obstacle-discs: how many cells a corridor box may grow beyond its segment per direction "
+                        "(default 8)")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
+
+
+def obstacle_discs(parser, args):
+    """the discs of --obstacle-discs as tuples of floats; the two corridor flags are errors without it"""
+    if args.obstacle_discs is None:
+        for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow)):
+            if value is not None:
+                parser.error(f"{flag} needs --obstacle-discs")
+        return None
+    discs = []
+    for text in args.obstacle_discs:
+        try:
+            disc = tuple(float(v) for v in text.split(","))
+        except ValueError:
+            disc = ()
+        if len(disc) != args.dim + 1:
+            parser.error(f"--obstacle-discs {text}: {args.dim} centre coordinates and a radius, separated by commas")
+        discs.append(disc)
+    return discs
 
 
 def main(argv=None):
@@ -92,6 +121,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args([] if argv is None else argv)
     stagger_search = stagger_search_keywords(parser, args)
+    discs = obstacle_discs(parser, args)
     print("------ WOW Fleet Collision-Free 2D Trajectory Generation ------")
 
     n_vehicles = args.n_agents
@@ -135,6 +165,13 @@ def main(argv=None):
             solver.assign_goals(method=args.assign_method)
             print(describe(solver.assignment_info))
 
+        if discs is not None:
+            from ..scenarios.obstacles import rasterize
+
+            occ, origin, cell = rasterize(space_dims, args.corridor_cell or min_distance / 4, discs=discs, margin=min_distance / 2)
+            solver.set_obstacles(occ, origin, cell)
+            co = solver.set_corridors(max_grow=8 if args.corridor_grow is None else args.corridor_grow)
+
         print("Generating trajectories...")
         start_time = time.time()
         solver.generate_trajectories(max_iterations=args.max_iterations)
@@ -144,6 +181,12 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
+        if discs is not None:
+            cr = solver.validate_corridor()
+            print(f"Corridors: {len(discs)} obstacles on a grid of {occ.shape[2]} x {occ.shape[1]} x {occ.shape[0]} cells of "
+                  f"{cell:g} m, boxes shrunk by {co['shrink']:.4f} m; " + ("every segment stays inside its box" if cr["inside"] else
+                  f"{cr['n_outside']} segments leave their box") + f" (largest excess {cr['max_excess']:.4f} m, vehicle "
+                  f"{cr['worst_vehicle']})")
         if args.repair_conflicts is not None:
             rep = solver.repair_conflicts(max_passes=args.repair_conflicts)
             counts = " -> ".join(str(n) for n in [rep["conflicts_before"]] + rep["conflicts_per_pass"])

@@ -73,6 +73,43 @@ def gather_delay_blocks(shard, mine, a0):
     return shard.allgather_records(rec)[list(_hip.DELAY_DTYPE.names)]
 
 
+def straight_reference(p0, pf, K):
+    """The default reference path of SCP.set_corridors: the straight line from start to goal, sampled uniformly at the states
+    j = 0 .. K -- (N, K + 1, D) from p0, pf (N, D)."""
+    p0, pf = np.asarray(p0, dtype=np.float64), np.asarray(pf, dtype=np.float64)
+    s = (np.arange(K + 1, dtype=np.float64) / float(K))[None, :, None]
+    return p0[:, None, :] + s * (pf - p0)[:, None, :]
+
+
+def check_position_boxes(N, K, D, pos_min, pos_max, lo, hi):
+    """Host validation of per-(vehicle, state) position boxes: (N, K, D) float arrays without NaN whose intersection with the
+    workspace box is not empty for any state j = 1 .. K-1 (state 0 is fixed to the start and never constrained).  Returns
+    (lo, hi) as contiguous float64 arrays; raises ValueError naming the first offending state."""
+    lo = np.ascontiguousarray(lo, dtype=np.float64)
+    hi = np.ascontiguousarray(hi, dtype=np.float64)
+    if lo.shape != (N, K, D) or hi.shape != (N, K, D):
+        raise ValueError(f"position boxes need shape (N, K, D) = ({N}, {K}, {D}), got {lo.shape} and {hi.shape}")
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("position boxes must not hold NaN (use -inf / +inf for an unconstrained entry)")
+    l = np.maximum(np.asarray(pos_min, dtype=np.float64), lo[:, 1:])
+    u = np.minimum(np.asarray(pos_max, dtype=np.float64), hi[:, 1:])
+    bad = np.argwhere(l > u)
+    if bad.size:
+        i, j, d = (int(x) for x in bad[0])
+        raise ValueError(f"position box of vehicle {i}, state {j + 1}, coordinate {d} is empty inside the workspace: "
+                         f"[{l[i, j, d]}, {u[i, j, d]}]")
+    return lo, hi
+
+
+def corridor_shrink(acc_min, acc_max, h, pad):
+    """shrink of SCP.set_corridors: a quadratic leaves the chord of its end values by at most |a| h^2 / 8; pad pays for the
+    QP's constraint tolerance"""
+    pad = float(pad)
+    if not (pad >= 0.0 and np.isfinite(pad)):
+        raise ValueError(f"pad={pad!r}: a finite number >= 0")
+    return max(abs(float(acc_min)), abs(float(acc_max))) * float(h) * float(h) / 8.0 + pad
+
+
 class SCP:
     def __init__(
         self,
@@ -194,6 +231,9 @@ class SCP:
         self._pairs = None
         self._holds = None  # (device table, count) of repair_conflicts while one of its passes runs
         self.staggered = None  # the fleet of the latest stagger_starts (its trajectories stay as they are)
+        self._obstacles = None  # set_obstacles: {"grid", "occ", "sat"} (device), the occupancy grid and its summed table
+        self._corridor = None   # set_corridors: {"cells", "grid"}: the boxes of the segments, what validate_solution checks
+        self._boxes = None      # (lo, hi) device tensors (N, K, D) by state: set_corridors / set_position_boxes
         self._dev = {}
         self.last_info = {}
 
@@ -217,6 +257,114 @@ class SCP:
         self.pos_min = np.array(space_dims[: self.D])
         self.pos_max = np.array(space_dims[self.D:])
         self.trajectories = None
+        self._obstacles = self._corridor = self._boxes = None  # (they belong to the scenario that is being replaced)
+
+    # ------------------------------------------------------------------------------------------------
+    # static obstacles (not in the reference): safe flight corridors as per-state position boxes, DESIGN.md section 3.9
+    # ------------------------------------------------------------------------------------------------
+    def _one_rank(self, what):
+        if self.shard.world != 1:
+            raise ValueError(f"{what} supports one rank only (world_size == 1)")
+
+    def set_obstacles(self, occ, origin, cell):
+        """Static obstacles as an occupancy grid: ``occ`` [nz][ny][nx] ([ny][nx] in 2-D; nonzero = occupied), ``origin`` the
+        lower corner of cell (0, 0, 0), ``cell`` the edge length -- what scenarios.obstacles.rasterize returns.  Uploads the
+        grid and prepares its summed table (scp_occupancy_prepare); corridors and boxes set before are dropped."""
+        self._one_rank("set_obstacles")
+        occ = np.asarray(occ)
+        if self.D == 2 and occ.ndim == 2:
+            occ = occ[None]
+        if occ.ndim != 3 or (self.D == 2 and occ.shape[0] != 1) or min(occ.shape) < 1:
+            raise ValueError(f"occ has shape {occ.shape}: need [nz][ny][nx]" + (" with nz = 1 (or [ny][nx])" if self.D == 2 else ""))
+        if occ.size > _hip.CORRIDOR_MAX_CELLS:
+            raise ValueError(f"the grid has {occ.size} cells, more than the supported 2^24")
+        origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+        cell = float(cell)
+        if origin.size != self.D or not np.isfinite(origin).all():
+            raise ValueError(f"origin needs {self.D} finite entries")
+        if not (cell > 0.0 and np.isfinite(cell)):
+            raise ValueError(f"cell={cell!r}: a finite number > 0")
+        grid = _hip.occupancy_grid(self.D, origin, cell, occ.shape[::-1])
+        occ_dev, sat = self._ctx.occupancy_prepare(self.D, grid, occ)
+        self._obstacles = {"grid": grid, "occ": occ_dev, "sat": sat, "prepare_ms": self._ctx.last_pair_ms()}
+        self._corridor = self._boxes = None
+
+    def set_corridors(self, reference=None, max_grow=8, pad=0.02, allow_open=False):
+        """Safe flight corridors around a reference path: for every vehicle and segment an axis-aligned box of free cells
+        (scp_corridor_boxes: the cells of the segment's two reference points, grown by at most ``max_grow`` cells per
+        direction), and for every state the intersection of the boxes of the two segments it ends, shrunk by
+        ``max(|acc_min|, |acc_max|) h^2 / 8 + pad`` (scp_corridor_state_boxes) -- with that the whole segment stays in its box,
+        not only its end states.  The state boxes become the bounds of the position rows of every QP of
+        generate_trajectories / scp_iteration / repair_conflicts; validate_solution(corridor=True) checks the result.
+
+        ``reference``: (N, K + 1, D), the reference point of every state j = 0 .. K; None: the straight line from start to
+        goal.  A segment whose reference points lie on occupied cells or outside the grid is blocked, a state whose
+        intersection is empty is open (unconstrained): both raise ValueError naming the first one unless ``allow_open``.
+        Returns {"n_blocked", "n_open", "shrink", "boxes_ms", "state_boxes_ms"} (device milliseconds of the two kernels)."""
+        self._one_rank("set_corridors")
+        if self._obstacles is None:
+            raise ValueError("set_corridors needs set_obstacles first")
+        if self.initial_positions is None or self.final_positions is None:
+            raise ValueError("set_corridors needs both set_initial_states and set_final_states first")
+        if isinstance(max_grow, bool) or not isinstance(max_grow, (int, np.integer)) or not 0 <= max_grow <= _hip.CORRIDOR_MAX_GROW:
+            raise ValueError(f"max_grow={max_grow!r}: a whole number of cells in [0, {_hip.CORRIDOR_MAX_GROW}]")
+        shrink = corridor_shrink(self.acc_min, self.acc_max, self.h, pad)
+        N, K, D, c = self.N, self.K, self.D, self._ctx
+        if reference is None:
+            reference = straight_reference(self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D), K)
+        reference = np.ascontiguousarray(reference, dtype=np.float64)
+        if reference.shape != (N, K + 1, D):
+            raise ValueError(f"reference needs shape (N, K + 1, D) = ({N}, {K + 1}, {D}), got {reference.shape}")
+        grid = self._obstacles["grid"]
+        cells, n_blocked = c.corridor_boxes(N, K, D, grid, self._obstacles["sat"], c.tensor(reference), int(max_grow))
+        boxes_ms = c.last_pair_ms()
+        lo, hi, n_open = c.corridor_state_boxes(N, K, D, grid, cells, shrink)
+        state_ms = c.last_pair_ms()
+        info = {"n_blocked": int(n_blocked.item()), "n_open": int(n_open.item()), "shrink": shrink, "boxes_ms": boxes_ms,
+                "state_boxes_ms": state_ms}
+        if (info["n_blocked"] or info["n_open"]) and not allow_open:
+            hc = cells.cpu().numpy()
+            blocked = np.argwhere(hc[..., 3] < hc[..., 0])
+            if blocked.size:
+                i, g = (int(x) for x in blocked[0])
+                raise ValueError(f"corridor: segment {g} of vehicle {i} is blocked (its reference points "
+                                 f"{reference[i, g].tolist()} -> {reference[i, g + 1].tolist()} lie on occupied cells or outside "
+                                 f"the grid); {info['n_blocked']} blocked segments, {info['n_open']} open states in all")
+            opened = np.argwhere(np.isinf(lo.cpu().numpy()[:, 1:, 0]))
+            i, j = (int(x) for x in opened[0])
+            raise ValueError(f"corridor: state {j + 1} of vehicle {i} is open (the boxes of segments {j} and {j + 1}, shrunk by "
+                             f"{shrink:.4g}, do not meet); {info['n_open']} open states in all")
+        check_position_boxes(N, K, D, self.pos_min, self.pos_max, lo.cpu().numpy(), hi.cpu().numpy())
+        self._corridor = {"cells": cells, "grid": grid}
+        self._boxes = (lo, hi)
+        self.last_info["corridor"] = info
+        return info
+
+    def set_position_boxes(self, lo, hi):
+        """Per-(vehicle, state) position boxes, the general form of set_corridors (waypoints, keep-in regions): ``lo`` / ``hi``
+        (N, K, D), state j = 0 .. K-1 of vehicle i must lie in [lo[i, j], hi[i, j]] intersected with the workspace box;
+        -inf / +inf leave an entry unconstrained, state 0 (the start) is never constrained.  Both None: no boxes.  Every QP
+        with boxes runs the round-2 persistent kernel or the three-launch pipeline."""
+        if lo is None and hi is None:
+            self._boxes = None
+            return
+        if lo is None or hi is None:
+            raise ValueError("set_position_boxes: lo and hi are both given or both None")
+        self._one_rank("set_position_boxes")
+        lo, hi = check_position_boxes(self.N, self.K, self.D, self.pos_min, self.pos_max, lo, hi)
+        self._boxes = (self._ctx.tensor(lo), self._ctx.tensor(hi))
+
+    def _apply_boxes(self, qp):
+        """the boxes into a QP whose problem has just been set (the Python-driven loops)"""
+        if self._boxes is not None:
+            self._one_rank("position boxes")
+            qp.set_position_boxes(*self._boxes)
+
+    def _native_boxes(self, nat):
+        """the boxes (or none: a pooled solver may remember a released object's) into the native solver, before solve / step"""
+        if self._boxes is not None:
+            self._one_rank("position boxes")
+        nat.set_position_boxes(*(self._boxes or (None, None)))
 
     # ------------------------------------------------------------------------------------------------
     # a0: states (scp.py:99-129)
@@ -329,6 +477,7 @@ class SCP:
         else:
             p0, v0, pf, vf = self._states()
             new.set_problem(self._limits(), self._space(), p0, v0, pf, vf)
+            self._apply_boxes(new)
         old.close()
         self._qp = new
         return new
@@ -338,6 +487,8 @@ class SCP:
     # ------------------------------------------------------------------------------------------------
     def generate_trajectories(self, max_iterations=15):
         """Main method to generate collision-free trajectories using SCP (scp.py:131-180)."""
+        if self._boxes is not None:
+            self._one_rank("generate_trajectories with position boxes")
         if self.native and self.shard.world == 1:
             return self._generate_trajectories_native(max_iterations)
         is_feasible = False
@@ -469,6 +620,7 @@ class SCP:
         if self.shard.world != 1:
             return self.scp_iteration_sharded(accelerations)
         nat = self._ensure_native()
+        self._native_boxes(nat)
         p0, v0, pf, vf = self._states()
         new, rec = nat.step(self._limits(), self._space(), p0, v0, pf, vf, self._native_options(),
                             self._to_device_acc(accelerations))
@@ -486,6 +638,7 @@ class SCP:
         agents and allgathered (one collective per SCP iteration, the north-star layout); False: every rank integrates
         all agents itself (N K^2 flops, cheaper than the collective below ~10^4 agents)."""
         nat = self._ensure_native()
+        self._native_boxes(nat)
         p0, v0, pf, vf = self._states()
         acc = self._to_device_acc(accelerations)
         opts = self._native_options()
@@ -517,6 +670,7 @@ class SCP:
         start_time = time.time()
         self._drop_bound_attributes()  # l_* / u_* are recomputed when somebody reads them (see __getattr__)
         nat = self._ensure_native()
+        self._native_boxes(nat)
         p0, v0, pf, vf = self._states()
         opts = self._native_options(max_iterations)
         acc, pos, vel, res, recs = nat.solve(self._limits(), self._space(), p0, v0, pf, vf, opts)
@@ -564,6 +718,7 @@ class SCP:
     def _precompute_constraint_matrices(self):
         p0, v0, pf, vf = self._fill_bound_attributes()
         self._ensure_qp().set_problem(self._limits(), self._space(), p0, v0, pf, vf)
+        self._apply_boxes(self._qp)
 
     _BOUND_ATTRS = ("l_jerk", "u_jerk", "l_acc", "u_acc", "l_vel", "u_vel", "l_pos", "u_pos")
 
@@ -825,7 +980,9 @@ class SCP:
         segments; -1 if lag 0 already violates), ``seconds`` (steps * h) and ``limited_by`` (the partner at lag steps + 1, -1
         where steps = S); ``least_tolerant_vehicle``: ``{"vehicle", "steps", "seconds", "partner", "time", "distance"}`` of
         the smallest ``steps`` (ties: the lowest index; partner, time and distance are those of lag steps + 1, or of lag S
-        where steps = S; None without a pair)."""
+        where steps = S; None without a pair).
+
+        After set_corridors the report also has ``corridor``, what validate_corridor() returns (tolerance 0)."""
         if conflicts and not continuous:
             raise ValueError("conflicts=True lists the conflicts of the continuous-time check: it needs continuous=True")
         if clearance and not continuous:
@@ -876,7 +1033,34 @@ class SCP:
             report.update(self._clearance_profiles(dev, q0, q1))
         if delay is not None:
             report.update(self._delay_margins(dev, int(delay)))
+        if self._corridor is not None:
+            report["corridor"] = self.validate_corridor(dev=dev if continuous else None)
         return report
+
+    def validate_corridor(self, tol=0.0, dev=None):
+        """Does every segment of every vehicle of the stored trajectories stay inside its un-shrunk corridor box (set_corridors)
+        over its whole duration, not only at its samples?  Exact per segment and coordinate (scp_check_corridor).  Returns
+        ``vehicles``: a dictionary of length-N arrays ``max_excess`` (the largest distance by which a segment leaves its box in
+        any coordinate; <= 0: inside), ``segment`` (where; -1: none judged), ``n_blocked`` (blocked segments are not judged)
+        and ``n_outside`` (segments with excess > tol); the totals ``n_outside``, ``n_blocked``, ``max_excess``,
+        ``worst_vehicle``; ``inside`` = no segment outside and none blocked; ``check_ms`` (device time).  validate_solution
+        includes it as ``report["corridor"]``.  The cells stay those of the latest set_corridors, also after
+        set_position_boxes(None, None): a plan made without boxes can be judged against them."""
+        if self._corridor is None:
+            raise ValueError("validate_corridor checks the boxes of set_corridors: call it first")
+        if self.trajectories is None:
+            raise ValueError("Trajectories not generated yet")
+        c = self._ctx
+        if dev is None:
+            dev = tuple(c.tensor(self.trajectories[k]) for k in ("positions", "velocities", "accelerations"))
+        st = c.check_corridor(self.N, self.K, self.D, self.h, self._corridor["grid"], self._corridor["cells"], *dev, tol=float(tol))
+        seg = np.where(st["segment"] == np.uint32(_hip.NO_INDEX), -1, st["segment"].astype(np.int64))
+        n_out, n_blk = int(st["n_outside"].sum()), int(st["n_blocked"].sum())
+        return {"vehicles": {"max_excess": st["max_excess"].copy(), "segment": seg, "n_blocked": st["n_blocked"].astype(np.int64),
+                             "n_outside": st["n_outside"].astype(np.int64)},
+                "n_outside": n_out, "n_blocked": n_blk, "max_excess": float(st["max_excess"].max()),
+                "worst_vehicle": int(np.argmax(st["max_excess"])), "inside": n_out == 0 and n_blk == 0,
+                "check_ms": c.last_pair_ms()}
 
     def _delay_margins(self, dev, S):
         """The delay part of validate_solution: one device pass (scp_delay_margins) over this rank's vehicles of the device
@@ -998,6 +1182,7 @@ class SCP:
                 "admm_steps_per_pass": [], "update_holds_ms": [], "apply_holds_ms": []}
         if found.size and max_passes > 0:
             self._ensure_qp().set_problem(self._limits(), self._space(), p0, v0, pf, vf)
+            self._apply_boxes(self._qp)
             self._rho_start = 0.0
             table, n_holds = c.hold_table(capacity=max(1024, 4 * found.size))
         try:

@@ -775,12 +775,117 @@ typedef struct scp_line_stats {  /* DEVICE, one per scenario, 32 bytes */
 int scp_straight_line_check(scp_ctx* ctx, int B, int N, int D, const double* start, const double* goal,
                             const int32_t* goal_of /* [B][N] or NULL */, double min_sep, scp_line_stats* stats /* [B] */);
 
+/* ---- static obstacles: safe flight corridors as per-step position boxes ---------------------------------------------------
+ * A purely additive part of ABI version 7: three structs and seven functions; no other entry point changes its behaviour or
+ * its bits while no boxes are set.  The obstacles are an occupancy grid; for every vehicle and every segment a box of free
+ * cells is grown around a reference path; state j must lie in the intersection of the boxes of the two segments it ends,
+ * which in the joint QP is a change of the bounds of position rows that exist already.  tests/corridor_ref.py restates every
+ * rule below in numpy, integers exactly and doubles bit for bit.
+ *
+ * Conventions.  STATE j = 0 .. K is the position at time j h: states 0 .. K-1 are the stored pos[.][j], state 0 is fixed to p0
+ * and state K to pf.  SEGMENT g = 0 .. K-1 runs from state g to state g + 1 with the kinematics of scp_check_separation:
+ * inside it a coordinate is p + t v + t^2/2 a, (p, v, a) = (pos, vel, acc)[i][g][d], t in [0, h].  Every floating-point
+ * formula below is evaluated with each product, quotient, sum and difference rounded on its own (no contraction).  max / min
+ * of two doubles take the first operand unless the second is strictly greater / smaller; NaN inputs are not supported except
+ * where a rule names them.
+ *
+ * Grid.  Cell (x, y, z) is the closed cube [origin_d + cell c_d, origin_d + cell (c_d + 1)] per coordinate; occ[(z ny + y) nx + x]
+ * != 0 means occupied.  In 2-D nz = 1 and origin[2] is ignored.  Supported: D in {2, 3}, every dim >= 1, nx ny nz <= 2^24,
+ * D = 2 => nz = 1, cell > 0 and finite, finite origin; anything else returns SCP_ERR_INVALID with a message.
+ *
+ * scp_occupancy_prepare: sat[(z ny + y) nx + x] = the number of occupied cells (x', y', z') with x' <= x, y' <= y, z' <= z
+ * (the inclusive prefix count; integers only).  Separate from the corridor call so that re-planning with new reference
+ * paths reuses it.  One launch per dimension (a wave scans a row along x, a thread walks a column along y / z); enqueued on
+ * the ctx's stream, no host read.  The number of occupied cells in the cell range [a, b] (inclusive per coordinate) is the
+ * inclusion-exclusion sum of sat over the 4 (8) corners (b or a - 1 per coordinate, a term with an index -1 is 0). */
+typedef struct scp_occupancy_grid { /* [host] */
+  double origin[3]; /* lower corner of cell (0,0,0); origin[2] ignored in 2-D */
+  double cell;      /* edge length, > 0, finite */
+  int32_t dims[3];  /* nx, ny, nz; nz = 1 in 2-D */
+  int32_t reserved;
+} scp_occupancy_grid;
+int scp_occupancy_prepare(scp_ctx* ctx, int D, const scp_occupancy_grid* grid,
+                          const uint8_t* occ /* DEVICE [nz][ny][nx], x fastest, nonzero = occupied */,
+                          int32_t* sat /* DEVICE, nx*ny*nz words */);
+
+/* scp_corridor_boxes: the box of segment g of vehicle i, in cells, from the reference points ref[i][g] and ref[i][g + 1].
+ *   Cell lookup.  f_d(x) = floor((x - origin_d) / cell): one subtraction, one division.  The coordinate is INSIDE if it is
+ *     finite and 0 <= f_d(x) < dims_d (compared as doubles); then c_d(x) = (int) f_d(x).
+ *   Seed.  lo_d = min(c_d(ref[g]), c_d(ref[g+1])), hi_d = the max, d < D; in 2-D lo_z = hi_z = 0.
+ *   Blocked.  If a coordinate (d < D) of either point is not inside, or the seed range [lo, hi] holds an occupied cell, the
+ *     segment is BLOCKED: its record is (0, 0, 0, -1, -1, -1) and it counts in *n_blocked.
+ *   Sweeps.  Otherwise sweeps repeat until a sweep extends nothing.  A sweep takes the directions in the order -x, +x, -y, +y
+ *     (3-D: then -z, +z).  Direction -d extends the box by one cell (lo_d -= 1) if (a) seed_lo_d - lo_d < max_grow, (b)
+ *     lo_d - 1 >= 0 and (c) the slab {c_d = lo_d - 1} x the box's CURRENT range in the other coordinates holds no occupied
+ *     cell; direction +d likewise with hi_d - seed_hi_d < max_grow, hi_d + 1 < dims_d and the slab {c_d = hi_d + 1}.
+ *     Extensions made earlier in the same sweep count.  (A direction that fails once fails ever after, so there are at most
+ *     2 D max_grow + 1 sweeps.)
+ * The record is cells[(i K + g) 6 ..] = lo_x, lo_y, lo_z, hi_x, hi_y, hi_z, inclusive.  A box never holds an occupied cell
+ * nor a cell outside the grid, contains both seed cells and is locally maximal.  Integers after the cell lookup; the result
+ * does not depend on the launch geometry.  One THREAD per (vehicle, segment): the work of a segment is a short serial chain
+ * of dependent table reads (4 per slab in 2-D, 8 in 3-D), which more lanes cannot shorten.
+ * Supported: N, K >= 1, 0 <= max_grow <= 1024.  *n_blocked is written (not accumulated).  No host read. */
+int scp_corridor_boxes(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, const int32_t* sat,
+                       const double* ref /* DEVICE [N][K+1][D]: reference point of every state */,
+                       int max_grow /* 0 .. 1024 cells */,
+                       int32_t* cells /* DEVICE [N][K][6] */, uint64_t* n_blocked /* DEVICE */);
+
+/* scp_corridor_state_boxes: the boxes of the states in metres.
+ *   Segment box.  L_d = origin_d + cell * (double)lo_d,  H_d = origin_d + cell * (double)(hi_d + 1).
+ *   State j = 1 .. K-1.  lo_d = max(L_d(seg j-1), L_d(seg j)) + shrink,  hi_d = min(H_d(seg j-1), H_d(seg j)) - shrink.
+ *   Open.  If either segment is blocked, or lo_d > hi_d for some d, the WHOLE state gets (-inf, +inf) in every coordinate
+ *     and counts in *n_open (written, not accumulated).  State 0 is always (-inf, +inf) and does not count.
+ * Why the shrink: inside a segment a coordinate is a quadratic in t, which leaves the chord of its end values by at most
+ * |a_d| h^2 / 8 (the maximum of t (h - t) / 2 |a_d|).  With shrink >= acc_max_abs h^2 / 8 + pad the end states lie in the
+ * shrunk intersections, both of which lie inside box g shrunk by `shrink`, so the whole segment lies inside box g -- up to
+ * the QP's constraint tolerance, which `pad` pays for.  Supported: finite shrink >= 0.  lo / hi are [N][K][D], indexed by
+ * state j = 0 .. K-1.  One thread per (vehicle, state).  No host read. */
+int scp_corridor_state_boxes(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, const int32_t* cells,
+                             double shrink /* >= 0 */, double* lo, double* hi /* DEVICE [N][K][D] */,
+                             uint64_t* n_open /* DEVICE */);
+
+/* scp_qp_set_position_boxes: per-(vehicle, state) position boxes into the bounds of the QP.  Call it after
+ * scp_qp_set_problem.  For state j = 1 .. K-1 and column c = (i, d) it rewrites row k = j - 1 of the position block of the
+ * fixed bounds (row 3K - 1 + k of "lf" / "uf"):
+ *   l = max(space_min_d, lo[i][j][d]) - off,   u = min(space_max_d, hi[i][j][d]) - off,
+ *   off = p0 + hk * v0 with hk = h * (double)(k + 1)   (the offset of scp_fixed_bounds),
+ * space, p0, v0 those of the latest scp_qp_set_problem.  Entry j = 0, the final row k = K - 1 and every other block keep
+ * their bits; entries (-inf, +inf) reproduce the bits of scp_qp_set_problem.  l > u is the caller's error (the QP is then
+ * infeasible; path_planning checks it on the host).  Enqueues one launch, no host read.  While boxes are set the QP's
+ * persistent path runs the round-2 kernel (SCP_PIPE_PERSIST) where it fits and the three-launch pipeline otherwise, never
+ * a lean kernel (SCP_PIPE_PERSIST16 / SCP_PIPE_PERSIST8L re-derive the bounds from space and the states), whatever
+ * settings.persistent says.  scp_qp_set_problem rewrites the bounds and so clears the boxes; scp_qp_clone_state copies
+ * them.  lo = hi = NULL is a no-op; exactly one NULL returns SCP_ERR_INVALID. */
+int scp_qp_set_position_boxes(scp_qp* qp, const double* lo, const double* hi /* DEVICE [N][K][D] by state, or both NULL */);
+/* The solver keeps the two pointers (the arrays must outlive its calls) and applies them right after every
+ * scp_qp_set_problem it makes -- QP#0, every step, a QP that moves to a larger workspace.  Both NULL: none (the default). */
+int scp_solver_set_position_boxes(scp_solver* s, const double* lo, const double* hi);
+
+/* scp_check_corridor: does every segment stay inside its (un-shrunk) box?  Exact per segment and coordinate: the candidates
+ * are t = 0, t = h and t* = -v / a if a != 0 and 0 < t* < h; the value at t is p + (t * v + ((0.5 * t) * t) * a) (the formula
+ * of scp_update_holds); lo_v / hi_v = the min / max over the candidates;
+ *   excess(segment) = max over d of max(L_d - lo_v, hi_v - H_d)      (<= 0: inside)
+ * with L, H of scp_corridor_state_boxes.  Blocked segments are counted, not judged.  Per vehicle: max_excess over its judged
+ * segments and the lowest g that attains it, n_blocked, n_outside = judged segments with excess > tol.  One wave per
+ * vehicle; deterministic.  Supported: finite h > 0, finite trajectories.  No host read. */
+typedef struct scp_corridor_stats { /* DEVICE, one per vehicle, 32 bytes */
+  double max_excess;  /* <= 0: inside; -inf: no segment judged */
+  uint32_t segment;   /* where (lowest g on ties); UINT32_MAX: none */
+  uint32_t n_blocked; /* its blocked segments (not judged) */
+  uint64_t n_outside; /* judged segments with excess > tol */
+  uint64_t reserved;
+} scp_corridor_stats;
+int scp_check_corridor(scp_ctx* ctx, int N, int K, int D, double h, const scp_occupancy_grid* grid, const int32_t* cells,
+                       const double* pos, const double* vel, const double* acc /* DEVICE [N][K][D] */, double tol,
+                       scp_corridor_stats* out /* DEVICE [N] */);
+
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
 int scp_gemm_f64(scp_ctx* ctx, int use_mfma, int R, int M, int C, double alpha, const double* A,
                  const double* X, double beta, double* Y);
 /* Copy one internal array of the solver (time-major device layout) to `out` (device, capacity `cap` doubles);
- * *n_out [host] = its length.  name: "x" [K][C], "zf" / "yf" / "fx" [4K-1][C] (fx = carried F x), "qx" [K][C] (carried S0 x),
+ * *n_out [host] = its length.  name: "x" [K][C], "zf" / "yf" / "fx" [4K-1][C] (fx = carried F x), "lf" / "uf" [4K-1][C] (the
+ * bounds of the fixed rows; tests/test_corridor_gpu.py), "qx" [K][C] (carried S0 x),
  * "zc" / "yc" per working row, "gval" per incidence-list entry; "Hf" / "Minv" / "T" [K][K] row-major: the blocks of the
  * current rho (H_f, its inverse, T = S0 H_f^-1; tests/test_pipeline_iterates_gpu.py).  tests/test_qp_gpu.py compares the
  * state the persistent and the three-launch pipelines leave behind. */
