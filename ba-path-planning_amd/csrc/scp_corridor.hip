@@ -54,31 +54,6 @@ __global__ __launch_bounds__(256) void sat_lines_kernel(int64_t lines, int inner
 // ----------------------------------------------------------------------------------------------------
 // corridor boxes: one thread per (vehicle, segment)
 // ----------------------------------------------------------------------------------------------------
-__device__ inline int sat_at(const int32_t* __restrict__ sat, const CorridorGrid& g, int x, int y, int z) {
-  if (x < 0 || y < 0 || z < 0) return 0;
-  return sat[((int64_t)z * g.dims[1] + y) * g.dims[0] + x];
-}
-
-// occupied cells in the inclusive range [a, b]
-template <int D>
-__device__ inline int occupied_in(const int32_t* __restrict__ sat, const CorridorGrid& g, const int* a, const int* b) {
-  int n = sat_at(sat, g, b[0], b[1], b[2]) - sat_at(sat, g, a[0] - 1, b[1], b[2]) - sat_at(sat, g, b[0], a[1] - 1, b[2]) +
-          sat_at(sat, g, a[0] - 1, a[1] - 1, b[2]);
-  if (D == 3)
-    n -= sat_at(sat, g, b[0], b[1], a[2] - 1) - sat_at(sat, g, a[0] - 1, b[1], a[2] - 1) -
-         sat_at(sat, g, b[0], a[1] - 1, a[2] - 1) + sat_at(sat, g, a[0] - 1, a[1] - 1, a[2] - 1);
-  return n;
-}
-
-// the cell of a coordinate; false: not inside the grid (or not finite)
-__device__ inline bool cell_of(const CorridorGrid& g, int d, double x, int& c) {
-#pragma clang fp contract(off)
-  const double f = floor((x - g.origin[d]) / g.cell);
-  if (!(f >= 0.0 && f < (double)g.dims[d])) return false;  // (a NaN fails both)
-  c = (int)f;
-  return true;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void corridor_boxes_kernel(int64_t n_seg, int K, CorridorGrid g,
                                                               const int32_t* __restrict__ sat,
@@ -288,8 +263,10 @@ __global__ __launch_bounds__(256) void check_corridor_kernel(int N, int K, doubl
   }
 }
 
+}  // namespace
+
 // ----------------------------------------------------------------------------------------------------
-// host side
+// host side (the first three are shared with scp_reference.hip: scp_corridor_device.h)
 // ----------------------------------------------------------------------------------------------------
 int corridor_grid(scp_ctx* ctx, const char* who, int D, const scp_occupancy_grid* grid, CorridorGrid& g) {
   SCP_REQUIRE(ctx, D == 2 || D == 3, "%s: D=%d (2 or 3)", who, D);
@@ -322,8 +299,6 @@ int corridor_end(scp_ctx* ctx) {  // after the call's last launch: launch errors
   ctx->pair_ran = true;
   return SCP_OK;
 }
-
-}  // namespace
 
 extern "C" int scp_occupancy_prepare(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, const uint8_t* occ, int32_t* sat) {
   if (!ctx) return SCP_ERR_INVALID;

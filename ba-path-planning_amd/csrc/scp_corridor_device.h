@@ -1,4 +1,5 @@
-// Arithmetic shared by the kernels of scp_corridor.hip (the rules are stated in include/scp_hip.h, "static obstacles").
+// Arithmetic shared by the kernels of scp_corridor.hip and scp_reference.hip (the rules are stated in include/scp_hip.h,
+// "static obstacles").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,39 @@ struct CorridorGrid {  // scp_occupancy_grid by value, as the kernels take it
   double cell;
   int dims[3];
 };
+
+__device__ inline int sat_at(const int32_t* __restrict__ sat, const CorridorGrid& g, int x, int y, int z) {
+  if (x < 0 || y < 0 || z < 0) return 0;
+  return sat[((int64_t)z * g.dims[1] + y) * g.dims[0] + x];
+}
+
+// occupied cells in the inclusive range [a, b]
+template <int D>
+__device__ inline int occupied_in(const int32_t* __restrict__ sat, const CorridorGrid& g, const int* a, const int* b) {
+  int n = sat_at(sat, g, b[0], b[1], b[2]) - sat_at(sat, g, a[0] - 1, b[1], b[2]) - sat_at(sat, g, b[0], a[1] - 1, b[2]) +
+          sat_at(sat, g, a[0] - 1, a[1] - 1, b[2]);
+  if (D == 3)
+    n -= sat_at(sat, g, b[0], b[1], a[2] - 1) - sat_at(sat, g, a[0] - 1, b[1], a[2] - 1) -
+         sat_at(sat, g, b[0], a[1] - 1, a[2] - 1) + sat_at(sat, g, a[0] - 1, a[1] - 1, a[2] - 1);
+  return n;
+}
+
+// the cell of a coordinate; false: not inside the grid (or not finite)
+__device__ inline bool cell_of(const CorridorGrid& g, int d, double x, int& c) {
+#pragma clang fp contract(off)
+  const double f = floor((x - g.origin[d]) / g.cell);
+  if (!(f >= 0.0 && f < (double)g.dims[d])) return false;  // (a NaN fails both)
+  c = (int)f;
+  return true;
+}
+
+// host side of every call on an occupancy grid (scp_corridor.hip): the grid's validation (who: the call's name in messages),
+// the start of the timing bracket, and -- after the call's last launch -- launch errors and the end of the bracket
+struct scp_ctx;
+struct scp_occupancy_grid;
+int corridor_grid(scp_ctx* ctx, const char* who, int D, const scp_occupancy_grid* grid, CorridorGrid& g);
+int corridor_begin(scp_ctx* ctx);
+int corridor_end(scp_ctx* ctx);
 
 // the record of one segment: lo[0..3), hi[0..3), inclusive cell indices; blocked: (0, 0, 0, -1, -1, -1)
 struct CorridorCells {

@@ -238,6 +238,23 @@ CORRIDOR_MAX_CELLS = 1 << 24  # scp_occupancy_prepare
 CORRIDOR_MAX_GROW = 1024      # scp_corridor_boxes
 
 
+class PathInfo(C.Structure):
+    """struct scp_path_info (scp_reference_paths; one per vehicle, a DEVICE array)"""
+    _fields_ = [("status", C.c_int32), ("n_nodes", C.c_int32), ("start_node", C.c_int32), ("goal_node", C.c_int32)]
+
+
+PATH_INFO_DTYPE = np.dtype([("status", np.int32), ("n_nodes", np.int32), ("start_node", np.int32), ("goal_node", np.int32)])
+LATTICE_MAX_NODES = 32768     # SCP_LATTICE_MAX_NODES: scp_lattice_edges, scp_reference_paths
+PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that is not free",
+               2: "the goal lies off the lattice or on a block that is not free", 3: "the goal cannot be reached from the start",
+               4: "the path has more nodes than max_path"}
+
+
+def lattice_shape(D, grid, stride):
+    """(L_x, L_y, L_z) of the search lattice of an OccupancyGrid: dims_d div stride, L_z = 1 in 2-D"""
+    return tuple(int(grid.dims[d]) // int(stride) if d < D else 1 for d in range(3))
+
+
 def occupancy_grid(D, origin, cell, dims) -> OccupancyGrid:
     """scp_occupancy_grid from origin (D,), the cell size and dims = (nx, ny[, nz])"""
     g = OccupancyGrid()
@@ -271,6 +288,7 @@ EXPORTS = [
     "scp_assign_goals", "scp_straight_line_check", "scp_assign_goals_wide",
     "scp_occupancy_prepare", "scp_corridor_boxes", "scp_corridor_state_boxes", "scp_qp_set_position_boxes",
     "scp_solver_set_position_boxes", "scp_check_corridor",
+    "scp_lattice_edges", "scp_reference_paths",
 ]
 
 
@@ -384,6 +402,8 @@ def load_library():
     lib.scp_qp_set_position_boxes.argtypes = [vp, vp, vp]
     lib.scp_solver_set_position_boxes.argtypes = [vp, vp, vp]
     lib.scp_check_corridor.argtypes = [vp, i32, i32, i32, f64, pg, vp, vp, vp, vp, f64, vp]
+    lib.scp_lattice_edges.argtypes = [vp, i32, pg, vp, i32, i32, vp]
+    lib.scp_reference_paths.argtypes = [vp, i32, i32, i32, pg, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     _LIB, _LIB_PATH = lib, path
     return lib
 
@@ -453,7 +473,8 @@ class Context:
         per workgroup of delay_margins and of lag_conflicts, 0: chosen by the call; results never depend on them),
         "stg_batch_threads" (threads per workgroup of schedule_starts_batch: 0 chosen by the call, 256 or 1024; likewise),
         "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
-        never, 1 always; likewise)"""
+        never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths: 0 chosen by the call, 256,
+        512 or 1024; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
@@ -850,6 +871,35 @@ class Context:
         self.check(self.lib.scp_check_corridor(self.h, N, K, D, float(h), C.byref(grid), cells.data_ptr(), pos.data_ptr(),
                                                vel.data_ptr(), acc.data_ptr(), float(tol), out.data_ptr()))
         return out.cpu().numpy().view(CORRIDOR_STATS_DTYPE)[:N].copy()
+
+    # ---- static obstacles: reference paths by a lattice search -------------------------------------------------------------
+    def lattice_edges(self, D, grid: OccupancyGrid, sat, stride, clearance=0):
+        """scp_lattice_edges: the edge masks of the search lattice (int32 device tensor [nodes] holding the uint32 words).  No
+        host read."""
+        torch = _torch()
+        L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
+        edges = torch.empty(max(L[0] * L[1] * L[2], 1), dtype=torch.int32, device=self.tdev)
+        self.check(self.lib.scp_lattice_edges(self.h, int(D), C.byref(grid), sat.data_ptr(), int(stride), int(clearance),
+                                              edges.data_ptr()))
+        return edges
+
+    def reference_paths(self, N, K, D, grid: OccupancyGrid, stride, edges, p0, pf, max_path, ref, want_path=True, want_dist=False):
+        """scp_reference_paths: p0 / pf (N, D) and ref (N, K + 1, D) device tensors; ref is updated IN PLACE for the vehicles
+        whose path was found.  Returns (path (N, max_path) int32 device tensor or None, info as a uint8 device tensor of N
+        records of PATH_INFO_DTYPE, dist (N, nodes) int16 device tensor holding the uint16 words or None, n_failed int64
+        device tensor of one word).  No host read."""
+        torch = _torch()
+        L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
+        nodes = max(L[0] * L[1] * L[2], 1)
+        path = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_path else None
+        dist = torch.empty((N, nodes), dtype=torch.int16, device=self.tdev) if want_dist else None
+        info = torch.empty(max(N, 1) * PATH_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        n_failed = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_reference_paths(self.h, N, K, D, C.byref(grid), int(stride), edges.data_ptr(), p0.data_ptr(),
+                                                pf.data_ptr(), int(max_path), ref.data_ptr(),
+                                                path.data_ptr() if want_path else None, info.data_ptr(),
+                                                dist.data_ptr() if want_dist else None, n_failed.data_ptr()))
+        return path, info, dist, n_failed
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

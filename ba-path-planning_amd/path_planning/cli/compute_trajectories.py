@@ -92,15 +92,30 @@ def build_parser():
     p.add_argument("--corridor-grow", type=int, default=None, metavar="CELLS",
                    help="with --obstacle-discs: how many cells a corridor box may grow beyond its segment per direction "
                         "(default 8)")
+    p.add_argument("--corridor-search", action="store_true",
+                   help="with --obstacle-discs: the corridors follow paths found around the obstacles (a breadth-first search on "
+                        "a lattice of blocks of cells, one GPU workgroup per vehicle) instead of the straight lines, and one "
+                        "line says what was found")
+    p.add_argument("--corridor-stride", type=int, default=None, metavar="CELLS",
+                   help="with --corridor-search: edge length of a lattice block in cells (default: the smallest that keeps the "
+                        "lattice within 32768 nodes and a path across the map within the number of time steps)")
+    p.add_argument("--corridor-clearance", type=int, default=None, metavar="CELLS",
+                   help="with --corridor-search: free cells required around every lattice block on a path (default 0)")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
 
 
 def obstacle_discs(parser, args):
-    """the discs of --obstacle-discs as tuples of floats; the two corridor flags are errors without it"""
+    """the discs of --obstacle-discs as tuples of floats; the corridor flags are errors without it, --corridor-stride and
+    --corridor-clearance without --corridor-search"""
+    if not args.corridor_search:
+        for flag, value in (("--corridor-stride", args.corridor_stride), ("--corridor-clearance", args.corridor_clearance)):
+            if value is not None:
+                parser.error(f"{flag} needs --corridor-search")
     if args.obstacle_discs is None:
-        for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow)):
+        for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow),
+                            ("--corridor-search", args.corridor_search or None)):
             if value is not None:
                 parser.error(f"{flag} needs --obstacle-discs")
         return None
@@ -170,7 +185,14 @@ def main(argv=None):
 
             occ, origin, cell = rasterize(space_dims, args.corridor_cell or min_distance / 4, discs=discs, margin=min_distance / 2)
             solver.set_obstacles(occ, origin, cell)
-            co = solver.set_corridors(max_grow=8 if args.corridor_grow is None else args.corridor_grow)
+            reference = None
+            if args.corridor_search:
+                reference, fr = solver.find_reference(stride=args.corridor_stride, clearance=args.corridor_clearance or 0)
+                print(f"Corridor search: lattice of {' x '.join(str(n) for n in fr['lattice'])} blocks of {fr['stride']} cells "
+                      f"(clearance {fr['clearance']}), {n_vehicles - fr['n_failed']} of {n_vehicles} paths found, longest "
+                      f"E = {fr['max_edges']} for K = {solver.K}" + ("" if fr["guaranteed"] else " (no blocked segment is not "
+                      "guaranteed)") + f", {fr['edges_ms'] + fr['search_ms']:.3f} ms")
+            co = solver.set_corridors(reference=reference, max_grow=8 if args.corridor_grow is None else args.corridor_grow)
 
         print("Generating trajectories...")
         start_time = time.time()

@@ -25,6 +25,23 @@ def grid_shape(space_dims, cell):
     return origin.copy(), tuple(int(n) for n in dims)
 
 
+SEARCH_MAX_NODES = 32768  # SCP_LATTICE_MAX_NODES of include/scp_hip.h
+
+
+def default_search_stride(dims, K, D):
+    """The stride (cells per lattice block) SCP.find_reference uses by default on a grid dims = (nx, ny[, nz]): the smallest
+    s >= 1 with at most 32768 lattice nodes (prod(dims_d // s)) and max_d(dims_d) / s <= max(K - 2, 1), so that a path across
+    an unobstructed map has no more vertices than the trajectory has states (E <= K: consecutive reference points then lie on
+    one lattice edge or two adjacent ones, and no corridor segment is blocked)."""
+    dims = [int(n) for n in dims][:D]
+    if len(dims) != D or min(dims) < 1 or K < 1:
+        raise ValueError(f"dims={dims!r}, K={K!r}: {D} dimensions >= 1 and K >= 1")
+    s = 1
+    while int(np.prod([n // s for n in dims], dtype=np.int64)) > SEARCH_MAX_NODES or max(dims) > s * max(K - 2, 1):
+        s += 1
+    return s
+
+
 def _cell_edges(origin, cell, dims):
     """per coordinate: (lower edges, upper edges) of its cells"""
     out = []

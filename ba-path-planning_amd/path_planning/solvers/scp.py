@@ -26,6 +26,7 @@ import numpy as np
 
 from .. import _hip
 from .._sharding import Shard
+from ..scenarios.obstacles import default_search_stride
 from .conflicts import conflict_windows, pairs_from_index
 from .stagger import candidate_orders, refined_orders, schedule_key, staggered_fleet
 
@@ -217,7 +218,11 @@ class SCP:
                                   self._qp_row_capacity)
                 with _POOL_LOCK:
                     held = _POOL.get(self._pool_key)
-                    entry = held.pop() if held else None
+                    entry = None
+                    while held and entry is None:
+                        entry = held.pop()
+                        if not getattr(entry[0], "h", None):  # (collected in one cycle with its owner: the owner's finaliser
+                            entry = None                      # pooled the context, the context's own then destroyed it)
                     _POOL_STATS["hits" if entry else "misses"] += 1
                 if entry:
                     self._ctx, self._native = entry
@@ -231,7 +236,8 @@ class SCP:
         self._pairs = None
         self._holds = None  # (device table, count) of repair_conflicts while one of its passes runs
         self.staggered = None  # the fleet of the latest stagger_starts (its trajectories stay as they are)
-        self._obstacles = None  # set_obstacles: {"grid", "occ", "sat"} (device), the occupancy grid and its summed table
+        self._obstacles = None  # set_obstacles: {"grid", "occ", "sat"} (device), the occupancy grid and its summed table;
+                                # find_reference adds "edges": {(stride, clearance): the lattice's edge masks}
         self._corridor = None   # set_corridors: {"cells", "grid"}: the boxes of the segments, what validate_solution checks
         self._boxes = None      # (lo, hi) device tensors (N, K, D) by state: set_corridors / set_position_boxes
         self._dev = {}
@@ -298,10 +304,14 @@ class SCP:
         generate_trajectories / scp_iteration / repair_conflicts; validate_solution(corridor=True) checks the result.
 
         ``reference``: (N, K + 1, D), the reference point of every state j = 0 .. K; None: the straight line from start to
-        goal.  A segment whose reference points lie on occupied cells or outside the grid is blocked, a state whose
+        goal; "search": what find_reference() returns with its defaults (paths around the obstacles).  A segment whose reference points lie on occupied cells or outside the grid is blocked, a state whose
         intersection is empty is open (unconstrained): both raise ValueError naming the first one unless ``allow_open``.
         Returns {"n_blocked", "n_open", "shrink", "boxes_ms", "state_boxes_ms"} (device milliseconds of the two kernels)."""
         self._one_rank("set_corridors")
+        if isinstance(reference, str):
+            if reference != "search":
+                raise ValueError(f"reference={reference!r}: an array (N, K + 1, D), None (straight lines) or \"search\"")
+            reference, _ = self.find_reference()
         if self._obstacles is None:
             raise ValueError("set_corridors needs set_obstacles first")
         if self.initial_positions is None or self.final_positions is None:
@@ -339,6 +349,69 @@ class SCP:
         self._boxes = (lo, hi)
         self.last_info["corridor"] = info
         return info
+
+    def find_reference(self, stride=None, clearance=0, max_path=None, allow_unreachable=False):
+        """Reference paths around the obstacles, one per vehicle, for set_corridors(reference=...): a breadth-first search on
+        a lattice of blocks of ``stride`` x ``stride`` (x ``stride``) cells whose edges exist only where both blocks -- for a
+        diagonal move the whole 2 x 2 (2 x 2 x 2) group -- grown by ``clearance`` cells are free (scp_lattice_edges, once per
+        (stride, clearance)), then per vehicle the path with the fewest lattice moves from its start to its goal, sampled at
+        the states j = 0 .. K (scp_reference_paths: one workgroup per vehicle).  ``stride`` None:
+        scenarios.obstacles.default_search_stride; ``max_path`` None: min(lattice nodes, 8 K) nodes.
+
+        Returns (reference (N, K + 1, D) ndarray, info) and stores info as ``last_info["reference"]``: ``status`` (per vehicle:
+        0 found, 1 / 2 start / goal off the lattice or on a block that is not free, 3 unreachable, 4 longer than max_path),
+        ``n_nodes``, ``n_failed``, ``stride``, ``clearance``, ``lattice``, ``max_edges`` (the largest E = n_nodes + 1),
+        ``guaranteed`` (every found path has E <= K or 2 clearance >= stride ceil(E / K): set_corridors then reports no blocked
+        segment for those vehicles), ``edges_ms`` / ``search_ms`` (device milliseconds; edges_ms 0 when the masks were
+        cached).  A vehicle without a path keeps the straight line; unless ``allow_unreachable`` that raises ValueError."""
+        self._one_rank("find_reference")
+        if self._obstacles is None:
+            raise ValueError("find_reference needs set_obstacles first")
+        if self.initial_positions is None or self.final_positions is None:
+            raise ValueError("find_reference needs both set_initial_states and set_final_states first")
+        N, K, D, c = self.N, self.K, self.D, self._ctx
+        grid = self._obstacles["grid"]
+        dims = [int(grid.dims[d]) for d in range(D)]
+        if stride is None:
+            stride = default_search_stride(dims, K, D)
+        for name, value, least in (("stride", stride, 1), ("clearance", clearance, 0)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
+                raise ValueError(f"{name}={value!r}: a whole number of cells >= {least}")
+        stride, clearance = int(stride), int(clearance)
+        lattice = _hip.lattice_shape(D, grid, stride)
+        nodes = lattice[0] * lattice[1] * lattice[2]
+        if nodes < 1 or nodes > _hip.LATTICE_MAX_NODES:
+            raise ValueError(f"stride={stride}: a lattice of {lattice} nodes on a grid of {tuple(dims)} cells; supported are 1 .. "
+                             f"{_hip.LATTICE_MAX_NODES} nodes")
+        if max_path is None:
+            max_path = min(nodes, 8 * K)
+        if isinstance(max_path, bool) or not isinstance(max_path, (int, np.integer)) or not 1 <= max_path <= nodes:
+            raise ValueError(f"max_path={max_path!r}: a whole number of nodes in [1, {nodes}]")
+        cache = self._obstacles.setdefault("edges", {})
+        edges_ms = 0.0
+        if (stride, clearance) not in cache:
+            cache[stride, clearance] = c.lattice_edges(D, grid, self._obstacles["sat"], stride, clearance)
+            edges_ms = c.last_pair_ms()
+        p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
+        ref = c.tensor(straight_reference(p0, pf, K))
+        _, rec, _, n_failed = c.reference_paths(N, K, D, grid, stride, cache[stride, clearance], c.tensor(p0), c.tensor(pf),
+                                                int(max_path), ref, want_path=False)
+        search_ms = c.last_pair_ms()
+        rec = rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
+        found = rec["status"] == 0
+        E = rec["n_nodes"].astype(np.int64) + 1
+        info = {"status": rec["status"].copy(), "n_nodes": rec["n_nodes"].copy(), "n_failed": int(n_failed.item()),
+                "stride": stride, "clearance": clearance, "lattice": lattice[:D],
+                "max_edges": int(E[found].max()) if found.any() else 0,
+                "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
+                "edges_ms": edges_ms, "search_ms": search_ms}
+        self.last_info["reference"] = info
+        if info["n_failed"] and not allow_unreachable:
+            i = int(np.nonzero(~found)[0][0])
+            raise ValueError(f"reference path: vehicle {i} has none: {_hip.PATH_STATUS[int(rec['status'][i])]} (status "
+                             f"{int(rec['status'][i])}; stride {stride}, clearance {clearance}, lattice {lattice[:D]}); "
+                             f"{info['n_failed']} vehicles without a path in all")
+        return ref.cpu().numpy(), info
 
     def set_position_boxes(self, lo, hi):
         """Per-(vehicle, state) position boxes, the general form of set_corridors (waypoints, keep-in regions): ``lo`` / ``hi``

@@ -161,7 +161,9 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     scp_schedule_starts_batch; a developer switch.
  *   "stg_batch_transposed" (default -1: chosen by the call, from 16 candidates on; 0 never; 1 always): scp_schedule_starts_batch
  *     first writes a transposed copy of the masks (N^2 words in the context's workspace) and reads the masks' columns from
- *     its rows; a developer switch. */
+ *     its rows; a developer switch.
+ *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths; a
+ *     developer switch. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -878,6 +880,72 @@ typedef struct scp_corridor_stats { /* DEVICE, one per vehicle, 32 bytes */
 int scp_check_corridor(scp_ctx* ctx, int N, int K, int D, double h, const scp_occupancy_grid* grid, const int32_t* cells,
                        const double* pos, const double* vel, const double* acc /* DEVICE [N][K][D] */, double tol,
                        scp_corridor_stats* out /* DEVICE [N] */);
+
+/* ---- static obstacles: reference paths by a lattice search ------------------------------------------------------------------
+ * A further additive part of ABI version 7: one struct and two functions; nothing above changes.  They find, for every
+ * vehicle, a path of free lattice nodes from its start to its goal and sample it at the states j = 0 .. K: the `ref` of
+ * scp_corridor_boxes for maps where the straight line is blocked.  Grid, cell lookup f_d, "inside" and the summed-table range
+ * count are those of scp_occupancy_prepare / scp_corridor_boxes.  Integers everywhere except the two formulas of "reference
+ * points", which are evaluated without contraction.  tests/reference_path_ref.py restates every rule in numpy / plain Python.
+ *
+ * Lattice.  Parameters: stride s >= 1 and clearance c >= 0, both in cells.  L_d = dims_d div s for d < D, L_z = 1 in 2-D.
+ *   Supported: every L_d >= 1 and nodes = L_x L_y L_z <= SCP_LATTICE_MAX_NODES; anything else returns SCP_ERR_INVALID with a
+ *   message.  Node (X, Y, Z) has the id (Z L_y + Y) L_x + X; its BLOCK is the cell range [X_d s, X_d s + s - 1] per
+ *   coordinate d < D (z: [0, 0] in 2-D).  Cells beyond L_d s belong to no node.
+ * Directions.  A code n = 0 .. 26 means dx = n mod 3 - 1, dy = (n div 3) mod 3 - 1, dz = n div 9 - 1; 2-D uses the codes with
+ *   dz = 0; code 13 is the node itself.  DIRECTION ORDER: the codes other than 13 sorted by |dx| + |dy| + |dz|, then by code
+ *   (straight moves before diagonal ones).
+ *
+ * scp_lattice_edges (once per map, stride and clearance; independent of the vehicles).  Bit n of edges[node] is set iff the
+ *   neighbour in direction n lies in the lattice AND the cell range spanned by the two blocks (min of the lows, max of the
+ *   highs), grown by c cells per coordinate d < D on both sides and then clipped to the grid, holds no occupied cell: one
+ *   summed-table query (4 reads in 2-D, 8 in 3-D).  Bit 13 is therefore "the node's grown block is free" (the node is
+ *   PASSABLE) and is implied by every other set bit; bits 27 .. 31 are 0; edges are symmetric; a diagonal edge exists only
+ *   if the whole 2 x 2 (2 x 2 x 2) group of blocks is free, so a path never cuts a corner.  One thread per node.
+ *
+ * scp_reference_paths, per vehicle i from p0[i], pf[i]:
+ *   Start node: the cell of p0 by the cell lookup, X_d = c_d div s.  STATUS 1 if a coordinate (d < D) is not inside, or some
+ *     X_d >= L_d, or the node is not passable.  STATUS 2: the same for the goal, tested only if the start passed.
+ *   dist: the breadth-first distance from the GOAL node over the edges at unit cost, uint16, 0xFFFF = unreached (a reached
+ *     distance is at most 32767).  STATUS 3 if the start is unreached.  m = dist[start] + 1 is the number of nodes of the
+ *     path; STATUS 4 if m > max_path.
+ *   Path: node_0 = start; node_{t+1} = the first neighbour of node_t, in direction order, whose edge bit is set and whose
+ *     dist equals dist(node_t) - 1.  dist is unique, so nothing depends on how the search is scheduled.
+ *   Reference points: V_0 = p0; for t = 1 .. m, V_t = the centre of node_{t-1}: origin_d + cell * ((double)(X_d s) + 0.5 *
+ *     (double)s); V_{m+1} = pf; E = m + 1.  For state j = 0 .. K, with q = (j E) div K and r = (j E) mod K in 64-bit integers:
+ *     the point is V_E if q == E (only j = K), otherwise V_q + ((double)r / (double)K) * (V_{q+1} - V_q), every operation
+ *     rounded on its own, also for r = 0.  Only coordinates d < D are written.
+ *   A vehicle with status != 0: its rows of `ref` are NOT written (ref is in/out: the caller's pre-filled points stay), its
+ *     path row is all -1 and its n_nodes 0.  info[i].start_node / goal_node is the node's id wherever the point lies on the
+ *     lattice and was tested, else -1 (the goal is not tested with status 1).  *n_failed is written, not accumulated.
+ *   dist_out (for tests): the vehicle's dist as the search leaves it.  The search stops after the level that reaches the
+ *     start, so nodes farther from the goal than the start read 0xFFFF like the unreachable ones; with status 1 or 2 every
+ *     entry reads 0xFFFF, with start node = goal node every entry but the goal's.
+ * Why such a path serves as a corridor reference: if E <= K, two consecutive reference points lie on one edge or on two
+ * adjacent ones, so their seed range lies inside cell ranges the edge rule has found free: scp_corridor_boxes reports no
+ * blocked segment for that vehicle at any clearance >= 0.  Beyond that, with f = ceil(E / K), 2 c >= s f is sufficient.
+ *
+ * ONE workgroup per vehicle and no workgroup waits for another; dist lives in the workgroup's LDS (64 KiB plus a few
+ * control words, static, two workgroups per CU); the search runs level by level with one barrier per level, at most `nodes`
+ * levels, and stops as soon as the start is reached or a level changes nothing; one thread then walks the path and the
+ * threads write the K + 1 points side by side.  The edge masks are read from global memory.  Supported: N, K >= 1, 1 <=
+ * max_path <= nodes, the same stride as the edges were made with.  Both calls: argument checks, enqueue on the ctx's stream,
+ * no host read, timing through scp_ctx_last_pair_ms. */
+#define SCP_LATTICE_MAX_NODES 32768
+int scp_lattice_edges(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, const int32_t* sat, int stride, int clearance,
+                      uint32_t* edges /* DEVICE [nodes] */);
+typedef struct scp_path_info { /* DEVICE, one per vehicle, 16 bytes */
+  int32_t status;     /* 0 found; 1 start, 2 goal off the lattice or not passable; 3 unreachable; 4 longer than max_path */
+  int32_t n_nodes;    /* m; 0 unless status == 0 */
+  int32_t start_node; /* -1 where it could not be determined */
+  int32_t goal_node;
+} scp_path_info;
+int scp_reference_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+                        const double* p0, const double* pf /* DEVICE [N][D] */, int max_path,
+                        double* ref /* DEVICE [N][K+1][D], in/out */,
+                        int32_t* path /* DEVICE [N][max_path] or NULL; entries beyond n_nodes are -1 */,
+                        scp_path_info* info /* DEVICE [N] */, uint16_t* dist_out /* DEVICE [N][nodes] or NULL */,
+                        uint64_t* n_failed /* DEVICE */);
 
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
