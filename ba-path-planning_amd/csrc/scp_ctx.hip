@@ -117,6 +117,12 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
     ctx->ref_path_threads = value;
     return SCP_OK;
   }
+  if (strcmp(key, "shorten_threads") == 0) {  // scp_shorten_paths (same results; tests/test_shorten_gpu.py compares them)
+    if (value != 0 && value != 64 && value != 128 && value != 256)
+      return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0, 64, 128 or 256)", key, value);
+    ctx->shorten_threads = value;
+    return SCP_OK;
+  }
   if (strcmp(key, "assign_wide_min_bidders") == 0) {
     if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
     ctx->asgw_min_bidders = value;

@@ -4,6 +4,7 @@
 // search"); tests/reference_path_ref.py is their restatement (integers exactly, the points bit for bit: no contraction).
 #include "scp_common.h"
 #include "scp_corridor_device.h"
+#include "scp_lattice_device.h"
 
 #include <cmath>
 
@@ -11,12 +12,6 @@ namespace {
 
 constexpr int LATTICE_SELF = 13;          // the direction code of the node itself
 constexpr unsigned DIST_UNREACHED = 0xFFFFu;
-
-struct Lattice {
-  int L[3];    // nodes per coordinate (L[2] = 1 in 2-D)
-  int nodes;   // L[0] L[1] L[2] <= SCP_LATTICE_MAX_NODES
-  int stride;  // cells per block edge
-};
 
 // direction order: the codes other than 13 by |dx| + |dy| + |dz|, then by code
 struct DirectionOrder {
@@ -83,20 +78,6 @@ __device__ inline bool node_of(const Lattice& lt, const CorridorGrid& g, const d
   }
   node = (X[2] * lt.L[1] + X[1]) * lt.L[0] + X[0];
   return ok;
-}
-
-// V_t of vehicle i, coordinate d: p0, the centres of the path's nodes, pf
-__device__ inline double reference_vertex(const Lattice& lt, const CorridorGrid& g, const int32_t* path, int m,
-                                          const double* p0, const double* pf, int t, int d) {
-#pragma clang fp contract(off)
-  if (t == 0) return p0[d];
-  if (t == m + 1) return pf[d];
-  const int node = path[t - 1];
-  const int X = d == 0 ? node % lt.L[0] : d == 1 ? (node / lt.L[0]) % lt.L[1] : node / (lt.L[0] * lt.L[1]);
-  const double half = 0.5 * (double)lt.stride;
-  const double mid = (double)(X * lt.stride) + half;
-  const double off = g.cell * mid;
-  return g.origin[d] + off;
 }
 
 enum { CTL_STATUS = 0, CTL_START, CTL_GOAL, CTL_NODES, CTL_CHANGED /* 3 words */, CTL_REACHED = CTL_CHANGED + 3 /* 3 words */,
@@ -262,22 +243,6 @@ __global__ __launch_bounds__(1024) void reference_paths_kernel(int K, Lattice lt
       }
     }
   }
-}
-
-// the lattice of a grid; SCP_ERR_INVALID with a message where it is not supported
-int lattice_of(scp_ctx* ctx, const char* who, int D, const CorridorGrid& g, int stride, Lattice& lt) {
-  SCP_REQUIRE(ctx, stride >= 1, "%s: stride=%d (>= 1 cells)", who, stride);
-  int64_t nodes = 1;
-  for (int d = 0; d < 3; ++d) {
-    lt.L[d] = d < D ? g.dims[d] / stride : 1;
-    SCP_REQUIRE(ctx, lt.L[d] >= 1, "%s: stride=%d exceeds grid dimension %d (%d cells)", who, stride, d, g.dims[d]);
-    nodes *= lt.L[d];
-    SCP_REQUIRE(ctx, nodes <= SCP_LATTICE_MAX_NODES, "%s: the lattice has more than %d nodes: use a larger stride", who,
-                SCP_LATTICE_MAX_NODES);
-  }
-  lt.nodes = (int)nodes;
-  lt.stride = stride;
-  return SCP_OK;
 }
 
 }  // namespace

@@ -250,6 +250,15 @@ PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that
                4: "the path has more nodes than max_path"}
 
 
+class ShortenInfo(C.Structure):
+    """struct scp_shorten_info (scp_shorten_paths; one per vehicle, a DEVICE array)"""
+    _fields_ = [("n_kept", C.c_int32), ("n_vertices", C.c_int32), ("length", C.c_double), ("length_before", C.c_double)]
+
+
+SHORTEN_INFO_DTYPE = np.dtype([("n_kept", np.int32), ("n_vertices", np.int32), ("length", np.float64),
+                               ("length_before", np.float64)])
+
+
 def lattice_shape(D, grid, stride):
     """(L_x, L_y, L_z) of the search lattice of an OccupancyGrid: dims_d div stride, L_z = 1 in 2-D"""
     return tuple(int(grid.dims[d]) // int(stride) if d < D else 1 for d in range(3))
@@ -288,7 +297,7 @@ EXPORTS = [
     "scp_assign_goals", "scp_straight_line_check", "scp_assign_goals_wide",
     "scp_occupancy_prepare", "scp_corridor_boxes", "scp_corridor_state_boxes", "scp_qp_set_position_boxes",
     "scp_solver_set_position_boxes", "scp_check_corridor",
-    "scp_lattice_edges", "scp_reference_paths",
+    "scp_lattice_edges", "scp_reference_paths", "scp_shorten_paths",
 ]
 
 
@@ -404,6 +413,7 @@ def load_library():
     lib.scp_check_corridor.argtypes = [vp, i32, i32, i32, f64, pg, vp, vp, vp, vp, f64, vp]
     lib.scp_lattice_edges.argtypes = [vp, i32, pg, vp, i32, i32, vp]
     lib.scp_reference_paths.argtypes = [vp, i32, i32, i32, pg, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.scp_shorten_paths.argtypes = [vp, i32, i32, i32, pg, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
     _LIB, _LIB_PATH = lib, path
     return lib
 
@@ -474,7 +484,8 @@ class Context:
         "stg_batch_threads" (threads per workgroup of schedule_starts_batch: 0 chosen by the call, 256 or 1024; likewise),
         "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
         never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths: 0 chosen by the call, 256,
-        512 or 1024; likewise)"""
+        512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
+        256; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
@@ -900,6 +911,20 @@ class Context:
                                                 path.data_ptr() if want_path else None, info.data_ptr(),
                                                 dist.data_ptr() if want_dist else None, n_failed.data_ptr()))
         return path, info, dist, n_failed
+
+    def shorten_paths(self, N, K, D, grid: OccupancyGrid, sat, stride, clearance, p0, pf, max_path, path, info, ref, want_kept=True):
+        """scp_shorten_paths: path (N, max_path) int32 and info as reference_paths returned them, p0 / pf (N, D) and ref
+        (N, K + 1, D) device tensors; ref is updated IN PLACE for the vehicles whose status is 0.  Returns (kept (N, max_path)
+        int32 device tensor or None, out as a uint8 device tensor of N records of SHORTEN_INFO_DTYPE).  No host read."""
+        torch = _torch()
+        kept = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_kept else None
+        out = torch.empty(max(N, 1) * SHORTEN_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_shorten_paths(self.h, N, K, D, C.byref(grid), sat.data_ptr(), int(stride), int(clearance),
+                                              p0.data_ptr(), pf.data_ptr(), int(max_path),
+                                              path.data_ptr() if path is not None else None,
+                                              info.data_ptr() if info is not None else None, ref.data_ptr(),
+                                              kept.data_ptr() if want_kept else None, out.data_ptr()))
+        return kept, out
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

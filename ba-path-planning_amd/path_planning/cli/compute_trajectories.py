@@ -100,7 +100,11 @@ def build_parser():
                    help="with --corridor-search: edge length of a lattice block in cells (default: the smallest that keeps the "
                         "lattice within 32768 nodes and a path across the map within the number of time steps)")
     p.add_argument("--corridor-clearance", type=int, default=None, metavar="CELLS",
-                   help="with --corridor-search: free cells required around every lattice block on a path (default 0)")
+                   help="with --corridor-search: free cells required around every lattice block on a path (default 0; with "
+                        "--corridor-shorten the stride)")
+    p.add_argument("--corridor-shorten", action="store_true",
+                   help="with --corridor-search: every path is cut down to the lattice nodes it cannot skip and its reference "
+                        "points are spaced evenly by length (one GPU wave per vehicle)")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -108,9 +112,10 @@ def build_parser():
 
 def obstacle_discs(parser, args):
     """the discs of --obstacle-discs as tuples of floats; the corridor flags are errors without it, --corridor-stride and
-    --corridor-clearance without --corridor-search"""
+    --corridor-clearance and --corridor-shorten without --corridor-search"""
     if not args.corridor_search:
-        for flag, value in (("--corridor-stride", args.corridor_stride), ("--corridor-clearance", args.corridor_clearance)):
+        for flag, value in (("--corridor-stride", args.corridor_stride), ("--corridor-clearance", args.corridor_clearance),
+                            ("--corridor-shorten", args.corridor_shorten or None)):
             if value is not None:
                 parser.error(f"{flag} needs --corridor-search")
     if args.obstacle_discs is None:
@@ -129,6 +134,14 @@ def obstacle_discs(parser, args):
             parser.error(f"--obstacle-discs {text}: {args.dim} centre coordinates and a radius, separated by commas")
         discs.append(disc)
     return discs
+
+
+def shortened_summary(fr):
+    """the part of the search's line that --corridor-shorten adds: kept vertices and the two lengths"""
+    found = fr["status"] == 0
+    return (f"; shortened to {int(fr['n_kept'][found].sum())} of {int(fr['n_nodes'][found].sum())} nodes, total length "
+            f"{float(fr['length'][found].sum()):.2f} m (lattice paths {float(fr['length_before'][found].sum()):.2f} m), "
+            f"{fr['shorten_ms']:.3f} ms")
 
 
 def main(argv=None):
@@ -187,11 +200,14 @@ def main(argv=None):
             solver.set_obstacles(occ, origin, cell)
             reference = None
             if args.corridor_search:
-                reference, fr = solver.find_reference(stride=args.corridor_stride, clearance=args.corridor_clearance or 0)
+                if args.corridor_shorten:
+                    reference, fr = solver.shorten_reference(stride=args.corridor_stride, clearance=args.corridor_clearance)
+                else:
+                    reference, fr = solver.find_reference(stride=args.corridor_stride, clearance=args.corridor_clearance or 0)
                 print(f"Corridor search: lattice of {' x '.join(str(n) for n in fr['lattice'])} blocks of {fr['stride']} cells "
                       f"(clearance {fr['clearance']}), {n_vehicles - fr['n_failed']} of {n_vehicles} paths found, longest "
                       f"E = {fr['max_edges']} for K = {solver.K}" + ("" if fr["guaranteed"] else " (no blocked segment is not "
-                      "guaranteed)") + f", {fr['edges_ms'] + fr['search_ms']:.3f} ms")
+                      "guaranteed)") + f", {fr['edges_ms'] + fr['search_ms']:.3f} ms" + (shortened_summary(fr) if args.corridor_shorten else ""))
             co = solver.set_corridors(reference=reference, max_grow=8 if args.corridor_grow is None else args.corridor_grow)
 
         print("Generating trajectories...")

@@ -304,14 +304,16 @@ class SCP:
         generate_trajectories / scp_iteration / repair_conflicts; validate_solution(corridor=True) checks the result.
 
         ``reference``: (N, K + 1, D), the reference point of every state j = 0 .. K; None: the straight line from start to
-        goal; "search": what find_reference() returns with its defaults (paths around the obstacles).  A segment whose reference points lie on occupied cells or outside the grid is blocked, a state whose
+        goal; "search": what find_reference() returns with its defaults (paths around the obstacles); "shortened": what
+        shorten_reference() returns with its defaults (those paths cut down to the corners they need).  A segment whose reference points lie on occupied cells or outside the grid is blocked, a state whose
         intersection is empty is open (unconstrained): both raise ValueError naming the first one unless ``allow_open``.
         Returns {"n_blocked", "n_open", "shrink", "boxes_ms", "state_boxes_ms"} (device milliseconds of the two kernels)."""
         self._one_rank("set_corridors")
         if isinstance(reference, str):
-            if reference != "search":
-                raise ValueError(f"reference={reference!r}: an array (N, K + 1, D), None (straight lines) or \"search\"")
-            reference, _ = self.find_reference()
+            if reference not in ("search", "shortened"):
+                raise ValueError(f"reference={reference!r}: an array (N, K + 1, D), None (straight lines), \"search\" or "
+                                 "\"shortened\"")
+            reference, _ = self.find_reference() if reference == "search" else self.shorten_reference()
         if self._obstacles is None:
             raise ValueError("set_corridors needs set_obstacles first")
         if self.initial_positions is None or self.final_positions is None:
@@ -364,16 +366,29 @@ class SCP:
         ``guaranteed`` (every found path has E <= K or 2 clearance >= stride ceil(E / K): set_corridors then reports no blocked
         segment for those vehicles), ``edges_ms`` / ``search_ms`` (device milliseconds; edges_ms 0 when the masks were
         cached).  A vehicle without a path keeps the straight line; unless ``allow_unreachable`` that raises ValueError."""
-        self._one_rank("find_reference")
+        if clearance is None:
+            raise ValueError("clearance=None: a whole number of cells >= 0")
+        found = self._search_reference("find_reference", stride, clearance, max_path, want_path=False)
+        info = found["info"]
+        self.last_info["reference"] = info
+        self._require_paths(info, allow_unreachable)
+        return found["ref"].cpu().numpy(), info
+
+    def _search_reference(self, who, stride, clearance, max_path, want_path):
+        """the checks and the two calls of find_reference -> {"ref", "path", "rec" (device tensors), "p0", "pf", "max_path",
+        "info": what find_reference reports}"""
+        self._one_rank(who)
         if self._obstacles is None:
-            raise ValueError("find_reference needs set_obstacles first")
+            raise ValueError(f"{who} needs set_obstacles first")
         if self.initial_positions is None or self.final_positions is None:
-            raise ValueError("find_reference needs both set_initial_states and set_final_states first")
+            raise ValueError(f"{who} needs both set_initial_states and set_final_states first")
         N, K, D, c = self.N, self.K, self.D, self._ctx
         grid = self._obstacles["grid"]
         dims = [int(grid.dims[d]) for d in range(D)]
         if stride is None:
             stride = default_search_stride(dims, K, D)
+        if clearance is None:  # (shorten_reference: the stride)
+            clearance = stride
         for name, value, least in (("stride", stride, 1), ("clearance", clearance, 0)):
             if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
                 raise ValueError(f"{name}={value!r}: a whole number of cells >= {least}")
@@ -394,10 +409,11 @@ class SCP:
             edges_ms = c.last_pair_ms()
         p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
         ref = c.tensor(straight_reference(p0, pf, K))
-        _, rec, _, n_failed = c.reference_paths(N, K, D, grid, stride, cache[stride, clearance], c.tensor(p0), c.tensor(pf),
-                                                int(max_path), ref, want_path=False)
+        d_p0, d_pf = c.tensor(p0), c.tensor(pf)
+        path, dev_rec, _, n_failed = c.reference_paths(N, K, D, grid, stride, cache[stride, clearance], d_p0, d_pf,
+                                                       int(max_path), ref, want_path=want_path)
         search_ms = c.last_pair_ms()
-        rec = rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
+        rec = dev_rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
         found = rec["status"] == 0
         E = rec["n_nodes"].astype(np.int64) + 1
         info = {"status": rec["status"].copy(), "n_nodes": rec["n_nodes"].copy(), "n_failed": int(n_failed.item()),
@@ -405,13 +421,43 @@ class SCP:
                 "max_edges": int(E[found].max()) if found.any() else 0,
                 "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
                 "edges_ms": edges_ms, "search_ms": search_ms}
-        self.last_info["reference"] = info
+        return {"ref": ref, "path": path, "rec": dev_rec, "p0": d_p0, "pf": d_pf, "max_path": int(max_path), "info": info}
+
+    @staticmethod
+    def _require_paths(info, allow_unreachable):
         if info["n_failed"] and not allow_unreachable:
-            i = int(np.nonzero(~found)[0][0])
-            raise ValueError(f"reference path: vehicle {i} has none: {_hip.PATH_STATUS[int(rec['status'][i])]} (status "
-                             f"{int(rec['status'][i])}; stride {stride}, clearance {clearance}, lattice {lattice[:D]}); "
-                             f"{info['n_failed']} vehicles without a path in all")
-        return ref.cpu().numpy(), info
+            i = int(np.nonzero(info["status"] != 0)[0][0])
+            raise ValueError(f"reference path: vehicle {i} has none: {_hip.PATH_STATUS[int(info['status'][i])]} (status "
+                             f"{int(info['status'][i])}; stride {info['stride']}, clearance {info['clearance']}, lattice "
+                             f"{info['lattice']}); {info['n_failed']} vehicles without a path in all")
+
+    def shorten_reference(self, stride=None, clearance=None, max_path=None, allow_unreachable=False):
+        """find_reference's paths, shortened: of every lattice path only the nodes that cannot be skipped are kept -- a node
+        sees another if every lattice step of the straight run between them, grown by ``clearance`` cells, is free -- and
+        the states j = 0 .. K are placed evenly by chord length along start, kept block centres, goal (scp_shorten_paths: one
+        wave per vehicle).  ``clearance`` None: ``stride``, with which every path shorter than K block edges is guaranteed;
+        the other parameters are find_reference's.
+
+        Returns (reference (N, K + 1, D) ndarray, info) and stores info as ``last_info["reference"]``: what find_reference
+        reports (its ``guaranteed`` replaced), and per vehicle ``n_kept`` (0 without a path), ``length`` / ``length_before``
+        (metres, after / before) and ``delta`` = floor(length / (K cell)) + 1, the most cells two consecutive reference points
+        lie apart per coordinate; ``guaranteed``: every found vehicle has clearance >= delta (set_corridors then reports no
+        blocked segment for those vehicles); ``shorten_ms`` (device milliseconds)."""
+        found = self._search_reference("shorten_reference", stride, clearance, max_path, want_path=True)
+        info = found["info"]
+        N, K, D, c = self.N, self.K, self.D, self._ctx
+        grid = self._obstacles["grid"]
+        _, out = c.shorten_paths(N, K, D, grid, self._obstacles["sat"], info["stride"], info["clearance"], found["p0"],
+                                 found["pf"], found["max_path"], found["path"], found["rec"], found["ref"], want_kept=False)
+        info["shorten_ms"] = c.last_pair_ms()
+        out = out.cpu().numpy().view(_hip.SHORTEN_INFO_DTYPE)[:N]
+        ok = info["status"] == 0
+        info["n_kept"], info["length"], info["length_before"] = out["n_kept"].copy(), out["length"].copy(), out["length_before"].copy()
+        info["delta"] = np.floor(out["length"] / (float(K) * float(grid.cell))).astype(np.int64) + 1
+        info["guaranteed"] = bool((info["clearance"] >= info["delta"])[ok].all())
+        self.last_info["reference"] = info
+        self._require_paths(info, allow_unreachable)
+        return found["ref"].cpu().numpy(), info
 
     def set_position_boxes(self, lo, hi):
         """Per-(vehicle, state) position boxes, the general form of set_corridors (waypoints, keep-in regions): ``lo`` / ``hi``

@@ -163,7 +163,9 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     first writes a transposed copy of the masks (N^2 words in the context's workspace) and reads the masks' columns from
  *     its rows; a developer switch.
  *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths; a
- *     developer switch. */
+ *     developer switch.
+ *   "shorten_threads" (default 0: chosen by the call; or 64, 128 or 256): threads per workgroup of scp_shorten_paths (one
+ *     wave per vehicle, so 1, 2 or 4 vehicles per workgroup); a developer switch. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -946,6 +948,65 @@ int scp_reference_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_g
                         int32_t* path /* DEVICE [N][max_path] or NULL; entries beyond n_nodes are -1 */,
                         scp_path_info* info /* DEVICE [N] */, uint16_t* dist_out /* DEVICE [N][nodes] or NULL */,
                         uint64_t* n_failed /* DEVICE */);
+
+/* ---- static obstacles: shortened reference paths ------------------------------------------------------------------------------
+ * A further additive part of ABI version 7: one struct and one function; nothing above changes.  The path of
+ * scp_reference_paths is a lattice path: it minimises the number of moves, takes straight moves before diagonal ones, and
+ * passes through the centres of the start and the goal block.  scp_shorten_paths keeps only the nodes that cannot be skipped
+ * and places the K + 1 reference points evenly by chord length.  Grid, cell lookup, the summed-table range count, lattice,
+ * node ids, blocks and block centres are those of scp_lattice_edges / scp_reference_paths.  Integers everywhere except
+ * "lengths" and "reference points", which are doubles with every operation rounded on its own (no contraction).
+ * tests/shorten_ref.py restates every rule in numpy / plain Python.
+ *
+ * Visibility clear(A, B) of two lattice nodes, with stride s and clearance c.  X^A, X^B the node coordinates, d = X^B - X^A,
+ *   n = max over the coordinates q < D of |d_q|.  n = 0 is clear.  For each step k = 0 .. n-1 and coordinate q < D:
+ *     u0 = X^A_q n + d_q k,  u1 = u0 + d_q  (both >= 0),  lo_q = min(u0, u1) div n,  hi_q = (max(u0, u1) + n - 1) div n;
+ *   the step's cell range is [lo_q s - c, hi_q s + s - 1 + c], clipped to the grid (z: [0, 0] in 2-D).  clear holds iff no
+ *   step's range holds an occupied cell: one summed-table query per step.  Evaluation may stop at the first occupied step.
+ *   A node id outside the lattice is clear of nothing.  Consequences: clear is symmetric (step k of (B, A) has the range of
+ *   step n-1-k of (A, B)); for lattice neighbours it equals the edge bit of scp_lattice_edges made with the same (s, c);
+ *   every point of the segment between the two block centres lies in the un-grown range of some step (at parameter
+ *   (k + x) / n, 0 <= x <= 1, coordinate q of the centre line is (u0 + x d_q) / n + 1/2 blocks, inside [lo_q, hi_q + 1]), so
+ *   every cell within c cells of the segment is free; and the same holds with one or both centres replaced by any point of
+ *   that end's block, which moves every point of the segment by at most s / 2 cells per coordinate while the un-grown step
+ *   ranges extend s / 2 beyond the centre line.
+ * Kept nodes, for a vehicle with status 0 and path node_0 .. node_{m-1}: t_0 = 0; while t_i < m - 1, t_{i+1} is the LARGEST t
+ *   in (t_i, m-1] with clear(node_{t_i}, node_t).  It exists where the path was made with the same (s, c): t_i + 1 is a
+ *   neighbour over a set edge (where no t is clear -- a path of other parameters -- t_i + 1 is taken).  The kept list t_0 <
+ *   .. < t_{n-1} = m - 1 has n = n_kept >= 1 entries (m = 1: n = 1) and does not depend on how the candidates are scheduled.
+ * Vertices.  nv = max(n, 2); W_0 = p0, W_{nv-1} = pf, and for 0 < i < n-1 W_i = the centre of node_{t_i} (the block-centre
+ *   formula of scp_reference_paths).  The centres of the start block and of the goal block are NOT vertices.
+ * Lengths.  len_i = sqrt(sum over d < D, in order, of (W_{i+1,d} - W_{i,d})^2), the sum starting from 0.0; S_0 = 0, S_{i+1} =
+ *   S_i + len_i; length = S_{nv-1}.  length_before is the same sum over V_0 .. V_{m+1} of scp_reference_paths.
+ * Reference points by chord length.  State 0 is W_0, state K is W_{nv-1}.  For 0 < j < K: target = ((double)j / (double)K) *
+ *   length; i = the smallest index with S_{i+1} >= target; if len_i == 0 the point is W_i, otherwise w = min((target - S_i) /
+ *   len_i, 1.0) and the point is W_i + w * (W_{i+1} - W_i).  Only coordinates d < D are written.
+ * A vehicle whose status is not 0 keeps its rows of `ref`; its kept row is all -1 and its record all zeros.  kept[i][e] = t_e
+ * for e < n_kept (an index into the vehicle's path row), -1 beyond.
+ * Why it serves as a corridor reference: consecutive reference points are at most length / K apart along the polyline,
+ * hence in every coordinate, so their cells differ by at most delta = floor(length / (K cell)) + 1 per coordinate.  Both
+ * points lie on one edge of the polyline or on two adjacent ones; if c >= delta, their seed range of scp_corridor_boxes lies
+ * inside a step range grown by c, which was found free: no segment of that vehicle is blocked.  With c = s that holds for
+ * every path shorter than K block edges.
+ *
+ * ONE wave per vehicle: the lanes test 64 candidates t at a time from the goal's end, the first block of 64 in which a lane
+ * sees the anchor ends the anchor's search (the largest t by ballot); the lanes then sum the lengths and write the points side
+ * by side.  No LDS, no barrier, no workgroup waits for another; every loop is bounded: anchors <= m, blocks <= ceil(m / 64)
+ * per anchor, steps <= max L_d per candidate.  The outputs do not depend on the launch geometry.  kept = NULL: the list lives in
+ * the context's workspace.  Supported: N, K >= 1, 1 <= max_path <= nodes, clearance >= 0 (beyond the grid's widest dimension
+ * it is that dimension), path / info as scp_reference_paths wrote them with the same stride and max_path.  Argument checks,
+ * enqueue on the ctx's stream, no host read, timing through scp_ctx_last_pair_ms. */
+typedef struct scp_shorten_info { /* DEVICE, one per vehicle, 24 bytes */
+  int32_t n_kept;       /* n; 0 unless the vehicle's status == 0 */
+  int32_t n_vertices;   /* nv; 0 likewise */
+  double length;        /* of the shortened polyline */
+  double length_before; /* of p0, the block centres, pf */
+} scp_shorten_info;
+int scp_shorten_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, const int32_t* sat, int stride,
+                      int clearance, const double* p0, const double* pf /* DEVICE [N][D] */, int max_path,
+                      const int32_t* path /* DEVICE [N][max_path], required */, const scp_path_info* info /* DEVICE [N] */,
+                      double* ref /* DEVICE [N][K+1][D], in/out */, int32_t* kept /* DEVICE [N][max_path] or NULL */,
+                      scp_shorten_info* out /* DEVICE [N] */);
 
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
