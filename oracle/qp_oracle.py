@@ -248,7 +248,7 @@ def working_rows(prob, rows):
 
 
 def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, st: Settings | None = None,
-                    rows0=None, trace=None, snapshots=None, snap_out=None, zero_qx=None):
+                    rows0=None, trace=None, snapshots=None, snap_out=None, zero_qx=None, pos_boxes=None):
     """Joint QP  min ||x||^2  s.t. fixed rows and ALL collision rows (eta, l_col; None -> QP#0).
 
     Exact constraint generation: ADMM runs on the fixed rows plus a working set W of collision rows;
@@ -263,11 +263,13 @@ def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, 
 
     zero_qx = (m, c): a deliberate fault for the sensitivity controls of the step-level tests -- during ADMM step m (1-based)
     the collision rows read S0 x of column c = i D + d as zero, the way a stale or skipped S0 x slab would look.
+
+    pos_boxes = (lo, hi), (N, K, D) by state: per-state position boxes over the position rows (so.fixed_bounds).
     """
     st = st or Settings()
     N, K, D, h = prob.N, prob.K, prob.D, prob.h
     ops = FixedOps(K, h)
-    b = so.fixed_bounds(prob)
+    b = so.fixed_bounds(prob) if pos_boxes is None else so.fixed_bounds(prob, pos_boxes)
     lj, uj = b["jerk"]
     la, ua = b["acc"]
     lv, uv = b["vel"]
@@ -499,17 +501,19 @@ def admm_structured(prob: so.Problem, eta=None, l_col=None, dist=None, x0=None, 
 # SCP outer loop (scp.py:131-180), oracle form
 # ---------------------------------------------------------------------------------------------
 def scp_solve(prob: so.Problem, max_iterations=15, st: Settings | None = None, force_iterations=None, log=None,
-              carry_rho=False):
+              carry_rho=False, pos_boxes=None):
     """generate_trajectories (scp.py:131-180) on top of admm_structured.
 
     carry_rho (the solver's opt-in of the same name): the joint QP of iteration n + 1 starts at the rho iteration n ended
     with instead of st.rho (the reference builds a new OSQP object per iteration, scp.py:441).
 
+    pos_boxes: per-state position boxes of every QP of the loop (admm_structured).
+
     `is_feasible` is evaluated once on QP#0's trajectory and never refreshed (scp.py:144, :152).
     force_iterations: run exactly that many loop bodies regardless of the flags (bench mode)."""
     st = st or Settings(max_iter=10000)  # scp.py:442
     st0 = dataclasses.replace(st, max_iter=min(st.max_iter, 4000))  # OSQP default for QP#0 (scp.py:360)
-    x, _, info0 = admm_structured(prob, st=st0)
+    x, _, info0 = admm_structured(prob, st=st0, pos_boxes=pos_boxes)
     if info0["status_val"] not in (1, 2):  # scp.py:363-365
         raise RuntimeError(f"OSQP failed: {info0['status']}")
     infos = [info0]
@@ -527,7 +531,7 @@ def scp_solve(prob: so.Problem, max_iterations=15, st: Settings | None = None, f
         prev_pos, _ = so.kinematics(prob, x)
         eta, l_col, dist = so.linearize_pairs(prob, prev_pos)
         st_it = dataclasses.replace(st, rho=infos[-1]["rho"]) if (carry_rho and len(infos) > 1) else st
-        x_new, _, info = admm_structured(prob, eta, l_col, dist, x0=x, st=st_it)
+        x_new, _, info = admm_structured(prob, eta, l_col, dist, x0=x, st=st_it, pos_boxes=pos_boxes)
         infos.append(info)
         rel = float(np.linalg.norm((x_new - x).ravel()) / np.linalg.norm(x.ravel()))  # scp.py:157-159
         rels.append(rel)

@@ -133,12 +133,17 @@ def fixed_matrices_explicit(prob: Problem):
     return lift(J), lift(Id), lift(V), lift(S)
 
 
-def fixed_bounds(prob: Problem):
+def fixed_bounds(prob: Problem, pos_boxes=None):
     """Bounds of the fixed rows in the reference's stacking order jerk, acc, vel, pos
     (scp.py:189-190, :194-195, :206-224, :234-257, stacked at :342-358).
 
     Returns dict of (l, u) arrays; vel/pos/acc have shape (N, K, D), jerk (N, K-1, D); flattening
-    each in C order gives the reference's row order."""
+    each in C order gives the reference's row order.
+
+    pos_boxes = (lo, hi), both (N, K, D) by state (not part of the reference: the per-state position boxes of
+    scp_qp_set_position_boxes, include/scp_hip.h): position row k = 0 .. K-2 (state k + 1) becomes
+    [max(lo, pos_min) - off, min(hi, pos_max) - off], each side selected first and the offset subtracted after; state 0
+    and the final-position row are untouched.  None: every array is what it was without the argument."""
     N, K, D, h = prob.N, prob.K, prob.D, prob.h
     l_jerk = np.full((N, K - 1, D), float(prob.jerk_min))
     u_jerk = np.full((N, K - 1, D), float(prob.jerk_max))
@@ -159,6 +164,12 @@ def fixed_bounds(prob: Problem):
     off = prob.p0[:, None, :] + (h * kp1)[None, :, None] * prob.v0[:, None, :]
     l_pos[:, : K - 1, :] = prob.pos_min[None, None, :] - off[:, : K - 1, :]  # scp.py:251-254
     u_pos[:, : K - 1, :] = prob.pos_max[None, None, :] - off[:, : K - 1, :]
+    if pos_boxes is not None:
+        lo, hi = (np.asarray(a, dtype=float) for a in pos_boxes)
+        assert lo.shape == (N, K, D) and hi.shape == (N, K, D), (lo.shape, hi.shape)
+        bl, bu = lo[:, 1:, :], hi[:, 1:, :]
+        l_pos[:, : K - 1, :] = np.where(bl > prob.pos_min, bl, prob.pos_min) - off[:, : K - 1, :]
+        u_pos[:, : K - 1, :] = np.where(bu < prob.pos_max, bu, prob.pos_max) - off[:, : K - 1, :]
     l_pos[:, K - 1, :] = prob.pf - off[:, K - 1, :]  # scp.py:256-257
     u_pos[:, K - 1, :] = prob.pf - off[:, K - 1, :]
     return {

@@ -145,8 +145,9 @@ def _qp(ctx, prob, **kw):
     return qp
 
 
-@pytest.mark.parametrize("D", [2, 3])
-def test_bound_overwrite_bit_for_bit(ctx, D):
+def bound_overwrite_case(D):
+    """(prob, space, lo, hi): a small problem with non-zero start velocities and a random box pattern with -inf / +inf
+    entries and boxes wider than the workspace [0, 20]^D (also the oracle's pattern: tests/test_oracle_boxes_cpu.py)"""
     rng = np.random.default_rng(D)
     N, K, h = 3, 6, 0.3
     space = [0.0] * D + [20.0] * D
@@ -154,14 +155,21 @@ def test_bound_overwrite_bit_for_bit(ctx, D):
     v0 = rng.normal(0, 0.5, (N, D))
     prob = so.make_problem(N, (K + 0.5) * h, h, 0.5, space, p0, pf, v0=v0)
     assert prob.K == K
-    qp = _qp(ctx, prob)
-    base = {k: qp.peek(k).cpu().numpy().copy() for k in ("lf", "uf")}
-    C = N * D
-    assert base["lf"].size == (4 * K - 1) * C
     lo = rng.uniform(-5, 12, (N, K, D))
     hi = lo + rng.uniform(0.1, 15, (N, K, D))
     lo[rng.random((N, K, D)) < 0.2] = -np.inf
     hi[rng.random((N, K, D)) < 0.2] = np.inf
+    return prob, space, lo, hi
+
+
+@pytest.mark.parametrize("D", [2, 3])
+def test_bound_overwrite_bit_for_bit(ctx, D):
+    prob, space, lo, hi = bound_overwrite_case(D)
+    N, K, h = prob.N, prob.K, prob.h
+    qp = _qp(ctx, prob)
+    base = {k: qp.peek(k).cpu().numpy().copy() for k in ("lf", "uf")}
+    C = N * D
+    assert base["lf"].size == (4 * K - 1) * C
     qp.set_position_boxes(ctx.tensor(lo), ctx.tensor(hi))
     got = {k: qp.peek(k).cpu().numpy().reshape(4 * K - 1, C) for k in ("lf", "uf")}
     wl, wu = cr.position_rows(K, h, space, prob.p0, prob.v0, lo, hi)
