@@ -641,6 +641,13 @@ extern "C" int scp_qp_clone_state(scp_qp* dst, const scp_qp* src) {
 #define CP(field, bytes) SCP_HIP_CHECK(ctx, hipMemcpyAsync(b.field, a.field, (bytes), hipMemcpyDeviceToDevice, s))
   CP(lf, nf); CP(uf, nf); CP(zf, nf); CP(yf, nf); CP(x, nx);
   CP(states, (size_t)4 * src->C * sizeof(double));
+  // S0 x and F x as the source's last check left them travel along: formed again from x (scp_qp_exact_qx) they would differ
+  // in the last bits, and the solve in the larger workspace would no longer be the solve that did not have to grow
+  const bool qx = src->dv.qx;
+  if (qx) {
+    SCP_HIP_CHECK(ctx, hipMemcpyAsync(b.HQ + (int64_t)src->K * src->C, scp_qp_qx(src), nx, hipMemcpyDeviceToDevice, s));
+    CP(fx, nf);
+  }
   if (nw) {
     CP(w_row, nw * sizeof(int64_t)); CP(w_k, nw * sizeof(int)); CP(w_i, nw * sizeof(int)); CP(w_j, nw * sizeof(int));
     CP(w_eta, nw * src->D * sizeof(double)); CP(w_l, nw * sizeof(double)); CP(zc, nw * sizeof(double));
@@ -656,7 +663,7 @@ extern "C" int scp_qp_clone_state(scp_qp* dst, const scp_qp* src) {
   dst->st = src->st;
   dst->problem_set = true;
   dst->has_boxes = src->has_boxes;  // (lf / uf were copied)
-  qp_on_x_set(dst, false);
+  qp_on_x_set(dst, qx);
   QP_CHECK(scp_qp_build_kkt(dst));
   dst->reset_done = true;
   SCP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // src's workspace may be released by the caller right after
