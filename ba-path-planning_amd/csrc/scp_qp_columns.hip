@@ -9,6 +9,8 @@
 // matrix cores (v_mfma_f64_16x16x4_f64, operand pre-packed in lane order by scp_qp_kkt.hip).  Kernel boundaries
 // remain only where the algorithm needs the whole grid: the inner products and the row gather/scatter (scp_qp_rows.hip).
 // cg_iters > 1 and use_mfma = 0 / 2 run on the generic pipeline of scp_qp_generic.hip (one product per launch).
+// The blocks the kernels here share are in scp_qp_device.h: column_At (A^T v by reverse scans), column_forward (F p and
+// S0 p by forward scans), admm_project (projection and dual update of a row).
 #include "scp_qp_device.h"
 
 namespace {
@@ -44,11 +46,10 @@ __device__ unsigned long long scp_phase_clk[64];
 constexpr int SQ_BLOCKS = 128;
 // Column kernel of the single-step pipeline (launch 1 of 3).  With F x carried like S0 x,
 //   r = sigma x + A^T(rho z - y) - H x = -2 x + F^T W' + S0^T G,   W' = rho w (z_f - F x) - y_f,
-// (H_f = (2 + sigma) I + rho F^T w F), then p = H_f^{-1} r, S0 p, F p.  F = [J ; I ; V ; S] and S0 are the jerk
-// stencil and the first / second cumulative sums of the integrator (scp.py:10-28, :489-491), so
-//   F^T W' + S0^T G = J^T w_j + w_a + rsum(h w_v + h^2/2 (w_p - g)) + h^2/2 g + h^2 rsum_excl(rsum(w_p + g))
-//   V p = h csum(p),  S p = h^2 (csum_excl(csum p) + csum(p)/2),  S0 p = h^2 (csum_excl(csum p) - csum(p)[k-1]/2)
-// cost one wave-wide scan each instead of a dense product: the only matrix left is H_f^{-1} (the KKT solve, MFMA).
+// (H_f = (2 + sigma) I + rho F^T w F), then p = H_f^{-1} r, S0 p, F p.  F^T W' + S0^T G and S0 p, F p cost wave-wide
+// scans instead of dense products: the only matrix left is H_f^{-1} (the KKT solve, MFMA).  This kernel spells out what
+// column_At (with - 2 x folded in) and column_forward of scp_qp_device.h state, and the tile product of qp0_col_kernel:
+// called from helpers each came out slower here (profiles/column_blocks_device_code.md, section 4).
 // Streaming the dense blocks (220 KB per workgroup for 16 columns) from L2 was 7 us of this kernel's 16.
 // One wave per column for the scans (E time steps per lane), waves [0, ceil(K/16)) for the MFMA tiles.
 template <int E>
@@ -393,7 +394,6 @@ __global__ __launch_bounds__(FT) void qp0_col_kernel(int K, int Rf, int64_t C, d
   const int c = threadIdx.x & 15, kg = threadIdx.x >> 4;
   const bool cok = c0 + c < C;
   const int tK = (K + 15) >> 4, nks = (K + 3) >> 2;
-  const double hh = h * h;
   double aM[CHB];
   tile_prefetch<CHB>(pMinv, nks, wave < tK ? wave : 0, 0, nks, aM);
   double z[RU], y[RU], lo[RU], hi[RU], rw[RU];
@@ -416,30 +416,18 @@ __global__ __launch_bounds__(FT) void qp0_col_kernel(int K, int Rf, int64_t C, d
       if (r < Rf) Wt[c * RSF + r] = rw[u] * z[u] - y[u];
     }
     __syncthreads();
-    {  // right-hand side: time steps in descending order (reverse cumulative sums as ascending scans)
-      const double* Wc = Wt + wave * RSF;
-      const int KM = 64 * E - 1;
-      double wj[E], wa[E], u1[E], u2[E], xk[E];
+    {  // right-hand side sigma x + F^T(rho w z - y)
+      double xk[E], atw[E];
 #pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int k = KM - (lane * E + e);
-        const bool ok = k < K;
-        wj[e] = k < K - 1 ? Wc[k] : 0.0;
-        wa[e] = ok ? Wc[K - 1 + k] : 0.0;
-        const double wv = ok ? Wc[2 * K - 1 + k] : 0.0;
-        u2[e] = ok ? Wc[3 * K - 1 + k] : 0.0;
-        xk[e] = ok ? Xt[wave * RSK + k] : 0.0;
-        u1[e] = h * wv + 0.5 * hh * u2[e];
+      for (int e = 0; e < E; ++e) {  // read ahead of the scans: after them the LDS round trip is on the critical path
+        const int k = (64 * E - 1) - (lane * E + e);
+        xk[e] = k < K ? Xt[wave * RSK + k] : 0.0;
       }
-      double d1[E], d2[E], s1[E], s2[E], wjp[E];
-      wave_scan<E>(u1, d1, s1);
-      wave_scan<E>(u2, s1, s2);
-      wave_scan<E>(s1, s2, d2);
-      wave_next<E>(wj, wjp);
+      column_At<E, false>(K, h, Wt + wave * RSF, nullptr, atw);
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        const int k = KM - (lane * E + e);
-        if (k < K) Rt[wave * RSK + k] = (((wjp[e] - wj[e]) / h + wa[e]) + d1[e] + hh * d2[e]) + sigma * xk[e];
+        const int k = (64 * E - 1) - (lane * E + e);
+        if (k < K) Rt[wave * RSK + k] = atw[e] + sigma * xk[e];
       }
     }
     __syncthreads();
@@ -468,27 +456,18 @@ __global__ __launch_bounds__(FT) void qp0_col_kernel(int K, int Rf, int64_t C, d
       }
     }
     __syncthreads();
-    {  // z~ = F x~ (forward scans), x+ = alpha x~ + (1 - alpha) x
-      double* Wc = Wt + wave * RSF;
-      double pk[E], c1[E], c2[E], t1[E], t2[E], pn[E];
+    {  // z~ = F x~, x+ = alpha x~ + (1 - alpha) x
+      double pk[E];
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int k = lane * E + e;
         pk[e] = k < K ? Pt[wave * RSK + k] : 0.0;
       }
-      wave_scan<E>(pk, c1, t1);
-      wave_scan<E>(c1, t2, c2);
-      wave_next<E>(pk, pn);
+      column_forward<E, false>(K, h, pk, Wt + wave * RSF, nullptr);
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const int k = lane * E + e;
-        if (k < K) {
-          if (k < K - 1) Wc[k] = (pn[e] - pk[e]) / h;
-          Wc[K - 1 + k] = pk[e];
-          Wc[2 * K - 1 + k] = h * c1[e];
-          Wc[3 * K - 1 + k] = hh * (c2[e] + 0.5 * c1[e]);
-          Xt[wave * RSK + k] = alpha * pk[e] + (1.0 - alpha) * Xt[wave * RSK + k];
-        }
+        if (k < K) Xt[wave * RSK + k] = alpha * pk[e] + (1.0 - alpha) * Xt[wave * RSK + k];
       }
     }
     __syncthreads();
@@ -497,9 +476,8 @@ __global__ __launch_bounds__(FT) void qp0_col_kernel(int K, int Rf, int64_t C, d
     for (int u = 0; u < RU; ++u) {
       const int r = kg + u * (FT / CB);
       if (cok && r < Rf) {
-        const double zh = alpha * Wt[c * RSF + r] + (1.0 - alpha) * z[u];
-        const double zn = fmin(fmax(zh + y[u] / rw[u], lo[u]), hi[u]);
-        const double yn = y[u] + rw[u] * (zh - zn);
+        double zn, yn;
+        admm_project(alpha * Wt[c * RSF + r] + (1.0 - alpha) * z[u], y[u], rw[u], lo[u], hi[u], zn, yn);
         if (emit) dy_out[(int64_t)r * C + c0 + c] = yn - y[u];
         y[u] = yn;
         z[u] = zn;
@@ -629,10 +607,9 @@ __global__ __launch_bounds__(256) void cg1_update_kernel(int K, int Rf, int64_t 
       const int row = seg * (16 * UPD_RPT) + u * 16 + (threadIdx.x >> 4);
       if (row < Rf) {
         const int64_t g = (int64_t)row * C + col;
-        const double zh = alpha * fma(a, v1[u], v0[u]) + (1.0 - alpha) * v2[u];
         const double y = v3[u];
-        const double zn = fmin(fmax(zh + y / rr[u], v4[u]), v5[u]);
-        const double yn = y + rr[u] * (zh - zn);
+        double zn, yn;
+        admm_project(alpha * fma(a, v1[u], v0[u]) + (1.0 - alpha) * v2[u], y, rr[u], v4[u], v5[u], zn, yn);
         yf[g] = yn;
         zf[g] = zn;
         Fx[g] = fma(aa, v1[u], v0[u]);
@@ -670,9 +647,8 @@ __global__ __launch_bounds__(256) void cg1_update_kernel(int K, int Rf, int64_t 
     tc += e[d] * (fma(a, pi[d], qi[d]) - fma(a, pj[d], qj[d]));
     ax += e[d] * (fma(aa, pi[d], qi[d]) - fma(aa, pj[d], qj[d]));
   }
-  const double zh = alpha * tc + (1.0 - alpha) * z;
-  const double zn = fmax(zh + y / rho_c, lo);
-  const double yn = y + rho_c * (zh - zn);
+  double zn, yn;
+  admm_project(alpha * tc + (1.0 - alpha) * z, y, rho_c, lo, zn, yn);
   yc[n] = yn;
   zc[n] = zn;
   if (dyc) dyc[n] = fmin(yn - y, 0.0);  // u = +inf: projected onto the polar of the recession cone
@@ -759,34 +735,6 @@ namespace {
 // reduced on the host -- 7 same-address atomics per workgroup cost more than the rest of the kernel
 constexpr int RS_RP = 0, RS_NAX = 1, RS_NZ = 2, RS_RD = 3, RS_NPX = 4, RS_NATY = 5, RS_NDY = 6, RS_SUPP = 7, RS_NATDY = 8;
 
-// A^T v for one column (one wave), v = (v_f in Vc[0, Rf), v_c gathered in Gc[0, K)), time steps in DESCENDING order
-// (k = KM - i): reverse cumulative sums as ascending scans.  Returns the value for step k of index (lane, e).
-template <int E>
-__device__ inline void column_At(int K, double h, const double* Vc, const double* Gc, double (&out)[E]) {
-  const int lane = threadIdx.x & 63, KM = 64 * E - 1;
-  const double hh = h * h;
-  double yj[E], ya[E], u1[E], u2[E], g[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int k = KM - (lane * E + e);
-    const bool ok = k < K;
-    yj[e] = k < K - 1 ? Vc[k] : 0.0;
-    ya[e] = ok ? Vc[K - 1 + k] : 0.0;
-    const double yv = ok ? Vc[2 * K - 1 + k] : 0.0;
-    const double yp = ok ? Vc[3 * K - 1 + k] : 0.0;
-    g[e] = ok ? Gc[k] : 0.0;
-    u1[e] = h * yv + 0.5 * hh * (yp - g[e]);
-    u2[e] = yp + g[e];
-  }
-  double d1[E], d2[E], s1[E], s2[E], yjp[E];
-  wave_scan<E>(u1, d1, s1);
-  wave_scan<E>(u2, s1, s2);
-  wave_scan<E>(s1, s2, d2);
-  wave_next<E>(yj, yjp);
-#pragma unroll
-  for (int e = 0; e < E; ++e) out[e] = ((yjp[e] - yj[e]) / h + ya[e]) + (d1[e] + 0.5 * hh * g[e]) + hh * d2[e];
-}
-
 // Column part of the check, with the integrator blocks as wave scans like cg1_col_kernel (one wave per column):
 //   F x, S0 x (stored: the pipeline's carried slabs are refreshed exactly), A^T y = F^T y_f + S0^T G(yc), the maxima of
 //   the primal / dual residuals over this block's 16 columns and, with_dy (dyf / gval2 hold delta-y of the last
@@ -815,7 +763,6 @@ __global__ __launch_bounds__(FT) void cg1_resid_col_kernel(int K, int Rf, int64_
   const int c = threadIdx.x & 15, kg = threadIdx.x >> 4;
   const bool cok = c0 + c < C;
   const int col = (int)(c0 + c), agent = col / D, dd_ = col - agent * D;
-  const double hh = h * h;
   double ndy = 0.0, supp = 0.0, natdy = 0.0;
   PHASE_MARK(32);
   for (int k = kg; k < K; k += FT / CB) {
@@ -840,7 +787,7 @@ __global__ __launch_bounds__(FT) void cg1_resid_col_kernel(int K, int Rf, int64_
   double rd = 0.0, npx = 0.0, nat = 0.0;
   {
     double aty[E];
-    column_At<E>(K, h, YF + wave * RSF, Gx + wave * RSK, aty);
+    column_At<E, true>(K, h, YF + wave * RSF, Gx + wave * RSK, aty);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int k = (64 * E - 1) - (lane * E + e);
@@ -867,7 +814,7 @@ __global__ __launch_bounds__(FT) void cg1_resid_col_kernel(int K, int Rf, int64_
     }
     __syncthreads();
     double atdy[E];
-    column_At<E>(K, h, YF + wave * RSF, G2 + wave * RSK, atdy);
+    column_At<E, true>(K, h, YF + wave * RSF, G2 + wave * RSK, atdy);
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int k = (64 * E - 1) - (lane * E + e);
@@ -876,29 +823,14 @@ __global__ __launch_bounds__(FT) void cg1_resid_col_kernel(int K, int Rf, int64_
   }
   PHASE_MARK(35);
   {
-    // F x and S0 x in ascending order (every lane of this wave is done with its column of YF)
-    double* Yc = YF + wave * RSF;
-    double pk[E], c1[E], c2[E], t1[E], t2[E], c1p[E], pn[E];
+    // F x and S0 x (every lane of this wave is done with its column of YF)
+    double xk[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const int k = lane * E + e;
-      pk[e] = k < K ? Xt[wave * RSK + k] : 0.0;
+      xk[e] = k < K ? Xt[wave * RSK + k] : 0.0;
     }
-    wave_scan<E>(pk, c1, t1);
-    wave_scan<E>(c1, t2, c2);
-    wave_prev<E>(c1, c1p);
-    wave_next<E>(pk, pn);
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int k = lane * E + e;
-      if (k < K) {
-        Qt[wave * RSK + k] = hh * (c2[e] - 0.5 * c1p[e]);
-        if (k < K - 1) Yc[k] = (pn[e] - pk[e]) / h;
-        Yc[K - 1 + k] = pk[e];
-        Yc[2 * K - 1 + k] = h * c1[e];
-        Yc[3 * K - 1 + k] = hh * (c2[e] + 0.5 * c1[e]);
-      }
-    }
+    column_forward<E, true>(K, h, xk, YF + wave * RSF, Qt + wave * RSK);
   }
   __syncthreads();
   PHASE_MARK(36);

@@ -1,5 +1,6 @@
 // Device-side helpers shared by the column kernels of the joint QP (scp_qp_columns.hip, scp_qp_rows.hip, scp_qp_persist.hip): wave-wide
-// scans on data-parallel-primitive (DPP) moves, MFMA operand prefetch, LDS padding.  gfx950 only.
+// scans on data-parallel-primitive (DPP) moves, MFMA operand prefetch, LDS padding, and the blocks of a column kernel built
+// on them (column_At, column_forward, admm_project; the last also used by scp_qp_generic.hip).  gfx950 only.
 #pragma once
 #include "scp_qp_internal.h"
 #include "scp_wave_device.h"
@@ -102,5 +103,86 @@ __host__ __device__ inline int pad_col(int n) { return ((n + 29) / 32) * 32 + 2;
 // incidence-list cell of (time step k, agent): agent-major, so that the entries of a block of consecutive agents are one
 // contiguous range (the persistent kernel keeps them in LDS)
 __host__ __device__ inline int cell_of(int k, int agent, int K) { return agent * K + k; }
+
+// ---- the blocks of a column kernel (scp_qp_columns.hip): one wave per column c = (agent, axis), E time steps per lane, the
+// column's vectors in LDS.  F = [J ; I ; V ; S] and S0 are the jerk stencil and the first / second cumulative sums of the
+// integrator (scp.py:10-28, :489-491), so each block costs wave-wide scans instead of a dense product.  The order of every
+// sum below is the one oracle/qp_oracle.py:admm_structured restates; the persistent kernels hold their own lane-per-step
+// copies of the same formulas (scp_qp_persist_device.h).
+
+// A^T v = F^T v_f + S0^T G for one column, v_f in Vc[0, 4K - 1), G (the gathered collision-row values) in Gc[0, K):
+//   J^T v_j + v_a + rsum(h v_v + h^2/2 (v_p - g)) + h^2/2 g + h^2 rsum_excl(rsum(v_p + g))
+// Index i = lane E + e runs over the time steps in DESCENDING order (k = 64 E - 1 - i), so the reverse cumulative sums are
+// ascending scans over the lanes; out[e] belongs to that k.  WITH_G = false (no collision rows: Gc is not read) drops the
+// terms in g instead of adding zeros, which could flip the sign of a zero.
+template <int E, bool WITH_G>
+__device__ __forceinline__ void column_At(int K, double h, const double* Vc, const double* Gc, double (&out)[E]) {
+  const int lane = threadIdx.x & 63, KM = 64 * E - 1;
+  const double hh = h * h;
+  double vj[E], va[E], u1[E], u2[E], g[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int k = KM - (lane * E + e);
+    const bool ok = k < K;
+    vj[e] = k < K - 1 ? Vc[k] : 0.0;
+    va[e] = ok ? Vc[K - 1 + k] : 0.0;
+    const double vv = ok ? Vc[2 * K - 1 + k] : 0.0;
+    const double vp = ok ? Vc[3 * K - 1 + k] : 0.0;
+    if constexpr (WITH_G) {
+      g[e] = ok ? Gc[k] : 0.0;
+      u1[e] = h * vv + 0.5 * hh * (vp - g[e]);
+      u2[e] = vp + g[e];
+    } else {
+      u2[e] = vp;
+      u1[e] = h * vv + 0.5 * hh * u2[e];
+    }
+  }
+  double d1[E], d2[E], s1[E], s2[E], vjp[E];
+  wave_scan<E>(u1, d1, s1);   // d1 = rsum(u1)
+  wave_scan<E>(u2, s1, s2);   // s1 = rsum(u2)
+  wave_scan<E>(s1, s2, d2);   // d2 = rsum_excl(rsum(u2))
+  wave_next<E>(vj, vjp);      // v_j[k - 1]
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    if constexpr (WITH_G) out[e] = ((vjp[e] - vj[e]) / h + va[e]) + (d1[e] + 0.5 * hh * g[e]) + hh * d2[e];
+    else out[e] = ((vjp[e] - vj[e]) / h + va[e]) + d1[e] + hh * d2[e];
+  }
+}
+
+// F p -> Wc[0, 4K - 1) and, WITH_S0, S0 p -> Qc[0, K) for one column, p[e] = p at time step k = lane E + e (0 beyond K):
+//   J p = (p[k+1] - p[k]) / h,  I p,  V p = h csum(p),  S p = h^2 (csum_excl(csum p) + csum(p)/2),
+//   S0 p = h^2 (csum_excl(csum p) - csum(p)[k-1]/2)
+template <int E, bool WITH_S0>
+__device__ __forceinline__ void column_forward(int K, double h, const double (&p)[E], double* Wc, double* Qc) {
+  const int lane = threadIdx.x & 63;
+  const double hh = h * h;
+  double c1[E], c2[E], t1[E], t2[E], c1p[E], pn[E];
+  wave_scan<E>(p, c1, t1);   // c1 = csum(p)
+  wave_scan<E>(c1, t2, c2);  // c2 = csum_excl(csum(p))
+  if constexpr (WITH_S0) wave_prev<E>(c1, c1p);
+  wave_next<E>(p, pn);
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int k = lane * E + e;
+    if (k < K) {
+      if constexpr (WITH_S0) Qc[k] = hh * (c2[e] - 0.5 * c1p[e]);
+      if (k < K - 1) Wc[k] = (pn[e] - p[e]) / h;
+      Wc[K - 1 + k] = p[e];
+      Wc[2 * K - 1 + k] = h * c1[e];
+      Wc[3 * K - 1 + k] = hh * (c2[e] + 0.5 * c1[e]);
+    }
+  }
+}
+
+// Projection and dual update of one row from its relaxed value zh (OSQP steps 5-6):
+//   zn = clamp(zh + y / rho_r, lo, hi),  yn = y + rho_r (zh - zn);   without hi: a collision row (u = +inf)
+__device__ __forceinline__ void admm_project(double zh, double y, double rho_r, double lo, double hi, double& zn, double& yn) {
+  zn = fmin(fmax(zh + y / rho_r, lo), hi);
+  yn = y + rho_r * (zh - zn);
+}
+__device__ __forceinline__ void admm_project(double zh, double y, double rho_r, double lo, double& zn, double& yn) {
+  zn = fmax(zh + y / rho_r, lo);
+  yn = y + rho_r * (zh - zn);
+}
 
 }  // namespace scpdev

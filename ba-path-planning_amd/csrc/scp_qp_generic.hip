@@ -2,7 +2,7 @@
 // beyond the column kernels (choose_pipeline in scp_qp.hip), and is the plain statement of the algorithm described at the
 // top of scp_qp.hip.  This file owns its elementwise / PCG / residual kernels and what launches them: one ADMM iteration,
 // the termination check, the second half of the infeasibility certificate, and the exact S0 x / F x products.
-#include "scp_qp_internal.h"
+#include "scp_qp_device.h"
 
 #include <algorithm>
 
@@ -94,10 +94,9 @@ __global__ __launch_bounds__(256) void admm_fixed_update_kernel(int64_t nf, int6
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t < nf) {
     const double rr = rho * wrow[t / C];
-    const double zh = alpha * tf[t] + (1.0 - alpha) * zf[t];
-    const double y = yf[t];
-    const double zn = fmin(fmax(zh + y / rr, lf[t]), uf[t]);
-    yf[t] = y + rr * (zh - zn);
+    double zn, yn;
+    scpdev::admm_project(alpha * tf[t] + (1.0 - alpha) * zf[t], yf[t], rr, lf[t], uf[t], zn, yn);
+    yf[t] = yn;
     zf[t] = zn;
   }
   if (t < nx) x[t] = alpha * xt[t] + (1.0 - alpha) * x[t];
@@ -119,10 +118,9 @@ __global__ __launch_bounds__(256) void admm_row_update_kernel(int64_t nW, int64_
   double tc = 0.0;
 #pragma unroll
   for (int d = 0; d < D; ++d) tc += weta[n * D + d] * (Q[bi + d] - Q[bj + d]);
-  const double zh = alpha * tc + (1.0 - alpha) * zc[n];
-  const double y = yc[n];
-  const double zn = fmax(zh + y / rho, wl[n]);
-  yc[n] = y + rho * (zh - zn);
+  double zn, yn;
+  scpdev::admm_project(alpha * tc + (1.0 - alpha) * zc[n], yc[n], rho, wl[n], zn, yn);
+  yc[n] = yn;
   zc[n] = zn;
 }
 
