@@ -36,9 +36,13 @@ class HipError(RuntimeError):
         self.code = code
 
 
-class QpSettings(C.Structure):
-    """struct scp_qp_settings"""
+class PairStats(C.Structure):
+    """the result of a pairwise pass (DEVICE): Context.stats"""
+    _fields_ = [("min_dist", C.c_double), ("first_violation", C.c_uint64), ("n_selected", C.c_uint64),
+                ("max_violation", C.c_double)]
 
+
+class QpSettings(C.Structure):
     _fields_ = [
         ("rho", C.c_double), ("sigma", C.c_double), ("alpha", C.c_double), ("rho_eq_scale", C.c_double),
         ("eps_abs", C.c_double), ("eps_rel", C.c_double), ("max_iter", C.c_int32),
@@ -53,8 +57,6 @@ MAX_ROUNDS_RECORDED = 24
 
 
 class SolveOptions(C.Structure):
-    """struct scp_solve_options"""
-
     _fields_ = [
         ("max_iterations", C.c_int32), ("max_rounds", C.c_int32), ("max_iter0", C.c_int32), ("max_iter", C.c_int32),
         ("refresh_feasibility", C.c_int32), ("polish", C.c_int32), ("working_set_margin", C.c_double),
@@ -64,8 +66,6 @@ class SolveOptions(C.Structure):
 
 
 class QpRecord(C.Structure):
-    """struct scp_qp_record"""
-
     _fields_ = [
         ("status_val", C.c_int32), ("iter", C.c_int32), ("rho_updates", C.c_int32), ("cg_iters_total", C.c_int32),
         ("rounds", C.c_int32), ("pipeline", C.c_int32), ("working_rows", C.c_int64), ("unresolved_rows", C.c_int64),
@@ -89,10 +89,12 @@ class QpRecord(C.Structure):
         d["linearize_ms"], d["violations_ms"] = float(self.linearize_ms), float(self.violations_ms)
         return d
 
+    def iteration_dict(self):
+        """as_dict() of the record of an SCP iteration, with its relative step and wall time"""
+        return dict(self.as_dict(), rel_step=float(self.rel_step), time_sec=float(self.time_sec))
+
 
 class SolveResult(C.Structure):
-    """struct scp_solve_result"""
-
     _fields_ = [
         ("n_iterations", C.c_int32), ("converged", C.c_int32), ("initially_feasible", C.c_int32),
         ("feasible_at_exit", C.c_int32), ("polished", C.c_int32), ("qp0_status", C.c_int32), ("n_records", C.c_int32),
@@ -102,8 +104,6 @@ class SolveResult(C.Structure):
 
 
 class QpInfo(C.Structure):
-    """struct scp_qp_info"""
-
     _fields_ = [
         ("status_val", C.c_int32), ("iter", C.c_int32), ("rho_updates", C.c_int32), ("cg_iters_total", C.c_int32),
         ("working_rows", C.c_int64), ("r_prim", C.c_double), ("r_dual", C.c_double), ("rho", C.c_double),
@@ -119,8 +119,6 @@ class QpInfo(C.Structure):
 
 
 class GenParams(C.Structure):
-    """struct scp_gen_params"""
-
     _fields_ = [
         ("pitch", C.c_double), ("jitter", C.c_double), ("layer_gap", C.c_double), ("min_sep", C.c_double),
         ("block", C.c_int32), ("max_tries", C.c_int32), ("sweeps", C.c_int32), ("reserved", C.c_int32),
@@ -128,73 +126,67 @@ class GenParams(C.Structure):
 
 
 class GenStats(C.Structure):
-    """struct scp_gen_stats (one per scenario; a DEVICE array of them is what scp_generate_grid_swap writes)"""
-
+    """one per scenario; a DEVICE array of them is what scp_generate_grid_swap writes"""
     _fields_ = [
         ("sweeps", C.c_int32), ("unmet_blocks", C.c_int32), ("conflicts", C.c_int64), ("min_approach", C.c_double),
         ("ok", C.c_int32), ("reserved", C.c_int32),
     ]
 
 
-GEN_STATS_DTYPE = np.dtype([("sweeps", np.int32), ("unmet_blocks", np.int32), ("conflicts", np.int64),
-                            ("min_approach", np.float64), ("ok", np.int32), ("reserved", np.int32)])
+GEN_STATS_DTYPE = np.dtype(GenStats)
 
 
 class SeparationStats(C.Structure):
-    """struct scp_separation_stats (scp_check_separation)"""
+    """scp_check_separation"""
     _fields_ = [("min_dist", C.c_double), ("sample_min_dist", C.c_double), ("argmin_t", C.c_double),
                 ("argmin_row", C.c_uint64), ("first_violation", C.c_uint64), ("n_violating", C.c_uint64)]
 
 
 class Conflict(C.Structure):
-    """struct scp_conflict (scp_list_conflicts): one violating segment"""
+    """scp_list_conflicts: one violating segment"""
     _fields_ = [("row", C.c_uint64), ("min_dist", C.c_double), ("t_min", C.c_double), ("t_enter", C.c_double),
                 ("t_exit", C.c_double), ("pieces", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-CONFLICT_DTYPE = np.dtype([("row", np.uint64), ("min_dist", np.float64), ("t_min", np.float64), ("t_enter", np.float64),
-                           ("t_exit", np.float64), ("pieces", np.uint32), ("reserved", np.uint32)])
+CONFLICT_DTYPE = np.dtype(Conflict)
 
 
 class Hold(C.Structure):
-    """struct scp_hold (scp_update_holds / scp_apply_holds): a fixed separating half-plane in place of one collision row"""
+    """scp_update_holds / scp_apply_holds: a fixed separating half-plane in place of one collision row"""
     _fields_ = [("row", C.c_uint64), ("eta", C.c_double * 3), ("margin", C.c_double), ("reserved", C.c_uint64)]
 
 
-HOLD_DTYPE = np.dtype([("row", np.uint64), ("eta", np.float64, (3,)), ("margin", np.float64), ("reserved", np.uint64)])
+HOLD_DTYPE = np.dtype(Hold)
 HOLD_MAX_TABLE = 1 << 20  # SCP_HOLD_MAX_TABLE
 
 
 class Clearance(C.Structure):
-    """struct scp_clearance (scp_clearance_profile): the closest approach of one vehicle or of one time step"""
+    """scp_clearance_profile: the closest approach of one vehicle or of one time step"""
     _fields_ = [("min_dist", C.c_double), ("t_min", C.c_double), ("row", C.c_uint64), ("sample_min_dist", C.c_double),
                 ("n_violating", C.c_uint64), ("reserved", C.c_uint64)]
 
 
-CLEARANCE_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("row", np.uint64),
-                            ("sample_min_dist", np.float64), ("n_violating", np.uint64), ("reserved", np.uint64)])
+CLEARANCE_DTYPE = np.dtype(Clearance)
 
 
 class DelayMargin(C.Structure):
-    """struct scp_delay_margin (scp_delay_margins): the closest approach of one vehicle started s steps late"""
+    """scp_delay_margins: the closest approach of one vehicle started s steps late"""
     _fields_ = [("min_dist", C.c_double), ("t_min", C.c_double), ("partner", C.c_uint32), ("segment", C.c_uint32),
                 ("n_violating", C.c_uint64)]
 
 
-DELAY_DTYPE = np.dtype([("min_dist", np.float64), ("t_min", np.float64), ("partner", np.uint32), ("segment", np.uint32),
-                        ("n_violating", np.uint64)])
+DELAY_DTYPE = np.dtype(DelayMargin)
 
 NO_INDEX = 2**32 - 1  # UINT32_MAX: "none" in the partner / segment of a delay margin
 
 
 class StartScheduleStats(C.Structure):
-    """struct scp_start_schedule_stats (scp_schedule_starts; DEVICE)"""
+    """scp_schedule_starts; DEVICE"""
     _fields_ = [("n_delayed", C.c_int32), ("n_unplaced", C.c_int32), ("max_delay", C.c_int32), ("first_unplaced", C.c_int32),
                 ("total_delay", C.c_int64), ("reserved", C.c_int64 * 3)]
 
 
-START_SCHEDULE_STATS_DTYPE = np.dtype([("n_delayed", np.int32), ("n_unplaced", np.int32), ("max_delay", np.int32),
-                                       ("first_unplaced", np.int32), ("total_delay", np.int64), ("reserved", np.int64, (3,))])
+START_SCHEDULE_STATS_DTYPE = np.dtype(StartScheduleStats)
 
 MAX_LAG = 63          # scp_lag_conflicts / scp_schedule_starts: one bit per lag in a 64-bit word
 SCHEDULE_MAX_N = 16384  # scp_schedule_starts
@@ -203,47 +195,44 @@ SCHEDULE_OBJECTIVES = {"makespan": 0, "total": 1}  # its `objective`
 
 
 class AssignStats(C.Structure):
-    """struct scp_assign_stats (scp_assign_goals; one per scenario, a DEVICE array)"""
+    """scp_assign_goals; one per scenario, a DEVICE array"""
     _fields_ = [("cost_q", C.c_int64), ("cost_q_identity", C.c_int64), ("quantum", C.c_double), ("rounds", C.c_int64),
                 ("bids", C.c_int64), ("phases", C.c_int32), ("status", C.c_int32)]
 
 
-ASSIGN_STATS_DTYPE = np.dtype([("cost_q", np.int64), ("cost_q_identity", np.int64), ("quantum", np.float64),
-                               ("rounds", np.int64), ("bids", np.int64), ("phases", np.int32), ("status", np.int32)])
+ASSIGN_STATS_DTYPE = np.dtype(AssignStats)
 
 
 class LineStats(C.Structure):
-    """struct scp_line_stats (scp_straight_line_check; one per scenario, a DEVICE array)"""
+    """scp_straight_line_check; one per scenario, a DEVICE array"""
     _fields_ = [("min_approach", C.c_double), ("arg_i", C.c_int32), ("arg_j", C.c_int32), ("n_close", C.c_int64),
                 ("n_opposed", C.c_int64)]
 
 
-LINE_STATS_DTYPE = np.dtype([("min_approach", np.float64), ("arg_i", np.int32), ("arg_j", np.int32), ("n_close", np.int64),
-                             ("n_opposed", np.int64)])
+LINE_STATS_DTYPE = np.dtype(LineStats)
 
 class OccupancyGrid(C.Structure):
-    """struct scp_occupancy_grid (host): the geometry of an occupancy grid"""
+    """host: the geometry of an occupancy grid"""
     _fields_ = [("origin", C.c_double * 3), ("cell", C.c_double), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
 
 
 class CorridorStats(C.Structure):
-    """struct scp_corridor_stats (scp_check_corridor; one per vehicle, a DEVICE array)"""
+    """scp_check_corridor; one per vehicle, a DEVICE array"""
     _fields_ = [("max_excess", C.c_double), ("segment", C.c_uint32), ("n_blocked", C.c_uint32), ("n_outside", C.c_uint64),
                 ("reserved", C.c_uint64)]
 
 
-CORRIDOR_STATS_DTYPE = np.dtype([("max_excess", np.float64), ("segment", np.uint32), ("n_blocked", np.uint32),
-                                 ("n_outside", np.uint64), ("reserved", np.uint64)])
+CORRIDOR_STATS_DTYPE = np.dtype(CorridorStats)
 CORRIDOR_MAX_CELLS = 1 << 24  # scp_occupancy_prepare
 CORRIDOR_MAX_GROW = 1024      # scp_corridor_boxes
 
 
 class PathInfo(C.Structure):
-    """struct scp_path_info (scp_reference_paths; one per vehicle, a DEVICE array)"""
+    """scp_reference_paths; one per vehicle, a DEVICE array"""
     _fields_ = [("status", C.c_int32), ("n_nodes", C.c_int32), ("start_node", C.c_int32), ("goal_node", C.c_int32)]
 
 
-PATH_INFO_DTYPE = np.dtype([("status", np.int32), ("n_nodes", np.int32), ("start_node", np.int32), ("goal_node", np.int32)])
+PATH_INFO_DTYPE = np.dtype(PathInfo)
 LATTICE_MAX_NODES = 32768     # SCP_LATTICE_MAX_NODES: scp_lattice_edges, scp_reference_paths
 PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that is not free",
                2: "the goal lies off the lattice or on a block that is not free", 3: "the goal cannot be reached from the start",
@@ -251,12 +240,21 @@ PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that
 
 
 class ShortenInfo(C.Structure):
-    """struct scp_shorten_info (scp_shorten_paths; one per vehicle, a DEVICE array)"""
+    """scp_shorten_paths; one per vehicle, a DEVICE array"""
     _fields_ = [("n_kept", C.c_int32), ("n_vertices", C.c_int32), ("length", C.c_double), ("length_before", C.c_double)]
 
 
-SHORTEN_INFO_DTYPE = np.dtype([("n_kept", np.int32), ("n_vertices", np.int32), ("length", np.float64),
-                               ("length_before", np.float64)])
+SHORTEN_INFO_DTYPE = np.dtype(ShortenInfo)
+
+# Every struct of include/scp_hip.h -> its mirror above, the only Python statement of the layout (each *_DTYPE derives from it)
+STRUCTS = {
+    "scp_pair_stats": PairStats, "scp_qp_settings": QpSettings, "scp_solve_options": SolveOptions, "scp_qp_record": QpRecord,
+    "scp_solve_result": SolveResult, "scp_qp_info": QpInfo, "scp_gen_params": GenParams, "scp_gen_stats": GenStats,
+    "scp_separation_stats": SeparationStats, "scp_conflict": Conflict, "scp_hold": Hold, "scp_clearance": Clearance,
+    "scp_delay_margin": DelayMargin, "scp_start_schedule_stats": StartScheduleStats, "scp_assign_stats": AssignStats,
+    "scp_line_stats": LineStats, "scp_occupancy_grid": OccupancyGrid, "scp_corridor_stats": CorridorStats,
+    "scp_path_info": PathInfo, "scp_shorten_info": ShortenInfo,
+}
 
 
 def lattice_shape(D, grid, stride):
@@ -278,27 +276,91 @@ NO_ROW = 2**64 - 1  # UINT64_MAX: "no such row" in the stats of the pairwise pas
 
 ABI_VERSION = 7  # SCP_ABI_VERSION of include/scp_hip.h this binding matches (checked when the library is loaded)
 
-EXPORTS = [
-    "scp_set_host_wait", "scp_abi_version", "scp_ctx_create", "scp_ctx_destroy", "scp_last_error", "scp_ctx_synchronize",
-    "scp_ctx_last_pair_ms", "scp_ctx_set_option", "scp_ctx_set_near_pass", "scp_ctx_near_pass_counts", "scp_ctx_peek_scratch_map",
-    "scp_kinematics", "scp_fixed_bounds", "scp_linearize_pairs", "scp_select_pairs", "scp_check_avoidance", "scp_qp_add_rows_at",
-    "scp_check_separation", "scp_ctx_last_separation_solved", "scp_list_conflicts",
-    "scp_clearance_profile", "scp_ctx_last_clearance_solved",
-    "scp_delay_margins", "scp_ctx_last_delay_solved",
-    "scp_lag_conflicts", "scp_ctx_last_lag_solved", "scp_schedule_starts", "scp_schedule_starts_batch",
-    "scp_update_holds", "scp_apply_holds",
-    "scp_collision_violations", "scp_collision_violations_at", "scp_gather_rows", "scp_rel_step", "scp_qp_default_settings",
-    "scp_qp_workspace_bytes", "scp_qp_create", "scp_qp_destroy", "scp_qp_update_settings", "scp_qp_set_problem",
-    "scp_qp_reset", "scp_qp_set_rho", "scp_qp_add_rows", "scp_qp_solve", "scp_qp_clone_state", "scp_qp_get_solution",
-    "scp_qp_get_duals", "scp_gemm_f64", "scp_qp_peek", "scp_qp_debug_set",
-    "scp_solve_default_options", "scp_solver_create", "scp_solver_destroy", "scp_solver_update_settings", "scp_solver_solve",
-    "scp_solver_step", "scp_solver_shard_begin", "scp_solver_shard_rows", "scp_solver_shard_qp", "scp_solver_shard_violations",
-    "scp_solver_shard_round_done", "scp_solver_shard_end", "scp_gen_default_params", "scp_generate_grid_swap",
-    "scp_assign_goals", "scp_straight_line_check", "scp_assign_goals_wide",
-    "scp_occupancy_prepare", "scp_corridor_boxes", "scp_corridor_state_boxes", "scp_qp_set_position_boxes",
-    "scp_solver_set_position_boxes", "scp_check_corridor",
-    "scp_lattice_edges", "scp_reference_paths", "scp_shorten_paths",
-]
+P = C.POINTER
+vp, i32, i64, f64, sz, cstr = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t, C.c_char_p
+pd, pu64, pg = P(f64), P(C.c_uint64), P(OccupancyGrid)
+
+# Every function of include/scp_hip.h, in its order: name -> (restype, argtypes).  vp: an opaque handle (scp_ctx*, scp_qp*,
+# scp_solver*) or a DEVICE address; P(...): a [host] pointer the library reads or writes through.
+PROTOTYPES = {
+    "scp_abi_version": (i32, []),
+    "scp_set_host_wait": (None, [i32]),
+    "scp_ctx_create": (i32, [i32, vp, P(vp)]),
+    "scp_ctx_destroy": (None, [vp]),
+    "scp_last_error": (cstr, [vp]),
+    "scp_ctx_synchronize": (i32, [vp]),
+    "scp_ctx_last_pair_ms": (i32, [vp, P(C.c_float)]),
+    "scp_ctx_set_option": (i32, [vp, cstr, i32]),
+    "scp_ctx_set_near_pass": (i32, [vp, i32]),
+    "scp_ctx_near_pass_counts": (i32, [vp, pu64, pu64]),
+    "scp_ctx_peek_scratch_map": (i32, [vp, vp, i64]),
+    "scp_kinematics": (i32, [vp, i32, i32, i32, f64, vp, vp, vp, vp, vp]),
+    "scp_fixed_bounds": (i32, [vp, i32, i32, i32, f64, pd, pd, vp, vp, vp, vp, vp, vp]),
+    "scp_linearize_pairs": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]),
+    "scp_select_pairs": (i32, [vp, i32, i32, i32, f64, i64, i64, vp, f64, vp, i64, vp, vp]),
+    "scp_check_avoidance": (i32, [vp, i32, i32, i32, f64, i64, i64, vp, vp]),
+    "scp_check_separation": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp]),
+    "scp_ctx_last_separation_solved": (i32, [vp, pu64]),
+    "scp_list_conflicts": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, i64, vp]),
+    "scp_clearance_profile": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp]),
+    "scp_ctx_last_clearance_solved": (i32, [vp, pu64]),
+    "scp_delay_margins": (i32, [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]),
+    "scp_ctx_last_delay_solved": (i32, [vp, pu64]),
+    "scp_lag_conflicts": (i32, [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]),
+    "scp_ctx_last_lag_solved": (i32, [vp, pu64]),
+    "scp_schedule_starts": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    "scp_schedule_starts_batch": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, P(i32)]),
+    "scp_update_holds": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp]),
+    "scp_apply_holds": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "scp_collision_violations": (i32, [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]),
+    "scp_collision_violations_at": (i32, [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]),
+    "scp_gather_rows": (i32, [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]),
+    "scp_rel_step": (i32, [vp, i64, vp, vp, pd]),
+    "scp_qp_default_settings": (None, [P(QpSettings)]),
+    "scp_qp_workspace_bytes": (sz, [i32, i32, i32, i64]),
+    "scp_qp_create": (i32, [vp, i32, i32, i32, f64, P(QpSettings), vp, sz, i64, P(vp)]),
+    "scp_qp_destroy": (None, [vp]),
+    "scp_qp_update_settings": (i32, [vp, P(QpSettings)]),
+    "scp_qp_set_problem": (i32, [vp, pd, pd, vp, vp, vp, vp]),
+    "scp_qp_reset": (i32, [vp, vp]),
+    "scp_qp_set_rho": (i32, [vp, f64]),
+    "scp_qp_add_rows": (i32, [vp, i64, vp, vp, vp]),
+    "scp_qp_add_rows_at": (i32, [vp, i64, vp, vp, vp, vp, f64]),
+    "scp_qp_solve": (i32, [vp, P(QpInfo)]),
+    "scp_qp_clone_state": (i32, [vp, vp]),
+    "scp_qp_get_solution": (i32, [vp, vp]),
+    "scp_qp_get_duals": (i32, [vp, vp, vp]),
+    "scp_solve_default_options": (None, [P(SolveOptions)]),
+    "scp_solver_create": (i32, [vp, i32, i32, i32, f64, f64, P(QpSettings), i64, P(vp)]),
+    "scp_solver_destroy": (None, [vp]),
+    "scp_solver_update_settings": (i32, [vp, P(QpSettings)]),
+    "scp_solver_solve": (i32, [vp, pd, pd, vp, vp, vp, vp, P(SolveOptions), vp, vp, vp, P(SolveResult), P(QpRecord), i32]),
+    "scp_solver_step": (i32, [vp, pd, pd, vp, vp, vp, vp, P(SolveOptions), vp, vp, P(QpRecord)]),
+    "scp_solver_shard_begin": (i32, [vp, pd, pd, vp, vp, vp, vp, P(SolveOptions), vp, vp, i64, i64, P(QpRecord), vp, i64, P(i64)]),
+    "scp_solver_shard_rows": (i32, [vp, vp, i64]),
+    "scp_solver_shard_qp": (i32, [vp, vp, i64, P(QpRecord)]),
+    "scp_solver_shard_violations": (i32, [vp, vp, i64, P(i64), pd]),
+    "scp_solver_shard_round_done": (i32, [vp, i64, f64, P(QpRecord), P(i32)]),
+    "scp_solver_shard_end": (i32, [vp, vp, P(QpRecord)]),
+    "scp_gen_default_params": (None, [P(GenParams)]),
+    "scp_generate_grid_swap": (i32, [vp, i32, i32, i32, pu64, P(GenParams), vp, vp, vp, vp]),
+    "scp_assign_goals": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+    "scp_assign_goals_wide": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+    "scp_straight_line_check": (i32, [vp, i32, i32, i32, vp, vp, vp, f64, vp]),
+    "scp_occupancy_prepare": (i32, [vp, i32, pg, vp, vp]),
+    "scp_corridor_boxes": (i32, [vp, i32, i32, i32, pg, vp, vp, i32, vp, vp]),
+    "scp_corridor_state_boxes": (i32, [vp, i32, i32, i32, pg, vp, f64, vp, vp, vp]),
+    "scp_qp_set_position_boxes": (i32, [vp, vp, vp]),
+    "scp_solver_set_position_boxes": (i32, [vp, vp, vp]),
+    "scp_check_corridor": (i32, [vp, i32, i32, i32, f64, pg, vp, vp, vp, vp, f64, vp]),
+    "scp_lattice_edges": (i32, [vp, i32, pg, vp, i32, i32, vp]),
+    "scp_reference_paths": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_shorten_paths": (i32, [vp, i32, i32, i32, pg, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_gemm_f64": (i32, [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]),
+    "scp_qp_peek": (i32, [vp, cstr, vp, i64, P(i64)]),
+    "scp_qp_debug_set": (i32, [vp, cstr, i32]),
+}
+EXPORTS = list(PROTOTYPES)
 
 
 def library_path():
@@ -319,101 +381,19 @@ def load_library():
     if not os.path.exists(path):
         raise HipError(-100, f"{path} not found: build the HIP extension first (make -C ba-path-planning_amd/csrc)")
     lib = C.CDLL(path)
-    vp, i32, i64, f64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_double, C.c_size_t
-    pd = C.POINTER(C.c_double)
-    lib.scp_abi_version.restype = i32
-    if lib.scp_abi_version() != ABI_VERSION:  # a stale build: struct layouts and entry points may not match this binding
+
+    def declare(name):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = PROTOTYPES[name]
+        return fn
+
+    version = declare("scp_abi_version")()
+    if version != ABI_VERSION:  # a stale build: struct layouts and entry points may not match this binding
         raise HipError(-4,  # SCP_ERR_STATE
-                       f"{path}: ABI version {lib.scp_abi_version()}, this binding needs {ABI_VERSION} -- rebuild "
+                       f"{path}: ABI version {version}, this binding needs {ABI_VERSION} -- rebuild "
                        "(python -c 'import __graft_entry__ as g; g.build()')")
-    lib.scp_set_host_wait.argtypes = [i32]
-    lib.scp_ctx_set_option.argtypes = [vp, C.c_char_p, i32]
-    lib.scp_ctx_set_option.restype = i32
-    lib.scp_set_host_wait.restype = None
-    lib.scp_ctx_set_near_pass.argtypes = [vp, i32]
-    lib.scp_ctx_near_pass_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.scp_ctx_peek_scratch_map.argtypes = [vp, vp, i64]
-    lib.scp_ctx_create.argtypes = [i32, vp, C.POINTER(vp)]
-    lib.scp_ctx_destroy.argtypes = [vp]
-    lib.scp_ctx_destroy.restype = None
-    lib.scp_last_error.argtypes = [vp]
-    lib.scp_last_error.restype = C.c_char_p
-    lib.scp_ctx_synchronize.argtypes = [vp]
-    lib.scp_ctx_last_pair_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.scp_kinematics.argtypes = [vp, i32, i32, i32, f64, vp, vp, vp, vp, vp]
-    lib.scp_fixed_bounds.argtypes = [vp, i32, i32, i32, f64, pd, pd, vp, vp, vp, vp, vp, vp]
-    lib.scp_linearize_pairs.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
-    lib.scp_select_pairs.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, f64, vp, i64, vp, vp]
-    lib.scp_check_avoidance.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp]
-    lib.scp_check_separation.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp]
-    lib.scp_ctx_last_separation_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.scp_list_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, i64, vp]
-    lib.scp_clearance_profile.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp]
-    lib.scp_ctx_last_clearance_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.scp_delay_margins.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
-    lib.scp_ctx_last_delay_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.scp_lag_conflicts.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp]
-    lib.scp_ctx_last_lag_solved.argtypes = [vp, C.POINTER(C.c_uint64)]
-    lib.scp_schedule_starts.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    lib.scp_schedule_starts_batch.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.POINTER(C.c_int32)]
-    lib.scp_update_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp]
-    lib.scp_apply_holds.argtypes = [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    lib.scp_collision_violations.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]
-    lib.scp_collision_violations_at.argtypes = [vp, i32, i32, i32, f64, i64, i64, vp, vp, f64, vp, i64, vp, vp]
-    lib.scp_gather_rows.argtypes = [vp, i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp]
-    lib.scp_rel_step.argtypes = [vp, i64, vp, vp, pd]
-    lib.scp_qp_default_settings.argtypes = [C.POINTER(QpSettings)]
-    lib.scp_qp_default_settings.restype = None
-    lib.scp_qp_workspace_bytes.argtypes = [i32, i32, i32, i64]
-    lib.scp_qp_workspace_bytes.restype = sz
-    lib.scp_qp_create.argtypes = [vp, i32, i32, i32, f64, C.POINTER(QpSettings), vp, sz, i64, C.POINTER(vp)]
-    lib.scp_qp_destroy.argtypes = [vp]
-    lib.scp_qp_destroy.restype = None
-    lib.scp_qp_update_settings.argtypes = [vp, C.POINTER(QpSettings)]
-    lib.scp_qp_set_problem.argtypes = [vp, pd, pd, vp, vp, vp, vp]
-    lib.scp_qp_reset.argtypes = [vp, vp]
-    lib.scp_qp_set_rho.argtypes = [vp, f64]
-    lib.scp_qp_add_rows.argtypes = [vp, i64, vp, vp, vp]
-    lib.scp_qp_add_rows_at.argtypes = [vp, i64, vp, vp, vp, vp, f64]
-    lib.scp_qp_solve.argtypes = [vp, C.POINTER(QpInfo)]
-    lib.scp_qp_clone_state.argtypes = [vp, vp]
-    lib.scp_qp_get_solution.argtypes = [vp, vp]
-    lib.scp_qp_get_duals.argtypes = [vp, vp, vp]
-    lib.scp_gemm_f64.argtypes = [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]
-    lib.scp_qp_peek.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
-    lib.scp_qp_debug_set.argtypes = [vp, C.c_char_p, i32]
-    lib.scp_solve_default_options.argtypes = [C.POINTER(SolveOptions)]
-    lib.scp_solve_default_options.restype = None
-    lib.scp_solver_create.argtypes = [vp, i32, i32, i32, f64, f64, C.POINTER(QpSettings), i64, C.POINTER(vp)]
-    lib.scp_solver_destroy.argtypes = [vp]
-    lib.scp_solver_destroy.restype = None
-    lib.scp_solver_update_settings.argtypes = [vp, C.POINTER(QpSettings)]
-    lib.scp_solver_step.argtypes = [vp, pd, pd, vp, vp, vp, vp, C.POINTER(SolveOptions), vp, vp, C.POINTER(QpRecord)]
-    lib.scp_solver_solve.argtypes = [vp, pd, pd, vp, vp, vp, vp, C.POINTER(SolveOptions), vp, vp, vp, C.POINTER(SolveResult),
-                                     C.POINTER(QpRecord), i32]
-    lib.scp_solver_shard_begin.argtypes = [vp, pd, pd, vp, vp, vp, vp, C.POINTER(SolveOptions), vp, vp, i64, i64,
-                                           C.POINTER(QpRecord), vp, i64, C.POINTER(i64)]
-    lib.scp_solver_shard_rows.argtypes = [vp, vp, i64]
-    lib.scp_solver_shard_qp.argtypes = [vp, vp, i64, C.POINTER(QpRecord)]
-    lib.scp_solver_shard_violations.argtypes = [vp, vp, i64, C.POINTER(i64), C.POINTER(C.c_double)]
-    lib.scp_solver_shard_round_done.argtypes = [vp, i64, f64, C.POINTER(QpRecord), C.POINTER(i32)]
-    lib.scp_solver_shard_end.argtypes = [vp, vp, C.POINTER(QpRecord)]
-    lib.scp_gen_default_params.argtypes = [C.POINTER(GenParams)]
-    lib.scp_gen_default_params.restype = None
-    lib.scp_generate_grid_swap.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_uint64), C.POINTER(GenParams), vp, vp, vp, vp]
-    lib.scp_assign_goals.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
-    lib.scp_assign_goals_wide.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]
-    lib.scp_straight_line_check.argtypes = [vp, i32, i32, i32, vp, vp, vp, f64, vp]
-    pg = C.POINTER(OccupancyGrid)
-    lib.scp_occupancy_prepare.argtypes = [vp, i32, pg, vp, vp]
-    lib.scp_corridor_boxes.argtypes = [vp, i32, i32, i32, pg, vp, vp, i32, vp, vp]
-    lib.scp_corridor_state_boxes.argtypes = [vp, i32, i32, i32, pg, vp, f64, vp, vp, vp]
-    lib.scp_qp_set_position_boxes.argtypes = [vp, vp, vp]
-    lib.scp_solver_set_position_boxes.argtypes = [vp, vp, vp]
-    lib.scp_check_corridor.argtypes = [vp, i32, i32, i32, f64, pg, vp, vp, vp, vp, f64, vp]
-    lib.scp_lattice_edges.argtypes = [vp, i32, pg, vp, i32, i32, vp]
-    lib.scp_reference_paths.argtypes = [vp, i32, i32, i32, pg, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    lib.scp_shorten_paths.argtypes = [vp, i32, i32, i32, pg, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    for name in PROTOTYPES:
+        declare(name)
     _LIB, _LIB_PATH = lib, path
     return lib
 
@@ -450,8 +430,18 @@ def _torch():
 
 
 def _harr(values):
-    a = np.ascontiguousarray(values, dtype=np.float64)
-    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+    """[host] const double* to a float64 copy of values (the pointer keeps its array alive)"""
+    return np.ascontiguousarray(values, dtype=np.float64).ctypes.data_as(pd)
+
+
+def _ptr(t):
+    """the device address of an optional tensor (None: NULL)"""
+    return t.data_ptr() if t is not None else None
+
+
+def _decode(struct, t):
+    """the device tensor t, which holds one `struct`, as that ctypes Structure -- synchronises"""
+    return struct.from_buffer_copy(t.cpu().numpy().tobytes())
 
 
 class Context:
@@ -471,7 +461,7 @@ class Context:
         if rc != SCP_OK:
             raise HipError(rc, "scp_ctx_create failed")
         self.h = h
-        self.stats = torch.zeros(4, dtype=torch.float64, device=self.tdev)  # struct scp_pair_stats
+        self.stats = torch.zeros(C.sizeof(PairStats) // 8, dtype=torch.float64, device=self.tdev)
 
     def set_option(self, key, value):
         """scp_ctx_set_option: "kernel_timing" (HIP events around the pairwise kernels and QP solves; 0 saves ~25 queue packets
@@ -539,10 +529,14 @@ class Context:
 
     def read_stats(self):
         """(min_dist, first_violation, n_selected, max_violation) -- synchronises."""
-        torch = _torch()
-        raw = self.stats.cpu().numpy()
-        u = raw.view(np.uint64)
-        return float(raw[0]), int(u[1]), int(u[2]), float(raw[3])
+        st = _decode(PairStats, self.stats)
+        return st.min_dist, st.first_violation, st.n_selected, st.max_violation
+
+    def _solved(self, fn):
+        """one of the scp_ctx_last_*_solved counters -- synchronises"""
+        n = C.c_uint64()
+        self.check(fn(self.h, C.byref(n)))
+        return int(n.value)
 
     def last_pair_ms(self):
         ms = C.c_float()
@@ -553,17 +547,15 @@ class Context:
     def kinematics(self, N, K, D, h, acc, p0, v0, want_vel=True):
         pos = self.empty(N, K, D)
         vel = self.empty(N, K, D) if want_vel else None
-        self.check(self.lib.scp_kinematics(self.h, N, K, D, h, acc.data_ptr(), p0.data_ptr(), v0.data_ptr(),
-                                           pos.data_ptr(), vel.data_ptr() if want_vel else None))
+        self.check(self.lib.scp_kinematics(self.h, N, K, D, h, acc.data_ptr(), p0.data_ptr(), v0.data_ptr(), pos.data_ptr(),
+                                           _ptr(vel)))
         return pos, vel
 
     def fixed_bounds(self, N, K, D, h, limits, space, p0, v0, pf, vf):
         m = N * D * (4 * K - 1)
         lo, hi = self.empty(m), self.empty(m)
-        la, lp = _harr(limits)
-        sa, sp = _harr(space)
-        self.check(self.lib.scp_fixed_bounds(self.h, N, K, D, h, lp, sp, p0.data_ptr(), v0.data_ptr(), pf.data_ptr(),
-                                             vf.data_ptr(), lo.data_ptr(), hi.data_ptr()))
+        self.check(self.lib.scp_fixed_bounds(self.h, N, K, D, h, _harr(limits), _harr(space), p0.data_ptr(), v0.data_ptr(),
+                                             pf.data_ptr(), vf.data_ptr(), lo.data_ptr(), hi.data_ptr()))
         return lo, hi
 
     def check_avoidance(self, N, K, D, R, pos, q_begin=0, q_end=None):
@@ -585,7 +577,7 @@ class Context:
         if getattr(self, "sep_stats", None) is None:
             self.sep_stats = torch.zeros(C.sizeof(SeparationStats) // 8, dtype=torch.float64, device=self.tdev)
         self.check(self.lib.scp_check_separation(*args, self.sep_stats.data_ptr()))
-        st = SeparationStats.from_buffer_copy(self.sep_stats.cpu().numpy().tobytes())
+        st = _decode(SeparationStats, self.sep_stats)
         return {f: getattr(st, f) for f, _ in SeparationStats._fields_}
 
     def list_conflicts(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None, capacity=None):
@@ -608,13 +600,17 @@ class Context:
     def hold_table(self, holds=None, capacity=None):
         """A device table for update_holds / apply_holds: (uint8 tensor of `capacity` scp_hold records, int64 count tensor)
         holding the records `holds` (a HOLD_DTYPE array sorted by row; None: empty)."""
-        torch = _torch()
         holds = np.zeros(0, dtype=HOLD_DTYPE) if holds is None else np.ascontiguousarray(holds, dtype=HOLD_DTYPE)
-        cap = max(int(holds.size if capacity is None else capacity), holds.size, 1)
-        table = torch.zeros(cap * HOLD_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
-        if holds.size:
-            table[: holds.nbytes] = torch.from_numpy(holds.view(np.uint8).copy()).to(self.tdev)
-        return table, torch.full((1,), int(holds.size), dtype=torch.int64, device=self.tdev)
+        return self._upload_records(holds, max(int(holds.size if capacity is None else capacity), 1) * HOLD_DTYPE.itemsize)
+
+    def _upload_records(self, rec, nbytes=0):
+        """-> (zeroed uint8 device buffer of at least nbytes that begins with the structured array rec, int64 device tensor of
+        one word holding len(rec))"""
+        torch = _torch()
+        buf = torch.zeros(max(int(nbytes), rec.nbytes, 1), dtype=torch.uint8, device=self.tdev)
+        if rec.size:
+            buf[: rec.nbytes] = torch.from_numpy(rec.view(np.uint8).copy()).to(self.tdev)
+        return buf, torch.full((1,), int(rec.size), dtype=torch.int64, device=self.tdev)
 
     def read_holds(self, table, n):
         """the first n records of a device table as a numpy structured array (HOLD_DTYPE) -- synchronises"""
@@ -629,11 +625,7 @@ class Context:
         table with n_holds restored -- synchronises."""
         torch = _torch()
         args = self._trajectory_args(N, K, D, h, R, pos, vel, acc, q_begin, q_end)
-        rec = np.ascontiguousarray(conflicts, dtype=CONFLICT_DTYPE)
-        c_dev = torch.zeros(max(rec.nbytes, 1), dtype=torch.uint8, device=self.tdev)
-        if rec.size:
-            c_dev[: rec.nbytes] = torch.from_numpy(rec.view(np.uint8).copy()).to(self.tdev)
-        c_n = torch.full((1,), int(rec.size), dtype=torch.int64, device=self.tdev)
+        c_dev, c_n = self._upload_records(np.ascontiguousarray(conflicts, dtype=CONFLICT_DTYPE))
         size = HOLD_DTYPE.itemsize
         before = int(n_holds.item())
         for _ in range(2):
@@ -664,9 +656,7 @@ class Context:
 
     def last_clearance_solved(self):
         """segments of the latest clearance_profile that needed the quartic's minimum"""
-        n = C.c_uint64()
-        self.check(self.lib.scp_ctx_last_clearance_solved(self.h, C.byref(n)))
-        return int(n.value)
+        return self._solved(self.lib.scp_ctx_last_clearance_solved)
 
     def delay_margins(self, N, K, D, h, R, pos, vel, acc, max_lag, a_begin=0, a_end=None):
         """scp_delay_margins for the vehicles [a_begin, a_end) and the lags 0 .. max_lag: the clearance of every vehicle
@@ -683,9 +673,7 @@ class Context:
 
     def last_delay_solved(self):
         """segments of the latest delay_margins that needed the quartic's minimum"""
-        n = C.c_uint64()
-        self.check(self.lib.scp_ctx_last_delay_solved(self.h, C.byref(n)))
-        return int(n.value)
+        return self._solved(self.lib.scp_ctx_last_delay_solved)
 
     def lag_conflicts(self, N, K, D, h, R, pos, vel, acc, max_lag, a_begin=0, a_end=None, device=False):
         """scp_lag_conflicts for the vehicles [a_begin, a_end) and the lags 0 .. max_lag: bit s of mask[a - a_begin][b] says
@@ -703,32 +691,38 @@ class Context:
 
     def last_lag_solved(self):
         """segments of the latest lag_conflicts that needed the quartic's minimum"""
-        n = C.c_uint64()
-        self.check(self.lib.scp_ctx_last_lag_solved(self.h, C.byref(n)))
-        return int(n.value)
+        return self._solved(self.lib.scp_ctx_last_lag_solved)
+
+    def _schedule_masks(self, mask, who):
+        """the (N, N) pair-lag masks of schedule_starts* (numpy uint64 array or int64 tensor) as an int64 device tensor, and N"""
+        torch = _torch()
+        if not torch.is_tensor(mask):
+            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint64).view(np.int64))
+        mask = mask.to(device=self.tdev, dtype=torch.int64).contiguous()
+        if mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
+            raise ValueError(f"{who}: the masks must be (N, N), not {tuple(mask.shape)}")
+        return mask, int(mask.shape[0])
+
+    def _int32_tensor(self, a):
+        """an array or tensor of indices as a contiguous int32 device tensor of the same shape"""
+        torch = _torch()
+        t = a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32))
+        return t.to(device=self.tdev, dtype=torch.int32).contiguous()
 
     def schedule_starts(self, mask, max_lag, order=None):
         """scp_schedule_starts: the greedy launch schedule of the (N, N) pair-lag masks (a numpy uint64 array or the int64
         device tensor of lag_conflicts(device=True)), the vehicles taken in `order` (a permutation; None: 0 .. N-1).  Returns
         the delays (numpy int32, -1: unplaced) and the stats as a dictionary -- synchronises."""
         torch = _torch()
-        if not torch.is_tensor(mask):
-            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint64).view(np.int64))
-        mask = mask.to(device=self.tdev, dtype=torch.int64).contiguous()
-        if mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
-            raise ValueError(f"schedule_starts: the masks must be (N, N), not {tuple(mask.shape)}")
-        N = int(mask.shape[0])
-        od = None
-        if order is not None:
-            od = order if torch.is_tensor(order) else torch.as_tensor(np.ascontiguousarray(order, dtype=np.int32))
-            od = od.to(device=self.tdev, dtype=torch.int32).reshape(-1).contiguous()
-            if od.numel() != N:
-                raise ValueError(f"schedule_starts: order has {od.numel()} entries for {N} vehicles")
+        mask, N = self._schedule_masks(mask, "schedule_starts")
+        od = None if order is None else self._int32_tensor(order).reshape(-1)
+        if od is not None and od.numel() != N:
+            raise ValueError(f"schedule_starts: order has {od.numel()} entries for {N} vehicles")
         delay = torch.empty(max(N, 1), dtype=torch.int32, device=self.tdev)
         stats = torch.zeros(C.sizeof(StartScheduleStats), dtype=torch.uint8, device=self.tdev)
-        self.check(self.lib.scp_schedule_starts(self.h, N, int(max_lag), mask.data_ptr(), od.data_ptr() if od is not None else None,
-                                                delay.data_ptr(), stats.data_ptr()))
-        st = StartScheduleStats.from_buffer_copy(stats.cpu().numpy().tobytes())
+        self.check(self.lib.scp_schedule_starts(self.h, N, int(max_lag), mask.data_ptr(), _ptr(od), delay.data_ptr(),
+                                                stats.data_ptr()))
+        st = _decode(StartScheduleStats, stats)
         return delay[:N].cpu().numpy(), {f: int(getattr(st, f)) for f, _ in StartScheduleStats._fields_ if f != "reserved"}
 
     def schedule_starts_batch(self, mask, max_lag, orders, objective="makespan"):
@@ -740,16 +734,10 @@ class Context:
         torch = _torch()
         if objective not in SCHEDULE_OBJECTIVES:
             raise ValueError(f"schedule_starts_batch: objective={objective!r} (need one of {sorted(SCHEDULE_OBJECTIVES)})")
-        if not torch.is_tensor(mask):
-            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint64).view(np.int64))
-        mask = mask.to(device=self.tdev, dtype=torch.int64).contiguous()
-        if mask.dim() != 2 or mask.shape[0] != mask.shape[1]:
-            raise ValueError(f"schedule_starts_batch: the masks must be (N, N), not {tuple(mask.shape)}")
-        N = int(mask.shape[0])
-        od = orders if torch.is_tensor(orders) else torch.as_tensor(np.ascontiguousarray(orders, dtype=np.int32))
+        mask, N = self._schedule_masks(mask, "schedule_starts_batch")
+        od = self._int32_tensor(orders)
         if od.dim() != 2 or od.shape[1] != N or od.shape[0] < 1:
             raise ValueError(f"schedule_starts_batch: orders must be (B, {N}) with B >= 1, not {tuple(od.shape)}")
-        od = od.to(device=self.tdev, dtype=torch.int32).contiguous()
         B = int(od.shape[0])
         delay = torch.empty((B, max(N, 1)), dtype=torch.int32, device=self.tdev)
         stats = torch.zeros(B * START_SCHEDULE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
@@ -762,9 +750,7 @@ class Context:
 
     def last_separation_solved(self):
         """segments of the latest check_separation that needed the quartic's minimum (the rest: one comparison)"""
-        n = C.c_uint64()
-        self.check(self.lib.scp_ctx_last_separation_solved(self.h, C.byref(n)))
-        return int(n.value)
+        return self._solved(self.lib.scp_ctx_last_separation_solved)
 
     def rel_step(self, a_new, a_prev):
         out = (C.c_double * 3)()
@@ -820,8 +806,8 @@ class Context:
         goal_of = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int32, device=self.tdev)
         prices = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int64, device=self.tdev) if want_prices else None
         stats = torch.empty(max(B, 1) * ASSIGN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
-        self.check(fn(self.h, B, N, D, s.data_ptr(), g.data_ptr(), goal_of.data_ptr(),
-                      prices.data_ptr() if want_prices else None, int(max_rounds_per_phase), stats.data_ptr()))
+        self.check(fn(self.h, B, N, D, s.data_ptr(), g.data_ptr(), goal_of.data_ptr(), _ptr(prices), int(max_rounds_per_phase),
+                      stats.data_ptr()))
         return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
 
     def straight_line_check(self, start, goal, goal_of=None, min_sep=0.0):
@@ -831,13 +817,9 @@ class Context:
         torch = _torch()
         s, g = self._scenario_points(start, goal)
         B, N, D = (int(v) for v in s.shape)
-        gof = None
-        if goal_of is not None:
-            gof = goal_of if torch.is_tensor(goal_of) else torch.as_tensor(np.ascontiguousarray(goal_of, dtype=np.int32))
-            gof = gof.to(device=self.tdev, dtype=torch.int32).reshape(B, N).contiguous()
+        gof = None if goal_of is None else self._int32_tensor(goal_of).reshape(B, N)
         stats = torch.empty(max(B, 1) * LINE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
-        self.check(self.lib.scp_straight_line_check(self.h, B, N, D, s.data_ptr(), g.data_ptr(),
-                                                    gof.data_ptr() if gof is not None else None, float(min_sep),
+        self.check(self.lib.scp_straight_line_check(self.h, B, N, D, s.data_ptr(), g.data_ptr(), _ptr(gof), float(min_sep),
                                                     stats.data_ptr()))
         return stats.cpu().numpy().view(LINE_STATS_DTYPE)
 
@@ -907,9 +889,8 @@ class Context:
         info = torch.empty(max(N, 1) * PATH_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
         n_failed = torch.zeros(1, dtype=torch.int64, device=self.tdev)
         self.check(self.lib.scp_reference_paths(self.h, N, K, D, C.byref(grid), int(stride), edges.data_ptr(), p0.data_ptr(),
-                                                pf.data_ptr(), int(max_path), ref.data_ptr(),
-                                                path.data_ptr() if want_path else None, info.data_ptr(),
-                                                dist.data_ptr() if want_dist else None, n_failed.data_ptr()))
+                                                pf.data_ptr(), int(max_path), ref.data_ptr(), _ptr(path), info.data_ptr(),
+                                                _ptr(dist), n_failed.data_ptr()))
         return path, info, dist, n_failed
 
     def shorten_paths(self, N, K, D, grid: OccupancyGrid, sat, stride, clearance, p0, pf, max_path, path, info, ref, want_kept=True):
@@ -920,10 +901,8 @@ class Context:
         kept = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_kept else None
         out = torch.empty(max(N, 1) * SHORTEN_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
         self.check(self.lib.scp_shorten_paths(self.h, N, K, D, C.byref(grid), sat.data_ptr(), int(stride), int(clearance),
-                                              p0.data_ptr(), pf.data_ptr(), int(max_path),
-                                              path.data_ptr() if path is not None else None,
-                                              info.data_ptr() if info is not None else None, ref.data_ptr(),
-                                              kept.data_ptr() if want_kept else None, out.data_ptr()))
+                                              p0.data_ptr(), pf.data_ptr(), int(max_path), _ptr(path), _ptr(info),
+                                              ref.data_ptr(), _ptr(kept), out.data_ptr()))
         return kept, out
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
@@ -982,35 +961,38 @@ class PairPass:
         self.sel_cap = int(min(max(self.rows, 1), max(need, 2 * self.sel_cap)))
         self.sel = torch.empty(self.sel_cap, dtype=torch.int64, device=self.ctx.tdev)
 
+    def _pass(self, call, timer):
+        """Runs a pass that fills self.sel: call() makes the library call.  It is repeated with a longer list while the list was
+        too short (the library then merged nothing into the working-set bitmap).  Returns (the rows as a tensor of their own,
+        min_dist, first_violation, max_violation); the device time of the pass goes to self.<timer>."""
+        c = self.ctx
+        while True:
+            c.check(call())
+            min_dist, first, n_sel, max_v = c.read_stats()
+            setattr(self, timer, c.last_pair_ms() if self.nq > 0 else 0.0)
+            if n_sel <= self.sel_cap:
+                return self.sel[:n_sel].clone(), min_dist, first, max_v
+            self._grow(n_sel)
+
     def linearize(self, pos_prev, p0, v0, margin):
         """a5: fills eta/l, returns (rows tensor (n,), min_dist, first_violation)."""
         c = self.ctx
-        while True:
-            c.check(c.lib.scp_linearize_pairs(c.h, self.N, self.K, self.D, self.R, self.h, self.q_begin, self.q_end,
-                                              pos_prev.data_ptr(), p0.data_ptr(), v0.data_ptr(), self.eta.data_ptr(),
-                                              self.l.data_ptr(), margin, self.sel.data_ptr(), self.sel_cap,
-                                              self.bitmap.data_ptr(), c.stats.data_ptr()))
-            min_dist, first, n_sel, _ = c.read_stats()
-            self.last_linearize_ms = c.last_pair_ms() if self.nq > 0 else 0.0
-            if n_sel <= self.sel_cap:
-                self.pos_prev = pos_prev
-                return self.sel[:n_sel].clone(), min_dist, first
-            self._grow(n_sel)
+        rows, min_dist, first, _ = self._pass(lambda: c.lib.scp_linearize_pairs(
+            c.h, self.N, self.K, self.D, self.R, self.h, self.q_begin, self.q_end, pos_prev.data_ptr(), p0.data_ptr(),
+            v0.data_ptr(), self.eta.data_ptr(), self.l.data_ptr(), margin, self.sel.data_ptr(), self.sel_cap,
+            self.bitmap.data_ptr(), c.stats.data_ptr()), "last_linearize_ms")
+        self.pos_prev = pos_prev
+        return rows, min_dist, first
 
     def select(self, pos_prev, margin):
         """a5 without the row stream (scp_select_pairs): the same selection, bitmap and a8 statistics as linearize(), eta / l
         are not written; returns (rows tensor (n,), min_dist, first_violation)."""
         c = self.ctx
-        while True:
-            c.check(c.lib.scp_select_pairs(c.h, self.N, self.K, self.D, self.R, self.q_begin, self.q_end,
-                                           pos_prev.data_ptr(), margin, self.sel.data_ptr(), self.sel_cap,
-                                           self.bitmap.data_ptr(), c.stats.data_ptr()))
-            min_dist, first, n_sel, _ = c.read_stats()
-            self.last_linearize_ms = c.last_pair_ms() if self.nq > 0 else 0.0
-            if n_sel <= self.sel_cap:
-                self.pos_prev = pos_prev
-                return self.sel[:n_sel].clone(), min_dist, first
-            self._grow(n_sel)
+        rows, min_dist, first, _ = self._pass(lambda: c.lib.scp_select_pairs(
+            c.h, self.N, self.K, self.D, self.R, self.q_begin, self.q_end, pos_prev.data_ptr(), margin, self.sel.data_ptr(),
+            self.sel_cap, self.bitmap.data_ptr(), c.stats.data_ptr()), "last_linearize_ms")
+        self.pos_prev = pos_prev
+        return rows, min_dist, first
 
     def violations(self, pos_new, p0, v0, feas_tol, recompute=True):
         """rows outside the working set violated at pos_new -> (rows tensor, max_violation).
@@ -1018,24 +1000,16 @@ class PairPass:
         recompute (default): eta and l are recomputed from the linearisation point kept by linearize() instead of
         streaming the stored rows back from HBM (scp_collision_violations_at); False reads the stored rows."""
         c = self.ctx
-        while True:
-            if recompute and self.pos_prev is not None:
-                c.check(c.lib.scp_collision_violations_at(c.h, self.N, self.K, self.D, self.R, self.q_begin, self.q_end,
-                                                          self.pos_prev.data_ptr(), pos_new.data_ptr(), feas_tol,
-                                                          self.sel.data_ptr(), self.sel_cap, self.bitmap.data_ptr(),
-                                                          c.stats.data_ptr()))
-            else:
-                c.check(c.lib.scp_collision_violations(c.h, self.N, self.K, self.D, self.h, self.q_begin, self.q_end,
-                                                       self.eta.data_ptr(), self.l.data_ptr(), pos_new.data_ptr(),
-                                                       p0.data_ptr(), v0.data_ptr(), feas_tol, self.sel.data_ptr(),
-                                                       self.sel_cap, self.bitmap.data_ptr(), c.stats.data_ptr()))
-            _, _, n_sel, max_v = c.read_stats()
-            self.last_violations_ms = c.last_pair_ms() if self.nq > 0 else 0.0
-            if n_sel <= self.sel_cap:
-                return self.sel[:n_sel].clone(), max_v
-            # the list was too short: the library merged nothing into the working-set bitmap (n_selected > capacity), so
-            # the pass is simply repeated with a longer list
-            self._grow(n_sel)
+        if recompute and self.pos_prev is not None:
+            rows, _, _, max_v = self._pass(lambda: c.lib.scp_collision_violations_at(
+                c.h, self.N, self.K, self.D, self.R, self.q_begin, self.q_end, self.pos_prev.data_ptr(), pos_new.data_ptr(),
+                feas_tol, self.sel.data_ptr(), self.sel_cap, self.bitmap.data_ptr(), c.stats.data_ptr()), "last_violations_ms")
+        else:
+            rows, _, _, max_v = self._pass(lambda: c.lib.scp_collision_violations(
+                c.h, self.N, self.K, self.D, self.h, self.q_begin, self.q_end, self.eta.data_ptr(), self.l.data_ptr(),
+                pos_new.data_ptr(), p0.data_ptr(), v0.data_ptr(), feas_tol, self.sel.data_ptr(), self.sel_cap,
+                self.bitmap.data_ptr(), c.stats.data_ptr()), "last_violations_ms")
+        return rows, max_v
 
     def apply_holds(self, table, n, p0, v0):
         """scp_apply_holds on the stored rows of the latest linearize(): the holds of this pair range overwrite their rows of
@@ -1111,10 +1085,8 @@ class QP:
         self.ctx.check(self.ctx.lib.scp_qp_update_settings(self.h_qp, C.byref(self.settings)))
 
     def set_problem(self, limits, space, p0, v0, pf, vf):
-        la, lp = _harr(limits)
-        sa, sp = _harr(space)
-        self.ctx.check(self.ctx.lib.scp_qp_set_problem(self.h_qp, lp, sp, p0.data_ptr(), v0.data_ptr(), pf.data_ptr(),
-                                                       vf.data_ptr()))
+        self.ctx.check(self.ctx.lib.scp_qp_set_problem(self.h_qp, _harr(limits), _harr(space), p0.data_ptr(), v0.data_ptr(),
+                                                       pf.data_ptr(), vf.data_ptr()))
 
     def set_position_boxes(self, lo, hi):
         """scp_qp_set_position_boxes: per-(vehicle, state) position boxes lo / hi ((N, K, D) device tensors by state; both
@@ -1125,11 +1097,10 @@ class QP:
             for t in (lo, hi):
                 if tuple(t.shape) != (self.N, self.K, self.D) or not t.is_contiguous():
                     raise ValueError(f"set_position_boxes: boxes are contiguous ({self.N}, {self.K}, {self.D}) tensors")
-        self.ctx.check(self.ctx.lib.scp_qp_set_position_boxes(self.h_qp, lo.data_ptr() if lo is not None else None,
-                                                              hi.data_ptr() if hi is not None else None))
+        self.ctx.check(self.ctx.lib.scp_qp_set_position_boxes(self.h_qp, _ptr(lo), _ptr(hi)))
 
     def reset(self, x0=None):
-        self.ctx.check(self.ctx.lib.scp_qp_reset(self.h_qp, x0.data_ptr() if x0 is not None else None))
+        self.ctx.check(self.ctx.lib.scp_qp_reset(self.h_qp, _ptr(x0)))
         self.n_rows = 0
 
     def set_rho(self, rho):
@@ -1212,8 +1183,7 @@ class NativeSolver:
         if (lo is None) != (hi is None):
             raise ValueError("set_position_boxes: lo and hi are both given or both None")
         self._boxes = (lo, hi)
-        self.ctx.check(self.ctx.lib.scp_solver_set_position_boxes(self.h_solver, lo.data_ptr() if lo is not None else None,
-                                                                  hi.data_ptr() if hi is not None else None))
+        self.ctx.check(self.ctx.lib.scp_solver_set_position_boxes(self.h_solver, _ptr(lo), _ptr(hi)))
 
     def default_options(self, **kw) -> SolveOptions:
         o = SolveOptions()
@@ -1222,30 +1192,30 @@ class NativeSolver:
             setattr(o, k, v)
         return o
 
+    def _problem_args(self, limits, space, p0, v0, pf, vf, options):
+        """the arguments solve, step and shard_begin begin with (limits and space are [host] arrays)"""
+        return (self.h_solver, _harr(limits), _harr(space), p0.data_ptr(), v0.data_ptr(), pf.data_ptr(), vf.data_ptr(),
+                C.byref(options))
+
     def solve(self, limits, space, p0, v0, pf, vf, options: SolveOptions):
         """-> (acc, pos, vel device tensors (N, K, D), SolveResult, [QpRecord ...])"""
         c = self.ctx
         out = c.empty(3, self.N, self.K, self.D)  # one buffer: the caller fetches all three arrays with ONE copy (out._base)
         acc, pos, vel = out[0], out[1], out[2]
-        la, lp = _harr(limits)
-        sa, sp = _harr(space)
         res = SolveResult()
         cap = int(options.max_iterations) + 2
         recs = (QpRecord * cap)()
-        c.check(c.lib.scp_solver_solve(self.h_solver, lp, sp, p0.data_ptr(), v0.data_ptr(), pf.data_ptr(), vf.data_ptr(),
-                                       C.byref(options), acc.data_ptr(), pos.data_ptr(), vel.data_ptr(), C.byref(res), recs,
-                                       cap))
+        c.check(c.lib.scp_solver_solve(*self._problem_args(limits, space, p0, v0, pf, vf, options), acc.data_ptr(),
+                                       pos.data_ptr(), vel.data_ptr(), C.byref(res), recs, cap))
         return acc, pos, vel, res, [recs[i] for i in range(res.n_records)]
 
     def step(self, limits, space, p0, v0, pf, vf, options: SolveOptions, acc):
         """One SCP iteration from the accelerations `acc` (device (N, K, D)) -> (new accelerations, QpRecord)."""
         c = self.ctx
         out = c.empty(self.N, self.K, self.D)
-        la, lp = _harr(limits)
-        sa, sp = _harr(space)
         rec = QpRecord()
-        c.check(c.lib.scp_solver_step(self.h_solver, lp, sp, p0.data_ptr(), v0.data_ptr(), pf.data_ptr(), vf.data_ptr(),
-                                      C.byref(options), acc.data_ptr(), out.data_ptr(), C.byref(rec)))
+        c.check(c.lib.scp_solver_step(*self._problem_args(limits, space, p0, v0, pf, vf, options), acc.data_ptr(),
+                                      out.data_ptr(), C.byref(rec)))
         return out, rec
 
     # ---- the step split at its exchange points (multi-GPU: one pair range per rank, see scp_hip.h) ----------------------
@@ -1268,14 +1238,12 @@ class NativeSolver:
     def shard_begin(self, limits, space, p0, v0, pf, vf, options: SolveOptions, acc, pos_in, q_begin, q_end):
         """-> (QpRecord, this rank's selected row ids (device int64 tensor, ascending))"""
         c = self.ctx
-        la, lp = _harr(limits)
-        sa, sp = _harr(space)
         rec = QpRecord()
         n = C.c_int64()
         buf = self._rows_buffer()
-        c.check(c.lib.scp_solver_shard_begin(self.h_solver, lp, sp, p0.data_ptr(), v0.data_ptr(), pf.data_ptr(), vf.data_ptr(),
-                                             C.byref(options), acc.data_ptr(), pos_in.data_ptr() if pos_in is not None else None,
-                                             int(q_begin), int(q_end), C.byref(rec), buf.data_ptr(), buf.numel(), C.byref(n)))
+        c.check(c.lib.scp_solver_shard_begin(*self._problem_args(limits, space, p0, v0, pf, vf, options), acc.data_ptr(),
+                                             _ptr(pos_in), int(q_begin), int(q_end), C.byref(rec), buf.data_ptr(), buf.numel(),
+                                             C.byref(n)))
         return rec, self._fetch_rows(int(n.value))
 
     def shard_qp(self, rows, rec):

@@ -208,8 +208,7 @@ class SCP:
         if self.reuse_native:
             import torch
 
-            known = {k for k, _ in _hip.QpSettings._fields_}
-            st = _hip.default_settings(**{k: v for k, v in self._qp_overrides.items() if k in known})
+            st = self._qp_settings()
             tdev = torch.device("cuda", int(device))
             on_default = torch.cuda.is_available() and (torch.cuda.current_stream(tdev).cuda_stream
                                                         == torch.cuda.default_stream(tdev).cuda_stream)
@@ -572,11 +571,24 @@ class SCP:
         d = self._dev
         return d["p0"], d["v0"], d["pf"], d["vf"]
 
+    def _qp_settings(self):
+        """the library's default QP settings with the qp_settings overrides that are fields of scp_qp_settings (max_iter0 is not)"""
+        known = {k for k, _ in _hip.QpSettings._fields_}
+        return _hip.default_settings(**{k: v for k, v in self._qp_overrides.items() if k in known})
+
+    def _warn_joint_qp(self, info):
+        """the warning of scp.py:446-447, or ours when constraint generation stopped (max_rounds or the iteration budget) with
+        violated rows outside the working set: x then solves the QP over the working set only, not the full one of scp.py:399-451"""
+        if info["status_val"] not in (1, 2):
+            self._print(f"Warning: OSQP status {info['status']}")
+        elif info["unresolved_rows"]:
+            self._print(f"Warning: OSQP status constraint generation stopped with {info['unresolved_rows']} violated collision "
+                        f"rows outside the working set (max violation {info['max_violation']:.3e})")
+
     def _ensure_qp(self):
         if self._qp is None:
-            known = {k for k, _ in _hip.QpSettings._fields_}
-            st = _hip.default_settings(**{k: v for k, v in self._qp_overrides.items() if k in known})
-            self._qp = _hip.QP(self._ctx, self.N, self.K, self.D, self.h, st, row_capacity=self._qp_row_capacity)
+            self._qp = _hip.QP(self._ctx, self.N, self.K, self.D, self.h, self._qp_settings(),
+                               row_capacity=self._qp_row_capacity)
         return self._qp
 
     def _ensure_pairs(self):
@@ -630,12 +642,7 @@ class SCP:
                 # multi-rank: the iteration natively, split only at its exchange points (same bits as one rank)
                 new_acc, it_info = self.scp_iteration_sharded(acc)
                 rel_step_norm = it_info["rel_step"]
-                if it_info["status_val"] not in (1, 2):  # scp.py:446-447
-                    self._print(f"Warning: OSQP status {it_info['status']}")
-                elif it_info["unresolved_rows"]:
-                    self._print(f"Warning: OSQP status constraint generation stopped with {it_info['unresolved_rows']} "
-                                f"violated collision rows outside the working set (max violation "
-                                f"{it_info['max_violation']:.3e})")
+                self._warn_joint_qp(it_info)
             else:
                 new_acc = self._solve_with_avoidance_constraints(acc)
                 _, _, rel_step_norm = self._ctx.rel_step(new_acc, acc)  # scp.py:157-159 (no zero guard)
@@ -717,9 +724,7 @@ class SCP:
 
     def _ensure_native(self):
         if self._native is None:
-            known = {k for k, _ in _hip.QpSettings._fields_}
-            st = _hip.default_settings(**{k: v for k, v in self._qp_overrides.items() if k in known})
-            self._native = _hip.NativeSolver(self._ctx, self.N, self.K, self.D, self.h, self.R, st,
+            self._native = _hip.NativeSolver(self._ctx, self.N, self.K, self.D, self.h, self.R, self._qp_settings(),
                                              row_capacity=self._qp_row_capacity)
         return self._native
 
@@ -743,7 +748,7 @@ class SCP:
         p0, v0, pf, vf = self._states()
         new, rec = nat.step(self._limits(), self._space(), p0, v0, pf, vf, self._native_options(),
                             self._to_device_acc(accelerations))
-        info = dict(rec.as_dict(), rel_step=float(rec.rel_step), time_sec=float(rec.time_sec))
+        info = rec.iteration_dict()
         self._last_qp_info = info
         return new, info
 
@@ -778,7 +783,7 @@ class SCP:
             rows, max_v = self.shard.allgather_ids(rows, extra=max_v)
             more = nat.shard_round_done(int(rows.numel()), max_v, rec)
         new = nat.shard_end(rec)
-        info = dict(rec.as_dict(), rel_step=float(rec.rel_step), time_sec=float(rec.time_sec))
+        info = rec.iteration_dict()
         self._last_qp_info = info
         return new, info
 
@@ -803,13 +808,9 @@ class SCP:
                         f"{res.first_violation_i} and {res.first_violation_j}: distance = {res.first_violation_distance:.3f}")
         its = []
         for n, r in enumerate(recs[1:1 + res.n_iterations]):
-            d = dict(r.as_dict(), rel_step=float(r.rel_step), time_sec=float(r.time_sec))
+            d = r.iteration_dict()
             self._print(f"SCP Iteration {n+1}")
-            if d["status_val"] not in (1, 2):  # scp.py:446-447
-                self._print(f"Warning: OSQP status {d['status']}")
-            elif d["unresolved_rows"]:
-                self._print(f"Warning: OSQP status constraint generation stopped with {d['unresolved_rows']} violated "
-                            f"collision rows outside the working set (max violation {d['max_violation']:.3e})")
+            self._warn_joint_qp(d)
             self._print(d["rel_step"])
             if d["rel_step"] <= self.convergence_tolerance:
                 self._print(f"Converged after {n+1} iterations.")
@@ -962,13 +963,7 @@ class SCP:
             self._qp.update_settings(eps_abs=saved[0], eps_rel=saved[1], max_iter=saved[2])
         self._last_qp_info = dict(info, **total, rounds=len(added), added=added, unresolved_rows=added[-1],
                                   max_violation=max_v)
-        if info["status_val"] not in (1, 2):  # scp.py:446-447
-            self._print(f"Warning: OSQP status {info['status']}")
-        elif added[-1]:
-            # constraint generation stopped (max_rounds or the iteration budget) with violated rows still outside the
-            # working set: x solves the QP over the working set only, not the full joint QP of scp.py:399-451
-            self._print(f"Warning: OSQP status constraint generation stopped with {added[-1]} violated collision rows "
-                        f"outside the working set (max violation {max_v:.3e})")
+        self._warn_joint_qp(self._last_qp_info)
         return x
 
     def _joint_qp_rounds(self, acc, p0, v0, pp, qp, max_iter, eps):

@@ -15,34 +15,143 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "scp_hip.h")
 
 
+def header_text():
+    """include/scp_hip.h without its comments"""
+    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+
+
+def header_structs(text):
+    """{struct name: [field names in order]} of every `typedef struct scp_x { ... } scp_x;` with a body"""
+    out = {}
+    for name, body in re.findall(r"^typedef struct (scp_\w+)\s*\{(.*?)\}\s*\w+\s*;", text, flags=re.M | re.S):
+        out[name] = [re.match(r"\w+", d.strip()).group(0)  # `double r_prim, r_dual;` declares two, `added[N]` is `added`
+                     for decl in body.split(";") if decl.strip()
+                     for d in decl.strip().split(None, 1)[1].split(",")]
+    return out
+
+
+def header_functions(text):
+    """{function: (return type, [parameter types])} of every declaration that starts in column 0 and ends in `);`, as C
+    type strings without `const` and blanks (`double*`, `scp_ctx**`, `int`); the static inline helper is no declaration"""
+    def ctype(s):
+        return re.sub(r"\bconst\b|\s+", "", s)
+
+    out = {}
+    for ret, name, params in re.findall(r"^(?!typedef|static)(\w[\w \*]*?)\b(scp_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.M):
+        params = [p.strip() for p in params.split(",")]
+        out[name] = (ctype(ret), [] if params == ["void"] else [ctype(re.sub(r"\w+$", "", p)) for p in params])
+    return out
+
+
+C_SCALARS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
+             **{f"{u}int{b}_t": getattr(ctypes, f"c_{u}int{b}") for u in ("", "u") for b in (8, 16, 32, 64)}}
+OPAQUE = ("void", "scp_ctx", "scp_qp", "scp_solver")  # handles and untyped addresses
+
+
+def scalar_class(ct):
+    """(kind, bytes) of a ctypes scalar: c_size_t and c_uint64 are one class where they are one type"""
+    code = ct._type_
+    return ("f" if code in "fd" else "u" if code.isupper() else "i"), ctypes.sizeof(ct)
+
+
+def type_mismatch(c, ct, structs):
+    """why the ctypes type `ct` of a table row does not fit the C type `c` of the header (None: it fits)"""
+    if c == "void" or ct is None:
+        return None if (c == "void" and ct is None) else f"{c} against {ct}"
+    if c == "char*":
+        return None if ct is ctypes.c_char_p else f"const char* against {ct}"
+    if not c.endswith("*"):
+        ok = isinstance(ct, type) and issubclass(ct, ctypes._SimpleCData) and ct not in (ctypes.c_void_p, ctypes.c_char_p)
+        return None if ok and scalar_class(ct) == scalar_class(C_SCALARS[c]) else f"{c} against {ct}"
+    pointee = c[:-1]
+    if ct is ctypes.c_void_p:  # an opaque handle or a device address
+        return f"{c} against c_void_p" if pointee.endswith("*") else None
+    if not (isinstance(ct, type) and issubclass(ct, ctypes._Pointer)):
+        return f"{c} against {ct}"
+    to = ct._type_
+    if pointee.endswith("*"):
+        return None if to is ctypes.c_void_p else f"{c} against a pointer to {to}"
+    if pointee in structs:
+        return None if to is structs[pointee] else f"{c} against a pointer to {to}"
+    if pointee in OPAQUE:
+        return f"{c} is opaque: c_void_p, not a pointer to {to}"
+    ok = issubclass(to, ctypes._SimpleCData) and scalar_class(to) == scalar_class(C_SCALARS[pointee])
+    return None if ok else f"{c} against a pointer to {to}"
+
+
+def prototype_errors(table, structs, declared):
+    """every disagreement between a prototype table (name -> (restype, argtypes)) and the header's declarations"""
+    errors = [f"{n}: declared in the header, no row in the table" for n in declared if n not in table]
+    errors += [f"{n}: a row in the table, not declared in the header" for n in table if n not in declared]
+    for name in sorted(set(table) & set(declared)):
+        (restype, argtypes), (ret, params) = table[name], declared[name]
+        why = type_mismatch(ret, restype, structs)
+        if why:
+            errors.append(f"{name}: return type {why}")
+        if len(argtypes) != len(params):
+            errors.append(f"{name}: {len(argtypes)} argtypes for {len(params)} parameters")
+            continue
+        for i, (c, ct) in enumerate(zip(params, argtypes)):
+            why = type_mismatch(c, ct, structs)
+            if why:
+                errors.append(f"{name}: parameter {i} {why}")
+    return errors
+
+
+def c_layouts(structs, tmp_path):
+    """{struct: (sizeof, {field: (offsetof, sizeof)})} as gcc sees include/scp_hip.h, for the fields the mirrors name (a
+    field the header lacks does not compile), and SCP_ABI_VERSION"""
+    import subprocess
+
+    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "scp_hip.h"', "int main(void) {"]
+    for name, cls in structs.items():
+        src.append(f'  printf("{name} %zu", sizeof({name}));')
+        src += [f'  printf(" {f} %zu %zu", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for f, *_ in cls._fields_]
+        src.append('  printf("\\n");')
+    src.append('  printf("abi %d\\n", SCP_ABI_VERSION);\n  return 0; }')
+    (tmp_path / "layout.c").write_text("\n".join(src))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I", os.path.dirname(HEADER), str(tmp_path / "layout.c"), "-o", str(exe)], check=True)
+    out = {}
+    for words in map(str.split, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()):
+        rest = words[2:]
+        out[words[0]] = (int(words[1]), {rest[i]: (int(rest[i + 1]), int(rest[i + 2])) for i in range(0, len(rest), 3)})
+    return out, out.pop("abi")[0]
+
+
+def struct_errors(structs, layouts, declared):
+    """every disagreement between the mirrors (C struct name -> ctypes Structure), the C compiler's layouts and the field
+    lists of the header"""
+    errors = [f"{n}: a struct of the header without a mirror" for n in declared if n not in structs]
+    for name, cls in structs.items():
+        fields = [f for f, *_ in cls._fields_]
+        if name not in declared or name not in layouts:
+            errors.append(f"{name}: a mirror of no struct of the header")
+            continue
+        if fields != declared[name]:
+            errors.append(f"{name}: fields {fields}, the header declares {declared[name]}")
+        size, at = layouts[name]
+        if ctypes.sizeof(cls) != size:
+            errors.append(f"{name}: {ctypes.sizeof(cls)} bytes, {size} in C")
+        for f in fields:
+            got = (getattr(cls, f).offset, getattr(cls, f).size)
+            if f in at and got != at[f]:
+                errors.append(f"{name}.{f}: (offset, size) {got}, {at[f]} in C")
+    return errors
+
+
 def test_library_exports_every_declared_symbol():
     from path_planning import _hip
 
     path = _hip.library_path()
     assert os.path.exists(path), "build first: python -c 'import __graft_entry__ as g; g.build()'"
     lib = ctypes.CDLL(path)
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(scp_[a-z0-9_]+)\s*\(", text)) - {"scp_eta_stride"}  # static inline helper
-    assert declared == set(_hip.EXPORTS), declared ^ set(_hip.EXPORTS)
+    declared = set(re.findall(r"\b(scp_[a-z0-9_]+)\s*\(", header_text())) - {"scp_eta_stride"}  # static inline helper
+    assert declared == set(_hip.EXPORTS) == set(_hip.PROTOTYPES), declared ^ set(_hip.EXPORTS)
+    assert len(_hip.EXPORTS) == len(set(_hip.EXPORTS))
     for name in sorted(declared):
         assert hasattr(lib, name), name
     assert lib.scp_abi_version() == _hip.ABI_VERSION == int(re.search(r"#define SCP_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
-    # struct layouts agree with the header
-    import subprocess
-    import tempfile
-
-    with tempfile.TemporaryDirectory() as tmp:  # sizeof as the C compiler sees the header
-        src = os.path.join(tmp, "sz.c")
-        with open(src, "w") as f:
-            f.write('#include <stdio.h>\n#include "scp_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu", sizeof(scp_qp_settings), '
-                    'sizeof(scp_qp_info), sizeof(scp_pair_stats), sizeof(scp_solve_options), sizeof(scp_qp_record), '
-                    'sizeof(scp_solve_result));return 0;}\n')
-        exe = os.path.join(tmp, "sz")
-        subprocess.run(["gcc", "-I", os.path.dirname(HEADER), src, "-o", exe], check=True)
-        sizes = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    assert [ctypes.sizeof(_hip.QpSettings), ctypes.sizeof(_hip.QpInfo), 32, ctypes.sizeof(_hip.SolveOptions),
-            ctypes.sizeof(_hip.QpRecord), ctypes.sizeof(_hip.SolveResult)] == sizes, sizes
     s = _hip.default_settings()
     assert (s.rho, s.sigma, s.alpha, s.eps_abs, s.eps_rel, s.max_iter, s.check_termination) == (
         0.1, 1e-6, 1.6, 1e-3, 1e-3, 4000, 25)  # OSQP defaults
@@ -203,40 +312,75 @@ def test_graft_entry_build_runs_on_cpu():
     g.build()
 
 
-def test_ctypes_structs_match_the_header(tmp_path):
-    """The ctypes mirrors of the [host] structs (scp_qp_settings, scp_qp_info, scp_solve_options, scp_qp_record,
-    scp_solve_result, scp_pair_stats) have the size and the field offsets gcc gives the C declarations of include/scp_hip.h."""
-    import ctypes
-    import subprocess
+HOST_STRUCTS = ("scp_qp_settings", "scp_qp_info", "scp_pair_stats", "scp_solve_options", "scp_qp_record", "scp_solve_result")
 
+
+def test_ctypes_structs_match_the_header(tmp_path):
+    """Every struct of include/scp_hip.h has a ctypes mirror in _hip.STRUCTS, and every mirror has the size, the field names
+    and, for every field, the offset and the size that gcc gives the C declaration; each numpy dtype derives from its mirror."""
     from path_planning import _hip
 
-    fields = {
-        "scp_qp_settings": (_hip.QpSettings, ["rho", "max_iter", "cg_iters", "rho_col_scale", "persistent"]),
-        "scp_qp_info": (_hip.QpInfo, ["status_val", "working_rows", "solve_ms", "pipeline", "rho_switches_in_kernel"]),
-        "scp_solve_options": (_hip.SolveOptions, ["max_iterations", "working_set_margin", "convergence_tolerance", "row_free",
-                                                  "carry_rho"]),
-        "scp_qp_record": (_hip.QpRecord, ["status_val", "pipeline", "working_rows", "added", "rel_step", "violations_ms",
-                                          "persist_launches", "reserved"]),
-        "scp_solve_result": (_hip.SolveResult, ["n_iterations", "first_violation", "time_sec"]),
-    }
-    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "scp_hip.h"', "int main(void) {"]
-    for name, (_, fs) in fields.items():
-        src.append(f'  printf("{name} %zu", sizeof({name}));')
-        for f in fs:
-            src.append(f'  printf(" %zu", offsetof({name}, {f}));')
-        src.append('  printf("\\n");')
-    src.append('  printf("abi %d\\n", SCP_ABI_VERSION);')
-    src.append("  return 0; }")
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    got = {ln.split()[0]: [int(v) for v in ln.split()[1:]] for ln in out if ln.strip()}
-    for name, (cls, fs) in fields.items():
-        want = [ctypes.sizeof(cls)] + [getattr(cls, f).offset for f in fs]
-        assert got[name] == want, (name, got[name], want)
-    assert got["abi"] == [_hip.ABI_VERSION]
+    declared = header_structs(header_text())
+    assert sorted(declared) == sorted(re.findall(r"typedef struct (scp_\w+)\s*\{", header_text())), "the parser lost a struct"
+    assert set(HOST_STRUCTS) <= set(declared), sorted(declared)
+    layouts, abi = c_layouts(_hip.STRUCTS, tmp_path)
+    assert struct_errors(_hip.STRUCTS, layouts, declared) == []
+    for name in HOST_STRUCTS:  # (spelled out: the sizes of the six structs the host reads or writes)
+        assert ctypes.sizeof(_hip.STRUCTS[name]) == layouts[name][0], name
+    assert ctypes.sizeof(_hip.PairStats) == 32
+    for name, value in vars(_hip).items():
+        if name.endswith("_DTYPE"):
+            mirror = [cls for cls in _hip.STRUCTS.values() if np.dtype(cls) == value]
+            assert len(mirror) == 1 and value.itemsize == ctypes.sizeof(mirror[0]), name
+    assert abi == _hip.ABI_VERSION
     assert _hip.pipeline_names(0) == "none" and _hip.pipeline_names((1 << 1) | (1 << 3)) == "persistent+three-launch"
     assert _hip.pipeline_names(1 << 7) == "persistent8-lean"
+
+
+def test_prototypes_match_the_header():
+    """Every function include/scp_hip.h declares has a row in _hip.PROTOTYPES and the reverse; arity, every parameter and the
+    return type agree in class (scalars: kind and byte size; const char*: c_char_p; pointers: c_void_p for handles and device
+    addresses, POINTER(Mirror) only for that very struct, POINTER(scalar) for a pointee of that kind and size)."""
+    from path_planning import _hip
+
+    declared = header_functions(header_text())
+    named = set(re.findall(r"\b(scp_[a-z0-9_]+)\s*\(", header_text())) - {"scp_eta_stride"}  # (as the export test finds them)
+    assert set(declared) == named, "the parser lost a declaration: " + str(set(declared) ^ named)
+    assert prototype_errors(_hip.PROTOTYPES, _hip.STRUCTS, declared) == []
+
+
+def test_abi_checks_report_broken_copies():
+    """The two comparisons above find what they are there to find: wrong copies of the tables are reported by name.  Plain
+    Python on copies: nothing is compiled, loaded or called (the layouts are those of the mirrors the test above holds to C)."""
+    from path_planning import _hip
+
+    text = header_text()
+    declared, table = header_functions(text), dict(_hip.PROTOTYPES)
+
+    def report(name, restype, argtypes):
+        return prototype_errors(dict(table, **{name: (restype, argtypes)}), _hip.STRUCTS, declared)
+
+    res, args = table["scp_list_conflicts"]
+    i = args.index(ctypes.c_int64)
+    narrow = report("scp_list_conflicts", res, args[:i] + [ctypes.c_int32] + args[i + 1:])  # an i32 where C takes int64_t
+    assert len(narrow) == 1 and narrow[0].startswith(f"scp_list_conflicts: parameter {i} int64_t"), narrow
+    dropped = report("scp_list_conflicts", res, args[:i] + args[i + 1:])
+    assert dropped == [f"scp_list_conflicts: {len(args) - 1} argtypes for {len(args)} parameters"], dropped
+    assert table["scp_ctx_destroy"][0] is None
+    default = report("scp_ctx_destroy", ctypes.c_int, table["scp_ctx_destroy"][1])  # restype left at ctypes' default
+    assert default == [f"scp_ctx_destroy: return type void against {ctypes.c_int}"], default
+    missing = prototype_errors({k: v for k, v in table.items() if k != "scp_abi_version"}, _hip.STRUCTS, declared)
+    assert missing == ["scp_abi_version: declared in the header, no row in the table"], missing
+    other = report("scp_qp_solve", res, [ctypes.c_void_p, ctypes.POINTER(_hip.QpRecord)])  # a pointer to the wrong struct
+    assert len(other) == 1 and other[0].startswith("scp_qp_solve: parameter 1 scp_qp_info*"), other
+
+    good = _hip.Conflict._fields_
+
+    class Swapped(ctypes.Structure):  # scp_conflict with min_dist and t_min exchanged: the same size, the same field set
+        _fields_ = [good[0], good[2], good[1], *good[3:]]
+
+    layouts = {name: (ctypes.sizeof(cls), {f: (getattr(cls, f).offset, getattr(cls, f).size) for f, *_ in cls._fields_})
+               for name, cls in _hip.STRUCTS.items()}
+    found = struct_errors(dict(_hip.STRUCTS, scp_conflict=Swapped), layouts, header_structs(text))
+    assert len(found) == 3 and found[0].startswith("scp_conflict: fields ['row', 't_min', 'min_dist'"), found
+    assert [e.split(":")[0] for e in found[1:]] == ["scp_conflict.t_min", "scp_conflict.min_dist"], found
