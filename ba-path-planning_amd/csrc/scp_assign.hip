@@ -1,11 +1,14 @@
 // Goal assignment for interchangeable vehicles and the straight-line check (include/scp_hip.h states both rules; the numpy
 // restatement the tests compare against bit for bit is tests/assignment_ref.py).
 //
-//   asg_auction_kernel  ONE workgroup per scenario, the whole epsilon-scaled Jacobi auction in one launch.  In LDS: the prices,
+//   asg_auction_kernel  (a template on where c_ij comes from: the coordinates -- scp_assign_goals -- or a matrix in global
+//                       memory -- scp_assign_costs; everything below is the one copy both run)
+//                       ONE workgroup per scenario, the whole epsilon-scaled Jacobi auction in one launch.  In LDS: the prices,
 //                       every person's pending bid, per goal its owner and the lowest-index bidder of the round's highest bid,
 //                       per person its goal (>= 0), -1 (unassigned) or -2 - j1 (a bid for j1 is pending).  A round is
 //                         A  one wave per unassigned person (persons dealt round-robin to the waves), lanes striding over the
-//                            goals: costs recomputed from the points (read through the caches), best / second best by shuffles
+//                            goals: costs recomputed from the points (read through the caches) or read from the person's
+//                            row of the matrix (consecutive words), best / second best by shuffles
 //                         B  the goal's price := max(price, bids) by 64-bit LDS atomicMax -- every bid exceeds the old price
 //                         C  among the bidders whose bid IS the new price the lowest index, by LDS atomicMin
 //                         D  that bidder takes the goal, its previous owner and the losers are unassigned again
@@ -26,8 +29,43 @@ namespace {
 constexpr int ASG_MAXN = 4096;
 constexpr int LINE_TILE = 256;
 
+// Where c_ij comes from.  A source is made from the kernel's arguments for scenario b (the pointers themselves stay
+// __restrict__ parameters of the kernel), hands a bidding wave what it needs of person i (row) and states c_ij from that (at)
+// or from the indices alone (pair).
+struct AsgFromPoints {  // scp_assign_goals: asg_cost of the coordinates, recomputed wherever it is needed
+  static constexpr bool kMatrix = false;
+  const double* start;
+  const double* goal;
+  int D, sh;
+  struct Row {
+    double a[3];
+  };
+  __device__ AsgFromPoints(int b, int N, int D_, const double* s, const double* g, const int32_t*)
+      : start(s + (int64_t)b * N * D_), goal(g + (int64_t)b * N * D_), D(D_), sh(0) {}
+  __device__ Row row(int i, int) const {
+    const double* p = start + (int64_t)i * D;  // (constant indices: the row stays in registers)
+    return Row{{p[0], p[1], D == 3 ? p[2] : 0.0}};
+  }
+  __device__ long long at(const Row& r, int j) const { return asg_cost(r.a, goal + (int64_t)j * D, D, sh); }
+  __device__ long long pair(int i, int j, int) const { return asg_cost(start + (int64_t)i * D, goal + (int64_t)j * D, D, sh); }
+};
+
+struct AsgFromMatrix {  // scp_assign_costs: row i of the scenario's matrix, the lanes of a wave on consecutive words
+  static constexpr bool kMatrix = true;
+  const int32_t* cost;
+  struct Row {
+    const int32_t* c;
+  };
+  __device__ AsgFromMatrix(int b, int N, int, const double*, const double*, const int32_t* c) : cost(c + (int64_t)b * N * N) {}
+  __device__ Row row(int i, int N) const { return Row{cost + (int64_t)i * N}; }
+  __device__ long long at(const Row& r, int j) const { return r.c[j]; }
+  __device__ long long pair(int i, int j, int N) const { return cost[(int64_t)i * N + j]; }
+};
+
+template <class Src>
 __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const double* __restrict__ start,
-                                                           const double* __restrict__ goal, int32_t* __restrict__ goal_of,
+                                                           const double* __restrict__ goal, const int32_t* __restrict__ cost,
+                                                           int32_t* __restrict__ goal_of,
                                                            long long* __restrict__ prices, long long max_rounds,
                                                            scp_assign_stats* __restrict__ stats, int* bad_flag) {
 #pragma clang fp contract(off)
@@ -45,11 +83,43 @@ __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const d
 
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nwave = nthr >> 6;
   const int b = blockIdx.x;
-  const double* sb = start + (int64_t)b * N * D;
-  const double* gb = goal + (int64_t)b * N * D;
+  Src src(b, N, D, start, goal, cost);
 
-  // ---- quantisation: the box of all 2N points ----
-  {
+  if constexpr (Src::kMatrix) {
+    // ---- the largest entry of the scenario's matrix; a negative one is unusable ----
+    long long top = 0;
+    int bad = 0;
+    for (int64_t k = tid; k < (int64_t)N * N; k += nthr) {
+      const long long c = src.cost[k];
+      bad |= c < 0;
+      top = c > top ? c : top;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+      const long long o = __shfl_xor(top, off, 64);
+      top = o > top ? o : top;
+      bad |= __shfl_xor(bad, off, 64);
+    }
+    if (lane == 0) {
+      s_red[0][wave] = top;
+      s_bad[wave] = bad;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int anybad = 0;
+      for (int w = 0; w < nwave; ++w) {
+        anybad |= s_bad[w];
+        top = s_red[0][w] > top ? s_red[0][w] : top;
+      }
+      const long long e0 = ((long long)(N + 1) * top) / 2;
+      s_shift = 0;
+      s_eps0 = e0 > 1 ? e0 : 1;
+      s_isbad = anybad;
+    }
+    __syncthreads();  // (s_red is next written after the auction's barriers)
+  } else {
+    // ---- quantisation: the box of all 2N points ----
+    const double* sb = src.start;
+    const double* gb = src.goal;
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     int bad = 0;
     for (int k = tid; k < 2 * N; k += nthr) {
@@ -106,6 +176,7 @@ __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const d
     __syncthreads();
   }
   const int sh = s_shift;
+  if constexpr (!Src::kMatrix) src.sh = sh;
   if (s_isbad) {  // (workgroup-uniform) the host turns the flag into SCP_ERR_INVALID
     for (int i = tid; i < N; i += nthr) {
       goal_of[(int64_t)b * N + i] = i;
@@ -157,12 +228,11 @@ __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const d
           while (m) {
             const int pi = base + (__ffsll((long long)m) - 1) * nwave + wave;
             m &= m - 1;
-            double a[3];
-            for (int d = 0; d < D; ++d) a[d] = sb[(int64_t)pi * D + d];
+            const typename Src::Row mine_row = src.row(pi, N);
             long long v1 = LLONG_MIN, v2 = LLONG_MIN;
             int j1 = INT_MAX;
             for (int j = lane; j < N; j += 64) {
-              const long long v = -np1 * asg_cost(a, gb + (int64_t)j * D, D, sh) - s_price[j];
+              const long long v = -np1 * src.at(mine_row, j) - s_price[j];
               if (v > v1) {
                 v2 = v1;
                 v1 = v;
@@ -239,9 +309,9 @@ __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const d
     const int g = status == 0 ? s_gof[i] : i;
     goal_of[(int64_t)b * N + i] = g;
     if (prices) prices[(int64_t)b * N + i] = s_price[i];
-    const long long cii = asg_cost(sb + (int64_t)i * D, gb + (int64_t)i * D, D, sh);
+    const long long cii = src.pair(i, i, N);
     ci += cii;
-    cq += g == i ? cii : asg_cost(sb + (int64_t)i * D, gb + (int64_t)g * D, D, sh);
+    cq += g == i ? cii : src.pair(i, g, N);
   }
   cq = asg_wave_sum(cq);
   ci = asg_wave_sum(ci);
@@ -257,7 +327,7 @@ __global__ __launch_bounds__(1024) void asg_auction_kernel(int N, int D, const d
       st.cost_q += s_red[0][w];
       st.cost_q_identity += s_red[1][w];
     }
-    st.quantum = ldexp(1.0, -sh);
+    st.quantum = Src::kMatrix ? 1.0 : ldexp(1.0, -sh);
     st.rounds = rounds;
     st.bids = bids;
     st.phases = phases;
@@ -409,6 +479,38 @@ __global__ __launch_bounds__(64) void line_finish_kernel(int ntri, const LinePar
 
 }  // namespace
 
+// the launch behind both calls: one workgroup per scenario, the raised word of the mapped host flag -> SCP_ERR_INVALID
+template <class Src>
+static int asg_run(scp_ctx* ctx, const char* who, const char* unusable, bool timed, int B, int N, int D, const double* start,
+                   const double* goal, const int32_t* cost, int32_t* goal_of, int64_t* prices, int64_t max_rounds_per_phase,
+                   scp_assign_stats* stats) {
+  static_assert(sizeof(scp_assign_stats) == 48, "scp_assign_stats is 48 bytes");
+  const long long guard = max_rounds_per_phase > 0 ? (long long)max_rounds_per_phase : 256ll * N + 4096;
+  SCP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  if (const int rc = asg_host_flag(ctx)) return rc;
+  const size_t lds = (size_t)N * (2 * sizeof(long long) + 3 * sizeof(int));  // 28 N bytes: 112 KiB at N = 4096
+  if (lds > 48 * 1024)
+    SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, reinterpret_cast<const void*>(asg_auction_kernel<Src>), lds));
+  // small scenarios: four waves, so that several workgroups share a compute unit; large ones: sixteen
+  const int threads = N <= 512 ? 256 : 1024;
+  hipStream_t st = ctx->stream;
+  volatile int* hflag = ctx->h_gen_flag;
+  *hflag = 0;
+  if (timed && ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev0, st));
+  asg_auction_kernel<Src><<<B, threads, lds, st>>>(N, D, start, goal, cost, goal_of, (long long*)prices, guard, stats,
+                                                   ctx->d_gen_flag);
+  hipError_t e = hipGetLastError();
+  if (timed && e == hipSuccess) {
+    if (ctx->timing) SCP_HIP_CHECK(ctx, hipEventRecord(ctx->pair_ev1, st));
+    ctx->pair_timed = ctx->timing != 0;
+    ctx->pair_ran = true;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return scp_fail(ctx, SCP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+  SCP_REQUIRE(ctx, *hflag == 0, "%s: %s", who, unusable);
+  return SCP_OK;
+}
+
 extern "C" int scp_assign_goals(scp_ctx* ctx, int B, int N, int D, const double* start, const double* goal, int32_t* goal_of,
                                 int64_t* prices, int64_t max_rounds_per_phase, scp_assign_stats* stats) {
   if (!ctx) return SCP_ERR_INVALID;
@@ -416,24 +518,18 @@ extern "C" int scp_assign_goals(scp_ctx* ctx, int B, int N, int D, const double*
   SCP_REQUIRE(ctx, B >= 1, "assign_goals: B = %d (need B >= 1)", B);
   SCP_REQUIRE(ctx, N >= 1 && N <= ASG_MAXN, "assign_goals: N = %d (need 1 <= N <= %d)", N, ASG_MAXN);
   SCP_REQUIRE(ctx, D == 2 || D == 3, "assign_goals: D = %d (need 2 or 3)", D);
-  static_assert(sizeof(scp_assign_stats) == 48, "scp_assign_stats is 48 bytes");
-  const long long guard = max_rounds_per_phase > 0 ? (long long)max_rounds_per_phase : 256ll * N + 4096;
-  SCP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  if (const int rc = asg_host_flag(ctx)) return rc;
-  const size_t lds = (size_t)N * (2 * sizeof(long long) + 3 * sizeof(int));  // 28 N bytes: 112 KiB at N = 4096
-  if (lds > 48 * 1024)
-    SCP_HIP_CHECK(ctx, scp_raise_lds_limit(ctx->device, reinterpret_cast<const void*>(asg_auction_kernel), lds));
-  // small scenarios: four waves, so that several workgroups share a compute unit; large ones: sixteen
-  const int threads = N <= 512 ? 256 : 1024;
-  hipStream_t st = ctx->stream;
-  volatile int* hflag = ctx->h_gen_flag;
-  *hflag = 0;
-  asg_auction_kernel<<<B, threads, lds, st>>>(N, D, start, goal, goal_of, (long long*)prices, guard, stats, ctx->d_gen_flag);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return scp_fail(ctx, SCP_ERR_HIP, "assign_goals: %s", hipGetErrorString(e));
-  SCP_REQUIRE(ctx, *hflag == 0, "assign_goals: a coordinate is not finite, or the range of the points overflows");
-  return SCP_OK;
+  return asg_run<AsgFromPoints>(ctx, "assign_goals", "a coordinate is not finite, or the range of the points overflows", false, B,
+                                N, D, start, goal, nullptr, goal_of, prices, max_rounds_per_phase, stats);
+}
+
+extern "C" int scp_assign_costs(scp_ctx* ctx, int B, int N, const int32_t* cost, int32_t* goal_of, int64_t* prices,
+                                int64_t max_rounds_per_phase, scp_assign_stats* stats) {
+  if (!ctx) return SCP_ERR_INVALID;
+  SCP_REQUIRE(ctx, cost && goal_of && stats, "assign_costs: NULL argument");
+  SCP_REQUIRE(ctx, B >= 1, "assign_costs: B = %d (need B >= 1)", B);
+  SCP_REQUIRE(ctx, N >= 1 && N <= ASG_MAXN, "assign_costs: N = %d (need 1 <= N <= %d)", N, ASG_MAXN);
+  return asg_run<AsgFromMatrix>(ctx, "assign_costs", "a cost is negative", true, B, N, 0, nullptr, nullptr, cost, goal_of, prices,
+                                max_rounds_per_phase, stats);
 }
 
 extern "C" int scp_straight_line_check(scp_ctx* ctx, int B, int N, int D, const double* start, const double* goal,

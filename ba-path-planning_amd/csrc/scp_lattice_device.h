@@ -1,5 +1,6 @@
-// The search lattice shared by scp_reference.hip and scp_shorten.hip: its shape, node coordinates, block centres and the
-// vertices of a lattice path (the rules are stated in include/scp_hip.h, "reference paths by a lattice search").
+// The search lattice shared by scp_reference.hip, scp_lattice_dist.hip and scp_shorten.hip: its shape, node coordinates, the
+// node of a point, the directions, the level-by-level search, block centres and the vertices of a lattice path (the rules
+// are stated in include/scp_hip.h, "reference paths by a lattice search").
 #pragma once
 #include "scp_common.h"
 #include "scp_corridor_device.h"
@@ -9,6 +10,106 @@ struct Lattice {
   int nodes;   // L[0] L[1] L[2] <= SCP_LATTICE_MAX_NODES
   int stride;  // cells per block edge
 };
+
+constexpr int LATTICE_SELF = 13;  // the direction code of the node itself
+constexpr unsigned DIST_UNREACHED = 0xFFFFu;
+
+// direction order: the codes other than 13 by |dx| + |dy| + |dz|, then by code
+struct DirectionOrder {
+  int code[26];
+  constexpr DirectionOrder() : code{} {
+    int k = 0;
+    for (int len = 1; len <= 3; ++len)
+      for (int n = 0; n < 27; ++n) {
+        const int dx = n % 3 - 1, dy = (n / 3) % 3 - 1, dz = n / 9 - 1;
+        if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) + (dz < 0 ? -dz : dz) == len) code[k++] = n;
+      }
+  }
+};
+static __constant__ DirectionOrder DIRECTION_ORDER;
+
+// the id offset of the neighbour in direction n
+__device__ inline int direction_offset(const Lattice& lt, int n) {
+  const int dx = n % 3 - 1, dy = (n / 3) % 3 - 1, dz = n / 9 - 1;
+  return (dz * lt.L[1] + dy) * lt.L[0] + dx;
+}
+
+// the node of a point; false: a coordinate is not inside the grid or lies beyond the lattice
+template <int D>
+__device__ inline bool node_of(const Lattice& lt, const CorridorGrid& g, const double* p, int& node) {
+  int X[3] = {0, 0, 0};
+  bool ok = true;
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    int c = 0;
+    if (!cell_of(g, d, p[d], c)) ok = false;
+    X[d] = c / lt.stride;
+    if (X[d] >= lt.L[d]) ok = false;
+  }
+  node = (X[2] * lt.L[1] + X[1]) * lt.L[0] + X[0];
+  return ok;
+}
+
+// the node of a point if it lies on the lattice and is passable, else -1
+template <int D>
+__device__ inline int passable_node_of(const Lattice& lt, const CorridorGrid& g, const uint32_t* __restrict__ edges,
+                                       const double* p) {
+  int node = -1;
+  if (!node_of<D>(lt, g, p, node)) return -1;
+  return (edges[node] >> LATTICE_SELF & 1u) ? node : -1;
+}
+
+// The breadth-first search of one workgroup (every thread calls it with the same arguments), level by level from `origin`
+// with dist[origin] = 0 and every other entry DIST_UNREACHED on entry, behind a barrier.  In level l a node becomes l + 1 if
+// it is unreached and has a neighbour at l over a set edge bit; a concurrent store turns 0xFFFF into l + 1 and neither equals
+// l, so the reads of a level need no order among themselves.  The two flags of a level live in slot l mod 3 of `changed` /
+// `reached` (3 LDS words each, zero on entry): written in the sweep, read by everybody after the barrier, cleared by thread 0
+// two levels later (after everybody has read them, before anybody writes them again).
+// A move changes every coordinate by at most one, so a node at l + 1 lies within l + 1 of the origin per coordinate: the
+// sweep of level l walks that box only (the same dist as a sweep over every node).
+// The search ends after the level that changes nothing or -- the stop condition -- reaches the node `stop_at` (-1: none, the
+// field is then complete).  One barrier per level, at most `nodes` levels.
+__device__ __forceinline__ void lattice_search(const Lattice& lt, const uint32_t* __restrict__ edges, uint16_t* dist, int* changed_flag,
+                                      int* reached_flag, int origin, int stop_at, bool go) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  const int G[3] = {origin % lt.L[0], (origin / lt.L[0]) % lt.L[1], origin / (lt.L[0] * lt.L[1])};
+  for (int level = 0; level < lt.nodes && go; ++level) {  // (go is the same in every thread: both exits are the workgroup's)
+    const int slot = level % 3;
+    int lo[3], w[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      lo[d] = G[d] - (level + 1) > 0 ? G[d] - (level + 1) : 0;
+      const int hi = G[d] + (level + 1) < lt.L[d] - 1 ? G[d] + (level + 1) : lt.L[d] - 1;
+      w[d] = hi - lo[d] + 1;
+    }
+    const int count = w[0] * w[1] * w[2];
+    const bool whole = count == lt.nodes;
+    bool changed = false, reached = false;
+    for (int idx = tid; idx < count; idx += T) {
+      const int node = whole ? idx : ((lo[2] + idx / (w[0] * w[1])) * lt.L[1] + lo[1] + (idx / w[0]) % w[1]) * lt.L[0] + lo[0] + idx % w[0];
+      if (dist[node] != DIST_UNREACHED) continue;
+      uint32_t m = edges[node];
+      if (!(m >> LATTICE_SELF & 1u)) continue;
+      m &= ~(1u << LATTICE_SELF) & 0x7FFFFFFu;
+      while (m) {
+        const int n = __ffs(m) - 1;
+        m &= m - 1;
+        const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
+        if ((unsigned)nb < (unsigned)lt.nodes && dist[nb] == level) {
+          dist[node] = (uint16_t)(level + 1);
+          changed = true;
+          if (node == stop_at) reached = true;
+          break;
+        }
+      }
+    }
+    if (changed) changed_flag[slot] = 1;
+    if (reached) reached_flag[slot] = 1;
+    __syncthreads();
+    go = changed_flag[slot] != 0 && reached_flag[slot] == 0;
+    if (tid == 0) changed_flag[(level + 2) % 3] = reached_flag[(level + 2) % 3] = 0;
+  }
+}
 
 // coordinate d of a node
 __device__ inline int lattice_coord(const Lattice& lt, int node, int d) {

@@ -10,29 +10,6 @@
 
 namespace {
 
-constexpr int LATTICE_SELF = 13;          // the direction code of the node itself
-constexpr unsigned DIST_UNREACHED = 0xFFFFu;
-
-// direction order: the codes other than 13 by |dx| + |dy| + |dz|, then by code
-struct DirectionOrder {
-  int code[26];
-  constexpr DirectionOrder() : code{} {
-    int k = 0;
-    for (int len = 1; len <= 3; ++len)
-      for (int n = 0; n < 27; ++n) {
-        const int dx = n % 3 - 1, dy = (n / 3) % 3 - 1, dz = n / 9 - 1;
-        if ((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy) + (dz < 0 ? -dz : dz) == len) code[k++] = n;
-      }
-  }
-};
-__constant__ DirectionOrder DIRECTION_ORDER;
-
-// the id offset of the neighbour in direction n
-__device__ inline int direction_offset(const Lattice& lt, int n) {
-  const int dx = n % 3 - 1, dy = (n / 3) % 3 - 1, dz = n / 9 - 1;
-  return (dz * lt.L[1] + dy) * lt.L[0] + dx;
-}
-
 // ----------------------------------------------------------------------------------------------------
 // edge masks: one thread per node
 // ----------------------------------------------------------------------------------------------------
@@ -64,22 +41,6 @@ __global__ __launch_bounds__(256) void lattice_edges_kernel(Lattice lt, Corridor
 // ----------------------------------------------------------------------------------------------------
 // search, path and reference points: one workgroup per vehicle
 // ----------------------------------------------------------------------------------------------------
-// the node of a point; false: a coordinate is not inside the grid or lies beyond the lattice
-template <int D>
-__device__ inline bool node_of(const Lattice& lt, const CorridorGrid& g, const double* p, int& node) {
-  int X[3] = {0, 0, 0};
-  bool ok = true;
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    int c = 0;
-    if (!cell_of(g, d, p[d], c)) ok = false;
-    X[d] = c / lt.stride;
-    if (X[d] >= lt.L[d]) ok = false;
-  }
-  node = (X[2] * lt.L[1] + X[1]) * lt.L[0] + X[0];
-  return ok;
-}
-
 enum { CTL_STATUS = 0, CTL_START, CTL_GOAL, CTL_NODES, CTL_CHANGED /* 3 words */, CTL_REACHED = CTL_CHANGED + 3 /* 3 words */,
        CTL_WORDS = CTL_REACHED + 3 };
 
@@ -128,50 +89,8 @@ __global__ __launch_bounds__(1024) void reference_paths_kernel(int K, Lattice lt
   for (int node = tid; node < lt.nodes; node += T) dist[node] = searching && node == goal ? 0 : DIST_UNREACHED;
   __syncthreads();
 
-  // level by level from the goal.  In level l a node becomes l + 1 if it is unreached and has a neighbour at l over a set edge
-  // bit; a concurrent store turns 0xFFFF into l + 1 and neither equals l, so the reads of a level need no order among
-  // themselves.  The two flags of a level live in slot l mod 3: written in the sweep, read by everybody after the barrier,
-  // cleared by thread 0 two levels later (after everybody has read them, before anybody writes them again).
-  // A move changes every coordinate by at most one, so a node at l + 1 lies within l + 1 of the goal per coordinate: the
-  // sweep of level l walks that box only (the same dist as a sweep over every node).
-  bool go = searching && start != goal;
-  const int G[3] = {goal % lt.L[0], (goal / lt.L[0]) % lt.L[1], goal / (lt.L[0] * lt.L[1])};
-  for (int level = 0; level < lt.nodes && go; ++level) {  // (go is the same in every thread: both exits are the workgroup's)
-    const int slot = level % 3;
-    int lo[3], w[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      lo[d] = G[d] - (level + 1) > 0 ? G[d] - (level + 1) : 0;
-      const int hi = G[d] + (level + 1) < lt.L[d] - 1 ? G[d] + (level + 1) : lt.L[d] - 1;
-      w[d] = hi - lo[d] + 1;
-    }
-    const int count = w[0] * w[1] * w[2];
-    const bool whole = count == lt.nodes;
-    bool changed = false, reached = false;
-    for (int idx = tid; idx < count; idx += T) {
-      const int node = whole ? idx : ((lo[2] + idx / (w[0] * w[1])) * lt.L[1] + lo[1] + (idx / w[0]) % w[1]) * lt.L[0] + lo[0] + idx % w[0];
-      if (dist[node] != DIST_UNREACHED) continue;
-      uint32_t m = edges[node];
-      if (!(m >> LATTICE_SELF & 1u)) continue;
-      m &= ~(1u << LATTICE_SELF) & 0x7FFFFFFu;
-      while (m) {
-        const int n = __ffs(m) - 1;
-        m &= m - 1;
-        const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
-        if ((unsigned)nb < (unsigned)lt.nodes && dist[nb] == level) {
-          dist[node] = (uint16_t)(level + 1);
-          changed = true;
-          if (node == start) reached = true;
-          break;
-        }
-      }
-    }
-    if (changed) ctl[CTL_CHANGED + slot] = 1;
-    if (reached) ctl[CTL_REACHED + slot] = 1;
-    __syncthreads();
-    go = ctl[CTL_CHANGED + slot] != 0 && ctl[CTL_REACHED + slot] == 0;
-    if (tid == 0) ctl[CTL_CHANGED + (level + 2) % 3] = ctl[CTL_REACHED + (level + 2) % 3] = 0;
-  }
+  // level by level from the goal, until the start is reached or a level changes nothing
+  lattice_search(lt, edges, dist, ctl + CTL_CHANGED, ctl + CTL_REACHED, goal, start, searching && start != goal);
 
   if (dist_out)
     for (int node = tid; node < lt.nodes; node += T) dist_out[i * lt.nodes + node] = dist[node];

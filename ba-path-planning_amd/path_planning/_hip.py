@@ -201,6 +201,8 @@ class AssignStats(C.Structure):
 
 
 ASSIGN_STATS_DTYPE = np.dtype(AssignStats)
+ASSIGN_MAX_COST = 2**31 - 1  # SCP_ASSIGN_MAX_COST: the largest entry of scp_assign_costs
+ASSIGN_COSTS_MAX_N = 4096    # scp_assign_costs (and scp_assign_goals)
 
 
 class LineStats(C.Structure):
@@ -234,6 +236,7 @@ class PathInfo(C.Structure):
 
 PATH_INFO_DTYPE = np.dtype(PathInfo)
 LATTICE_MAX_NODES = 32768     # SCP_LATTICE_MAX_NODES: scp_lattice_edges, scp_reference_paths
+HOPS_UNREACHED = 0xFFFF       # scp_lattice_distances: no path, or a point without a node
 PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that is not free",
                2: "the goal lies off the lattice or on a block that is not free", 3: "the goal cannot be reached from the start",
                4: "the path has more nodes than max_path"}
@@ -346,6 +349,7 @@ PROTOTYPES = {
     "scp_generate_grid_swap": (i32, [vp, i32, i32, i32, pu64, P(GenParams), vp, vp, vp, vp]),
     "scp_assign_goals": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
     "scp_assign_goals_wide": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+    "scp_assign_costs": (i32, [vp, i32, i32, vp, vp, vp, i64, vp]),
     "scp_straight_line_check": (i32, [vp, i32, i32, i32, vp, vp, vp, f64, vp]),
     "scp_occupancy_prepare": (i32, [vp, i32, pg, vp, vp]),
     "scp_corridor_boxes": (i32, [vp, i32, i32, i32, pg, vp, vp, i32, vp, vp]),
@@ -355,6 +359,7 @@ PROTOTYPES = {
     "scp_check_corridor": (i32, [vp, i32, i32, i32, f64, pg, vp, vp, vp, vp, f64, vp]),
     "scp_lattice_edges": (i32, [vp, i32, pg, vp, i32, i32, vp]),
     "scp_reference_paths": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_lattice_distances": (i32, [vp, i32, pg, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "scp_shorten_paths": (i32, [vp, i32, i32, i32, pg, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "scp_gemm_f64": (i32, [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]),
     "scp_qp_peek": (i32, [vp, cstr, vp, i64, P(i64)]),
@@ -810,6 +815,32 @@ class Context:
                       stats.data_ptr()))
         return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
 
+    def assign_costs(self, cost, max_rounds_per_phase=0, want_prices=False):
+        """scp_assign_costs: the assignment that minimises sum_i cost[i][goal_of[i]], by the auction of assign_goals on the
+        caller's matrix.  cost: (B, N, N) or (N, N) whole numbers in [0, ASSIGN_MAX_COST], an array or a device tensor
+        (cost[b][i][j]: person i, goal j).  Returns goal_of (B, N) int32 device tensor, the stats (ASSIGN_STATS_DTYPE, B
+        entries; quantum is 1.0) and the prices ((B, N) int64 device tensor, or None).  Synchronises; last_pair_ms() is the
+        kernel's time."""
+        torch = _torch()
+        c = cost if torch.is_tensor(cost) else torch.as_tensor(np.ascontiguousarray(cost))
+        if c.is_floating_point() or c.is_complex() or c.dtype == torch.bool:
+            raise ValueError(f"cost of dtype {c.dtype}: need whole numbers")
+        c = c[None] if c.dim() == 2 else c
+        if c.dim() != 3 or c.shape[1] != c.shape[2]:
+            raise ValueError(f"cost {tuple(c.shape)} must be (B, N, N) or (N, N)")
+        if c.dtype != torch.int32:
+            if c.numel() and int(c.max()) > ASSIGN_MAX_COST:
+                raise ValueError(f"a cost exceeds SCP_ASSIGN_MAX_COST = {ASSIGN_MAX_COST}")
+            c = c.clamp(min=-1).to(torch.int32)  # (a negative entry stays negative: the call reports it)
+        c = c.to(device=self.tdev).contiguous()
+        B, N = int(c.shape[0]), int(c.shape[1])
+        goal_of = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int32, device=self.tdev)
+        prices = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int64, device=self.tdev) if want_prices else None
+        stats = torch.empty(max(B, 1) * ASSIGN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_assign_costs(self.h, B, N, c.data_ptr(), goal_of.data_ptr(), _ptr(prices),
+                                             int(max_rounds_per_phase), stats.data_ptr()))
+        return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
+
     def straight_line_check(self, start, goal, goal_of=None, min_sep=0.0):
         """scp_straight_line_check: closest approach, close pairs and opposed pairs of the equal-time straight-line motions
         start_i -> goal[goal_of[i]] (goal_of None: the identity) of B scenarios, as a numpy structured array
@@ -892,6 +923,25 @@ class Context:
                                                 pf.data_ptr(), int(max_path), ref.data_ptr(), _ptr(path), info.data_ptr(),
                                                 _ptr(dist), n_failed.data_ptr()))
         return path, info, dist, n_failed
+
+    def lattice_distances(self, D, grid: OccupancyGrid, stride, edges, src, dst, want_dist=False):
+        """scp_lattice_distances: src (n_src, D) and dst (n_dst, D) device tensors, edges as lattice_edges made them with the
+        same stride.  Returns (hops (n_src, n_dst) int16 device tensor holding the uint16 words -- HOPS_UNREACHED where there
+        is no path or a point has no node --, src_node (n_src,) and dst_node (n_dst,) int32 device tensors (-1: off the
+        lattice or on a block that is not free), dist (n_src, nodes) int16 device tensor holding the uint16 words, or None).
+        No host read."""
+        torch = _torch()
+        L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
+        nodes = max(L[0] * L[1] * L[2], 1)
+        n_src, n_dst = int(src.shape[0]), int(dst.shape[0])
+        hops = torch.empty((max(n_src, 1), max(n_dst, 1)), dtype=torch.int16, device=self.tdev)
+        src_node = torch.empty(max(n_src, 1), dtype=torch.int32, device=self.tdev)
+        dst_node = torch.empty(max(n_dst, 1), dtype=torch.int32, device=self.tdev)
+        dist = torch.empty((max(n_src, 1), nodes), dtype=torch.int16, device=self.tdev) if want_dist else None
+        self.check(self.lib.scp_lattice_distances(self.h, int(D), C.byref(grid), int(stride), edges.data_ptr(), n_src,
+                                                  src.data_ptr(), n_dst, dst.data_ptr(), hops.data_ptr(), src_node.data_ptr(),
+                                                  dst_node.data_ptr(), _ptr(dist)))
+        return hops, src_node, dst_node, dist
 
     def shorten_paths(self, N, K, D, grid: OccupancyGrid, sat, stride, clearance, p0, pf, max_path, path, info, ref, want_kept=True):
         """scp_shorten_paths: path (N, max_path) int32 and info as reference_paths returned them, p0 / pf (N, D) and ref

@@ -82,6 +82,11 @@ def build_parser():
     p.add_argument("--assign-method", choices=("auto", "single", "wide"), default="auto",
                    help="--assign-goals through the one-workgroup auction (single, up to 4096 vehicles), the whole-GPU one (wide, "
                         "up to 65536) or whichever fits (auto); the assignment is the same")
+    p.add_argument("--assign-cost", choices=("line", "path"), default="line",
+                   help="with --assign-goals: pair by squared straight-line distance (line), or by the length of the paths "
+                        "the lattice search finds around the obstacles (path: needs --obstacle-discs, takes --corridor-stride "
+                        "and --corridor-clearance; up to 4096 vehicles) -- the line then shows the lattice moves before and "
+                        "after")
     p.add_argument("--obstacle-discs", nargs="+", default=None, metavar="X,Y[,Z],R",
                    help="static obstacles: discs (spheres in 3-D) given as centre and radius; before the solve, safe flight "
                         "corridors around the straight lines from start to goal become per-step position boxes of the QP, and "
@@ -112,13 +117,19 @@ def build_parser():
 
 def obstacle_discs(parser, args):
     """the discs of --obstacle-discs as tuples of floats; the corridor flags are errors without it, --corridor-stride and
-    --corridor-clearance and --corridor-shorten without --corridor-search"""
+    --corridor-clearance without --corridor-search or --assign-cost path, --corridor-shorten without --corridor-search"""
+    by_path = args.assign_cost == "path"
+    if by_path and not args.assign_goals:
+        parser.error("--assign-cost needs --assign-goals")
     if not args.corridor_search:
-        for flag, value in (("--corridor-stride", args.corridor_stride), ("--corridor-clearance", args.corridor_clearance),
+        for flag, value in (("--corridor-stride", None if by_path else args.corridor_stride),
+                            ("--corridor-clearance", None if by_path else args.corridor_clearance),
                             ("--corridor-shorten", args.corridor_shorten or None)):
             if value is not None:
                 parser.error(f"{flag} needs --corridor-search")
     if args.obstacle_discs is None:
+        if by_path:
+            parser.error("--assign-cost path needs --obstacle-discs")
         for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow),
                             ("--corridor-search", args.corridor_search or None)):
             if value is not None:
@@ -187,7 +198,7 @@ def main(argv=None):
         print(f"Successfully generated positions for {n_vehicles} vehicles")
         solver.set_initial_states(np.asarray(initial_positions))
         solver.set_final_states(np.asarray(final_positions))
-        if args.assign_goals:
+        if args.assign_goals and args.assign_cost == "line":
             from ..scenarios.assignment import describe
 
             solver.assign_goals(method=args.assign_method)
@@ -198,6 +209,11 @@ def main(argv=None):
 
             occ, origin, cell = rasterize(space_dims, args.corridor_cell or min_distance / 4, discs=discs, margin=min_distance / 2)
             solver.set_obstacles(occ, origin, cell)
+            if args.assign_goals and args.assign_cost == "path":  # (the pairing sees the map: after it, before the search)
+                from ..scenarios.assignment import describe
+
+                solver.assign_goals(cost="path", stride=args.corridor_stride, clearance=args.corridor_clearance or 0)
+                print(describe(solver.assignment_info))
             reference = None
             if args.corridor_search:
                 if args.corridor_shorten:

@@ -274,6 +274,10 @@ def build_parser():
                    help="interchangeable vehicles: pair vehicles and goals of every scenario so that the sum of squared "
                         "start-goal distances is minimal before it is solved; prints one line per scenario (cost, straight-line "
                         "minimum approach, opposed pairs, before -> after) and adds goal_assignment and assign_ms to its record")
+    p.add_argument("--assign-cost", choices=("line", "path"), default="line",
+                   help="--assign-goals by squared straight-line distance (line); path -- by the length of the paths around "
+                        "static obstacles -- needs a map, and the batch scenarios have none: compute-trajectories "
+                        "--obstacle-discs offers it")
     p.add_argument("--assign-method", choices=("auto", "single", "wide"), default="auto",
                    help="--assign-goals through the one-workgroup auction (single, up to 4096 vehicles), the whole-GPU one (wide, "
                         "up to 65536) or whichever fits (auto); the assignment is the same")
@@ -303,6 +307,9 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args([] if argv is None else argv)
     stagger_search = stagger_search_keywords(parser, args)
+    if args.assign_cost == "path":
+        parser.error("--assign-cost path needs static obstacles, which the batch scenarios do not have (see compute-trajectories "
+                     "--obstacle-discs --assign-goals --assign-cost path)")
     if args.streams > 1:
         # HIP maps streams onto 4 hardware queues by default and kernels of streams that share a queue run one after the
         # other -- a persistent QP kernel holds its queue for a millisecond.  Effective only before the runtime starts.

@@ -7,6 +7,10 @@ swaps, the instances on which the first linearised QP of the SCP is infeasible, 
 one workgroup per scenario or, for large single scenarios, on the whole chip (scp_assign_goals_wide; include/scp_hip.h
 states the rule, both forms write the same bytes); there is no CPU path: without a GPU these functions raise
 ``_hip.HipError`` like ``SCP``.
+
+Straight-line distance does not see walls.  assign_goals_costs runs the same auction on a matrix of the caller's own costs
+(scp_assign_costs), and path_costs builds such a matrix from the hop counts of the lattice search (scp_lattice_distances):
+SCP.assign_goals(cost="path") joins the two.
 """
 import numpy as np
 
@@ -71,10 +75,93 @@ def assign_goals(init, goal, device=0, min_sep=0.0, max_rounds_per_phase=0, meth
     return goal_of[0].cpu().numpy().astype(np.int64), one
 
 
+HOPS_UNREACHED = 0xFFFF  # scp_lattice_distances: no path between the two nodes, or a point without a node
+MAX_COST = 2 ** 31 - 1   # SCP_ASSIGN_MAX_COST
+MAX_TIE_BITS = 12
+
+
+def path_costs(hops, d2, power=2):
+    """Costs for assign_goals_costs from the hop counts of the lattice search: hops decide, the straight-line distance only
+    breaks ties among equal hops, and one unreachable pair costs more than any assignment without one.
+
+    hops: (N, N) whole numbers, hops[i][j] lattice moves from start i to goal j, HOPS_UNREACHED (0xFFFF, or -1 as the int16
+    view of it) where there is no path.  d2: (N, N) squared straight-line distances (>= 0).  power: 1 or 2 -- hops^2 prefers
+    even detours to one long one, as the squared distances of assign_goals do.  numpy arrays or torch tensors.
+      Hmax = the largest finite hop count;  b = the largest whole number in 0 .. 12 with N (Hmax^power + 1) 2^b <= 2^31 - 1;
+      finite pairs:      c = hops^power 2^b + floor(d2 / max d2 (2^b - 1))   (the second term 0 if max d2 == 0);
+      unreachable pairs: c = U = N (largest finite c) + 1   (<= 2^31 - 1 by the choice of b).
+    Raises ValueError if not even b = 0 fits.  Returns (cost (N, N) int64 ndarray, {"tie_bits": b, "unreachable_cost": U,
+    "max_hops": Hmax})."""
+    to_numpy = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    hops, d2 = to_numpy(hops), np.asarray(to_numpy(d2), dtype=np.float64)
+    if hops.dtype.kind not in "iu":
+        raise ValueError(f"hops of dtype {hops.dtype}: need whole numbers")
+    hops = hops.astype(np.int64) & 0xFFFF if hops.dtype.itemsize == 2 else hops.astype(np.int64)
+    if hops.ndim != 2 or hops.shape[0] != hops.shape[1] or d2.shape != hops.shape:
+        raise ValueError(f"hops {hops.shape} and d2 {d2.shape} must both be (N, N)")
+    if isinstance(power, bool) or power not in (1, 2):
+        raise ValueError(f"power={power!r}: 1 or 2")
+    if ((hops < 0) | (hops > HOPS_UNREACHED)).any() or not (d2 >= 0).all():
+        raise ValueError("hops must lie in [0, 0xFFFF] and d2 must be >= 0")
+    N = hops.shape[0]
+    finite = hops != HOPS_UNREACHED
+    Hmax = int(hops[finite].max()) if finite.any() else 0
+    fits = [b for b in range(MAX_TIE_BITS + 1) if N * (Hmax ** power + 1) * 2 ** b <= MAX_COST]
+    if not fits:
+        raise ValueError(f"path costs: {N} vehicles and paths of up to {Hmax} hops do not fit 31 bits with power={power} "
+                         f"(N (Hmax^power + 1) = {N * (Hmax ** power + 1)}): use power=1 or a larger stride")
+    b = fits[-1]
+    top = float(d2.max()) if d2.size else 0.0
+    tie = np.floor(d2 / top * float(2 ** b - 1)).astype(np.int64) if top > 0.0 else np.zeros(hops.shape, dtype=np.int64)
+    cost = np.where(finite, hops, 0) ** power * 2 ** b + tie
+    U = N * (int(cost[finite].max()) if finite.any() else 0) + 1
+    cost = np.where(finite, cost, U)
+    return cost, {"tie_bits": b, "unreachable_cost": U, "max_hops": Hmax}
+
+
+def assign_goals_costs(cost, device=0, max_rounds_per_phase=0):
+    """The assignment that minimises sum_i cost[i][goal_of[i]] for the caller's own costs (scp_assign_costs: the auction of
+    assign_goals on a matrix, exact).  cost: (N, N) or (B, N, N) whole numbers in [0, 2^31 - 1], N <= 4096; cost[i][j] is what
+    vehicle i pays for goal j.
+
+    Returns (goal_of, info).  (N, N): goal_of a numpy int array of length N and info a dict of scalars -- ``cost_q`` /
+    ``cost_q_identity`` (the sum with the assignment / with the given pairing), ``quantum`` (1.0), ``rounds``, ``bids``,
+    ``phases``, ``status`` (0 ok, 1: the round limit was hit and goal_of is the identity), ``assign_ms`` (device
+    milliseconds).  (B, N, N): goal_of a (B, N) int32 device tensor and arrays of length B (assign_ms one number)."""
+    ctx = _context(device)
+    single = getattr(cost, "ndim", None) == 2 or (not hasattr(cost, "ndim") and np.ndim(cost) == 2)
+    goal_of, st, _ = ctx.assign_costs(cost, max_rounds_per_phase=max_rounds_per_phase)
+    ms = ctx.last_pair_ms()
+    if single:
+        info = {k: st[k][0].item() for k in _ASSIGN_KEYS}
+        info["assign_ms"] = ms
+        return goal_of[0].cpu().numpy().astype(np.int64), info
+    info = {k: st[k].copy() for k in _ASSIGN_KEYS}
+    info["assign_ms"] = ms
+    return goal_of, info
+
+
+def hop_totals(hops, goal_of=None):
+    """{"sum", "max", "n_unreachable"} of hops[i][goal_of[i]] (goal_of None: the identity); sum and max over the reachable
+    pairs"""
+    hops = np.asarray(hops)
+    h = hops[np.arange(hops.shape[0]), np.arange(hops.shape[0]) if goal_of is None else np.asarray(goal_of)].astype(np.int64)
+    ok = h != HOPS_UNREACHED
+    return {"sum": int(h[ok].sum()), "max": int(h[ok].max()) if ok.any() else 0, "n_unreachable": int((~ok).sum())}
+
+
 def describe(info):
-    """one line for the CLIs: cost (m^2), straight-line closest approach and opposed pairs, before -> after"""
+    """one line for the CLIs: cost (m^2), straight-line closest approach and opposed pairs, before -> after; with path costs
+    the hop totals before -> after come first"""
     q, lb, la = info["quantum"], info["line_before"], info["line_after"]
     note = "" if info["status"] == 0 else " [round limit: pairing kept]"
+    if "hops_assigned" in info:
+        hi, ha = info["hops_identity"], info["hops_assigned"]
+        return (f"Goal assignment by path length: {hi['sum']} -> {ha['sum']} lattice moves in all (longest {hi['max']} -> "
+                f"{ha['max']}), pairs without a path {info['n_unreachable_identity']} -> {info['n_unreachable_assigned']}, "
+                f"straight-line minimum approach {lb['min_approach']:.4f} -> {la['min_approach']:.4f} m, opposed pairs "
+                f"{lb['n_opposed']} -> {la['n_opposed']} ({info['phases']} phases, {info['rounds']} rounds, "
+                f"{info['distances_ms'] + info['assign_ms']:.3f} ms){note}")
     return (f"Goal assignment: cost {info['cost_q_identity'] * q:.3f} -> {info['cost_q'] * q:.3f} m^2, straight-line minimum "
             f"approach {lb['min_approach']:.4f} -> {la['min_approach']:.4f} m, opposed pairs {lb['n_opposed']} -> "
             f"{la['n_opposed']} ({info['phases']} phases, {info['rounds']} rounds){note}")

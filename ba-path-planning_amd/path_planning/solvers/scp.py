@@ -376,12 +376,39 @@ class SCP:
     def _search_reference(self, who, stride, clearance, max_path, want_path):
         """the checks and the two calls of find_reference -> {"ref", "path", "rec" (device tensors), "p0", "pf", "max_path",
         "info": what find_reference reports}"""
+        stride, clearance, lattice, edges, edges_ms = self._lattice_edges(who, stride, clearance)
+        N, K, D, c = self.N, self.K, self.D, self._ctx
+        grid = self._obstacles["grid"]
+        nodes = lattice[0] * lattice[1] * lattice[2]
+        if max_path is None:
+            max_path = min(nodes, 8 * K)
+        if isinstance(max_path, bool) or not isinstance(max_path, (int, np.integer)) or not 1 <= max_path <= nodes:
+            raise ValueError(f"max_path={max_path!r}: a whole number of nodes in [1, {nodes}]")
+        p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
+        ref = c.tensor(straight_reference(p0, pf, K))
+        d_p0, d_pf = c.tensor(p0), c.tensor(pf)
+        path, dev_rec, _, n_failed = c.reference_paths(N, K, D, grid, stride, edges, d_p0, d_pf, int(max_path), ref,
+                                                       want_path=want_path)
+        search_ms = c.last_pair_ms()
+        rec = dev_rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
+        found = rec["status"] == 0
+        E = rec["n_nodes"].astype(np.int64) + 1
+        info = {"status": rec["status"].copy(), "n_nodes": rec["n_nodes"].copy(), "n_failed": int(n_failed.item()),
+                "stride": stride, "clearance": clearance, "lattice": lattice[:D],
+                "max_edges": int(E[found].max()) if found.any() else 0,
+                "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
+                "edges_ms": edges_ms, "search_ms": search_ms}
+        return {"ref": ref, "path": path, "rec": dev_rec, "p0": d_p0, "pf": d_pf, "max_path": int(max_path), "info": info}
+
+    def _lattice_edges(self, who, stride, clearance):
+        """the checks of a call on the search lattice and its edge masks, made once per (stride, clearance) and map ->
+        (stride, clearance, lattice (L_x, L_y, L_z), edges (device tensor), edges_ms: 0 when the masks were cached)"""
         self._one_rank(who)
         if self._obstacles is None:
             raise ValueError(f"{who} needs set_obstacles first")
         if self.initial_positions is None or self.final_positions is None:
             raise ValueError(f"{who} needs both set_initial_states and set_final_states first")
-        N, K, D, c = self.N, self.K, self.D, self._ctx
+        K, D, c = self.K, self.D, self._ctx
         grid = self._obstacles["grid"]
         dims = [int(grid.dims[d]) for d in range(D)]
         if stride is None:
@@ -397,30 +424,12 @@ class SCP:
         if nodes < 1 or nodes > _hip.LATTICE_MAX_NODES:
             raise ValueError(f"stride={stride}: a lattice of {lattice} nodes on a grid of {tuple(dims)} cells; supported are 1 .. "
                              f"{_hip.LATTICE_MAX_NODES} nodes")
-        if max_path is None:
-            max_path = min(nodes, 8 * K)
-        if isinstance(max_path, bool) or not isinstance(max_path, (int, np.integer)) or not 1 <= max_path <= nodes:
-            raise ValueError(f"max_path={max_path!r}: a whole number of nodes in [1, {nodes}]")
         cache = self._obstacles.setdefault("edges", {})
         edges_ms = 0.0
         if (stride, clearance) not in cache:
             cache[stride, clearance] = c.lattice_edges(D, grid, self._obstacles["sat"], stride, clearance)
             edges_ms = c.last_pair_ms()
-        p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
-        ref = c.tensor(straight_reference(p0, pf, K))
-        d_p0, d_pf = c.tensor(p0), c.tensor(pf)
-        path, dev_rec, _, n_failed = c.reference_paths(N, K, D, grid, stride, cache[stride, clearance], d_p0, d_pf,
-                                                       int(max_path), ref, want_path=want_path)
-        search_ms = c.last_pair_ms()
-        rec = dev_rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
-        found = rec["status"] == 0
-        E = rec["n_nodes"].astype(np.int64) + 1
-        info = {"status": rec["status"].copy(), "n_nodes": rec["n_nodes"].copy(), "n_failed": int(n_failed.item()),
-                "stride": stride, "clearance": clearance, "lattice": lattice[:D],
-                "max_edges": int(E[found].max()) if found.any() else 0,
-                "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
-                "edges_ms": edges_ms, "search_ms": search_ms}
-        return {"ref": ref, "path": path, "rec": dev_rec, "p0": d_p0, "pf": d_pf, "max_path": int(max_path), "info": info}
+        return stride, clearance, lattice, cache[stride, clearance], edges_ms
 
     @staticmethod
     def _require_paths(info, allow_unreachable):
@@ -518,7 +527,8 @@ class SCP:
         self.goal_assignment = None
         self.assignment_info = None
 
-    def assign_goals(self, min_sep=None, method="auto"):
+    def assign_goals(self, min_sep=None, method="auto", cost="line", stride=None, clearance=0, power=2,
+                     allow_unreachable=False):
         """Interchangeable vehicles: re-pair vehicles and goals so that the sum of squared start-goal distances is minimal
         (scp_assign_goals).  Call it after set_initial_states and set_final_states; the final positions AND velocities are
         permuted, so vehicle i then flies to the goal given as number ``goal_assignment[i]``.  ``goal_assignment`` always
@@ -526,11 +536,30 @@ class SCP:
         ``assignment_info`` holds the auction's statistics and the straight-line checks before / after (min_sep, default the
         minimum distance, is their "close" threshold).  ``method``: "single" (scp_assign_goals, up to 4096 vehicles), "wide"
         (scp_assign_goals_wide, up to 65536) or "auto" (wide from 1024 vehicles, where it is faster); the result does not
-        depend on it.  Returns
-        goal_assignment."""
-        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS, assign_method
+        depend on it.
 
-        assign = assign_method(self._ctx, method, self.N)
+        ``cost``: "line" pairs by squared straight-line distance, which does not see walls; "path" (after set_obstacles) by
+        the number of moves of find_reference's lattice search between every start and every goal (scp_lattice_distances on
+        the lattice of ``stride`` / ``clearance``, the edge masks shared with find_reference), raised to ``power`` (1 or 2),
+        the straight-line distance only breaking ties (scenarios.assignment.path_costs), through the same auction on that
+        matrix (scp_assign_costs; up to 4096 vehicles, ``method`` is not used).  ``assignment_info`` then also holds
+        ``hops_identity`` / ``hops_assigned`` ({"sum", "max"} over the pairs that have a path), ``n_unreachable_identity`` /
+        ``n_unreachable_assigned``, ``tie_bits``, ``unreachable_cost``, ``max_hops``, ``stride``, ``clearance``, ``lattice``
+        and the device milliseconds ``edges_ms``, ``distances_ms``, ``assign_ms``.  If even the best pairing leaves a vehicle
+        without a path, no pairing connects every vehicle: ValueError naming one, unless ``allow_unreachable``.
+
+        Returns goal_assignment."""
+        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS, assign_method, hop_totals, path_costs
+
+        if cost not in ("line", "path"):
+            raise ValueError(f"cost={cost!r}: \"line\" or \"path\"")
+        if cost == "path":
+            if self.N > _hip.ASSIGN_COSTS_MAX_N:
+                raise ValueError(f"assign_goals(cost=\"path\") supports up to {_hip.ASSIGN_COSTS_MAX_N} vehicles (one N x N cost "
+                                 f"matrix in one workgroup), not {self.N}; cost=\"line\" goes up to 65536")
+            stride, clearance, lattice, edges, edges_ms = self._lattice_edges("assign_goals(cost=\"path\")", stride, clearance)
+        else:
+            assign = assign_method(self._ctx, method, self.N)
         if self.initial_positions is None or self.final_positions is None:
             raise ValueError("assign_goals needs both set_initial_states and set_final_states first")
         if self._final_given is None:
@@ -538,13 +567,34 @@ class SCP:
         pf, vf = (a.reshape(self.N, self.D) for a in self._final_given)
         start = self.initial_positions.reshape(1, self.N, self.D)
         sep = float(self.R if min_sep is None else min_sep)
-        goal_of, st, _ = assign(start, pf[None])
+        if cost == "path":
+            c, s0 = self._ctx, start[0]
+            hops, _, _, _ = c.lattice_distances(self.D, self._obstacles["grid"], stride, edges, c.tensor(s0), c.tensor(pf))
+            distances_ms = c.last_pair_ms()
+            hops = hops.cpu().numpy().view(np.uint16)
+            diff = s0[:, None, :] - pf[None, :, :]
+            costs, how = path_costs(hops, (diff * diff).sum(-1), power)
+            goal_of, st, _ = c.assign_costs(costs[None])
+            assign_ms = c.last_pair_ms()
+        else:
+            goal_of, st, _ = assign(start, pf[None])
         before = self._ctx.straight_line_check(start, pf[None], None, sep)
         after = self._ctx.straight_line_check(start, pf[None], goal_of, sep)
         info = {k: st[k][0].item() for k in _ASSIGN_KEYS}
         info["line_before"] = {k: before[k][0].item() for k in _LINE_KEYS}
         info["line_after"] = {k: after[k][0].item() for k in _LINE_KEYS}
         perm = goal_of[0].cpu().numpy().astype(np.int64)
+        if cost == "path":
+            hi, ha = hop_totals(hops), hop_totals(hops, perm)
+            info.update(how, hops_identity={k: hi[k] for k in ("sum", "max")}, hops_assigned={k: ha[k] for k in ("sum", "max")},
+                        n_unreachable_identity=hi["n_unreachable"], n_unreachable_assigned=ha["n_unreachable"], stride=stride,
+                        clearance=clearance, lattice=lattice[:self.D], edges_ms=edges_ms, distances_ms=distances_ms,
+                        assign_ms=assign_ms)
+            if ha["n_unreachable"] and not allow_unreachable:
+                i = int(np.flatnonzero(hops[np.arange(self.N), perm] == 0xFFFF)[0])
+                raise ValueError(f"assign_goals(cost=\"path\"): no pairing connects every vehicle -- in the best one "
+                                 f"{ha['n_unreachable']} vehicles have no path, vehicle {i} among them (stride {stride}, "
+                                 f"clearance {clearance}, lattice {lattice[:self.D]}); allow_unreachable=True pairs the rest")
         self.final_positions = pf[perm].flatten()
         self.final_velocities = vf[perm].flatten()
         self._dev.pop("p0", None)

@@ -764,6 +764,24 @@ int scp_assign_goals_wide(scp_ctx* ctx, int B, int N, int D, const double* start
                           const double* goal /* [B][N][D] */, int32_t* goal_of /* [B][N] */, int64_t* prices /* [B][N] or NULL */,
                           int64_t max_rounds_per_phase, scp_assign_stats* stats /* [B] */);
 
+/* The same auction on costs the caller states (a further additive part of ABI version 7: this one function and one
+ * constant).  The rule of scp_assign_goals word for word -- phases, eps scaling, bids, tie rules, the guard and its identity
+ * fallback with status 1, N = 1 -- with
+ *   c_ij = cost[b][i][j]  (person i, goal j; 0 <= c_ij <= SCP_ASSIGN_MAX_COST),   top = max_ij c_ij of the scenario,
+ *   eps_0 = max(1, ((N + 1) top) / 2),   stats.quantum = 1.0,   cost_q / cost_q_identity = the sums of the entries.
+ * goal_of is EXACTLY optimal for the matrix (sum_i cost[i][goal_of[i]] is minimal); tests/assign_paths_ref.py restates the
+ * rule, and on the matrix c and the top of scp_assign_goals's quantisation it gives that call's bytes.  The price bound above
+ * (C = (N + 1) 2^31) holds as written.  A negative entry raises the mapped host word like unusable coordinates: the call
+ * returns SCP_ERR_INVALID after the launch, outputs then undefined.  One workgroup per scenario -- the kernel of
+ * scp_assign_goals with its costs loaded from row i of the matrix (a bidding wave reads consecutive words) instead of
+ * recomputed from coordinates; the matrix is read once more at the start for top.  Supported: B >= 1, 1 <= N <= 4096 (there is
+ * no wide form: an N x N matrix for 65536 vehicles is out of scope).  cost [B][N][N], goal_of [B][N], prices [B][N] (or NULL)
+ * and stats [B] are DEVICE pointers.  Enqueued on the ctx's stream; synchronises; timing through scp_ctx_last_pair_ms. */
+#define SCP_ASSIGN_MAX_COST 2147483647
+int scp_assign_costs(scp_ctx* ctx, int B, int N, const int32_t* cost /* DEVICE [B][N][N], cost[b][i][j] */,
+                     int32_t* goal_of /* [B][N] */, int64_t* prices /* [B][N] or NULL */, int64_t max_rounds_per_phase,
+                     scp_assign_stats* stats /* [B] */);
+
 /* Straight-line check: one pass per scenario over the pairs i < j of the motions start_i -> goal[goal_of[i]] (goal_of NULL:
  * the identity).  d^2 is the squared closest approach of the "Block draw" rule above (the generator's device function, so a
  * grid-swap-device scenario's min_approach is scp_gen_stats.min_approach bit for bit), with r0 = s_i - s_j and
@@ -949,6 +967,29 @@ int scp_reference_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_g
                         int32_t* path /* DEVICE [N][max_path] or NULL; entries beyond n_nodes are -1 */,
                         scp_path_info* info /* DEVICE [N] */, uint16_t* dist_out /* DEVICE [N][nodes] or NULL */,
                         uint64_t* n_failed /* DEVICE */);
+
+/* Lattice distances (a further additive part of ABI version 7: this one function): the hop counts of the search between
+ * EVERY source and EVERY destination, for costs that see the obstacles (scp_assign_costs).  The lattice, the node of a point
+ * and "passable" are those of scp_lattice_edges / scp_reference_paths; edges are the masks scp_lattice_edges made with the
+ * same stride.  Integers only; tests/assign_paths_ref.py restates the rule.
+ *   Node of a point: its node id, or -1 where scp_reference_paths would give status 1 or 2: a coordinate (d < D) is not
+ *     inside the grid, some X_d >= L_d, or the node is not passable.  src_node[a] / dst_node[b] report it.
+ *   dist of source a: the breadth-first distance from src_node[a] over the set edge bits at unit cost (a diagonal move counts
+ *     1), uint16, 0xFFFF = unreached.  The field is COMPLETE: the search ends when a level changes nothing.  With
+ *     src_node[a] = -1 every entry reads 0xFFFF.
+ *   hops[a][b] = dist[dst_node[b]]; 0xFFFF if either node is -1 or the destination is unreached; 0 on the same node.  Edge
+ *     masks are symmetric, so the search from the start gives the distances of a search from the goal.
+ *   dist_out (for tests): the complete field of every source.
+ * ONE workgroup per source and no workgroup waits for another; dist lives in the workgroup's LDS (the layout of
+ * scp_reference_paths: 64 KiB plus a few control words, static, two workgroups per CU); the level sweep is that call's, one
+ * barrier per level, at most `nodes` levels; every workgroup looks the destinations' nodes up for itself.  Supported: n_src,
+ * n_dst >= 1, nodes <= SCP_LATTICE_MAX_NODES.  Argument checks, enqueue on the ctx's stream, no host read, timing through
+ * scp_ctx_last_pair_ms as scp_reference_paths. */
+int scp_lattice_distances(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+                          int n_src, const double* src /* DEVICE [n_src][D] */, int n_dst,
+                          const double* dst /* DEVICE [n_dst][D] */, uint16_t* hops /* DEVICE [n_src][n_dst] */,
+                          int32_t* src_node /* DEVICE [n_src] */, int32_t* dst_node /* DEVICE [n_dst] */,
+                          uint16_t* dist_out /* DEVICE [n_src][nodes] or NULL */);
 
 /* ---- static obstacles: shortened reference paths ------------------------------------------------------------------------------
  * A further additive part of ABI version 7: one struct and one function; nothing above changes.  The path of
