@@ -217,19 +217,8 @@ __global__ __launch_bounds__(256) void check_corridor_kernel(int N, int K, doubl
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const double p = pos[s * D + d], v = vel[s * D + d], a = acc[s * D + d];
-      double lo_v = p + (0.0 * v + ((0.5 * 0.0) * 0.0) * a);
-      double hi_v = lo_v;
-      const double end = p + (h * v + ((0.5 * h) * h) * a);
-      lo_v = corridor_min(lo_v, end);
-      hi_v = corridor_max(hi_v, end);
-      if (a != 0.0) {
-        const double ts = -v / a;
-        if (ts > 0.0 && ts < h) {
-          const double mid = p + (ts * v + ((0.5 * ts) * ts) * a);
-          lo_v = corridor_min(lo_v, mid);
-          hi_v = corridor_max(hi_v, mid);
-        }
-      }
+      double lo_v, hi_v;
+      corridor_extremes(p, v, a, 0.0, h, lo_v, hi_v);
       double L, H;
       corridor_metres(g, c, d, L, H);
       excess = corridor_max(excess, corridor_max(L - lo_v, hi_v - H));

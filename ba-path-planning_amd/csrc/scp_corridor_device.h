@@ -1,5 +1,5 @@
-// Arithmetic shared by the kernels of scp_corridor.hip and scp_reference.hip (the rules are stated in include/scp_hip.h,
-// "static obstacles").
+// Arithmetic shared by the kernels of scp_corridor.hip, scp_reference.hip and scp_obstacle_dist.hip (the rules are stated in
+// include/scp_hip.h, "static obstacles").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,3 +74,22 @@ __device__ inline void corridor_metres(const CorridorGrid& g, const CorridorCell
 // max / min that take the first operand unless the second is strictly greater / smaller
 __device__ inline double corridor_max(double a, double b) { return b > a ? b : a; }
 __device__ inline double corridor_min(double a, double b) { return b < a ? b : a; }
+
+// the extremes of one coordinate p + t v + t^2/2 a over [t0, t1]: the candidates are t0, t1 and t* = -v / a if a != 0 and
+// t0 < t* < t1; the value at t is p + (t * v + ((0.5 * t) * t) * a); lo_v / hi_v by corridor_min / corridor_max in that order
+__device__ inline void corridor_extremes(double p, double v, double a, double t0, double t1, double& lo_v, double& hi_v) {
+#pragma clang fp contract(off)
+  lo_v = p + (t0 * v + ((0.5 * t0) * t0) * a);
+  hi_v = lo_v;
+  const double end = p + (t1 * v + ((0.5 * t1) * t1) * a);
+  lo_v = corridor_min(lo_v, end);
+  hi_v = corridor_max(hi_v, end);
+  if (a != 0.0) {
+    const double ts = -v / a;
+    if (ts > t0 && ts < t1) {
+      const double mid = p + (ts * v + ((0.5 * ts) * ts) * a);
+      lo_v = corridor_min(lo_v, mid);
+      hi_v = corridor_max(hi_v, mid);
+    }
+  }
+}

@@ -249,6 +249,19 @@ class ShortenInfo(C.Structure):
 
 SHORTEN_INFO_DTYPE = np.dtype(ShortenInfo)
 
+
+class ObstacleStats(C.Structure):
+    """scp_obstacle_clearance; one per vehicle, a DEVICE array"""
+    _fields_ = [("min_sq", C.c_uint32), ("segment", C.c_uint32), ("piece", C.c_uint32), ("cell", C.c_int32),
+                ("n_touch", C.c_uint32), ("n_off", C.c_uint32), ("n_wide", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+OBSTACLE_STATS_DTYPE = np.dtype(ObstacleStats)
+OBSTACLE_MAX_PIECES = 16      # SCP_OBSTACLE_MAX_PIECES: pieces per segment of scp_obstacle_clearance
+OBSTACLE_MAX_RANGE = 4096     # SCP_OBSTACLE_MAX_RANGE: cells of a piece's range beyond which it is not judged
+OBSTACLE_MAX_DIM = 32768      # scp_obstacle_distance: the largest grid dimension
+DIST_NONE = 2**32 - 1         # UINT32_MAX: a field without an occupied cell, a record without a judged piece
+
 # Every struct of include/scp_hip.h -> its mirror above, the only Python statement of the layout (each *_DTYPE derives from it)
 STRUCTS = {
     "scp_pair_stats": PairStats, "scp_qp_settings": QpSettings, "scp_solve_options": SolveOptions, "scp_qp_record": QpRecord,
@@ -256,7 +269,7 @@ STRUCTS = {
     "scp_separation_stats": SeparationStats, "scp_conflict": Conflict, "scp_hold": Hold, "scp_clearance": Clearance,
     "scp_delay_margin": DelayMargin, "scp_start_schedule_stats": StartScheduleStats, "scp_assign_stats": AssignStats,
     "scp_line_stats": LineStats, "scp_occupancy_grid": OccupancyGrid, "scp_corridor_stats": CorridorStats,
-    "scp_path_info": PathInfo, "scp_shorten_info": ShortenInfo,
+    "scp_path_info": PathInfo, "scp_shorten_info": ShortenInfo, "scp_obstacle_stats": ObstacleStats,
 }
 
 
@@ -361,6 +374,8 @@ PROTOTYPES = {
     "scp_reference_paths": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "scp_lattice_distances": (i32, [vp, i32, pg, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "scp_shorten_paths": (i32, [vp, i32, i32, i32, pg, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_obstacle_distance": (i32, [vp, i32, pg, vp, i32, vp]),
+    "scp_obstacle_clearance": (i32, [vp, i32, i32, i32, f64, pg, vp, vp, i32, vp, vp, vp, vp, vp]),
     "scp_gemm_f64": (i32, [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]),
     "scp_qp_peek": (i32, [vp, cstr, vp, i64, P(i64)]),
     "scp_qp_debug_set": (i32, [vp, cstr, i32]),
@@ -954,6 +969,31 @@ class Context:
                                               p0.data_ptr(), pf.data_ptr(), int(max_path), _ptr(path), _ptr(info),
                                               ref.data_ptr(), _ptr(kept), out.data_ptr()))
         return kept, out
+
+    # ---- static obstacles: distance field and clearance -------------------------------------------------------------------
+    def obstacle_distance(self, D, grid: OccupancyGrid, occ, gap=1):
+        """scp_obstacle_distance: occ a uint8 device tensor [nz][ny][nx] (as occupancy_prepare returns it) -> the squared
+        distance field in cells, an int32 device tensor [nz][ny][nx] holding the uint32 words (DIST_NONE everywhere on an
+        empty map).  No host read."""
+        torch = _torch()
+        shape = (int(grid.dims[2]), int(grid.dims[1]), int(grid.dims[0]))
+        if tuple(occ.shape) != shape:
+            raise ValueError(f"occupancy grid of shape {tuple(occ.shape)}, the geometry says [nz][ny][nx] = {shape}")
+        field = torch.empty(shape, dtype=torch.int32, device=self.tdev)
+        self.check(self.lib.scp_obstacle_distance(self.h, int(D), C.byref(grid), occ.data_ptr(), int(gap), field.data_ptr()))
+        return field
+
+    def obstacle_clearance(self, N, K, D, h, grid: OccupancyGrid, sat, field, pieces, pos, vel, acc):
+        """scp_obstacle_clearance: field as obstacle_distance made it with gap = 1, sat of the same grid, pos / vel / acc
+        (N, K, D) device tensors.  Returns (one record per vehicle as a numpy structured array (OBSTACLE_STATS_DTYPE),
+        step_min as a numpy uint64 array [K]) -- synchronises."""
+        torch = _torch()
+        out = torch.empty(max(N, 1) * OBSTACLE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        step_min = torch.empty(max(K, 1), dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_obstacle_clearance(self.h, N, K, D, float(h), C.byref(grid), sat.data_ptr(), field.data_ptr(),
+                                                   int(pieces), pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), out.data_ptr(),
+                                                   step_min.data_ptr()))
+        return out.cpu().numpy().view(OBSTACLE_STATS_DTYPE)[:N].copy(), step_min.cpu().numpy().view(np.uint64)[:K].copy()
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

@@ -110,6 +110,12 @@ def build_parser():
     p.add_argument("--corridor-shorten", action="store_true",
                    help="with --corridor-search: every path is cut down to the lattice nodes it cannot skip and its reference "
                         "points are spaced evenly by length (one GPU wave per vehicle)")
+    p.add_argument("--obstacle-clearance", type=int, nargs="?", const=4, default=None, metavar="PIECES",
+                   help="with --obstacle-discs: after the solve (and --repair-conflicts) the plan is judged against the map "
+                        "itself, not against its corridor boxes: every segment is cut into PIECES pieces (1 .. 16, default 4) "
+                        "and one line gives the fleet's guaranteed clearance from the occupied cells, the vehicle, segment and "
+                        "time where it is attained, and how many pieces touch an occupied cell, leave the map or are too "
+                        "wide to judge")
     p.add_argument("--no-plots", action="store_true")
     p.add_argument("--save-prefix", default=None, help="write <prefix>_2d.pdf and <prefix>_snapshots.pdf")
     return p
@@ -131,10 +137,12 @@ def obstacle_discs(parser, args):
         if by_path:
             parser.error("--assign-cost path needs --obstacle-discs")
         for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow),
-                            ("--corridor-search", args.corridor_search or None)):
+                            ("--corridor-search", args.corridor_search or None), ("--obstacle-clearance", args.obstacle_clearance)):
             if value is not None:
                 parser.error(f"{flag} needs --obstacle-discs")
         return None
+    if args.obstacle_clearance is not None and not 1 <= args.obstacle_clearance <= 16:
+        parser.error(f"--obstacle-clearance {args.obstacle_clearance}: 1 .. 16 pieces per segment")
     discs = []
     for text in args.obstacle_discs:
         try:
@@ -153,6 +161,21 @@ def shortened_summary(fr):
     return (f"; shortened to {int(fr['n_kept'][found].sum())} of {int(fr['n_nodes'][found].sum())} nodes, total length "
             f"{float(fr['length'][found].sum()):.2f} m (lattice paths {float(fr['length_before'][found].sum()):.2f} m), "
             f"{fr['shorten_ms']:.3f} ms")
+
+
+def obstacle_clearance_summary(oc, time_step):
+    """the line of --obstacle-clearance from what SCP.obstacle_clearance returns"""
+    v = oc["worst_vehicle"]
+    ve = oc["vehicles"]
+    if np.isfinite(oc["clearance"]):
+        g = int(ve["segment"][v])
+        where = (f"at least {oc['clearance']:.4f} m from the occupied cells (vehicle {v}, segment {g}, t = {g * time_step:.2f} .. "
+                 f"{(g + 1) * time_step:.2f} s)")
+    else:
+        where = "no piece judged against an occupied cell"
+    return (f"Obstacle clearance: {where}; {oc['n_touch']} pieces touch an occupied cell, {oc['n_off']} off the map, "
+            f"{oc['n_wide']} too wide to judge; " + ("clear" if oc["clear"] else "NOT clear")
+            + f" (field {oc['field_ms']:.3f} ms, pass {oc['check_ms']:.3f} ms)")
 
 
 def main(argv=None):
@@ -247,6 +270,8 @@ def main(argv=None):
             print(f"Conflict repair: {counts} conflicting segments in {rep['passes']} passes ({rep['holds']} holds, stopped by "
                   f"{rep['stopped_by']}), cost ratio {rep['cost_ratio']:.4f}, {rep['time_sec']:.3f} s"
                   + ("" if rep["repaired"] else "; NOT repaired"))
+        if args.obstacle_clearance is not None:
+            print(obstacle_clearance_summary(solver.obstacle_clearance(pieces=args.obstacle_clearance), time_step))
         if args.stagger_starts is not None:
             st = solver.stagger_starts(args.stagger_starts, **stagger_search)
             print(f"Staggered starts: {st['n_delayed']} of {n_vehicles} vehicles delayed by up to {st['max_delay']} steps "

@@ -236,7 +236,8 @@ class SCP:
         self._holds = None  # (device table, count) of repair_conflicts while one of its passes runs
         self.staggered = None  # the fleet of the latest stagger_starts (its trajectories stay as they are)
         self._obstacles = None  # set_obstacles: {"grid", "occ", "sat"} (device), the occupancy grid and its summed table;
-                                # find_reference adds "edges": {(stride, clearance): the lattice's edge masks}
+                                # find_reference adds "edges": {(stride, clearance): the lattice's edge masks},
+                                # obstacle_distance_field / obstacle_clearance "field": {gap: (device field, its ms)}
         self._corridor = None   # set_corridors: {"cells", "grid"}: the boxes of the segments, what validate_solution checks
         self._boxes = None      # (lo, hi) device tensors (N, K, D) by state: set_corridors / set_position_boxes
         self._dev = {}
@@ -1225,6 +1226,78 @@ class SCP:
                 "n_outside": n_out, "n_blocked": n_blk, "max_excess": float(st["max_excess"].max()),
                 "worst_vehicle": int(np.argmax(st["max_excess"])), "inside": n_out == 0 and n_blk == 0,
                 "check_ms": c.last_pair_ms()}
+
+    def _obstacle_field(self, who, gap):
+        """the device field of the current obstacles at `gap` (made once per set_obstacles), and the device time it took"""
+        self._one_rank(who)
+        if self._obstacles is None:
+            raise ValueError(f"{who} needs set_obstacles first")
+        if isinstance(gap, bool) or gap not in (0, 1):
+            raise ValueError(f"gap={gap!r}: 0 (between cells) or 1 (between the closed cubes of the cells)")
+        cache = self._obstacles.setdefault("field", {})
+        if gap not in cache:
+            field = self._ctx.obstacle_distance(self.D, self._obstacles["grid"], self._obstacles["occ"], int(gap))
+            cache[gap] = (field, self._ctx.last_pair_ms())
+        return cache[gap]
+
+    def obstacle_distance_field(self, gap=1):
+        """The exact squared distance field of the obstacles (scp_obstacle_distance), in cells: a numpy uint32 array
+        [nz][ny][nx]; entry c = min over the occupied cells o of sum_d max(|c_d - o_d| - gap, 0)^2, 2^32 - 1 everywhere on an
+        empty map.  ``gap=0``: the squared Euclidean distance transform between cells.  ``gap=1``: the squared distance between
+        the closed cubes of the cells, so every point of cell c keeps at least cell * sqrt(field[c]) from the occupied
+        cells -- what obstacle_clearance reduces, and the input for choosing a corridor clearance or for plots.  The device
+        field is computed once per set_obstacles and gap."""
+        field, _ = self._obstacle_field("obstacle_distance_field", gap)
+        return field.cpu().numpy().view(np.uint32)
+
+    def obstacle_clearance(self, pieces=4, dev=None):
+        """How close does every vehicle of the stored trajectories come to the obstacles, where and when?  Judges the plan
+        against the map itself (scp_obstacle_clearance), whatever made the plan: it needs set_obstacles and trajectories, no
+        corridors and no boxes.  Every segment is cut into ``pieces`` (1 .. 16) pieces; a piece's value is the minimum of the
+        gap-1 distance field over the exact range of cells it passes through, so the piece keeps at least that distance.
+        Returns ``vehicles``: a dictionary of length-N arrays ``clearance`` (metres, a guaranteed lower bound: cell *
+        sqrt(min_sq); 0: may touch; inf: nothing judged or an empty map), ``min_sq`` (cells squared; -1 where clearance is
+        inf), ``segment``, ``piece``, ``cell`` (the linear index (z ny + y) nx + x of the cell that attains it; -1: none),
+        ``n_touch`` (pieces whose range holds an occupied cell), ``n_off`` (pieces off the map, not judged) and ``n_wide``
+        (pieces whose range holds more than 4096 cells, not judged: use more pieces); ``steps``: length-K arrays
+        ``clearance`` (the fleet's clearance within every time step) and ``vehicle`` (who attains it, the lowest index on
+        ties; -1 where no piece of the step was judged); the totals ``clearance``, ``worst_vehicle``, ``n_touch``, ``n_off``,
+        ``n_wide``; ``clear`` = no piece touches and none is wide; ``field_ms`` and ``check_ms`` (device time of the field,
+        made once per set_obstacles, and of the pass)."""
+        self._one_rank("obstacle_clearance")
+        if self._obstacles is None:
+            raise ValueError("obstacle_clearance needs set_obstacles first")
+        if self.trajectories is None:
+            raise ValueError("Trajectories not generated yet")
+        if isinstance(pieces, bool) or not isinstance(pieces, (int, np.integer)) or not 1 <= pieces <= _hip.OBSTACLE_MAX_PIECES:
+            raise ValueError(f"pieces={pieces!r}: a whole number in [1, {_hip.OBSTACLE_MAX_PIECES}]")
+        c, ob = self._ctx, self._obstacles
+        field, field_ms = self._obstacle_field("obstacle_clearance", 1)
+        if dev is None:
+            dev = tuple(c.tensor(self.trajectories[k]) for k in ("positions", "velocities", "accelerations"))
+        st, step_min = c.obstacle_clearance(self.N, self.K, self.D, self.h, ob["grid"], ob["sat"], field, int(pieces), *dev)
+        check_ms = c.last_pair_ms()
+        cell = float(ob["grid"].cell)
+
+        def metres(sq):  # (sq as int64; DIST_NONE: inf)
+            none = sq == _hip.DIST_NONE
+            return np.where(none, np.inf, cell * np.sqrt(np.where(none, 0, sq).astype(np.float64)))
+
+        sq = st["min_sq"].astype(np.int64)
+        none = sq == _hip.DIST_NONE
+        vehicles = {"clearance": metres(sq), "min_sq": np.where(none, -1, sq),
+                    "segment": np.where(none, -1, st["segment"].astype(np.int64)),
+                    "piece": np.where(none, -1, st["piece"].astype(np.int64)), "cell": st["cell"].astype(np.int64),
+                    "n_touch": st["n_touch"].astype(np.int64), "n_off": st["n_off"].astype(np.int64),
+                    "n_wide": st["n_wide"].astype(np.int64)}
+        step_sq = (step_min >> np.uint64(32)).astype(np.int64)
+        judged = step_min != np.uint64(2**64 - 1)
+        steps = {"clearance": metres(step_sq),
+                 "vehicle": np.where(judged, (step_min & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)}
+        n_touch, n_off, n_wide = (int(vehicles[k].sum()) for k in ("n_touch", "n_off", "n_wide"))
+        return {"vehicles": vehicles, "steps": steps, "clearance": float(vehicles["clearance"].min()),
+                "worst_vehicle": int(np.argmin(vehicles["clearance"])), "n_touch": n_touch, "n_off": n_off, "n_wide": n_wide,
+                "clear": n_touch == 0 and n_wide == 0, "field_ms": field_ms, "check_ms": check_ms}
 
     def _delay_margins(self, dev, S):
         """The delay part of validate_solution: one device pass (scp_delay_margins) over this rank's vehicles of the device

@@ -1050,6 +1050,84 @@ int scp_shorten_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_gri
                       double* ref /* DEVICE [N][K+1][D], in/out */, int32_t* kept /* DEVICE [N][max_path] or NULL */,
                       scp_shorten_info* out /* DEVICE [N] */);
 
+/* ---- static obstacles: distance field and clearance ---------------------------------------------------------------------------
+ * A further additive part of ABI version 7: one struct and two functions; nothing above changes.  Everything above helps a
+ * plan avoid the map; these two judge a plan against it, whatever made the plan: how close does every vehicle come to the
+ * occupied cells, where and when -- the counterpart of scp_clearance_profile with the map in place of the other vehicles.
+ * Grid, cell lookup f_d, "inside", occ and sat are those of scp_occupancy_prepare / scp_corridor_boxes; the kinematics of a
+ * segment and the min / max rule are those of scp_check_corridor.  Integers everywhere except "pieces" and "cell range",
+ * whose doubles are evaluated with every operation rounded on its own (no contraction).  tests/obstacle_distance_ref.py
+ * restates every rule in numpy / plain Python.
+ *
+ * scp_obstacle_distance (once per map and gap; independent of the vehicles).  For every cell c = (c_x, c_y, c_z)
+ *     field[(c_z ny + c_y) nx + c_x] = min over the occupied cells o of  sum over q < D of max(|c_q - o_q| - gap, 0)^2,
+ *   in integers; a map without an occupied cell gives UINT32_MAX everywhere.  gap = 0 is the squared Euclidean distance
+ *   transform between cells (in cells).  gap = 1 is the squared distance, in cells, between the CLOSED cubes of c and o; it
+ *   equals the gap = 0 field of the map dilated by one cell per coordinate (a cell is occupied if a cell within one step per
+ *   coordinate is).  Guarantee of gap = 1: for any point x whose cell lookup gives c, the distance from x to the union of the
+ *   closed occupied cells is at least cell * sqrt(field[c]) (x lies in the closed cube of c up to the rounding of the lookup,
+ *   and the distance between two sets bounds the distance from a point of one to the other).
+ *   Supported: the grids scp_occupancy_prepare supports with every dims_d <= 32768, so that a coordinate contributes less than
+ *   2^30 and no sum wraps; gap 0 or 1; anything else returns SCP_ERR_INVALID with a message.  A row, column or plane without
+ *   an occupied cell is an ordinary case (its cells take their values from the other coordinates).
+ *   The transform is separable: a pass along x (one wave per row: two sweeps with a carry leave the squared gap distance to the
+ *   nearest occupied cell of the row, UINT32_MAX without one), then along y and, in 3-D, along z one lower-envelope pass
+ *   out[c] = min over n' of in[c with c_q = n'] + max(|c_q - n'| - gap, 0)^2, entries UINT32_MAX skipped: one thread per cell, x
+ *   fastest, which starts from its own value, looks delta = 1, 2, .. cells to both sides and stops as soon as max(delta - gap,
+ *   0)^2 reaches the best so far -- every loop is bounded by a grid dimension.  A pass reads one buffer and writes another; the
+ *   second buffer (4 bytes per cell) lives in the context's workspace.  No LDS, no barrier, no workgroup waits for another;
+ *   the result does not depend on the launch geometry.  Launches are enqueued on the ctx's stream, no host read, timing
+ *   through scp_ctx_last_pair_ms. */
+int scp_obstacle_distance(scp_ctx* ctx, int D, const scp_occupancy_grid* grid,
+                          const uint8_t* occ /* DEVICE [nz][ny][nx], nonzero = occupied */, int gap /* 0 or 1 */,
+                          uint32_t* field /* DEVICE [nz][ny][nx] */);
+
+/* scp_obstacle_clearance: the guaranteed clearance of every vehicle of a plan from the occupied cells.  `field` is the gap = 1
+ * field of the same grid, `sat` its summed table.
+ *   Pieces.  Segment g of vehicle i is cut into `pieces` = P pieces, 1 <= P <= SCP_OBSTACLE_MAX_PIECES; piece s = 0 .. P-1 runs
+ *     over [t_s, t_{s+1}] with t_s = h * ((double)s / (double)P).  Per coordinate d < D the candidates are t_s, t_{s+1} and
+ *     t* = -v / a if a != 0 and t_s < t* < t_{s+1}; the value at t is p + (t * v + ((0.5 * t) * t) * a); lo_v = the min, hi_v =
+ *     the max over the candidates in that order (the min / max rule above).
+ *   Cell range.  flo = f_d(lo_v), fhi = f_d(hi_v), as doubles.  The piece is OFF the map, and counts in n_off, if for some
+ *     d < D either value is not finite, fhi < 0 or flo >= dims_d.  Otherwise its range is [max(flo, 0), min(fhi, dims_d - 1)]
+ *     per coordinate, [0, 0] along z in 2-D.  A piece whose range holds more than SCP_OBSTACLE_MAX_RANGE cells is WIDE: it
+ *     counts in n_wide and is not judged (so no lane loops over the grid; a finer cut makes the pieces narrower).
+ *   Judging.  The value of a judged piece is the minimum of `field` over its range, attained at the lowest linear cell index
+ *     among ties.  The piece TOUCHES, and counts in n_touch, if its range holds an occupied cell (one summed-table query).
+ *   Per vehicle: the smallest value over its judged pieces, the (segment, piece) and the cell where it is attained; ties keep
+ *     the lowest (segment, piece), then the lowest cell.  A value of UINT32_MAX (an empty map) is never "attained": the record
+ *     of a vehicle without a judged piece, or on an empty map, reads min_sq = segment = piece = UINT32_MAX, cell = -1.
+ *   Per time step: step_min[g] = min over the vehicles i with a judged piece in segment g of
+ *     ((smallest value over the judged pieces of segment g of vehicle i) << 32) | i,
+ *     UINT64_MAX where no piece of the step was judged: a 64-bit unsigned atomic minimum, so ties go to the lowest vehicle and
+ *     the array does not depend on the order of the updates.  The call initialises the array itself.
+ *   Guarantee.  Every point of a judged piece lies, up to the rounding of the cell lookup, in a cell of its range (per
+ *     coordinate the piece stays between lo_v and hi_v, and the lookup is monotone), so by the guarantee of the gap = 1 field
+ *     the piece keeps at least cell * sqrt(value) from every occupied cell; the vehicle keeps cell * sqrt(min_sq) over all its
+ *     judged pieces.  The bound is a lower bound: 0 says "may touch", and it tightens with more pieces and finer cells.  A piece
+ *     that is off the map or wide carries no statement.
+ * One wave per vehicle: a lane owns the segments lane, lane + 64, .. and walks their pieces, one atomic per judged segment;
+ * the records are reduced by shuffles under the tie rule.  No LDS, no barrier, no workgroup waits for another; loops are
+ * bounded by K, P and SCP_OBSTACLE_MAX_RANGE; the result does not depend on the launch geometry.  Supported: N, K >= 1, finite
+ * h > 0, finite trajectories, the grids of scp_obstacle_distance.  Enqueued on the ctx's stream, no host read, timing through
+ * scp_ctx_last_pair_ms. */
+#define SCP_OBSTACLE_MAX_PIECES 16
+#define SCP_OBSTACLE_MAX_RANGE 4096
+typedef struct scp_obstacle_stats { /* DEVICE, one per vehicle, 32 bytes */
+  uint32_t min_sq;  /* squared clearance in cells; UINT32_MAX: nothing judged, or an empty map */
+  uint32_t segment; /* where: the lowest (segment, piece) on ties; UINT32_MAX: none */
+  uint32_t piece;
+  int32_t cell;     /* the linear index of the cell of the range that attains it (the lowest on ties); -1: none */
+  uint32_t n_touch; /* judged pieces whose range holds an occupied cell */
+  uint32_t n_off;   /* pieces off the map (not judged) */
+  uint32_t n_wide;  /* pieces whose range holds more than SCP_OBSTACLE_MAX_RANGE cells (not judged) */
+  uint32_t reserved;
+} scp_obstacle_stats;
+int scp_obstacle_clearance(scp_ctx* ctx, int N, int K, int D, double h, const scp_occupancy_grid* grid, const int32_t* sat,
+                           const uint32_t* field /* DEVICE [nz][ny][nx], gap = 1 */, int pieces /* 1 .. 16 */,
+                           const double* pos, const double* vel, const double* acc /* DEVICE [N][K][D] */,
+                           scp_obstacle_stats* out /* DEVICE [N] */, uint64_t* step_min /* DEVICE [K] */);
+
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
 int scp_gemm_f64(scp_ctx* ctx, int use_mfma, int R, int M, int C, double alpha, const double* A,
