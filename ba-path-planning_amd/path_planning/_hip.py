@@ -278,6 +278,12 @@ def lattice_shape(D, grid, stride):
     return tuple(int(grid.dims[d]) // int(stride) if d < D else 1 for d in range(3))
 
 
+def lattice_nodes(D, grid, stride):
+    """the node count of that lattice, at least 1: what a buffer per node is sized for (a stride < 1 is left to the call)"""
+    L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
+    return max(L[0] * L[1] * L[2], 1)
+
+
 def occupancy_grid(D, origin, cell, dims) -> OccupancyGrid:
     """scp_occupancy_grid from origin (D,), the cell size and dims = (nx, ny[, nz])"""
     g = OccupancyGrid()
@@ -547,6 +553,24 @@ class Context:
         torch = _torch()
         return torch.empty(*shape, dtype=dtype or torch.float64, device=self.tdev)
 
+    def _record_buffer(self, n, dtype):
+        """an uninitialised uint8 device buffer for n records (at least one) of the structured dtype"""
+        torch = _torch()
+        return torch.empty(max(int(n), 1) * dtype.itemsize, dtype=torch.uint8, device=self.tdev)
+
+    @staticmethod
+    def _read_records(buf, n, dtype):
+        """the first n records of such a buffer as a numpy structured array of its own -- synchronises"""
+        return buf[: int(n) * dtype.itemsize].cpu().numpy().view(dtype).copy()
+
+    @staticmethod
+    def _grid_shape(grid, occ):
+        """[nz][ny][nx] of an OccupancyGrid, which the tensor occ must have"""
+        shape = (int(grid.dims[2]), int(grid.dims[1]), int(grid.dims[0]))
+        if tuple(occ.shape) != shape:
+            raise ValueError(f"occupancy grid of shape {tuple(occ.shape)}, the geometry says [nz][ny][nx] = {shape}")
+        return shape
+
     def read_stats(self):
         """(min_dist, first_violation, n_selected, max_violation) -- synchronises."""
         st = _decode(PairStats, self.stats)
@@ -609,11 +633,11 @@ class Context:
         cap = 1024 if capacity is None else int(capacity)
         n_found = torch.zeros(1, dtype=torch.int64, device=self.tdev)
         for _ in range(2):
-            out = torch.empty(max(cap, 1) * CONFLICT_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+            out = self._record_buffer(cap, CONFLICT_DTYPE)
             self.check(self.lib.scp_list_conflicts(*args, out.data_ptr(), cap, n_found.data_ptr()))
             n = int(n_found.item())
             if n <= cap:
-                return out[: n * CONFLICT_DTYPE.itemsize].cpu().numpy().view(CONFLICT_DTYPE).copy()
+                return self._read_records(out, n, CONFLICT_DTYPE)
             cap = n
         raise HipError(SCP_ERR_CAPACITY, f"list_conflicts: {n} records after a repetition sized for {cap}")
 
@@ -635,7 +659,7 @@ class Context:
     def read_holds(self, table, n):
         """the first n records of a device table as a numpy structured array (HOLD_DTYPE) -- synchronises"""
         n = int(n.item()) if hasattr(n, "item") else int(n)
-        return table[: n * HOLD_DTYPE.itemsize].cpu().numpy().view(HOLD_DTYPE).copy()
+        return self._read_records(table, n, HOLD_DTYPE)
 
     def update_holds(self, N, K, D, h, R, pos, vel, acc, conflicts, table, n_holds, pad, q_begin=0, q_end=None, grow=True):
         """scp_update_holds: one repair pass's update of a table of holds from a conflict list.  `conflicts`: a CONFLICT_DTYPE
@@ -666,13 +690,11 @@ class Context:
     def clearance_profile(self, N, K, D, h, R, pos, vel, acc, q_begin=0, q_end=None):
         """scp_clearance_profile over the pair range [q_begin, q_end): the closest approach of every vehicle and of every
         time step, as two numpy structured arrays (CLEARANCE_DTYPE) of length N and K -- synchronises."""
-        torch = _torch()
         args = self._trajectory_args(N, K, D, h, R, pos, vel, acc, q_begin, q_end)
-        size = CLEARANCE_DTYPE.itemsize
-        out = torch.empty((N + K) * size, dtype=torch.uint8, device=self.tdev)
-        self.check(self.lib.scp_clearance_profile(*args, out.data_ptr(), out.data_ptr() + N * size))
-        both = out.cpu().numpy().view(CLEARANCE_DTYPE)
-        return both[:N].copy(), both[N:].copy()
+        out = self._record_buffer(N + K, CLEARANCE_DTYPE)
+        self.check(self.lib.scp_clearance_profile(*args, out.data_ptr(), out.data_ptr() + N * CLEARANCE_DTYPE.itemsize))
+        both = self._read_records(out, N + K, CLEARANCE_DTYPE)
+        return both[:N], both[N:]
 
     def last_clearance_solved(self):
         """segments of the latest clearance_profile that needed the quartic's minimum"""
@@ -682,14 +704,12 @@ class Context:
         """scp_delay_margins for the vehicles [a_begin, a_end) and the lags 0 .. max_lag: the clearance of every vehicle
         started s steps late, as a numpy structured array (DELAY_DTYPE) of shape (a_end - a_begin, max_lag + 1) --
         synchronises."""
-        torch = _torch()
         a_end = N if a_end is None else a_end
         shape = (max(a_end - a_begin, 0), max(max_lag, 0) + 1)
-        out = torch.empty(max(shape[0] * shape[1], 1) * DELAY_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        out = self._record_buffer(shape[0] * shape[1], DELAY_DTYPE)
         self.check(self.lib.scp_delay_margins(self.h, N, K, D, h, R, a_begin, a_end, max_lag, pos.data_ptr(), vel.data_ptr(),
                                               acc.data_ptr(), out.data_ptr()))
-        n = shape[0] * shape[1] * DELAY_DTYPE.itemsize
-        return out[:n].cpu().numpy().view(DELAY_DTYPE).reshape(shape).copy()
+        return self._read_records(out, shape[0] * shape[1], DELAY_DTYPE).reshape(shape)
 
     def last_delay_solved(self):
         """segments of the latest delay_margins that needed the quartic's minimum"""
@@ -760,12 +780,12 @@ class Context:
             raise ValueError(f"schedule_starts_batch: orders must be (B, {N}) with B >= 1, not {tuple(od.shape)}")
         B = int(od.shape[0])
         delay = torch.empty((B, max(N, 1)), dtype=torch.int32, device=self.tdev)
-        stats = torch.zeros(B * START_SCHEDULE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        stats = self._record_buffer(B, START_SCHEDULE_STATS_DTYPE).zero_()
         best = C.c_int32(-1)
         self.check(self.lib.scp_schedule_starts_batch(self.h, N, int(max_lag), mask.data_ptr(), B, od.data_ptr(),
                                                       SCHEDULE_OBJECTIVES[objective], delay.data_ptr(), stats.data_ptr(),
                                                       C.byref(best)))
-        st = stats.cpu().numpy().view(START_SCHEDULE_STATS_DTYPE)
+        st = self._read_records(stats, B, START_SCHEDULE_STATS_DTYPE)
         return delay.cpu().numpy(), {f: st[f].copy() for f in START_SCHEDULE_STATS_DTYPE.names}, int(best.value)
 
     def last_separation_solved(self):
@@ -781,19 +801,17 @@ class Context:
         """scp_generate_grid_swap: B = len(seeds) scenarios of the grid-swap-device family in one call.
         Returns device tensors init (B, N, D), goal (B, N, D), space (B, 2D) and the stats as a numpy structured array
         (GEN_STATS_DTYPE) of B entries.  Synchronises."""
-        torch = _torch()
         sd = np.array([int(v) & UINT64_MAX for v in np.asarray(seeds).reshape(-1)], dtype=np.uint64)
         B = int(sd.size)
         p = params if params is not None else gen_params()
         init = self.empty(max(B, 1), max(N, 1), D)
         goal = self.empty(max(B, 1), max(N, 1), D)
         space = self.empty(max(B, 1), 2 * D)
-        stats = torch.empty(max(B, 1) * GEN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        stats = self._record_buffer(B, GEN_STATS_DTYPE)
         self.check(self.lib.scp_generate_grid_swap(self.h, B, int(N), int(D), sd.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                    C.byref(p), init.data_ptr(), goal.data_ptr(), space.data_ptr(),
                                                    stats.data_ptr()))
-        st = stats.cpu().numpy().view(GEN_STATS_DTYPE)
-        return init, goal, space, st
+        return init, goal, space, self._read_records(stats, max(B, 1), GEN_STATS_DTYPE)
 
     def _scenario_points(self, start, goal):
         """start / goal as contiguous float64 device tensors of one shape (B, N, D) (a single scenario (N, D) becomes B = 1)"""
@@ -825,10 +843,10 @@ class Context:
         B, N, D = (int(v) for v in s.shape)
         goal_of = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int32, device=self.tdev)
         prices = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int64, device=self.tdev) if want_prices else None
-        stats = torch.empty(max(B, 1) * ASSIGN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        stats = self._record_buffer(B, ASSIGN_STATS_DTYPE)
         self.check(fn(self.h, B, N, D, s.data_ptr(), g.data_ptr(), goal_of.data_ptr(), _ptr(prices), int(max_rounds_per_phase),
                       stats.data_ptr()))
-        return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
+        return goal_of, self._read_records(stats, max(B, 1), ASSIGN_STATS_DTYPE), prices
 
     def assign_costs(self, cost, max_rounds_per_phase=0, want_prices=False):
         """scp_assign_costs: the assignment that minimises sum_i cost[i][goal_of[i]], by the auction of assign_goals on the
@@ -851,23 +869,22 @@ class Context:
         B, N = int(c.shape[0]), int(c.shape[1])
         goal_of = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int32, device=self.tdev)
         prices = torch.empty((max(B, 1), max(N, 1)), dtype=torch.int64, device=self.tdev) if want_prices else None
-        stats = torch.empty(max(B, 1) * ASSIGN_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        stats = self._record_buffer(B, ASSIGN_STATS_DTYPE)
         self.check(self.lib.scp_assign_costs(self.h, B, N, c.data_ptr(), goal_of.data_ptr(), _ptr(prices),
                                              int(max_rounds_per_phase), stats.data_ptr()))
-        return goal_of, stats.cpu().numpy().view(ASSIGN_STATS_DTYPE), prices
+        return goal_of, self._read_records(stats, max(B, 1), ASSIGN_STATS_DTYPE), prices
 
     def straight_line_check(self, start, goal, goal_of=None, min_sep=0.0):
         """scp_straight_line_check: closest approach, close pairs and opposed pairs of the equal-time straight-line motions
         start_i -> goal[goal_of[i]] (goal_of None: the identity) of B scenarios, as a numpy structured array
         (LINE_STATS_DTYPE) of B entries.  Synchronises."""
-        torch = _torch()
         s, g = self._scenario_points(start, goal)
         B, N, D = (int(v) for v in s.shape)
         gof = None if goal_of is None else self._int32_tensor(goal_of).reshape(B, N)
-        stats = torch.empty(max(B, 1) * LINE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        stats = self._record_buffer(B, LINE_STATS_DTYPE)
         self.check(self.lib.scp_straight_line_check(self.h, B, N, D, s.data_ptr(), g.data_ptr(), _ptr(gof), float(min_sep),
                                                     stats.data_ptr()))
-        return stats.cpu().numpy().view(LINE_STATS_DTYPE)
+        return self._read_records(stats, max(B, 1), LINE_STATS_DTYPE)
 
     # ---- static obstacles: occupancy grid, corridor boxes, the corridor check ------------------------------------------
     def occupancy_prepare(self, D, grid: OccupancyGrid, occ):
@@ -877,9 +894,7 @@ class Context:
         if not torch.is_tensor(occ):
             occ = torch.as_tensor(np.ascontiguousarray(np.asarray(occ) != 0, dtype=np.uint8))
         occ = occ.to(device=self.tdev, dtype=torch.uint8).contiguous()
-        shape = (int(grid.dims[2]), int(grid.dims[1]), int(grid.dims[0]))
-        if tuple(occ.shape) != shape:
-            raise ValueError(f"occupancy grid of shape {tuple(occ.shape)}, the geometry says [nz][ny][nx] = {shape}")
+        shape = self._grid_shape(grid, occ)
         sat = torch.empty(shape, dtype=torch.int32, device=self.tdev)
         self.check(self.lib.scp_occupancy_prepare(self.h, int(D), C.byref(grid), occ.data_ptr(), sat.data_ptr()))
         return occ, sat
@@ -905,19 +920,17 @@ class Context:
 
     def check_corridor(self, N, K, D, h, grid: OccupancyGrid, cells, pos, vel, acc, tol=0.0):
         """scp_check_corridor: one record per vehicle as a numpy structured array (CORRIDOR_STATS_DTYPE) -- synchronises"""
-        torch = _torch()
-        out = torch.empty(max(N, 1) * CORRIDOR_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        out = self._record_buffer(N, CORRIDOR_STATS_DTYPE)
         self.check(self.lib.scp_check_corridor(self.h, N, K, D, float(h), C.byref(grid), cells.data_ptr(), pos.data_ptr(),
                                                vel.data_ptr(), acc.data_ptr(), float(tol), out.data_ptr()))
-        return out.cpu().numpy().view(CORRIDOR_STATS_DTYPE)[:N].copy()
+        return self._read_records(out, N, CORRIDOR_STATS_DTYPE)
 
     # ---- static obstacles: reference paths by a lattice search -------------------------------------------------------------
     def lattice_edges(self, D, grid: OccupancyGrid, sat, stride, clearance=0):
         """scp_lattice_edges: the edge masks of the search lattice (int32 device tensor [nodes] holding the uint32 words).  No
         host read."""
         torch = _torch()
-        L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
-        edges = torch.empty(max(L[0] * L[1] * L[2], 1), dtype=torch.int32, device=self.tdev)
+        edges = torch.empty(lattice_nodes(D, grid, stride), dtype=torch.int32, device=self.tdev)
         self.check(self.lib.scp_lattice_edges(self.h, int(D), C.byref(grid), sat.data_ptr(), int(stride), int(clearance),
                                               edges.data_ptr()))
         return edges
@@ -928,11 +941,10 @@ class Context:
         records of PATH_INFO_DTYPE, dist (N, nodes) int16 device tensor holding the uint16 words or None, n_failed int64
         device tensor of one word).  No host read."""
         torch = _torch()
-        L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
-        nodes = max(L[0] * L[1] * L[2], 1)
+        nodes = lattice_nodes(D, grid, stride)
         path = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_path else None
         dist = torch.empty((N, nodes), dtype=torch.int16, device=self.tdev) if want_dist else None
-        info = torch.empty(max(N, 1) * PATH_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        info = self._record_buffer(N, PATH_INFO_DTYPE)
         n_failed = torch.zeros(1, dtype=torch.int64, device=self.tdev)
         self.check(self.lib.scp_reference_paths(self.h, N, K, D, C.byref(grid), int(stride), edges.data_ptr(), p0.data_ptr(),
                                                 pf.data_ptr(), int(max_path), ref.data_ptr(), _ptr(path), info.data_ptr(),
@@ -946,8 +958,7 @@ class Context:
         lattice or on a block that is not free), dist (n_src, nodes) int16 device tensor holding the uint16 words, or None).
         No host read."""
         torch = _torch()
-        L = lattice_shape(D, grid, stride) if int(stride) >= 1 else (0, 0, 0)
-        nodes = max(L[0] * L[1] * L[2], 1)
+        nodes = lattice_nodes(D, grid, stride)
         n_src, n_dst = int(src.shape[0]), int(dst.shape[0])
         hops = torch.empty((max(n_src, 1), max(n_dst, 1)), dtype=torch.int16, device=self.tdev)
         src_node = torch.empty(max(n_src, 1), dtype=torch.int32, device=self.tdev)
@@ -964,7 +975,7 @@ class Context:
         int32 device tensor or None, out as a uint8 device tensor of N records of SHORTEN_INFO_DTYPE).  No host read."""
         torch = _torch()
         kept = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_kept else None
-        out = torch.empty(max(N, 1) * SHORTEN_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        out = self._record_buffer(N, SHORTEN_INFO_DTYPE)
         self.check(self.lib.scp_shorten_paths(self.h, N, K, D, C.byref(grid), sat.data_ptr(), int(stride), int(clearance),
                                               p0.data_ptr(), pf.data_ptr(), int(max_path), _ptr(path), _ptr(info),
                                               ref.data_ptr(), _ptr(kept), out.data_ptr()))
@@ -976,9 +987,7 @@ class Context:
         distance field in cells, an int32 device tensor [nz][ny][nx] holding the uint32 words (DIST_NONE everywhere on an
         empty map).  No host read."""
         torch = _torch()
-        shape = (int(grid.dims[2]), int(grid.dims[1]), int(grid.dims[0]))
-        if tuple(occ.shape) != shape:
-            raise ValueError(f"occupancy grid of shape {tuple(occ.shape)}, the geometry says [nz][ny][nx] = {shape}")
+        shape = self._grid_shape(grid, occ)
         field = torch.empty(shape, dtype=torch.int32, device=self.tdev)
         self.check(self.lib.scp_obstacle_distance(self.h, int(D), C.byref(grid), occ.data_ptr(), int(gap), field.data_ptr()))
         return field
@@ -988,12 +997,12 @@ class Context:
         (N, K, D) device tensors.  Returns (one record per vehicle as a numpy structured array (OBSTACLE_STATS_DTYPE),
         step_min as a numpy uint64 array [K]) -- synchronises."""
         torch = _torch()
-        out = torch.empty(max(N, 1) * OBSTACLE_STATS_DTYPE.itemsize, dtype=torch.uint8, device=self.tdev)
+        out = self._record_buffer(N, OBSTACLE_STATS_DTYPE)
         step_min = torch.empty(max(K, 1), dtype=torch.int64, device=self.tdev)
         self.check(self.lib.scp_obstacle_clearance(self.h, N, K, D, float(h), C.byref(grid), sat.data_ptr(), field.data_ptr(),
                                                    int(pieces), pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), out.data_ptr(),
                                                    step_min.data_ptr()))
-        return out.cpu().numpy().view(OBSTACLE_STATS_DTYPE)[:N].copy(), step_min.cpu().numpy().view(np.uint64)[:K].copy()
+        return self._read_records(out, N, OBSTACLE_STATS_DTYPE), step_min.cpu().numpy().view(np.uint64)[:K].copy()
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

@@ -17,6 +17,12 @@ def pairs_from_index(q, N):
     return i, q - off(i) + i + 1
 
 
+def pair_from_index(q, N):
+    """Lexicographic pair index -> (i, j), i < j (host helper, exact integer arithmetic)."""
+    i, j = pairs_from_index(q, N)
+    return int(i), int(j)
+
+
 def conflict_windows(records, N, K, h):
     """records: structured array with the fields of scp_conflict (row = k * pairs + q, min_dist, t_min, t_enter, t_exit,
     pieces), any order.  Returns one dict per window, sorted by (t_start, i, j):

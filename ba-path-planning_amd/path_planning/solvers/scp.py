@@ -15,27 +15,32 @@ Differences to the reference that a caller can observe (INTEGRATION.md has the f
     ``feasibility_tol``, ``max_rounds``, ``refresh_feasibility``, ``polish``/``polish_eps``, ``native``, ``row_free``, ``carry_rho``, ``kernel_timing``,
     ``qp_row_capacity``, ``reuse_native``, ``verbose``, ``rank``/``world_size``/``group`` (pair-range-sharded multi-GPU: the SCP iteration natively,
     split at its exchange points -- ``scp_iteration_sharded``).
+
+What is not in the reference lives in three state-free bases of SCP: static obstacles in _obstacles.py, the post-solve reports in
+_validation.py, goal assignment, repair and staggered starts in _fleet.py.
 """
 from __future__ import annotations
 
 import atexit
 import threading
 import time
+from collections import defaultdict
 
 import numpy as np
 
 from .. import _hip
 from .._sharding import Shard
-from ..scenarios.obstacles import default_search_stride
-from .conflicts import conflict_windows, pairs_from_index
-from .stagger import candidate_orders, refined_orders, schedule_key, staggered_fleet
+from ._fleet import FleetMethods
+from ._obstacles import ObstacleMethods, check_position_boxes, corridor_shrink, straight_reference  # noqa: F401
+from ._validation import ValidationMethods, gather_delay_blocks, segment_min_distance  # noqa: F401
+from .conflicts import pair_from_index
 
 # The reference's callers build a NEW solver object per scenario (compute_trajectories_batch.py:103-117).  Here an object owns a
 # library context and a native solver (device workspace, pinned host words, the K x K blocks cached per rho): ~0.7 ms to
 # create, against a 2.5 ms solve at 128 agents.  So the native halves of released SCP objects on the DEFAULT stream are kept,
 # per (device, shape, settings), and the next object of the same shape adopts them -- same results bit for bit (a pooled solver is what
 # compute-trajectories-batch has always reused per worker; tests/test_scp_gpu.py::test_released_solvers_are_reused).
-_POOL = {}
+_POOL = defaultdict(list)
 _POOL_LOCK = threading.Lock()
 _POOL_LIMIT = 4  # per key
 _POOL_STATS = {"hits": 0, "misses": 0, "returned": 0}
@@ -63,55 +68,7 @@ def clear_native_pool():
 atexit.register(clear_native_pool)
 
 
-def gather_delay_blocks(shard, mine, a0):
-    """The ranks' blocks of delay margins (DELAY_DTYPE, (vehicles of the rank, S + 1), the rank's first vehicle a0) concatenated
-    in vehicle order, flat: the records travel through Shard.allgather_records under the row id a (S + 1) + s, as their bytes."""
-    lags = mine.shape[1]
-    rec = np.empty(mine.size, dtype=[("row", np.uint64)] + _hip.DELAY_DTYPE.descr)
-    rec["row"] = a0 * lags + np.arange(mine.size)
-    for f in _hip.DELAY_DTYPE.names:
-        rec[f] = mine.reshape(-1)[f]
-    return shard.allgather_records(rec)[list(_hip.DELAY_DTYPE.names)]
-
-
-def straight_reference(p0, pf, K):
-    """The default reference path of SCP.set_corridors: the straight line from start to goal, sampled uniformly at the states
-    j = 0 .. K -- (N, K + 1, D) from p0, pf (N, D)."""
-    p0, pf = np.asarray(p0, dtype=np.float64), np.asarray(pf, dtype=np.float64)
-    s = (np.arange(K + 1, dtype=np.float64) / float(K))[None, :, None]
-    return p0[:, None, :] + s * (pf - p0)[:, None, :]
-
-
-def check_position_boxes(N, K, D, pos_min, pos_max, lo, hi):
-    """Host validation of per-(vehicle, state) position boxes: (N, K, D) float arrays without NaN whose intersection with the
-    workspace box is not empty for any state j = 1 .. K-1 (state 0 is fixed to the start and never constrained).  Returns
-    (lo, hi) as contiguous float64 arrays; raises ValueError naming the first offending state."""
-    lo = np.ascontiguousarray(lo, dtype=np.float64)
-    hi = np.ascontiguousarray(hi, dtype=np.float64)
-    if lo.shape != (N, K, D) or hi.shape != (N, K, D):
-        raise ValueError(f"position boxes need shape (N, K, D) = ({N}, {K}, {D}), got {lo.shape} and {hi.shape}")
-    if np.isnan(lo).any() or np.isnan(hi).any():
-        raise ValueError("position boxes must not hold NaN (use -inf / +inf for an unconstrained entry)")
-    l = np.maximum(np.asarray(pos_min, dtype=np.float64), lo[:, 1:])
-    u = np.minimum(np.asarray(pos_max, dtype=np.float64), hi[:, 1:])
-    bad = np.argwhere(l > u)
-    if bad.size:
-        i, j, d = (int(x) for x in bad[0])
-        raise ValueError(f"position box of vehicle {i}, state {j + 1}, coordinate {d} is empty inside the workspace: "
-                         f"[{l[i, j, d]}, {u[i, j, d]}]")
-    return lo, hi
-
-
-def corridor_shrink(acc_min, acc_max, h, pad):
-    """shrink of SCP.set_corridors: a quadratic leaves the chord of its end values by at most |a| h^2 / 8; pad pays for the
-    QP's constraint tolerance"""
-    pad = float(pad)
-    if not (pad >= 0.0 and np.isfinite(pad)):
-        raise ValueError(f"pad={pad!r}: a finite number >= 0")
-    return max(abs(float(acc_min)), abs(float(acc_max))) * float(h) * float(h) / 8.0 + pad
-
-
-class SCP:
+class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
     def __init__(
         self,
         n_vehicles=5,
@@ -235,10 +192,8 @@ class SCP:
         self._pairs = None
         self._holds = None  # (device table, count) of repair_conflicts while one of its passes runs
         self.staggered = None  # the fleet of the latest stagger_starts (its trajectories stay as they are)
-        self._obstacles = None  # set_obstacles: {"grid", "occ", "sat"} (device), the occupancy grid and its summed table;
-                                # find_reference adds "edges": {(stride, clearance): the lattice's edge masks},
-                                # obstacle_distance_field / obstacle_clearance "field": {gap: (device field, its ms)}
-        self._corridor = None   # set_corridors: {"cells", "grid"}: the boxes of the segments, what validate_solution checks
+        self._obstacles = None  # set_obstacles: the ObstacleMap (the grid on the device and what is derived from it once)
+        self._corridor = None   # set_corridors: {"cells"}: the boxes of the segments, what validate_solution checks
         self._boxes = None      # (lo, hi) device tensors (N, K, D) by state: set_corridors / set_position_boxes
         self._dev = {}
         self.last_info = {}
@@ -253,6 +208,21 @@ class SCP:
         if self.verbose and self.shard.rank == 0:
             print(*a)
 
+    def _require(self, who, *, one_rank=False, obstacles=False, states=False, trajectories=False):
+        """the preconditions of the entry point `who`, checked in this order"""
+        if one_rank and self.shard.world != 1:
+            raise ValueError(f"{who} supports one rank only (world_size == 1)")
+        if obstacles and self._obstacles is None:
+            raise ValueError(f"{who} needs set_obstacles first")
+        if states and (self.initial_positions is None or self.final_positions is None):
+            raise ValueError(f"{who} needs both set_initial_states and set_final_states first")
+        if trajectories and self.trajectories is None:
+            raise ValueError("Trajectories not generated yet")
+
+    def _device_trajectories(self):
+        """the stored trajectories on the device: (positions, velocities, accelerations)"""
+        return tuple(self._ctx.tensor(self.trajectories[k]) for k in ("positions", "velocities", "accelerations"))
+
     def set_space_dims(self, space_dims):
         """Change the workspace box of an existing solver (same N, T, h, R, dim).  Together with set_initial_states /
         set_final_states this lets one solver object -- its context, streams, pinned buffers and the QP workspace, whose
@@ -264,235 +234,6 @@ class SCP:
         self.pos_max = np.array(space_dims[self.D:])
         self.trajectories = None
         self._obstacles = self._corridor = self._boxes = None  # (they belong to the scenario that is being replaced)
-
-    # ------------------------------------------------------------------------------------------------
-    # static obstacles (not in the reference): safe flight corridors as per-state position boxes, DESIGN.md section 3.9
-    # ------------------------------------------------------------------------------------------------
-    def _one_rank(self, what):
-        if self.shard.world != 1:
-            raise ValueError(f"{what} supports one rank only (world_size == 1)")
-
-    def set_obstacles(self, occ, origin, cell):
-        """Static obstacles as an occupancy grid: ``occ`` [nz][ny][nx] ([ny][nx] in 2-D; nonzero = occupied), ``origin`` the
-        lower corner of cell (0, 0, 0), ``cell`` the edge length -- what scenarios.obstacles.rasterize returns.  Uploads the
-        grid and prepares its summed table (scp_occupancy_prepare); corridors and boxes set before are dropped."""
-        self._one_rank("set_obstacles")
-        occ = np.asarray(occ)
-        if self.D == 2 and occ.ndim == 2:
-            occ = occ[None]
-        if occ.ndim != 3 or (self.D == 2 and occ.shape[0] != 1) or min(occ.shape) < 1:
-            raise ValueError(f"occ has shape {occ.shape}: need [nz][ny][nx]" + (" with nz = 1 (or [ny][nx])" if self.D == 2 else ""))
-        if occ.size > _hip.CORRIDOR_MAX_CELLS:
-            raise ValueError(f"the grid has {occ.size} cells, more than the supported 2^24")
-        origin = np.asarray(origin, dtype=np.float64).reshape(-1)
-        cell = float(cell)
-        if origin.size != self.D or not np.isfinite(origin).all():
-            raise ValueError(f"origin needs {self.D} finite entries")
-        if not (cell > 0.0 and np.isfinite(cell)):
-            raise ValueError(f"cell={cell!r}: a finite number > 0")
-        grid = _hip.occupancy_grid(self.D, origin, cell, occ.shape[::-1])
-        occ_dev, sat = self._ctx.occupancy_prepare(self.D, grid, occ)
-        self._obstacles = {"grid": grid, "occ": occ_dev, "sat": sat, "prepare_ms": self._ctx.last_pair_ms()}
-        self._corridor = self._boxes = None
-
-    def set_corridors(self, reference=None, max_grow=8, pad=0.02, allow_open=False):
-        """Safe flight corridors around a reference path: for every vehicle and segment an axis-aligned box of free cells
-        (scp_corridor_boxes: the cells of the segment's two reference points, grown by at most ``max_grow`` cells per
-        direction), and for every state the intersection of the boxes of the two segments it ends, shrunk by
-        ``max(|acc_min|, |acc_max|) h^2 / 8 + pad`` (scp_corridor_state_boxes) -- with that the whole segment stays in its box,
-        not only its end states.  The state boxes become the bounds of the position rows of every QP of
-        generate_trajectories / scp_iteration / repair_conflicts; validate_solution(corridor=True) checks the result.
-
-        ``reference``: (N, K + 1, D), the reference point of every state j = 0 .. K; None: the straight line from start to
-        goal; "search": what find_reference() returns with its defaults (paths around the obstacles); "shortened": what
-        shorten_reference() returns with its defaults (those paths cut down to the corners they need).  A segment whose reference points lie on occupied cells or outside the grid is blocked, a state whose
-        intersection is empty is open (unconstrained): both raise ValueError naming the first one unless ``allow_open``.
-        Returns {"n_blocked", "n_open", "shrink", "boxes_ms", "state_boxes_ms"} (device milliseconds of the two kernels)."""
-        self._one_rank("set_corridors")
-        if isinstance(reference, str):
-            if reference not in ("search", "shortened"):
-                raise ValueError(f"reference={reference!r}: an array (N, K + 1, D), None (straight lines), \"search\" or "
-                                 "\"shortened\"")
-            reference, _ = self.find_reference() if reference == "search" else self.shorten_reference()
-        if self._obstacles is None:
-            raise ValueError("set_corridors needs set_obstacles first")
-        if self.initial_positions is None or self.final_positions is None:
-            raise ValueError("set_corridors needs both set_initial_states and set_final_states first")
-        if isinstance(max_grow, bool) or not isinstance(max_grow, (int, np.integer)) or not 0 <= max_grow <= _hip.CORRIDOR_MAX_GROW:
-            raise ValueError(f"max_grow={max_grow!r}: a whole number of cells in [0, {_hip.CORRIDOR_MAX_GROW}]")
-        shrink = corridor_shrink(self.acc_min, self.acc_max, self.h, pad)
-        N, K, D, c = self.N, self.K, self.D, self._ctx
-        if reference is None:
-            reference = straight_reference(self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D), K)
-        reference = np.ascontiguousarray(reference, dtype=np.float64)
-        if reference.shape != (N, K + 1, D):
-            raise ValueError(f"reference needs shape (N, K + 1, D) = ({N}, {K + 1}, {D}), got {reference.shape}")
-        grid = self._obstacles["grid"]
-        cells, n_blocked = c.corridor_boxes(N, K, D, grid, self._obstacles["sat"], c.tensor(reference), int(max_grow))
-        boxes_ms = c.last_pair_ms()
-        lo, hi, n_open = c.corridor_state_boxes(N, K, D, grid, cells, shrink)
-        state_ms = c.last_pair_ms()
-        info = {"n_blocked": int(n_blocked.item()), "n_open": int(n_open.item()), "shrink": shrink, "boxes_ms": boxes_ms,
-                "state_boxes_ms": state_ms}
-        if (info["n_blocked"] or info["n_open"]) and not allow_open:
-            hc = cells.cpu().numpy()
-            blocked = np.argwhere(hc[..., 3] < hc[..., 0])
-            if blocked.size:
-                i, g = (int(x) for x in blocked[0])
-                raise ValueError(f"corridor: segment {g} of vehicle {i} is blocked (its reference points "
-                                 f"{reference[i, g].tolist()} -> {reference[i, g + 1].tolist()} lie on occupied cells or outside "
-                                 f"the grid); {info['n_blocked']} blocked segments, {info['n_open']} open states in all")
-            opened = np.argwhere(np.isinf(lo.cpu().numpy()[:, 1:, 0]))
-            i, j = (int(x) for x in opened[0])
-            raise ValueError(f"corridor: state {j + 1} of vehicle {i} is open (the boxes of segments {j} and {j + 1}, shrunk by "
-                             f"{shrink:.4g}, do not meet); {info['n_open']} open states in all")
-        check_position_boxes(N, K, D, self.pos_min, self.pos_max, lo.cpu().numpy(), hi.cpu().numpy())
-        self._corridor = {"cells": cells, "grid": grid}
-        self._boxes = (lo, hi)
-        self.last_info["corridor"] = info
-        return info
-
-    def find_reference(self, stride=None, clearance=0, max_path=None, allow_unreachable=False):
-        """Reference paths around the obstacles, one per vehicle, for set_corridors(reference=...): a breadth-first search on
-        a lattice of blocks of ``stride`` x ``stride`` (x ``stride``) cells whose edges exist only where both blocks -- for a
-        diagonal move the whole 2 x 2 (2 x 2 x 2) group -- grown by ``clearance`` cells are free (scp_lattice_edges, once per
-        (stride, clearance)), then per vehicle the path with the fewest lattice moves from its start to its goal, sampled at
-        the states j = 0 .. K (scp_reference_paths: one workgroup per vehicle).  ``stride`` None:
-        scenarios.obstacles.default_search_stride; ``max_path`` None: min(lattice nodes, 8 K) nodes.
-
-        Returns (reference (N, K + 1, D) ndarray, info) and stores info as ``last_info["reference"]``: ``status`` (per vehicle:
-        0 found, 1 / 2 start / goal off the lattice or on a block that is not free, 3 unreachable, 4 longer than max_path),
-        ``n_nodes``, ``n_failed``, ``stride``, ``clearance``, ``lattice``, ``max_edges`` (the largest E = n_nodes + 1),
-        ``guaranteed`` (every found path has E <= K or 2 clearance >= stride ceil(E / K): set_corridors then reports no blocked
-        segment for those vehicles), ``edges_ms`` / ``search_ms`` (device milliseconds; edges_ms 0 when the masks were
-        cached).  A vehicle without a path keeps the straight line; unless ``allow_unreachable`` that raises ValueError."""
-        if clearance is None:
-            raise ValueError("clearance=None: a whole number of cells >= 0")
-        found = self._search_reference("find_reference", stride, clearance, max_path, want_path=False)
-        info = found["info"]
-        self.last_info["reference"] = info
-        self._require_paths(info, allow_unreachable)
-        return found["ref"].cpu().numpy(), info
-
-    def _search_reference(self, who, stride, clearance, max_path, want_path):
-        """the checks and the two calls of find_reference -> {"ref", "path", "rec" (device tensors), "p0", "pf", "max_path",
-        "info": what find_reference reports}"""
-        stride, clearance, lattice, edges, edges_ms = self._lattice_edges(who, stride, clearance)
-        N, K, D, c = self.N, self.K, self.D, self._ctx
-        grid = self._obstacles["grid"]
-        nodes = lattice[0] * lattice[1] * lattice[2]
-        if max_path is None:
-            max_path = min(nodes, 8 * K)
-        if isinstance(max_path, bool) or not isinstance(max_path, (int, np.integer)) or not 1 <= max_path <= nodes:
-            raise ValueError(f"max_path={max_path!r}: a whole number of nodes in [1, {nodes}]")
-        p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
-        ref = c.tensor(straight_reference(p0, pf, K))
-        d_p0, d_pf = c.tensor(p0), c.tensor(pf)
-        path, dev_rec, _, n_failed = c.reference_paths(N, K, D, grid, stride, edges, d_p0, d_pf, int(max_path), ref,
-                                                       want_path=want_path)
-        search_ms = c.last_pair_ms()
-        rec = dev_rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
-        found = rec["status"] == 0
-        E = rec["n_nodes"].astype(np.int64) + 1
-        info = {"status": rec["status"].copy(), "n_nodes": rec["n_nodes"].copy(), "n_failed": int(n_failed.item()),
-                "stride": stride, "clearance": clearance, "lattice": lattice[:D],
-                "max_edges": int(E[found].max()) if found.any() else 0,
-                "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
-                "edges_ms": edges_ms, "search_ms": search_ms}
-        return {"ref": ref, "path": path, "rec": dev_rec, "p0": d_p0, "pf": d_pf, "max_path": int(max_path), "info": info}
-
-    def _lattice_edges(self, who, stride, clearance):
-        """the checks of a call on the search lattice and its edge masks, made once per (stride, clearance) and map ->
-        (stride, clearance, lattice (L_x, L_y, L_z), edges (device tensor), edges_ms: 0 when the masks were cached)"""
-        self._one_rank(who)
-        if self._obstacles is None:
-            raise ValueError(f"{who} needs set_obstacles first")
-        if self.initial_positions is None or self.final_positions is None:
-            raise ValueError(f"{who} needs both set_initial_states and set_final_states first")
-        K, D, c = self.K, self.D, self._ctx
-        grid = self._obstacles["grid"]
-        dims = [int(grid.dims[d]) for d in range(D)]
-        if stride is None:
-            stride = default_search_stride(dims, K, D)
-        if clearance is None:  # (shorten_reference: the stride)
-            clearance = stride
-        for name, value, least in (("stride", stride, 1), ("clearance", clearance, 0)):
-            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
-                raise ValueError(f"{name}={value!r}: a whole number of cells >= {least}")
-        stride, clearance = int(stride), int(clearance)
-        lattice = _hip.lattice_shape(D, grid, stride)
-        nodes = lattice[0] * lattice[1] * lattice[2]
-        if nodes < 1 or nodes > _hip.LATTICE_MAX_NODES:
-            raise ValueError(f"stride={stride}: a lattice of {lattice} nodes on a grid of {tuple(dims)} cells; supported are 1 .. "
-                             f"{_hip.LATTICE_MAX_NODES} nodes")
-        cache = self._obstacles.setdefault("edges", {})
-        edges_ms = 0.0
-        if (stride, clearance) not in cache:
-            cache[stride, clearance] = c.lattice_edges(D, grid, self._obstacles["sat"], stride, clearance)
-            edges_ms = c.last_pair_ms()
-        return stride, clearance, lattice, cache[stride, clearance], edges_ms
-
-    @staticmethod
-    def _require_paths(info, allow_unreachable):
-        if info["n_failed"] and not allow_unreachable:
-            i = int(np.nonzero(info["status"] != 0)[0][0])
-            raise ValueError(f"reference path: vehicle {i} has none: {_hip.PATH_STATUS[int(info['status'][i])]} (status "
-                             f"{int(info['status'][i])}; stride {info['stride']}, clearance {info['clearance']}, lattice "
-                             f"{info['lattice']}); {info['n_failed']} vehicles without a path in all")
-
-    def shorten_reference(self, stride=None, clearance=None, max_path=None, allow_unreachable=False):
-        """find_reference's paths, shortened: of every lattice path only the nodes that cannot be skipped are kept -- a node
-        sees another if every lattice step of the straight run between them, grown by ``clearance`` cells, is free -- and
-        the states j = 0 .. K are placed evenly by chord length along start, kept block centres, goal (scp_shorten_paths: one
-        wave per vehicle).  ``clearance`` None: ``stride``, with which every path shorter than K block edges is guaranteed;
-        the other parameters are find_reference's.
-
-        Returns (reference (N, K + 1, D) ndarray, info) and stores info as ``last_info["reference"]``: what find_reference
-        reports (its ``guaranteed`` replaced), and per vehicle ``n_kept`` (0 without a path), ``length`` / ``length_before``
-        (metres, after / before) and ``delta`` = floor(length / (K cell)) + 1, the most cells two consecutive reference points
-        lie apart per coordinate; ``guaranteed``: every found vehicle has clearance >= delta (set_corridors then reports no
-        blocked segment for those vehicles); ``shorten_ms`` (device milliseconds)."""
-        found = self._search_reference("shorten_reference", stride, clearance, max_path, want_path=True)
-        info = found["info"]
-        N, K, D, c = self.N, self.K, self.D, self._ctx
-        grid = self._obstacles["grid"]
-        _, out = c.shorten_paths(N, K, D, grid, self._obstacles["sat"], info["stride"], info["clearance"], found["p0"],
-                                 found["pf"], found["max_path"], found["path"], found["rec"], found["ref"], want_kept=False)
-        info["shorten_ms"] = c.last_pair_ms()
-        out = out.cpu().numpy().view(_hip.SHORTEN_INFO_DTYPE)[:N]
-        ok = info["status"] == 0
-        info["n_kept"], info["length"], info["length_before"] = out["n_kept"].copy(), out["length"].copy(), out["length_before"].copy()
-        info["delta"] = np.floor(out["length"] / (float(K) * float(grid.cell))).astype(np.int64) + 1
-        info["guaranteed"] = bool((info["clearance"] >= info["delta"])[ok].all())
-        self.last_info["reference"] = info
-        self._require_paths(info, allow_unreachable)
-        return found["ref"].cpu().numpy(), info
-
-    def set_position_boxes(self, lo, hi):
-        """Per-(vehicle, state) position boxes, the general form of set_corridors (waypoints, keep-in regions): ``lo`` / ``hi``
-        (N, K, D), state j = 0 .. K-1 of vehicle i must lie in [lo[i, j], hi[i, j]] intersected with the workspace box;
-        -inf / +inf leave an entry unconstrained, state 0 (the start) is never constrained.  Both None: no boxes.  Every QP
-        with boxes runs the round-2 persistent kernel or the three-launch pipeline."""
-        if lo is None and hi is None:
-            self._boxes = None
-            return
-        if lo is None or hi is None:
-            raise ValueError("set_position_boxes: lo and hi are both given or both None")
-        self._one_rank("set_position_boxes")
-        lo, hi = check_position_boxes(self.N, self.K, self.D, self.pos_min, self.pos_max, lo, hi)
-        self._boxes = (self._ctx.tensor(lo), self._ctx.tensor(hi))
-
-    def _apply_boxes(self, qp):
-        """the boxes into a QP whose problem has just been set (the Python-driven loops)"""
-        if self._boxes is not None:
-            self._one_rank("position boxes")
-            qp.set_position_boxes(*self._boxes)
-
-    def _native_boxes(self, nat):
-        """the boxes (or none: a pooled solver may remember a released object's) into the native solver, before solve / step"""
-        if self._boxes is not None:
-            self._one_rank("position boxes")
-        nat.set_position_boxes(*(self._boxes or (None, None)))
 
     # ------------------------------------------------------------------------------------------------
     # a0: states (scp.py:99-129)
@@ -527,82 +268,6 @@ class SCP:
         self._final_given = None  # (assign_goals keeps the order given here)
         self.goal_assignment = None
         self.assignment_info = None
-
-    def assign_goals(self, min_sep=None, method="auto", cost="line", stride=None, clearance=0, power=2,
-                     allow_unreachable=False):
-        """Interchangeable vehicles: re-pair vehicles and goals so that the sum of squared start-goal distances is minimal
-        (scp_assign_goals).  Call it after set_initial_states and set_final_states; the final positions AND velocities are
-        permuted, so vehicle i then flies to the goal given as number ``goal_assignment[i]``.  ``goal_assignment`` always
-        refers to the order handed to set_final_states: a second call recomputes from those originals, it does not compose.
-        ``assignment_info`` holds the auction's statistics and the straight-line checks before / after (min_sep, default the
-        minimum distance, is their "close" threshold).  ``method``: "single" (scp_assign_goals, up to 4096 vehicles), "wide"
-        (scp_assign_goals_wide, up to 65536) or "auto" (wide from 1024 vehicles, where it is faster); the result does not
-        depend on it.
-
-        ``cost``: "line" pairs by squared straight-line distance, which does not see walls; "path" (after set_obstacles) by
-        the number of moves of find_reference's lattice search between every start and every goal (scp_lattice_distances on
-        the lattice of ``stride`` / ``clearance``, the edge masks shared with find_reference), raised to ``power`` (1 or 2),
-        the straight-line distance only breaking ties (scenarios.assignment.path_costs), through the same auction on that
-        matrix (scp_assign_costs; up to 4096 vehicles, ``method`` is not used).  ``assignment_info`` then also holds
-        ``hops_identity`` / ``hops_assigned`` ({"sum", "max"} over the pairs that have a path), ``n_unreachable_identity`` /
-        ``n_unreachable_assigned``, ``tie_bits``, ``unreachable_cost``, ``max_hops``, ``stride``, ``clearance``, ``lattice``
-        and the device milliseconds ``edges_ms``, ``distances_ms``, ``assign_ms``.  If even the best pairing leaves a vehicle
-        without a path, no pairing connects every vehicle: ValueError naming one, unless ``allow_unreachable``.
-
-        Returns goal_assignment."""
-        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS, assign_method, hop_totals, path_costs
-
-        if cost not in ("line", "path"):
-            raise ValueError(f"cost={cost!r}: \"line\" or \"path\"")
-        if cost == "path":
-            if self.N > _hip.ASSIGN_COSTS_MAX_N:
-                raise ValueError(f"assign_goals(cost=\"path\") supports up to {_hip.ASSIGN_COSTS_MAX_N} vehicles (one N x N cost "
-                                 f"matrix in one workgroup), not {self.N}; cost=\"line\" goes up to 65536")
-            stride, clearance, lattice, edges, edges_ms = self._lattice_edges("assign_goals(cost=\"path\")", stride, clearance)
-        else:
-            assign = assign_method(self._ctx, method, self.N)
-        if self.initial_positions is None or self.final_positions is None:
-            raise ValueError("assign_goals needs both set_initial_states and set_final_states first")
-        if self._final_given is None:
-            self._final_given = (self.final_positions.copy(), self.final_velocities.copy())
-        pf, vf = (a.reshape(self.N, self.D) for a in self._final_given)
-        start = self.initial_positions.reshape(1, self.N, self.D)
-        sep = float(self.R if min_sep is None else min_sep)
-        if cost == "path":
-            c, s0 = self._ctx, start[0]
-            hops, _, _, _ = c.lattice_distances(self.D, self._obstacles["grid"], stride, edges, c.tensor(s0), c.tensor(pf))
-            distances_ms = c.last_pair_ms()
-            hops = hops.cpu().numpy().view(np.uint16)
-            diff = s0[:, None, :] - pf[None, :, :]
-            costs, how = path_costs(hops, (diff * diff).sum(-1), power)
-            goal_of, st, _ = c.assign_costs(costs[None])
-            assign_ms = c.last_pair_ms()
-        else:
-            goal_of, st, _ = assign(start, pf[None])
-        before = self._ctx.straight_line_check(start, pf[None], None, sep)
-        after = self._ctx.straight_line_check(start, pf[None], goal_of, sep)
-        info = {k: st[k][0].item() for k in _ASSIGN_KEYS}
-        info["line_before"] = {k: before[k][0].item() for k in _LINE_KEYS}
-        info["line_after"] = {k: after[k][0].item() for k in _LINE_KEYS}
-        perm = goal_of[0].cpu().numpy().astype(np.int64)
-        if cost == "path":
-            hi, ha = hop_totals(hops), hop_totals(hops, perm)
-            info.update(how, hops_identity={k: hi[k] for k in ("sum", "max")}, hops_assigned={k: ha[k] for k in ("sum", "max")},
-                        n_unreachable_identity=hi["n_unreachable"], n_unreachable_assigned=ha["n_unreachable"], stride=stride,
-                        clearance=clearance, lattice=lattice[:self.D], edges_ms=edges_ms, distances_ms=distances_ms,
-                        assign_ms=assign_ms)
-            if ha["n_unreachable"] and not allow_unreachable:
-                i = int(np.flatnonzero(hops[np.arange(self.N), perm] == 0xFFFF)[0])
-                raise ValueError(f"assign_goals(cost=\"path\"): no pairing connects every vehicle -- in the best one "
-                                 f"{ha['n_unreachable']} vehicles have no path, vehicle {i} among them (stride {stride}, "
-                                 f"clearance {clearance}, lattice {lattice[:self.D]}); allow_unreachable=True pairs the rest")
-        self.final_positions = pf[perm].flatten()
-        self.final_velocities = vf[perm].flatten()
-        self._dev.pop("p0", None)
-        self.trajectories = None
-        self.goal_assignment = perm
-        self.assignment_info = info
-        return perm
 
     # ------------------------------------------------------------------------------------------------
     # device-side setup
@@ -670,7 +335,7 @@ class SCP:
     def generate_trajectories(self, max_iterations=15):
         """Main method to generate collision-free trajectories using SCP (scp.py:131-180)."""
         if self._boxes is not None:
-            self._one_rank("generate_trajectories with position boxes")
+            self._require("generate_trajectories with position boxes", one_rank=True)
         if self.native and self.shard.world == 1:
             return self._generate_trajectories_native(max_iterations)
         is_feasible = False
@@ -758,7 +423,7 @@ class SCP:
                 and not getattr(ctx, "options_changed", False))
         if keep:
             with _POOL_LOCK:
-                held = _POOL.setdefault(self._pool_key, [])
+                held = _POOL[self._pool_key]
                 if len(held) < _POOL_LIMIT:
                     held.append((ctx, nat))
                     _POOL_STATS["returned"] += 1
@@ -1113,498 +778,16 @@ class SCP:
         return False
 
     # ------------------------------------------------------------------------------------------------
-    # post-solve validation: one device pass over all pairs + the fixed rows on the host copy
-    # ------------------------------------------------------------------------------------------------
-    def validate_solution(self, continuous=False, conflicts=False, clearance=False, delay=None):
-        """Feasibility report of the stored trajectories: minimum pair distance over all stored samples and its
-        first violation of R - 0.01 (device reduction, generalises scp.py:597-615), worst violation of every bound
-        the reference imposes (scp.py:182-257) and of the final-state equalities (state K).
-
-        continuous=True adds what the samples cannot show: ``min_pair_distance_continuous`` (minimum over every segment,
-        not only its end points), ``collision_free_continuous`` (no segment below R - 0.01), ``n_violating_segments``,
-        ``first_violation_continuous`` and ``closest_approach`` (each ``{"timestep", "time", "vehicles", "distance"}`` or
-        None).
-
-        conflicts=True (with continuous=True) lists every between-sample conflict: ``conflicts``, one dictionary per pair and
-        contiguous stretch of time below R - 0.01 (conflicts.conflict_windows: vehicles, t_start, t_end, duration,
-        min_distance, t_min_distance, first_timestep, n_segments, pieces), sorted by start time, and ``n_conflicts``.
-
-        clearance=True (with continuous=True) adds the clearance profiles (scp_clearance_profile): ``vehicle_clearance``, a
-        dictionary of length-N arrays -- every vehicle's closest approach over the whole flight: ``min_distance``, ``time``
-        (seconds from the start), ``timestep``, ``partner``, ``sample_min_distance`` (at the samples only) and
-        ``n_violating_segments``; ``step_clearance``, a dictionary of length-K arrays -- the fleet's closest approach within
-        every segment: ``min_distance``, ``time``, ``vehicles`` (K x 2), ``sample_min_distance``, ``n_violating_segments``; and
-        ``most_exposed_vehicle``: ``{"vehicle", "partner", "time", "distance"}`` of the smallest vehicle clearance (None
-        without a pair).  A vehicle or step without a pair has min_distance inf, time nan and partner / vehicles -1.
-
-        delay=S (an int, 0 <= S <= K, with continuous=True) adds the delay margins (scp_delay_margins): how close every vehicle
-        comes to anybody if it ALONE starts s = 0 .. S steps late (held at its start, everybody else on schedule and parked at
-        the goal afterwards).  ``delay_margin``: a dictionary of N x (S + 1) arrays ``min_distance``, ``time`` (seconds from
-        the start; nan without a pair), ``partner`` (-1 without a pair) and ``n_violating_segments``; ``delay_tolerance``: a
-        dictionary of length-N arrays ``steps`` (the largest s <= S such that the lags 0 .. s are all free of violating
-        segments; -1 if lag 0 already violates), ``seconds`` (steps * h) and ``limited_by`` (the partner at lag steps + 1, -1
-        where steps = S); ``least_tolerant_vehicle``: ``{"vehicle", "steps", "seconds", "partner", "time", "distance"}`` of
-        the smallest ``steps`` (ties: the lowest index; partner, time and distance are those of lag steps + 1, or of lag S
-        where steps = S; None without a pair).
-
-        After set_corridors the report also has ``corridor``, what validate_corridor() returns (tolerance 0)."""
-        if conflicts and not continuous:
-            raise ValueError("conflicts=True lists the conflicts of the continuous-time check: it needs continuous=True")
-        if clearance and not continuous:
-            raise ValueError("clearance=True profiles the continuous-time check: it needs continuous=True")
-        if delay is not None:
-            if not continuous:
-                raise ValueError("delay=S delays the vehicles of the continuous-time check: it needs continuous=True")
-            if isinstance(delay, bool) or not isinstance(delay, (int, np.integer)) or not 0 <= delay <= self.K:
-                raise ValueError(f"delay={delay!r}: the largest delay is a whole number of steps in [0, K = {self.K}]")
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")
-        N, K, D, h = self.N, self.K, self.D, self.h
-        a, v, p = (self.trajectories[k] for k in ("accelerations", "velocities", "positions"))
-        q0, q1 = self.shard.pair_range()
-        c = self._ctx
-        dev = (c.tensor(p), c.tensor(v), c.tensor(a)) if continuous else (c.tensor(p),)  # one upload for every pass below
-        min_dist, first, _, _ = c.check_avoidance(N, K, D, self.R, dev[0], q0, q1)
-        min_dist = self.shard.all_min(min_dist)
-        first = self.shard.all_min_int(first)
-        pf = self.final_positions.reshape(N, D)
-        vf = self.final_velocities.reshape(N, D)
-        vK = v[:, K - 1] + h * a[:, K - 1]
-        pK = p[:, K - 1] + h * v[:, K - 1] + 0.5 * h * h * a[:, K - 1]
-        over = lambda x, lo, hi: float(max(0.0, (lo - x).max(), (x - hi).max()))  # noqa: E731
-        report = {
-            "min_pair_distance": min_dist,
-            "collision_free": first >= (1 << 63) - 1,
-            "first_violation": None,
-            "acc_violation": over(a, self.acc_min, self.acc_max),
-            "jerk_violation": over(np.diff(a, axis=1) / h, self.jerk_min, self.jerk_max),
-            "vel_violation": max(over(v[:, 1:], self.vel_min, self.vel_max), over(vK, self.vel_min, self.vel_max)),
-            "pos_violation": over(p[:, 1:], np.asarray(self.pos_min, float), np.asarray(self.pos_max, float)),
-            "final_position_error": float(np.abs(pK - pf).max()),
-            "final_velocity_error": float(np.abs(vK - vf).max()),
-        }
-        if not report["collision_free"]:
-            k, q = divmod(first, self.shard.pairs)
-            i, j = pair_from_index(q, N)
-            report["first_violation"] = {"timestep": int(k), "vehicles": (i, j),
-                                         "distance": float(np.linalg.norm(p[i, k] - p[j, k]))}
-        if continuous:
-            report.update(self._continuous_separation(p, v, a, dev, q0, q1))
-        if conflicts:
-            mine = c.list_conflicts(N, K, D, h, self.R, *dev, q0, q1)
-            report["conflicts"] = conflict_windows(self.shard.allgather_records(mine), N, K, h)
-            report["n_conflicts"] = len(report["conflicts"])
-        if clearance:
-            report.update(self._clearance_profiles(dev, q0, q1))
-        if delay is not None:
-            report.update(self._delay_margins(dev, int(delay)))
-        if self._corridor is not None:
-            report["corridor"] = self.validate_corridor(dev=dev if continuous else None)
-        return report
-
-    def validate_corridor(self, tol=0.0, dev=None):
-        """Does every segment of every vehicle of the stored trajectories stay inside its un-shrunk corridor box (set_corridors)
-        over its whole duration, not only at its samples?  Exact per segment and coordinate (scp_check_corridor).  Returns
-        ``vehicles``: a dictionary of length-N arrays ``max_excess`` (the largest distance by which a segment leaves its box in
-        any coordinate; <= 0: inside), ``segment`` (where; -1: none judged), ``n_blocked`` (blocked segments are not judged)
-        and ``n_outside`` (segments with excess > tol); the totals ``n_outside``, ``n_blocked``, ``max_excess``,
-        ``worst_vehicle``; ``inside`` = no segment outside and none blocked; ``check_ms`` (device time).  validate_solution
-        includes it as ``report["corridor"]``.  The cells stay those of the latest set_corridors, also after
-        set_position_boxes(None, None): a plan made without boxes can be judged against them."""
-        if self._corridor is None:
-            raise ValueError("validate_corridor checks the boxes of set_corridors: call it first")
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")
-        c = self._ctx
-        if dev is None:
-            dev = tuple(c.tensor(self.trajectories[k]) for k in ("positions", "velocities", "accelerations"))
-        st = c.check_corridor(self.N, self.K, self.D, self.h, self._corridor["grid"], self._corridor["cells"], *dev, tol=float(tol))
-        seg = np.where(st["segment"] == np.uint32(_hip.NO_INDEX), -1, st["segment"].astype(np.int64))
-        n_out, n_blk = int(st["n_outside"].sum()), int(st["n_blocked"].sum())
-        return {"vehicles": {"max_excess": st["max_excess"].copy(), "segment": seg, "n_blocked": st["n_blocked"].astype(np.int64),
-                             "n_outside": st["n_outside"].astype(np.int64)},
-                "n_outside": n_out, "n_blocked": n_blk, "max_excess": float(st["max_excess"].max()),
-                "worst_vehicle": int(np.argmax(st["max_excess"])), "inside": n_out == 0 and n_blk == 0,
-                "check_ms": c.last_pair_ms()}
-
-    def _obstacle_field(self, who, gap):
-        """the device field of the current obstacles at `gap` (made once per set_obstacles), and the device time it took"""
-        self._one_rank(who)
-        if self._obstacles is None:
-            raise ValueError(f"{who} needs set_obstacles first")
-        if isinstance(gap, bool) or gap not in (0, 1):
-            raise ValueError(f"gap={gap!r}: 0 (between cells) or 1 (between the closed cubes of the cells)")
-        cache = self._obstacles.setdefault("field", {})
-        if gap not in cache:
-            field = self._ctx.obstacle_distance(self.D, self._obstacles["grid"], self._obstacles["occ"], int(gap))
-            cache[gap] = (field, self._ctx.last_pair_ms())
-        return cache[gap]
-
-    def obstacle_distance_field(self, gap=1):
-        """The exact squared distance field of the obstacles (scp_obstacle_distance), in cells: a numpy uint32 array
-        [nz][ny][nx]; entry c = min over the occupied cells o of sum_d max(|c_d - o_d| - gap, 0)^2, 2^32 - 1 everywhere on an
-        empty map.  ``gap=0``: the squared Euclidean distance transform between cells.  ``gap=1``: the squared distance between
-        the closed cubes of the cells, so every point of cell c keeps at least cell * sqrt(field[c]) from the occupied
-        cells -- what obstacle_clearance reduces, and the input for choosing a corridor clearance or for plots.  The device
-        field is computed once per set_obstacles and gap."""
-        field, _ = self._obstacle_field("obstacle_distance_field", gap)
-        return field.cpu().numpy().view(np.uint32)
-
-    def obstacle_clearance(self, pieces=4, dev=None):
-        """How close does every vehicle of the stored trajectories come to the obstacles, where and when?  Judges the plan
-        against the map itself (scp_obstacle_clearance), whatever made the plan: it needs set_obstacles and trajectories, no
-        corridors and no boxes.  Every segment is cut into ``pieces`` (1 .. 16) pieces; a piece's value is the minimum of the
-        gap-1 distance field over the exact range of cells it passes through, so the piece keeps at least that distance.
-        Returns ``vehicles``: a dictionary of length-N arrays ``clearance`` (metres, a guaranteed lower bound: cell *
-        sqrt(min_sq); 0: may touch; inf: nothing judged or an empty map), ``min_sq`` (cells squared; -1 where clearance is
-        inf), ``segment``, ``piece``, ``cell`` (the linear index (z ny + y) nx + x of the cell that attains it; -1: none),
-        ``n_touch`` (pieces whose range holds an occupied cell), ``n_off`` (pieces off the map, not judged) and ``n_wide``
-        (pieces whose range holds more than 4096 cells, not judged: use more pieces); ``steps``: length-K arrays
-        ``clearance`` (the fleet's clearance within every time step) and ``vehicle`` (who attains it, the lowest index on
-        ties; -1 where no piece of the step was judged); the totals ``clearance``, ``worst_vehicle``, ``n_touch``, ``n_off``,
-        ``n_wide``; ``clear`` = no piece touches and none is wide; ``field_ms`` and ``check_ms`` (device time of the field,
-        made once per set_obstacles, and of the pass)."""
-        self._one_rank("obstacle_clearance")
-        if self._obstacles is None:
-            raise ValueError("obstacle_clearance needs set_obstacles first")
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")
-        if isinstance(pieces, bool) or not isinstance(pieces, (int, np.integer)) or not 1 <= pieces <= _hip.OBSTACLE_MAX_PIECES:
-            raise ValueError(f"pieces={pieces!r}: a whole number in [1, {_hip.OBSTACLE_MAX_PIECES}]")
-        c, ob = self._ctx, self._obstacles
-        field, field_ms = self._obstacle_field("obstacle_clearance", 1)
-        if dev is None:
-            dev = tuple(c.tensor(self.trajectories[k]) for k in ("positions", "velocities", "accelerations"))
-        st, step_min = c.obstacle_clearance(self.N, self.K, self.D, self.h, ob["grid"], ob["sat"], field, int(pieces), *dev)
-        check_ms = c.last_pair_ms()
-        cell = float(ob["grid"].cell)
-
-        def metres(sq):  # (sq as int64; DIST_NONE: inf)
-            none = sq == _hip.DIST_NONE
-            return np.where(none, np.inf, cell * np.sqrt(np.where(none, 0, sq).astype(np.float64)))
-
-        sq = st["min_sq"].astype(np.int64)
-        none = sq == _hip.DIST_NONE
-        vehicles = {"clearance": metres(sq), "min_sq": np.where(none, -1, sq),
-                    "segment": np.where(none, -1, st["segment"].astype(np.int64)),
-                    "piece": np.where(none, -1, st["piece"].astype(np.int64)), "cell": st["cell"].astype(np.int64),
-                    "n_touch": st["n_touch"].astype(np.int64), "n_off": st["n_off"].astype(np.int64),
-                    "n_wide": st["n_wide"].astype(np.int64)}
-        step_sq = (step_min >> np.uint64(32)).astype(np.int64)
-        judged = step_min != np.uint64(2**64 - 1)
-        steps = {"clearance": metres(step_sq),
-                 "vehicle": np.where(judged, (step_min & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)}
-        n_touch, n_off, n_wide = (int(vehicles[k].sum()) for k in ("n_touch", "n_off", "n_wide"))
-        return {"vehicles": vehicles, "steps": steps, "clearance": float(vehicles["clearance"].min()),
-                "worst_vehicle": int(np.argmin(vehicles["clearance"])), "n_touch": n_touch, "n_off": n_off, "n_wide": n_wide,
-                "clear": n_touch == 0 and n_wide == 0, "field_ms": field_ms, "check_ms": check_ms}
-
-    def _delay_margins(self, dev, S):
-        """The delay part of validate_solution: one device pass (scp_delay_margins) over this rank's vehicles of the device
-        tensors dev = (positions, velocities, accelerations); the ranks' blocks are concatenated, nothing is merged."""
-        N, K, D, h = self.N, self.K, self.D, self.h
-        a0, a1 = self.shard.agent_range()
-        mine = self._ctx.delay_margins(N, K, D, h, self.R, *dev, S, a0, a1)
-        e = gather_delay_blocks(self.shard, mine, a0).reshape(N, S + 1)
-        some = e["partner"] != np.uint32(_hip.NO_INDEX)
-        n_viol = e["n_violating"].astype(np.int64)
-        partner = np.where(some, e["partner"].astype(np.int64), -1)
-        margin = {"min_distance": e["min_dist"].copy(),
-                  "time": np.where(some, np.where(some, e["segment"], 0).astype(np.float64) * h + e["t_min"], np.nan),
-                  "partner": partner, "n_violating_segments": n_viol}
-        bad = n_viol > 0
-        steps = np.where(bad.any(axis=1), bad.argmax(axis=1), S + 1).astype(np.int64) - 1  # the first violating lag, less one
-        at = np.minimum(steps + 1, S)  # the lag that limits the vehicle (lag S where nothing does)
-        idx = np.arange(N)
-        tolerance = {"steps": steps, "seconds": steps * h, "limited_by": np.where(steps < S, partner[idx, at], -1)}
-        least = None
-        if N > 1:
-            v = int(np.argmin(steps))  # ties: the lowest index
-            least = {"vehicle": v, "steps": int(steps[v]), "seconds": float(steps[v] * h), "partner": int(partner[v, at[v]]),
-                     "time": float(margin["time"][v, at[v]]), "distance": float(margin["min_distance"][v, at[v]])}
-        return {"delay_margin": margin, "delay_tolerance": tolerance, "least_tolerant_vehicle": least}
-
-    def _clearance_profiles(self, dev, q0, q1):
-        """The clearance part of validate_solution: one device pass (scp_clearance_profile) over this rank's pair range of the
-        device tensors dev = (positions, velocities, accelerations), combined entry by entry over the ranks (lexicographic
-        minimum of (distance, row), minimum, integer sum)."""
-        N, K, D, h = self.N, self.K, self.D, self.h
-        pairs = self.shard.pairs
-        out = {}
-        for name, e in zip(("vehicle_clearance", "step_clearance"),
-                           self._ctx.clearance_profile(N, K, D, h, self.R, *dev, q0, q1)):
-            dist, row, t = self.shard.all_argmin_arrays(e["min_dist"], e["row"], e["t_min"])
-            some = row != np.uint64(_hip.NO_ROW)
-            r = np.where(some, row, 0).astype(np.int64)
-            k, q = np.divmod(r, max(pairs, 1))
-            i, j = pairs_from_index(q, N) if pairs else (np.zeros_like(q), np.zeros_like(q))
-            prof = {"min_distance": dist, "time": np.where(some, k * h + t, np.nan)}
-            if name == "vehicle_clearance":
-                prof["timestep"] = np.where(some, k, -1)
-                prof["partner"] = np.where(some, np.where(i == np.arange(N), j, i), -1)
-            else:
-                prof["vehicles"] = np.where(some[:, None], np.stack([i, j], axis=1), -1)
-            prof["sample_min_distance"] = self.shard.all_min(e["sample_min_dist"])
-            prof["n_violating_segments"] = self.shard.all_sum_int(e["n_violating"].astype(np.int64))
-            out[name] = prof
-        vc = out["vehicle_clearance"]
-        out["most_exposed_vehicle"] = None
-        if pairs:
-            best = int(np.argmin(vc["min_distance"]))  # the closest approach of the continuous-time check; of its two vehicles the first
-            out["most_exposed_vehicle"] = {"vehicle": best, "partner": int(vc["partner"][best]), "time": float(vc["time"][best]),
-                                           "distance": float(vc["min_distance"][best])}
-        return out
-
-    def _continuous_separation(self, p, v, a, dev, q0, q1):
-        """The continuous-time part of validate_solution: between two samples a vehicle flies p + t v + t^2/2 a (the
-        kinematics of the stored trajectories), so two vehicles can pass each other inside a segment while every sampled
-        distance is fine.  One device pass (scp_check_separation) over this rank's pair range of the device tensors dev (the
-        host arrays p, v, a uploaded), combined over the ranks."""
-        N, K, D, h = self.N, self.K, self.D, self.h
-        st = self._ctx.check_separation(N, K, D, h, self.R, *dev, q0, q1)
-        min_dist, row, t = self.shard.all_argmin(st["min_dist"], st["argmin_row"], st["argmin_t"])
-        first = self.shard.all_min_int(st["first_violation"])
-        n_viol = self.shard.all_sum_int(st["n_violating"])
-
-        def where(r):
-            k, q = divmod(int(r), self.shard.pairs)
-            return int(k), pair_from_index(q, N)
-
-        out = {"min_pair_distance_continuous": min_dist, "collision_free_continuous": n_viol == 0,
-               "n_violating_segments": n_viol, "first_violation_continuous": None, "closest_approach": None}
-        if self.shard.pairs and row < (1 << 63) - 1:
-            k, (i, j) = where(row)
-            out["closest_approach"] = {"timestep": k, "time": k * h + t, "vehicles": (i, j), "distance": min_dist}
-        if n_viol:
-            k, (i, j) = where(first)
-            m, t1 = segment_min_distance(p[i, k] - p[j, k], v[i, k] - v[j, k], a[i, k] - a[j, k], h)
-            out["first_violation_continuous"] = {"timestep": k, "time": k * h + t1, "vehicles": (i, j), "distance": m}
-        return out
-
-    # ------------------------------------------------------------------------------------------------
-    # repair of between-sample conflicts (not in the reference): holds, DESIGN.md section 3.7
-    # ------------------------------------------------------------------------------------------------
-    def repair_conflicts(self, max_passes=6, pad=0.02, max_iterations=15):
-        """Remove the between-sample conflicts of the stored trajectories (what validate_solution(continuous=True,
-        conflicts=True) lists) by HOLDS: for every conflicting segment the two collision rows at its ends are replaced by one
-        fixed half-plane eta . (p_i - p_j) >= R + margin, eta the direction of the closest approach, which keeps the pair
-        apart over the whole segment (include/scp_hip.h, scp_update_holds).  A PASS lists the conflicts, updates the table
-        of holds (a conflict that persists raises its margin by its shortfall + pad), re-runs the SCP loop from the stored
-        accelerations (at most max_iterations iterations, to the usual relative-step tolerance) and lists again.  Passes
-        repeat until no conflict is left, max_passes have run, or a QP of the pass ends with a status other than solved /
-        solved inaccurate -- then the trajectories from before that pass are kept.
-
-        Always the Python-driven, row-writing loop (the planes of all rows, 24 B per row, are allocated), whatever `native` /
-        `row_free` say; one rank only.  ``self.trajectories`` becomes the last accepted pass.  Returns (and stores in
-        ``last_info["repair"]``) a dictionary: ``conflicts_before`` and ``conflicts_per_pass`` (violating segments, the records
-        of scp_list_conflicts), ``passes``, ``holds``, ``repaired`` (no conflict left), ``stopped_by`` ("clean", "max_passes"
-        or "qp_status"), ``cost_ratio`` (sum of squared accelerations after / before), ``time_sec``; per pass also
-        ``iterations_per_pass``, ``admm_steps_per_pass``, ``update_holds_ms`` and ``apply_holds_ms`` (device time of the
-        table update and of the pass's last plane overwrite).  Without a conflict it returns at once with passes = 0 and
-        leaves the trajectories untouched."""
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")
-        if self.shard.world != 1:
-            raise ValueError("repair_conflicts supports one rank only (world_size == 1)")
-        t_start = time.perf_counter()
-        N, K, D, h, c = self.N, self.K, self.D, self.h, self._ctx
-        p0, v0, pf, vf = self._states()
-        traj = self.trajectories
-        acc = c.tensor(traj["accelerations"])
-        dev = (c.tensor(traj["positions"]), c.tensor(traj["velocities"]), acc)
-        cost_before = float(np.sum(traj["accelerations"] ** 2))
-        found = c.list_conflicts(N, K, D, h, self.R, *dev)
-        info = {"conflicts_before": int(found.size), "conflicts_per_pass": [], "passes": 0, "holds": 0, "repaired": found.size == 0,
-                "stopped_by": "clean" if found.size == 0 else "max_passes", "cost_ratio": 1.0, "iterations_per_pass": [],
-                "admm_steps_per_pass": [], "update_holds_ms": [], "apply_holds_ms": []}
-        if found.size and max_passes > 0:
-            self._ensure_qp().set_problem(self._limits(), self._space(), p0, v0, pf, vf)
-            self._apply_boxes(self._qp)
-            self._rho_start = 0.0
-            table, n_holds = c.hold_table(capacity=max(1024, 4 * found.size))
-        try:
-            while found.size and info["passes"] < max_passes:
-                table, n_holds, info["holds"] = c.update_holds(N, K, D, h, self.R, *dev, found, table, n_holds, pad)
-                info["update_holds_ms"].append(c.last_pair_ms())
-                self._holds = (table, n_holds)
-                x, iterations, steps, ok = acc, 0, 0, True
-                while iterations < max_iterations:
-                    new = self._solve_with_avoidance_constraints(x)
-                    iterations += 1
-                    steps += int(self._last_qp_info["iter"])
-                    ok = self._last_qp_info["status_val"] in (1, 2)
-                    if not ok:
-                        break
-                    _, _, rel = c.rel_step(new, x)
-                    x = new
-                    if rel <= self.convergence_tolerance:
-                        break
-                info["passes"] += 1
-                info["iterations_per_pass"].append(iterations)
-                info["admm_steps_per_pass"].append(steps)
-                info["apply_holds_ms"].append(float(self._pairs.last_holds_ms))
-                if not ok:
-                    info["stopped_by"] = "qp_status"
-                    break
-                pos, vel = self._kinematics(x)
-                acc, dev = x, (pos, vel, x)
-                found = c.list_conflicts(N, K, D, h, self.R, *dev)
-                info["conflicts_per_pass"].append(int(found.size))
-                self.trajectories = {"positions": pos.cpu().numpy(), "velocities": vel.cpu().numpy(),
-                                     "accelerations": x.cpu().numpy()}
-                if found.size == 0:
-                    info["repaired"], info["stopped_by"] = True, "clean"
-        finally:
-            self._holds = None
-        info["cost_ratio"] = float(np.sum(self.trajectories["accelerations"] ** 2)) / cost_before if cost_before > 0 else 1.0
-        info["time_sec"] = time.perf_counter() - t_start
-        self.last_info["repair"] = info
-        return info
-
-    # ------------------------------------------------------------------------------------------------
-    # staggered starts (not in the reference): pair-lag masks and a greedy launch schedule, DESIGN.md section 3.7
-    # ------------------------------------------------------------------------------------------------
-    def stagger_starts(self, max_delay, order=None, *, search=0, rounds=1, seed=0, objective="makespan"):
-        """Remove the between-sample conflicts of the stored trajectories WITHOUT changing a plan: some vehicles start a few
-        whole steps later, at most ``max_delay`` (an int in [0, min(K, 63)]).  One device pass computes, for every ordered pair
-        and every lag, whether the pair conflicts when the first vehicle starts that many steps after the second
-        (scp_lag_conflicts); a greedy schedule then takes the vehicles in ``order`` (a permutation of 0 .. N-1; None: by
-        index) and gives each the smallest delay that conflicts with nobody placed before it (scp_schedule_starts), -1 if
-        there is none -- such a vehicle is unplaced, flies undelayed and is reported.  No QP is solved, so this also serves
-        plans of ``generate_trajectories(max_iterations=0)`` and fleets whose joint QP fails.  One rank only.
-
-        ``self.trajectories`` is left untouched; the staggered fleet -- arrays (N, K + Dmax, D), Dmax the largest delay, every
-        vehicle held at its start before it leaves and parked at its goal after it has arrived -- is stored as
-        ``self.staggered`` ({"positions", "velocities", "accelerations", "delays"}) and judged by the continuous-time check.
-        Returns (and stores in ``last_info["stagger"]``) a dictionary: ``delays`` (int array, -1: unplaced), ``scheduled`` (every
-        vehicle placed), ``n_delayed``, ``n_unplaced``, ``max_delay``, ``total_delay``, ``conflicts_before`` /
-        ``conflicts_after`` (violating segments of the stored and of the staggered fleet, scp_check_separation),
-        ``min_distance_after``, ``horizon_steps`` (K + Dmax), ``lag_conflicts_ms`` / ``schedule_ms`` (device time of the two
-        calls) and ``time_sec``.
-
-        The greedy schedule depends on the order it takes the vehicles in.  ``search=B`` (an int in [1, 65535]; 0: the one order
-        above) schedules B candidate orders per round in one launch each (scp_schedule_starts_batch) and keeps the best under
-        ``objective`` -- "makespan": fewest unplaced vehicles, then the smallest largest delay, then the smallest total delay;
-        "total": fewest unplaced, then total, then largest.  Round 0 takes ``candidate_orders(N, B, default_rng(seed),
-        base=order)``, every later one of ``rounds`` takes ``refined_orders`` of the best so far; a later round replaces the
-        best only by a strictly smaller key, and the search stops when nobody is unplaced or delayed.  Candidate 0 of round 0 is
-        ``order`` itself, so the result is never worse than without the search.  The masks are computed once.  The info then
-        also has ``search``: ``candidates``, ``rounds_run``, ``best_round``, ``best_candidate``, ``best_order``, ``baseline``
-        (``n_unplaced`` / ``max_delay`` / ``total_delay`` / ``n_delayed`` of ``order``), ``improved`` and ``objective``;
-        ``schedule_ms`` is the sum over the rounds."""
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")
-        if self.shard.world != 1:
-            raise ValueError("stagger_starts supports one rank only (world_size == 1)")
-        top = min(self.K, _hip.MAX_LAG)
-        if isinstance(max_delay, bool) or not isinstance(max_delay, (int, np.integer)) or not 0 <= max_delay <= top:
-            raise ValueError(f"max_delay={max_delay!r}: the largest delay is a whole number of steps in [0, min(K, 63) = {top}]")
-        if self.N > _hip.SCHEDULE_MAX_N:
-            raise ValueError(f"stagger_starts schedules at most {_hip.SCHEDULE_MAX_N} vehicles")
-        if order is not None:
-            order = np.asarray(order, dtype=np.int64).reshape(-1)
-            if order.size != self.N or not np.array_equal(np.sort(order), np.arange(self.N)):
-                raise ValueError("order must be a permutation of 0 .. N-1")
-        if isinstance(search, bool) or not isinstance(search, (int, np.integer)) or not 0 <= search <= _hip.SCHEDULE_MAX_BATCH:
-            raise ValueError(f"search={search!r}: the candidate orders per round are an int in [0, {_hip.SCHEDULE_MAX_BATCH}]")
-        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or rounds < 1:
-            raise ValueError(f"rounds={rounds!r}: an int >= 1")
-        if objective not in _hip.SCHEDULE_OBJECTIVES:
-            raise ValueError(f"objective={objective!r}: one of {sorted(_hip.SCHEDULE_OBJECTIVES)}")
-        t_start = time.perf_counter()
-        N, K, D, h, c = self.N, self.K, self.D, self.h, self._ctx
-        S = int(max_delay)
-        host = tuple(self.trajectories[k] for k in ("positions", "velocities", "accelerations"))
-        dev = tuple(c.tensor(x) for x in host)
-        before = c.check_separation(N, K, D, h, self.R, *dev)
-        mask = c.lag_conflicts(N, K, D, h, self.R, *dev, S, device=True)
-        lag_ms = c.last_pair_ms()
-        if search:
-            delays, st, schedule_ms, found = self._search_start_orders(mask, S, order, int(search), int(rounds), seed, objective)
-        else:
-            delays, st = c.schedule_starts(mask, S, order)
-            schedule_ms = c.last_pair_ms()
-        pos, vel, acc = staggered_fleet(*host, h, delays)
-        horizon = pos.shape[1]
-        after = c.check_separation(N, horizon, D, h, self.R, c.tensor(pos), c.tensor(vel), c.tensor(acc))
-        self.staggered = {"positions": pos, "velocities": vel, "accelerations": acc, "delays": delays.astype(np.int64)}
-        info = {"delays": delays.astype(np.int64), "scheduled": st["n_unplaced"] == 0, "n_delayed": st["n_delayed"],
-                "n_unplaced": st["n_unplaced"], "max_delay": st["max_delay"], "total_delay": st["total_delay"],
-                "conflicts_before": int(before["n_violating"]), "conflicts_after": int(after["n_violating"]),
-                "min_distance_after": float(after["min_dist"]), "horizon_steps": int(horizon), "lag_conflicts_ms": lag_ms,
-                "schedule_ms": schedule_ms, "time_sec": time.perf_counter() - t_start}
-        if search:
-            info["search"] = found
-        self.last_info["stagger"] = info
-        return info
-
-    def _search_start_orders(self, mask, S, order, B, rounds, seed, objective):
-        """the order search of stagger_starts on the device masks: (delays, stats, device ms, the info's "search" entry)"""
-        c, N = self._ctx, self.N
-        rng = np.random.default_rng(seed)
-        fields = ("n_delayed", "n_unplaced", "max_delay", "first_unplaced", "total_delay")
-        best = None  # (key, order, delays, stats, round, candidate)
-        ms = 0.0
-        for r in range(rounds):
-            orders = candidate_orders(N, B, rng, base=order) if r == 0 else refined_orders(best[1], best[2], B, rng)
-            delays, stats, b = c.schedule_starts_batch(mask, S, orders, objective)
-            ms += c.last_pair_ms()
-            st = {f: int(stats[f][b]) for f in fields}
-            key = schedule_key(st["n_unplaced"], st["max_delay"], st["total_delay"], objective)
-            if r == 0:
-                baseline = {f: int(stats[f][0]) for f in ("n_unplaced", "max_delay", "total_delay", "n_delayed")}
-                base_key = schedule_key(baseline["n_unplaced"], baseline["max_delay"], baseline["total_delay"], objective)
-            if best is None or key < best[0]:
-                best = (key, orders[b].copy(), delays[b].copy(), st, r, b)
-            if best[0] == (0, 0, 0):
-                break
-        found = {"candidates": B, "rounds_run": r + 1, "best_round": best[4], "best_candidate": best[5],
-                 "best_order": best[1].astype(np.int64), "baseline": baseline, "improved": best[0] < base_key,
-                 "objective": objective}
-        return best[2], best[3], ms, found
-
-    # ------------------------------------------------------------------------------------------------
     # visualisation passthroughs (scp.py:644-840): host-side matplotlib over the stored numpy trajectories
     # ------------------------------------------------------------------------------------------------
     def visualize_trajectories(self, show_animation=False, save_path="trajectories.pdf"):
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")  # scp.py:646-647
+        self._require("visualize_trajectories", trajectories=True)  # scp.py:646-647
         from ..viz.plot_trajectories import plot_trajectories
 
         return plot_trajectories(self, show=show_animation, save_path=save_path)
 
     def visualize_time_snapshots(self, num_snapshots=5, save_path=None):
-        if self.trajectories is None:
-            raise ValueError("Trajectories not generated yet")  # scp.py:782-783
+        self._require("visualize_time_snapshots", trajectories=True)  # scp.py:782-783
         from ..viz.plot_trajectories import plot_time_snapshots
 
         return plot_time_snapshots(self, num_snapshots=num_snapshots, save_path=save_path)
-
-
-def segment_min_distance(d, w, b, h):
-    """Minimum over t in [0, h] of ||d + t w + t^2/2 b|| for ONE pair and segment, and the t it is attained at (host helper
-    of validate_solution(continuous=True): the report's details for a row the device pass has already picked).  The squared
-    distance is a quartic; its minimum is at 0, at h or at a real root of its derivative inside (0, h)."""
-    d, w, b = (np.asarray(x, dtype=np.float64) for x in (d, w, b))
-    c = [d @ d, 2.0 * (d @ w), w @ w + d @ b, w @ b, 0.25 * (b @ b)]
-    f = lambda t: c[0] + t * (c[1] + t * (c[2] + t * (c[3] + t * c[4])))  # noqa: E731
-    cand = [0.0, float(h)]
-    der = np.trim_zeros([4.0 * c[4], 3.0 * c[3], 2.0 * c[2], c[1]], "f")
-    if len(der) > 1:
-        # the real part of every root, clipped: a point of [0, h] can only over-estimate the minimum, a real root is kept as it is
-        cand += [float(min(max(r.real, 0.0), h)) for r in np.roots(der)]
-    vals = [f(t) for t in cand]
-    m = int(np.argmin(vals))
-    return float(np.sqrt(max(vals[m], 0.0))), cand[m]
-
-
-def pair_from_index(q, N):
-    """Lexicographic pair index -> (i, j), i < j (host helper, exact integer arithmetic)."""
-    i = int(((2 * N - 1) - np.sqrt(float((2 * N - 1) ** 2 - 8 * q))) // 2)
-    i = max(0, min(i, N - 2))
-    off = lambda a: a * (2 * N - a - 1) // 2
-    while off(i) > q:
-        i -= 1
-    while i < N - 2 and off(i + 1) <= q:
-        i += 1
-    return i, int(q - off(i) + i + 1)

@@ -169,6 +169,25 @@ def test_no_cpu_fallback():
         SCP(n_vehicles=2, time_horizon=1.0, time_step=0.2, min_distance=0.5, verbose=False)
 
 
+def test_scp_bases_do_not_shadow_each_other():
+    """SCP is one class assembled from state-free bases: a method name defined in two of them (or in a base and in SCP itself)
+    would silently hide one definition, and a base with an __init__ would run instead of, or be hidden by, SCP's."""
+    from path_planning.solvers.scp import SCP
+
+    bases = SCP.__bases__
+    assert [b.__name__ for b in bases] == ["ObstacleMethods", "ValidationMethods", "FleetMethods"]
+    owners = {}
+    for cls in (SCP,) + bases:
+        for name in vars(cls):
+            if not (name.startswith("__") and name.endswith("__")) or name == "__init__":
+                owners.setdefault(name, []).append(cls.__name__)
+    assert {n: o for n, o in owners.items() if len(o) > 1} == {}
+    assert owners["__init__"] == ["SCP"]
+    for b in bases:
+        assert b.__bases__ == (object,)
+        assert not [n for n, v in vars(b).items() if not n.startswith("__") and not callable(v) and not isinstance(v, staticmethod)]
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "ba-path-planning_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -172,7 +172,7 @@ def test_python_surface_and_argument_errors():
     for call in (s.obstacle_distance_field, s.obstacle_clearance):
         with pytest.raises(ValueError, match="set_obstacles"):
             call()
-    s._obstacles = {"grid": None}
+    s._obstacles = object()
     with pytest.raises(ValueError, match="not generated"):
         s.obstacle_clearance()
     s.trajectories = {}

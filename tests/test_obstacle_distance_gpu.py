@@ -144,9 +144,9 @@ def test_a_plan_with_searched_corridors_is_clear_of_the_map():
           f"(vehicle {rep['worst_vehicle']}), n_touch {rep['n_touch']}, per vehicle {rep['vehicles']['clearance'].tolist()}")
     assert co["inside"] and rep["clear"] and rep["n_touch"] == 0
     _check_report(s, rep, 4)
-    assert "field" in s._obstacles
+    assert 1 in s._obstacles.fields
     s.set_obstacles(*E.grid())  # a new map drops the cached field
-    assert "field" not in s._obstacles
+    assert 1 not in s._obstacles.fields
     s.close()
 
 

@@ -130,7 +130,7 @@ def test_find_reference_api(ctx):
     np.testing.assert_array_equal(info["status"], want["info"]["status"])
     np.testing.assert_array_equal(info["n_nodes"], want["info"]["n_nodes"])
     assert info["edges_ms"] > 0 and info["search_ms"] > 0
-    assert s.find_reference()[1]["edges_ms"] == 0.0 and list(s._obstacles["edges"]) == [(2, 0)]  # the masks are cached
+    assert s.find_reference()[1]["edges_ms"] == 0.0 and list(s._obstacles.edge_masks) == [(2, 0)]  # the masks are cached
     for bad in (dict(stride=0), dict(stride=2.0), dict(clearance=-1), dict(max_path=0), dict(max_path=401), dict(stride=41)):
         with pytest.raises(ValueError):
             s.find_reference(**bad)
@@ -157,7 +157,7 @@ def test_find_reference_api(ctx):
     assert short.find_reference()[1]["stride"] == 3  # 40 / 3 <= 18
     short.close()
     s.set_obstacles(occ, origin, cell)
-    assert "edges" not in s._obstacles  # a new map drops the cached masks
+    assert not s._obstacles.edge_masks  # a new map drops the cached masks
     s.close()
 
 
