@@ -72,7 +72,7 @@ struct scp_ctx {
   int stg_batch_threads;          // threads per workgroup of scp_schedule_starts_batch: 0 chosen by the call, 256 or 1024
   int stg_batch_transposed;       // it reads the masks' columns from a transposed copy it makes in sep_ws: -1 chosen by the
                                   // call (from 16 candidates on), 0 never, 1 always
-  int ref_path_threads;           // threads per workgroup of scp_reference_paths: 0 chosen by the call, 256, 512 or 1024
+  int ref_path_threads;           // threads per workgroup of scp_reference_paths and the weighted searches: 0 chosen by the call, 256, 512 or 1024
   int shorten_threads;            // threads per workgroup of scp_shorten_paths: 0 chosen by the call, 64, 128 or 256
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;

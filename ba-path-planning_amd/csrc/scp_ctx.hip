@@ -111,7 +111,7 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
     ctx->stg_batch_transposed = value;
     return SCP_OK;
   }
-  if (strcmp(key, "ref_path_threads") == 0) {  // scp_reference_paths (same results; tests/test_reference_path_gpu.py compares them)
+  if (strcmp(key, "ref_path_threads") == 0) {  // scp_reference_paths and the weighted searches (same results; the GPU tests compare them)
     if (value != 0 && value != 256 && value != 512 && value != 1024)
       return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0, 256, 512 or 1024)", key, value);
     ctx->ref_path_threads = value;

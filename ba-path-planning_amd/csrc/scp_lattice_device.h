@@ -1,5 +1,6 @@
-// The search lattice shared by scp_reference.hip, scp_lattice_dist.hip and scp_shorten.hip: its shape, node coordinates, the
-// node of a point, the directions, the level-by-level search, block centres and the vertices of a lattice path (the rules
+// The search lattice shared by scp_reference.hip, scp_lattice_dist.hip, scp_lattice_weighted.hip and scp_shorten.hip: its
+// shape, node coordinates, the node of a point, the directions, the level-by-level search, the weighted relaxation, block
+// centres, the vertices of a lattice path and the reference points along it (the rules
 // are stated in include/scp_hip.h, "reference paths by a lattice search").
 #pragma once
 #include "scp_common.h"
@@ -13,6 +14,7 @@ struct Lattice {
 
 constexpr int LATTICE_SELF = 13;  // the direction code of the node itself
 constexpr unsigned DIST_UNREACHED = 0xFFFFu;
+constexpr uint32_t COST_UNREACHED = 0xFFFFFFFFu;  // the weighted search (scp_lattice_weighted.hip)
 
 // direction order: the codes other than 13 by |dx| + |dy| + |dz|, then by code
 struct DirectionOrder {
@@ -27,6 +29,21 @@ struct DirectionOrder {
   }
 };
 static __constant__ DirectionOrder DIRECTION_ORDER;
+
+// twice the move weight W[|dx| + |dy| + |dz|] of every direction code (W = 70, 99, 121; 0 for the node itself)
+struct MoveCost {
+  uint32_t twice[27];
+  constexpr MoveCost() : twice{} {
+    constexpr uint32_t W[4] = {0, 70, 99, 121};
+    for (int n = 0; n < 27; ++n) twice[n] = 2 * W[(n % 3 != 1) + ((n / 3) % 3 != 1) + (n / 9 != 1)];
+  }
+};
+static __constant__ MoveCost MOVE_COST;
+
+// the cost w of the edge between two neighbours a and b, n the direction code from one to the other (pen NULL: zeros)
+__device__ inline uint32_t edge_cost(const uint32_t* __restrict__ pen, int a, int b, int n) {
+  return MOVE_COST.twice[n] + (pen ? pen[a] + pen[b] : 0u);
+}
 
 // the id offset of the neighbour in direction n
 __device__ inline int direction_offset(const Lattice& lt, int n) {
@@ -57,6 +74,25 @@ __device__ inline int passable_node_of(const Lattice& lt, const CorridorGrid& g,
   int node = -1;
   if (!node_of<D>(lt, g, p, node)) return -1;
   return (edges[node] >> LATTICE_SELF & 1u) ? node : -1;
+}
+
+// Status 0, 1 or 2 of a vehicle's end points (scp_reference_paths): 1 if the start lies off the lattice or is not passable,
+// 2 the same for the goal, tested only if the start passed.  start / goal: the node's id wherever the point lies on the
+// lattice and was tested, else -1.
+template <int D>
+__device__ inline int path_endpoints(const Lattice& lt, const CorridorGrid& g, const uint32_t* __restrict__ edges, const double* a0,
+                                     const double* af, int& start, int& goal) {
+  goal = -1;
+  if (!node_of<D>(lt, g, a0, start)) {
+    start = -1;
+    return 1;
+  }
+  if (!(edges[start] >> LATTICE_SELF & 1u)) return 1;
+  if (!node_of<D>(lt, g, af, goal)) {
+    goal = -1;
+    return 2;
+  }
+  return (edges[goal] >> LATTICE_SELF & 1u) ? 0 : 2;
 }
 
 // The breadth-first search of one workgroup (every thread calls it with the same arguments), level by level from `origin`
@@ -111,6 +147,62 @@ __device__ __forceinline__ void lattice_search(const Lattice& lt, const uint32_t
   }
 }
 
+// The weighted search of one workgroup (every thread calls it with the same arguments): sweeps from `origin` with
+// cost[origin] = 0 and every other entry COST_UNREACHED on entry, behind a barrier.  Pull form: a thread owns the nodes it
+// writes; a passable node reads its neighbours over its set edge bits and stores min(own, cost[nb] + w), w = edge_cost.  No two threads write one word and a 32-bit LDS read does not tear, so
+// a racing read sees an older or a newer upper bound: every stored value is the cost of a real walk (a simple one: a walk
+// back through the node costs more than the node holds), values only fall, and a sweep that changes nothing has read final
+// values everywhere -- the fixed point, which is the shortest-cost field whatever the schedule.  With weight * prefer <=
+// 32768 an edge costs at most 65778 and a simple path at most 32767 of them, so no sum (a candidate included) wraps.
+// The growing box of lattice_search holds here too: a node reachable in k moves lies within k of the origin per coordinate,
+// so sweep k walks the box of k + 1; if it changes nothing, the box's outer shell is unreached and nothing beyond it can be
+// reached.  Flags as in lattice_search (slot sweep mod 3 of `changed`, zero on entry); one barrier per sweep, at most
+// `nodes` sweeps (sweep k leaves every node at least as good as k + 1 synchronous Bellman-Ford rounds).
+__device__ __forceinline__ void lattice_relax(const Lattice& lt, const uint32_t* __restrict__ edges, const uint32_t* __restrict__ pen,
+                                              uint32_t* cost, int* changed_flag, int origin, bool go) {
+  const int tid = threadIdx.x, T = blockDim.x;
+  const int G[3] = {origin % lt.L[0], (origin / lt.L[0]) % lt.L[1], origin / (lt.L[0] * lt.L[1])};
+  for (int sweep = 0; sweep < lt.nodes && go; ++sweep) {  // (go is the same in every thread)
+    const int slot = sweep % 3;
+    int lo[3], w[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      lo[d] = G[d] - (sweep + 1) > 0 ? G[d] - (sweep + 1) : 0;
+      const int hi = G[d] + (sweep + 1) < lt.L[d] - 1 ? G[d] + (sweep + 1) : lt.L[d] - 1;
+      w[d] = hi - lo[d] + 1;
+    }
+    const int count = w[0] * w[1] * w[2];
+    const bool whole = count == lt.nodes;
+    bool changed = false;
+    for (int idx = tid; idx < count; idx += T) {
+      const int node = whole ? idx : ((lo[2] + idx / (w[0] * w[1])) * lt.L[1] + lo[1] + (idx / w[0]) % w[1]) * lt.L[0] + lo[0] + idx % w[0];
+      uint32_t m = edges[node];
+      if (!(m >> LATTICE_SELF & 1u)) continue;
+      m &= ~(1u << LATTICE_SELF) & 0x7FFFFFFu;
+      const uint32_t own = cost[node];
+      uint32_t best = own;
+      while (m) {
+        const int n = __ffs(m) - 1;
+        m &= m - 1;
+        const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
+        if ((unsigned)nb >= (unsigned)lt.nodes) continue;
+        const uint32_t c = cost[nb];
+        if (c == COST_UNREACHED) continue;
+        const uint32_t via = c + edge_cost(pen, node, nb, n);
+        best = via < best ? via : best;
+      }
+      if (best < own) {
+        cost[node] = best;
+        changed = true;
+      }
+    }
+    if (changed) changed_flag[slot] = 1;
+    __syncthreads();
+    go = changed_flag[slot] != 0;
+    if (tid == 0) changed_flag[(sweep + 2) % 3] = 0;
+  }
+}
+
 // coordinate d of a node
 __device__ inline int lattice_coord(const Lattice& lt, int node, int d) {
   return d == 0 ? node % lt.L[0] : d == 1 ? (node / lt.L[0]) % lt.L[1] : node / (lt.L[0] * lt.L[1]);
@@ -132,6 +224,32 @@ __device__ inline double reference_vertex(const Lattice& lt, const CorridorGrid&
   if (t == 0) return p0[d];
   if (t == m + 1) return pf[d];
   return lattice_centre(lt, g, path[t - 1], d);
+}
+
+// The K + 1 reference points of vehicle i along p0, the centres of its path's m nodes, pf (the rule "reference points" of
+// include/scp_hip.h), written side by side by the workgroup's threads: the hop search and the weighted search share it.
+template <int D>
+__device__ __forceinline__ void write_reference_points(const Lattice& lt, const CorridorGrid& g, int K, const int32_t* my_path, int m,
+                                                       const double* a0, const double* af, double* ref_i) {
+#pragma clang fp contract(off)
+  const int tid = threadIdx.x, T = blockDim.x;
+  const int64_t E = (int64_t)m + 1;
+  for (int j = tid; j <= K; j += T) {
+    const int64_t q = (int64_t)j * E / K, r = (int64_t)j * E % K;
+    double* out = ref_i + (int64_t)j * D;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const double v0 = reference_vertex(lt, g, my_path, m, a0, af, (int)q, d);
+      if (q == E) {
+        out[d] = v0;
+      } else {
+        const double v1 = reference_vertex(lt, g, my_path, m, a0, af, (int)q + 1, d);
+        const double w = (double)r / (double)K;
+        const double step = w * (v1 - v0);
+        out[d] = v0 + step;
+      }
+    }
+  }
 }
 
 // the lattice of a grid; SCP_ERR_INVALID with a message where it is not supported

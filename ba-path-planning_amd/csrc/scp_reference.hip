@@ -62,21 +62,8 @@ __global__ __launch_bounds__(1024) void reference_paths_kernel(int K, Lattice lt
 
   // start and goal: decided once, by one thread
   if (tid == 0) {
-    int start = -1, goal = -1, status = 0;
-    if (!node_of<D>(lt, g, a0, start)) {
-      start = -1;
-      status = 1;
-    } else if (!(edges[start] >> LATTICE_SELF & 1u)) {
-      status = 1;
-    }
-    if (status == 0) {
-      if (!node_of<D>(lt, g, af, goal)) {
-        goal = -1;
-        status = 2;
-      } else if (!(edges[goal] >> LATTICE_SELF & 1u)) {
-        status = 2;
-      }
-    }
+    int start = -1, goal = -1;
+    const int status = path_endpoints<D>(lt, g, edges, a0, af, start, goal);
     ctl[CTL_STATUS] = status;
     ctl[CTL_START] = start;
     ctl[CTL_GOAL] = goal;
@@ -142,26 +129,7 @@ __global__ __launch_bounds__(1024) void reference_paths_kernel(int K, Lattice lt
   if (ctl[CTL_STATUS] != 0) return;
 
   // the reference points, side by side
-  {
-#pragma clang fp contract(off)
-    const int64_t E = (int64_t)m + 1;
-    for (int j = tid; j <= K; j += T) {
-      const int64_t q = (int64_t)j * E / K, r = (int64_t)j * E % K;
-      double* out = ref + (i * (K + 1) + j) * D;
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        const double v0 = reference_vertex(lt, g, my_path, m, a0, af, (int)q, d);
-        if (q == E) {
-          out[d] = v0;
-        } else {
-          const double v1 = reference_vertex(lt, g, my_path, m, a0, af, (int)q + 1, d);
-          const double w = (double)r / (double)K;
-          const double step = w * (v1 - v0);
-          out[d] = v0 + step;
-        }
-      }
-    }
-  }
+  write_reference_points<D>(lt, g, K, my_path, m, a0, af, ref + i * (K + 1) * D);
 }
 
 }  // namespace

@@ -237,6 +237,9 @@ class PathInfo(C.Structure):
 PATH_INFO_DTYPE = np.dtype(PathInfo)
 LATTICE_MAX_NODES = 32768     # SCP_LATTICE_MAX_NODES: scp_lattice_edges, scp_reference_paths
 HOPS_UNREACHED = 0xFFFF       # scp_lattice_distances: no path, or a point without a node
+COST_UNREACHED = 0xFFFFFFFF   # scp_reference_paths_weighted, scp_lattice_costs: no path, or a point without a node
+MOVE_WEIGHTS = (70, 99, 121)  # W[1 .. 3] of the weighted search: a straight move, a diagonal one in a plane, one in space
+PENALTY_MAX_PRODUCT = 32768   # SCP_PENALTY_MAX_PRODUCT: the largest weight * prefer of scp_lattice_penalties
 PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that is not free",
                2: "the goal lies off the lattice or on a block that is not free", 3: "the goal cannot be reached from the start",
                4: "the path has more nodes than max_path"}
@@ -382,6 +385,9 @@ PROTOTYPES = {
     "scp_shorten_paths": (i32, [vp, i32, i32, i32, pg, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
     "scp_obstacle_distance": (i32, [vp, i32, pg, vp, i32, vp]),
     "scp_obstacle_clearance": (i32, [vp, i32, i32, i32, f64, pg, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_lattice_penalties": (i32, [vp, i32, pg, vp, i32, i32, i32, vp]),
+    "scp_reference_paths_weighted": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+    "scp_lattice_costs": (i32, [vp, i32, pg, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
     "scp_gemm_f64": (i32, [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]),
     "scp_qp_peek": (i32, [vp, cstr, vp, i64, P(i64)]),
     "scp_qp_debug_set": (i32, [vp, cstr, i32]),
@@ -499,8 +505,8 @@ class Context:
         per workgroup of delay_margins and of lag_conflicts, 0: chosen by the call; results never depend on them),
         "stg_batch_threads" (threads per workgroup of schedule_starts_batch: 0 chosen by the call, 256 or 1024; likewise),
         "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
-        never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths: 0 chosen by the call, 256,
-        512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
+        never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths, reference_paths_weighted
+        and lattice_costs: 0 chosen by the call, 256, 512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
         256; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
@@ -968,6 +974,52 @@ class Context:
                                                   src.data_ptr(), n_dst, dst.data_ptr(), hops.data_ptr(), src_node.data_ptr(),
                                                   dst_node.data_ptr(), _ptr(dist)))
         return hops, src_node, dst_node, dist
+
+    # ---- static obstacles: weighted search ----------------------------------------------------------------------------------
+    def lattice_penalties(self, D, grid: OccupancyGrid, field, stride, prefer, weight):
+        """scp_lattice_penalties: field as obstacle_distance made it with gap = 1 -> the node penalties weight * (prefer -
+        min(rho, prefer)), an int32 device tensor [nodes] holding the uint32 words.  No host read."""
+        torch = _torch()
+        pen = torch.empty(lattice_nodes(D, grid, stride), dtype=torch.int32, device=self.tdev)
+        self.check(self.lib.scp_lattice_penalties(self.h, int(D), C.byref(grid), _ptr(field), int(stride), int(prefer),
+                                                  int(weight), pen.data_ptr()))
+        return pen
+
+    def reference_paths_weighted(self, N, K, D, grid: OccupancyGrid, stride, edges, p0, pf, max_path, ref, pen=None,
+                                 want_path=True, want_cost=False):
+        """scp_reference_paths_weighted: the arguments of reference_paths and pen (as lattice_penalties made it with the same
+        stride; None: no penalties); ref is updated IN PLACE for the vehicles whose path was found.  Returns (path (N,
+        max_path) int32 device tensor or None, info as a uint8 device tensor of N records of PATH_INFO_DTYPE, path_cost (N,)
+        int32 device tensor holding the uint32 words -- COST_UNREACHED without a path --, cost (N, nodes) int32 device tensor
+        holding the uint32 words or None, n_failed int64 device tensor of one word).  No host read."""
+        torch = _torch()
+        nodes = lattice_nodes(D, grid, stride)
+        path = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_path else None
+        cost = torch.empty((max(N, 1), nodes), dtype=torch.int32, device=self.tdev) if want_cost else None
+        path_cost = torch.empty(max(N, 1), dtype=torch.int32, device=self.tdev)
+        info = self._record_buffer(N, PATH_INFO_DTYPE)
+        n_failed = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_reference_paths_weighted(self.h, N, K, D, C.byref(grid), int(stride), _ptr(edges), _ptr(pen),
+                                                         p0.data_ptr(), pf.data_ptr(), int(max_path), ref.data_ptr(), _ptr(path),
+                                                         info.data_ptr(), path_cost.data_ptr(), _ptr(cost), n_failed.data_ptr()))
+        return path, info, path_cost, cost, n_failed
+
+    def lattice_costs(self, D, grid: OccupancyGrid, stride, edges, src, dst, pen=None, want_cost=False):
+        """scp_lattice_costs: the arguments of lattice_distances and pen.  Returns (costs (n_src, n_dst) int32 device tensor
+        holding the uint32 words -- COST_UNREACHED where there is no path or a point has no node --, src_node (n_src,) and
+        dst_node (n_dst,) int32 device tensors, cost (n_src, nodes) int32 device tensor holding the uint32 words, or None).  No
+        host read."""
+        torch = _torch()
+        nodes = lattice_nodes(D, grid, stride)
+        n_src, n_dst = int(src.shape[0]), int(dst.shape[0])
+        costs = torch.empty((max(n_src, 1), max(n_dst, 1)), dtype=torch.int32, device=self.tdev)
+        src_node = torch.empty(max(n_src, 1), dtype=torch.int32, device=self.tdev)
+        dst_node = torch.empty(max(n_dst, 1), dtype=torch.int32, device=self.tdev)
+        cost = torch.empty((max(n_src, 1), nodes), dtype=torch.int32, device=self.tdev) if want_cost else None
+        self.check(self.lib.scp_lattice_costs(self.h, int(D), C.byref(grid), int(stride), _ptr(edges), _ptr(pen), n_src,
+                                              src.data_ptr(), n_dst, dst.data_ptr(), costs.data_ptr(), src_node.data_ptr(),
+                                              dst_node.data_ptr(), _ptr(cost)))
+        return costs, src_node, dst_node, cost
 
     def shorten_paths(self, N, K, D, grid: OccupancyGrid, sat, stride, clearance, p0, pf, max_path, path, info, ref, want_kept=True):
         """scp_shorten_paths: path (N, max_path) int32 and info as reference_paths returned them, p0 / pf (N, D) and ref

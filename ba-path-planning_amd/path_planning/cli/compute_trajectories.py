@@ -82,11 +82,12 @@ def build_parser():
     p.add_argument("--assign-method", choices=("auto", "single", "wide"), default="auto",
                    help="--assign-goals through the one-workgroup auction (single, up to 4096 vehicles), the whole-GPU one (wide, "
                         "up to 65536) or whichever fits (auto); the assignment is the same")
-    p.add_argument("--assign-cost", choices=("line", "path"), default="line",
+    p.add_argument("--assign-cost", choices=("line", "path", "length"), default="line",
                    help="with --assign-goals: pair by squared straight-line distance (line), or by the length of the paths "
                         "the lattice search finds around the obstacles (path: needs --obstacle-discs, takes --corridor-stride "
                         "and --corridor-clearance; up to 4096 vehicles) -- the line then shows the lattice moves before and "
-                        "after")
+                        "after; length: as path, by the weighted length of those paths (a diagonal move costs more than a "
+                        "straight one) and, with --corridor-keep-clear, their clearance")
     p.add_argument("--obstacle-discs", nargs="+", default=None, metavar="X,Y[,Z],R",
                    help="static obstacles: discs (spheres in 3-D) given as centre and radius; before the solve, safe flight "
                         "corridors around the straight lines from start to goal become per-step position boxes of the QP, and "
@@ -107,6 +108,15 @@ def build_parser():
     p.add_argument("--corridor-clearance", type=int, default=None, metavar="CELLS",
                    help="with --corridor-search: free cells required around every lattice block on a path (default 0; with "
                         "--corridor-shorten the stride)")
+    p.add_argument("--corridor-metric", choices=("hops", "length"), default=None,
+                   help="with --corridor-search: the search counts lattice moves (hops, the default) or weighs them by length, "
+                        "a diagonal move 99 / 70 of a straight one (length: run to its fixed point, one GPU workgroup per vehicle)")
+    p.add_argument("--corridor-keep-clear", type=int, default=None, metavar="CELLS",
+                   help="with --corridor-metric length or --assign-cost length: the clearance from the obstacles, in cells, "
+                        "below which a lattice node costs extra (default 0: length only)")
+    p.add_argument("--corridor-clear-weight", type=float, default=None, metavar="W",
+                   help="with --corridor-keep-clear: how many straight moves one missing cell of clearance costs per node passed "
+                        "(default 1)")
     p.add_argument("--corridor-shorten", action="store_true",
                    help="with --corridor-search: every path is cut down to the lattice nodes it cannot skip and its reference "
                         "points are spaced evenly by length (one GPU wave per vehicle)")
@@ -123,10 +133,20 @@ def build_parser():
 
 def obstacle_discs(parser, args):
     """the discs of --obstacle-discs as tuples of floats; the corridor flags are errors without it, --corridor-stride and
-    --corridor-clearance without --corridor-search or --assign-cost path, --corridor-shorten without --corridor-search"""
-    by_path = args.assign_cost == "path"
+    --corridor-clearance without --corridor-search or --assign-cost path / length, --corridor-shorten and --corridor-metric
+    without --corridor-search, --corridor-keep-clear without one of the two length searches, --corridor-clear-weight without
+    --corridor-keep-clear"""
+    by_path = args.assign_cost in ("path", "length")
     if by_path and not args.assign_goals:
         parser.error("--assign-cost needs --assign-goals")
+    if args.corridor_metric is not None and not args.corridor_search:
+        parser.error("--corridor-metric needs --corridor-search")
+    if args.corridor_keep_clear is not None and args.corridor_metric != "length" and args.assign_cost != "length":
+        parser.error("--corridor-keep-clear needs --corridor-metric length or --assign-cost length")
+    if args.corridor_keep_clear is not None and args.corridor_keep_clear < 0:
+        parser.error(f"--corridor-keep-clear {args.corridor_keep_clear}: a whole number of cells >= 0")
+    if args.corridor_clear_weight is not None and args.corridor_keep_clear is None:
+        parser.error("--corridor-clear-weight needs --corridor-keep-clear")
     if not args.corridor_search:
         for flag, value in (("--corridor-stride", None if by_path else args.corridor_stride),
                             ("--corridor-clearance", None if by_path else args.corridor_clearance),
@@ -135,7 +155,7 @@ def obstacle_discs(parser, args):
                 parser.error(f"{flag} needs --corridor-search")
     if args.obstacle_discs is None:
         if by_path:
-            parser.error("--assign-cost path needs --obstacle-discs")
+            parser.error(f"--assign-cost {args.assign_cost} needs --obstacle-discs")
         for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow),
                             ("--corridor-search", args.corridor_search or None), ("--obstacle-clearance", args.obstacle_clearance)):
             if value is not None:
@@ -232,10 +252,15 @@ def main(argv=None):
 
             occ, origin, cell = rasterize(space_dims, args.corridor_cell or min_distance / 4, discs=discs, margin=min_distance / 2)
             solver.set_obstacles(occ, origin, cell)
-            if args.assign_goals and args.assign_cost == "path":  # (the pairing sees the map: after it, before the search)
+            if args.corridor_metric == "length" or args.assign_cost == "length":
+                solver.set_search_metric("length", keep_clear=args.corridor_keep_clear or 0,
+                                         clear_weight=1.0 if args.corridor_clear_weight is None else args.corridor_clear_weight)
+            if args.assign_goals and args.assign_cost != "line":  # (the pairing sees the map: after it, before the search)
                 from ..scenarios.assignment import describe
 
-                solver.assign_goals(cost="path", stride=args.corridor_stride, clearance=args.corridor_clearance or 0)
+                solver.assign_goals(cost=args.assign_cost, stride=args.corridor_stride, clearance=args.corridor_clearance or 0)
+                if args.corridor_metric != "length":  # (--assign-cost length alone: the corridors' search still counts moves)
+                    solver.set_search_metric("hops")
                 print(describe(solver.assignment_info))
             reference = None
             if args.corridor_search:
@@ -246,7 +271,9 @@ def main(argv=None):
                 print(f"Corridor search: lattice of {' x '.join(str(n) for n in fr['lattice'])} blocks of {fr['stride']} cells "
                       f"(clearance {fr['clearance']}), {n_vehicles - fr['n_failed']} of {n_vehicles} paths found, longest "
                       f"E = {fr['max_edges']} for K = {solver.K}" + ("" if fr["guaranteed"] else " (no blocked segment is not "
-                      "guaranteed)") + f", {fr['edges_ms'] + fr['search_ms']:.3f} ms" + (shortened_summary(fr) if args.corridor_shorten else ""))
+                      "guaranteed)") + (f", by length (keep clear {fr['keep_clear']} cells): total cost {int(fr['cost'][fr['status'] == 0].sum())}"
+                                       if fr["metric"] == "length" else "")
+                      + f", {fr['edges_ms'] + fr['penalties_ms'] + fr['search_ms']:.3f} ms" + (shortened_summary(fr) if args.corridor_shorten else ""))
             co = solver.set_corridors(reference=reference, max_grow=8 if args.corridor_grow is None else args.corridor_grow)
 
         print("Generating trajectories...")

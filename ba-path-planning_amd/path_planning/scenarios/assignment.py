@@ -14,6 +14,7 @@ SCP.assign_goals(cost="path") joins the two.
 """
 import numpy as np
 
+from .. import _hip
 from .grid_swap_device import _context
 
 _ASSIGN_KEYS = ("cost_q", "cost_q_identity", "quantum", "rounds", "bids", "phases", "status")
@@ -119,6 +120,40 @@ def path_costs(hops, d2, power=2):
     return cost, {"tie_bits": b, "unreachable_cost": U, "max_hops": Hmax}
 
 
+COST_UNREACHED = _hip.COST_UNREACHED  # scp_lattice_costs: no path between the two nodes, or a point without a node
+
+
+def length_costs(costs, power=1):
+    """Costs for assign_goals_costs from the weighted lattice costs of scp_lattice_costs: length decides (it already separates
+    what equal hop counts lump together, so there are no tie bits), and one unreachable pair costs more than any assignment
+    without one.
+
+    costs: (N, N) whole numbers, costs[i][j] the lattice cost from start i to goal j, COST_UNREACHED (0xFFFFFFFF, or -1 as
+    the int32 view of it) where there is no path.  power: 1 or 2.  numpy arrays or torch tensors.
+      Lmax = the largest finite cost;  t = the smallest shift >= 0 with N ((Lmax >> t)^power + 1) <= 2^31 - 1;
+      finite pairs:      c = (L >> t)^power;
+      unreachable pairs: c = U = N (largest finite c) + 1   (<= 2^31 - 1 by the choice of t).
+    Returns (cost (N, N) int64 ndarray, {"shift": t, "unreachable_cost": U, "max_cost": Lmax})."""
+    to_numpy = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    L = to_numpy(costs)
+    if L.dtype.kind not in "iu":
+        raise ValueError(f"costs of dtype {L.dtype}: need whole numbers")
+    L = L.astype(np.int64) & 0xFFFFFFFF if L.dtype.itemsize == 4 else L.astype(np.int64)
+    if L.ndim != 2 or L.shape[0] != L.shape[1]:
+        raise ValueError(f"costs {L.shape} must be (N, N)")
+    if isinstance(power, bool) or power not in (1, 2):
+        raise ValueError(f"power={power!r}: 1 or 2")
+    if ((L < 0) | (L > COST_UNREACHED)).any():
+        raise ValueError("costs must lie in [0, 0xFFFFFFFF]")
+    N = L.shape[0]
+    finite = L != COST_UNREACHED
+    Lmax = int(L[finite].max()) if finite.any() else 0
+    t = next(t for t in range(33) if N * ((Lmax >> t) ** power + 1) <= MAX_COST)
+    cost = (np.where(finite, L, 0) >> t) ** power
+    U = N * (int(cost[finite].max()) if finite.any() else 0) + 1
+    return np.where(finite, cost, U), {"shift": t, "unreachable_cost": U, "max_cost": Lmax}
+
+
 def assign_goals_costs(cost, device=0, max_rounds_per_phase=0):
     """The assignment that minimises sum_i cost[i][goal_of[i]] for the caller's own costs (scp_assign_costs: the auction of
     assign_goals on a matrix, exact).  cost: (N, N) or (B, N, N) whole numbers in [0, 2^31 - 1], N <= 4096; cost[i][j] is what
@@ -141,13 +176,23 @@ def assign_goals_costs(cost, device=0, max_rounds_per_phase=0):
     return goal_of, info
 
 
-def hop_totals(hops, goal_of=None):
-    """{"sum", "max", "n_unreachable"} of hops[i][goal_of[i]] (goal_of None: the identity); sum and max over the reachable
-    pairs"""
-    hops = np.asarray(hops)
-    h = hops[np.arange(hops.shape[0]), np.arange(hops.shape[0]) if goal_of is None else np.asarray(goal_of)].astype(np.int64)
-    ok = h != HOPS_UNREACHED
+def pairing_totals(matrix, goal_of, unreached):
+    """{"sum", "max", "n_unreachable"} of matrix[i][goal_of[i]] (goal_of None: the identity); sum and max over the pairs whose
+    entry is not `unreached`"""
+    m = np.asarray(matrix)
+    h = m[np.arange(m.shape[0]), np.arange(m.shape[0]) if goal_of is None else np.asarray(goal_of)].astype(np.int64)
+    ok = h != unreached
     return {"sum": int(h[ok].sum()), "max": int(h[ok].max()) if ok.any() else 0, "n_unreachable": int((~ok).sum())}
+
+
+def hop_totals(hops, goal_of=None):
+    """pairing_totals of the hop counts of scp_lattice_distances"""
+    return pairing_totals(hops, goal_of, HOPS_UNREACHED)
+
+
+def length_totals(costs, goal_of=None):
+    """pairing_totals of the lattice costs of scp_lattice_costs"""
+    return pairing_totals(costs, goal_of, COST_UNREACHED)
 
 
 def describe(info):
@@ -155,6 +200,13 @@ def describe(info):
     the hop totals before -> after come first"""
     q, lb, la = info["quantum"], info["line_before"], info["line_after"]
     note = "" if info["status"] == 0 else " [round limit: pairing kept]"
+    if "length_assigned" in info:
+        li, la_ = info["length_identity"], info["length_assigned"]
+        return (f"Goal assignment by weighted path length: {li['sum']} -> {la_['sum']} in lattice costs (a straight move is 140; "
+                f"largest {li['max']} -> {la_['max']}), pairs without a path {info['n_unreachable_identity']} -> "
+                f"{info['n_unreachable_assigned']}, straight-line minimum approach {lb['min_approach']:.4f} -> "
+                f"{la['min_approach']:.4f} m, opposed pairs {lb['n_opposed']} -> {la['n_opposed']} ({info['phases']} phases, "
+                f"{info['rounds']} rounds, {info['distances_ms'] + info['assign_ms']:.3f} ms){note}")
     if "hops_assigned" in info:
         hi, ha = info["hops_identity"], info["hops_assigned"]
         return (f"Goal assignment by path length: {hi['sum']} -> {ha['sum']} lattice moves in all (longest {hi['max']} -> "

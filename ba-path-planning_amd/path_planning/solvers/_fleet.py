@@ -1,7 +1,7 @@
 """Fleet-level steps around the solve (not in the reference): goal assignment for interchangeable
 vehicles, repair of between-sample conflicts by holds, staggered starts.  FleetMethods is a state-free base of solvers.scp.SCP.
 It reads ``N``, ``K``, ``D``, ``h``, ``R``, ``convergence_tolerance``, ``initial_positions``, ``_obstacles``, ``_pairs``,
-``_last_qp_info`` and ``_ctx`` and calls ``_require`` / ``_device_trajectories`` / ``_lattice_edges`` / ``_states`` / ``_limits`` /
+``_last_qp_info``, ``_metric`` and ``_ctx`` and calls ``_require`` / ``_device_trajectories`` / ``_lattice_edges`` / ``_states`` / ``_limits`` /
 ``_space`` / ``_ensure_qp`` / ``_apply_boxes`` / ``_solve_with_avoidance_constraints`` / ``_kinematics``; it writes
 ``final_positions`` / ``final_velocities``, ``_final_given``, ``goal_assignment``, ``assignment_info``, ``_dev`` (assign_goals),
 ``trajectories``, ``_holds``, ``_rho_start``, ``last_info["repair"]`` (repair_conflicts), ``staggered``, ``last_info["stagger"]``
@@ -37,16 +37,25 @@ class FleetMethods:
         and the device milliseconds ``edges_ms``, ``distances_ms``, ``assign_ms``.  If even the best pairing leaves a vehicle
         without a path, no pairing connects every vehicle: ValueError naming one, unless ``allow_unreachable``.
 
-        Returns goal_assignment."""
-        from ..scenarios.assignment import _ASSIGN_KEYS, _LINE_KEYS, assign_method, hop_totals, path_costs
+        ``cost="length"`` pairs by the weighted length of the paths between every start and every goal (scp_lattice_costs: a
+        diagonal move costs more than a straight one, with the node penalties of set_search_metric's ``keep_clear`` /
+        ``clear_weight``; the setting's metric itself is not consulted), raised to ``power`` and shifted right until it fits 31 bits (scenarios.assignment.length_costs; no tie bits: length already separates what equal hop
+        counts lump together), through the same auction.  ``assignment_info`` then holds ``length_identity`` /
+        ``length_assigned`` ({"sum", "max"} of the lattice costs over the pairs that have a path), the unreachable counts,
+        ``shift``, ``unreachable_cost``, ``max_cost``, ``keep_clear``, ``stride``, ``clearance``, ``lattice`` and the device
+        milliseconds ``edges_ms``, ``penalties_ms``, ``distances_ms``, ``assign_ms``.
 
-        if cost not in ("line", "path"):
-            raise ValueError(f"cost={cost!r}: \"line\" or \"path\"")
-        if cost == "path":
+        Returns goal_assignment."""
+        from ..scenarios.assignment import (COST_UNREACHED, _ASSIGN_KEYS, _LINE_KEYS, assign_method, hop_totals, length_costs,
+                                            length_totals, path_costs)
+        if cost not in ("line", "path", "length"):
+            raise ValueError(f"cost={cost!r}: \"line\", \"path\" or \"length\"")
+        _, prefer, weight = self._metric
+        if cost != "line":
             if self.N > _hip.ASSIGN_COSTS_MAX_N:
-                raise ValueError(f"assign_goals(cost=\"path\") supports up to {_hip.ASSIGN_COSTS_MAX_N} vehicles (one N x N cost "
+                raise ValueError(f"assign_goals(cost=\"{cost}\") supports up to {_hip.ASSIGN_COSTS_MAX_N} vehicles (one N x N cost "
                                  f"matrix in one workgroup), not {self.N}; cost=\"line\" goes up to 65536")
-            stride, clearance, lattice, edges, edges_ms = self._lattice_edges("assign_goals(cost=\"path\")", stride, clearance)
+            stride, clearance, lattice, edges, edges_ms = self._lattice_edges(f"assign_goals(cost=\"{cost}\")", stride, clearance)
         else:
             assign = assign_method(self._ctx, method, self.N)
         self._require("assign_goals", states=True)
@@ -62,6 +71,15 @@ class FleetMethods:
             hops = hops.cpu().numpy().view(np.uint16)
             diff = s0[:, None, :] - pf[None, :, :]
             costs, how = path_costs(hops, (diff * diff).sum(-1), power)
+            goal_of, st, _ = c.assign_costs(costs[None])
+            assign_ms = c.last_pair_ms()
+        elif cost == "length":
+            c, s0 = self._ctx, start[0]
+            pen, penalties_ms = self._obstacles.penalties(stride, prefer, weight) if prefer > 0 and weight > 0 else (None, 0.0)
+            lengths, _, _, _ = c.lattice_costs(self.D, self._obstacles.grid, stride, edges, c.tensor(s0), c.tensor(pf), pen=pen)
+            distances_ms = c.last_pair_ms()
+            lengths = lengths.cpu().numpy().view(np.uint32)
+            costs, how = length_costs(lengths, power)
             goal_of, st, _ = c.assign_costs(costs[None])
             assign_ms = c.last_pair_ms()
         else:
@@ -82,6 +100,17 @@ class FleetMethods:
                 i = int(np.flatnonzero(hops[np.arange(self.N), perm] == 0xFFFF)[0])
                 raise ValueError(f"assign_goals(cost=\"path\"): no pairing connects every vehicle -- in the best one "
                                  f"{ha['n_unreachable']} vehicles have no path, vehicle {i} among them (stride {stride}, "
+                                 f"clearance {clearance}, lattice {lattice[:self.D]}); allow_unreachable=True pairs the rest")
+        if cost == "length":
+            li, la = length_totals(lengths), length_totals(lengths, perm)
+            info.update(how, length_identity={k: li[k] for k in ("sum", "max")}, length_assigned={k: la[k] for k in ("sum", "max")},
+                        n_unreachable_identity=li["n_unreachable"], n_unreachable_assigned=la["n_unreachable"], stride=stride,
+                        clearance=clearance, lattice=lattice[:self.D], keep_clear=prefer, edges_ms=edges_ms,
+                        penalties_ms=penalties_ms, distances_ms=distances_ms, assign_ms=assign_ms)
+            if la["n_unreachable"] and not allow_unreachable:
+                i = int(np.flatnonzero(lengths[np.arange(self.N), perm] == COST_UNREACHED)[0])
+                raise ValueError(f"assign_goals(cost=\"length\"): no pairing connects every vehicle -- in the best one "
+                                 f"{la['n_unreachable']} vehicles have no path, vehicle {i} among them (stride {stride}, "
                                  f"clearance {clearance}, lattice {lattice[:self.D]}); allow_unreachable=True pairs the rest")
         self.final_positions = pf[perm].flatten()
         self.final_velocities = vf[perm].flatten()

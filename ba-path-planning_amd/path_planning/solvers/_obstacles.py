@@ -3,7 +3,8 @@ reference paths around the obstacles, the distance field and the clearance of a 
 solvers.scp.SCP.  It reads ``N``, ``K``, ``D``, ``h``, ``acc_min`` / ``acc_max``, ``pos_min`` / ``pos_max``, ``initial_positions`` /
 ``final_positions``, ``trajectories`` and ``_ctx`` and calls ``_require`` / ``_device_trajectories``; it writes ``_obstacles`` (None
 or an ObstacleMap), ``_corridor`` (None or {"cells"}: the boxes of the segments, on the map's grid), ``_boxes`` (None or (lo, hi)
-device tensors (N, K, D) by state) and ``last_info["corridor"]`` / ``last_info["reference"]``."""
+device tensors (N, K, D) by state), ``_metric`` ((metric, prefer, weight) of set_search_metric) and ``last_info["corridor"]`` /
+``last_info["reference"]``."""
 import numpy as np
 
 from .. import _hip
@@ -15,6 +16,25 @@ def whole_number(value, lo, hi, message):
     bound), or ValueError(message)."""
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
         raise ValueError(message)
+
+
+def search_metric(metric, keep_clear, clear_weight):
+    """The checks of find_reference's ``metric`` / ``keep_clear`` / ``clear_weight`` -> (prefer, weight) of
+    scp_lattice_penalties: prefer = keep_clear cells, weight = round(70 clear_weight) (one missing cell of clearance costs
+    clear_weight straight moves per node passed)."""
+    if metric not in ("hops", "length"):
+        raise ValueError(f"metric={metric!r}: \"hops\" (fewest lattice moves) or \"length\" (weighted moves and clearance)")
+    whole_number(keep_clear, 0, None, f"keep_clear={keep_clear!r}: a whole number of cells >= 0")
+    if isinstance(clear_weight, bool) or not isinstance(clear_weight, (int, float, np.integer, np.floating)) or \
+            not (clear_weight >= 0 and np.isfinite(clear_weight)):
+        raise ValueError(f"clear_weight={clear_weight!r}: a finite number >= 0")
+    if keep_clear > 0 and metric == "hops":
+        raise ValueError(f"keep_clear={keep_clear} needs metric=\"length\": the search by hops does not read the distance field")
+    weight = int(round(_hip.MOVE_WEIGHTS[0] * float(clear_weight)))
+    if weight * int(keep_clear) > _hip.PENALTY_MAX_PRODUCT:
+        raise ValueError(f"keep_clear={keep_clear} with clear_weight={clear_weight}: round(70 clear_weight) keep_clear = "
+                         f"{weight * int(keep_clear)} exceeds {_hip.PENALTY_MAX_PRODUCT} (costs are 32-bit)")
+    return int(keep_clear), weight
 
 
 def straight_reference(p0, pf, K):
@@ -57,14 +77,15 @@ def corridor_shrink(acc_min, acc_max, h, pad):
 class ObstacleMap:
     """The map of one SCP.set_obstacles on the device: the geometry ``grid`` (scp_occupancy_grid), the occupancy ``occ``, its
     summed table ``sat`` and the device time ``prepare_ms`` of making it -- and what is derived from the map once and kept
-    while it lives: ``edge_masks`` {(stride, clearance): the search lattice's edge masks} and ``fields`` {gap: (distance
-    field, its device ms)}.  A new map is a new object, so both are dropped with the old one."""
+    while it lives: ``edge_masks`` {(stride, clearance): the search lattice's edge masks}, ``fields`` {gap: (distance
+    field, its device ms)} and ``node_penalties`` {(stride, prefer, weight): the weighted search's node penalties}.  A new map
+    is a new object, so all three are dropped with the old one."""
 
     def __init__(self, ctx, D, grid, occ):
         self.ctx, self.D, self.grid = ctx, D, grid
         self.occ, self.sat = ctx.occupancy_prepare(D, grid, occ)
         self.prepare_ms = ctx.last_pair_ms()
-        self.edge_masks, self.fields = {}, {}
+        self.edge_masks, self.fields, self.node_penalties = {}, {}, {}
 
     def edges(self, stride, clearance):
         """(the edge masks of the lattice of `stride` / `clearance` (device tensor), their device ms: 0.0 when cached)"""
@@ -73,6 +94,17 @@ class ObstacleMap:
             self.edge_masks[stride, clearance] = self.ctx.lattice_edges(self.D, self.grid, self.sat, stride, clearance)
             ms = self.ctx.last_pair_ms()
         return self.edge_masks[stride, clearance], ms
+
+    def penalties(self, stride, prefer, weight):
+        """(the node penalties of the lattice of `stride` from the gap-1 field (device tensor), their device ms -- the field's
+        included where this call made it --: 0.0 when cached)"""
+        ms = 0.0
+        if (stride, prefer, weight) not in self.node_penalties:
+            made = 1 not in self.fields
+            field, field_ms = self.field(1)
+            self.node_penalties[stride, prefer, weight] = self.ctx.lattice_penalties(self.D, self.grid, field, stride, prefer, weight)
+            ms = self.ctx.last_pair_ms() + (field_ms if made else 0.0)
+        return self.node_penalties[stride, prefer, weight], ms
 
     def field(self, gap):
         """(the distance field at `gap` (device tensor), the device ms of the call that made it)"""
@@ -157,6 +189,20 @@ class ObstacleMethods:
         self.last_info["corridor"] = info
         return info
 
+    def set_search_metric(self, metric="hops", keep_clear=0, clear_weight=1.0):
+        """What the lattice search of find_reference / shorten_reference / set_corridors(reference="search" / "shortened")
+        minimises from now on (the planner's setting: it outlives set_obstacles, and set_space_dims, which begins the next
+        scenario of a reused solver, returns it to the default).  ``metric``: "hops" counts lattice moves, a
+        diagonal one like a straight one (the default, scp_reference_paths); "length" searches by weighted length -- a straight
+        move 70, a diagonal one 99 or, in space, 121 (scp_reference_paths_weighted, run to its fixed point) -- and, with
+        ``keep_clear`` > 0, by clearance: every node whose block comes nearer to an obstacle than ``keep_clear`` cells (by the
+        gap-1 distance field, rounded down) pays ``clear_weight`` straight moves per missing cell on every edge that touches
+        it (scp_lattice_penalties, made once per map, stride and setting), so a path keeps to open space where that costs
+        less than the detour.  assign_goals(cost="length") weighs its paths with the same ``keep_clear`` / ``clear_weight``.
+        ValueError: a metric other than the two, keep_clear > 0 with "hops", round(70 clear_weight) keep_clear > 32768."""
+        self._require("set_search_metric", one_rank=True)
+        self._metric = (metric,) + search_metric(metric, keep_clear, clear_weight)
+
     def find_reference(self, stride=None, clearance=0, max_path=None, allow_unreachable=False):
         """Reference paths around the obstacles, one per vehicle, for set_corridors(reference=...): a breadth-first search on
         a lattice of blocks of ``stride`` x ``stride`` (x ``stride``) cells whose edges exist only where both blocks -- for a
@@ -170,7 +216,11 @@ class ObstacleMethods:
         ``n_nodes``, ``n_failed``, ``stride``, ``clearance``, ``lattice``, ``max_edges`` (the largest E = n_nodes + 1),
         ``guaranteed`` (every found path has E <= K or 2 clearance >= stride ceil(E / K): set_corridors then reports no blocked
         segment for those vehicles), ``edges_ms`` / ``search_ms`` (device milliseconds; edges_ms 0 when the masks were
-        cached).  A vehicle without a path keeps the straight line; unless ``allow_unreachable`` that raises ValueError."""
+        cached).  A vehicle without a path keeps the straight line; unless ``allow_unreachable`` that raises ValueError.
+
+        After set_search_metric("length", ...) the path is the cheapest by weighted length and clearance instead.  info
+        also holds ``metric``, ``keep_clear``, ``cost`` (int64 per vehicle: the path's weighted cost, with "hops" its number of
+        moves; -1 without a path) and ``penalties_ms`` (0.0 when cached or not needed)."""
         if clearance is None:
             raise ValueError("clearance=None: a whole number of cells >= 0")
         found = self._search_reference("find_reference", stride, clearance, max_path, want_path=False)
@@ -180,8 +230,9 @@ class ObstacleMethods:
         return found["ref"].cpu().numpy(), info
 
     def _search_reference(self, who, stride, clearance, max_path, want_path):
-        """the checks and the two calls of find_reference -> {"ref", "path", "rec" (device tensors), "p0", "pf", "max_path",
+        """the checks and the calls of find_reference -> {"ref", "path", "rec" (device tensors), "p0", "pf", "max_path",
         "info": what find_reference reports}"""
+        metric, prefer, weight = self._metric
         stride, clearance, lattice, edges, edges_ms = self._lattice_edges(who, stride, clearance)
         N, K, D, c = self.N, self.K, self.D, self._ctx
         nodes = lattice[0] * lattice[1] * lattice[2]
@@ -191,17 +242,26 @@ class ObstacleMethods:
         p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
         ref = c.tensor(straight_reference(p0, pf, K))
         d_p0, d_pf = c.tensor(p0), c.tensor(pf)
-        path, dev_rec, _, n_failed = c.reference_paths(N, K, D, self._obstacles.grid, stride, edges, d_p0, d_pf, int(max_path),
-                                                       ref, want_path=want_path)
+        pen, penalties_ms, path_cost = None, 0.0, None
+        if metric == "length":
+            if prefer > 0 and weight > 0:
+                pen, penalties_ms = self._obstacles.penalties(stride, prefer, weight)
+            path, dev_rec, path_cost, _, n_failed = c.reference_paths_weighted(N, K, D, self._obstacles.grid, stride, edges, d_p0,
+                                                                               d_pf, int(max_path), ref, pen=pen, want_path=want_path)
+        else:
+            path, dev_rec, _, n_failed = c.reference_paths(N, K, D, self._obstacles.grid, stride, edges, d_p0, d_pf, int(max_path),
+                                                           ref, want_path=want_path)
         search_ms = c.last_pair_ms()
         rec = dev_rec.cpu().numpy().view(_hip.PATH_INFO_DTYPE)[:N]
         found = rec["status"] == 0
+        cost = rec["n_nodes"].astype(np.int64) - 1 if path_cost is None else path_cost.cpu().numpy().view(np.uint32)[:N].astype(np.int64)
         E = rec["n_nodes"].astype(np.int64) + 1
         info = {"status": rec["status"].copy(), "n_nodes": rec["n_nodes"].copy(), "n_failed": int(n_failed.item()),
                 "stride": stride, "clearance": clearance, "lattice": lattice[:D],
                 "max_edges": int(E[found].max()) if found.any() else 0,
                 "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
-                "edges_ms": edges_ms, "search_ms": search_ms}
+                "edges_ms": edges_ms, "search_ms": search_ms, "metric": metric, "keep_clear": prefer,
+                "cost": np.where(found, cost, -1), "penalties_ms": penalties_ms}
         return {"ref": ref, "path": path, "rec": dev_rec, "p0": d_p0, "pf": d_pf, "max_path": int(max_path), "info": info}
 
     def _lattice_edges(self, who, stride, clearance):
@@ -238,7 +298,8 @@ class ObstacleMethods:
         sees another if every lattice step of the straight run between them, grown by ``clearance`` cells, is free -- and
         the states j = 0 .. K are placed evenly by chord length along start, kept block centres, goal (scp_shorten_paths: one
         wave per vehicle).  ``clearance`` None: ``stride``, with which every path shorter than K block edges is guaranteed;
-        the other parameters are find_reference's.
+        the other parameters are find_reference's (after set_search_metric("length", ...) the weighted path is what gets
+        shortened).
 
         Returns (reference (N, K + 1, D) ndarray, info) and stores info as ``last_info["reference"]``: what find_reference
         reports (its ``guaranteed`` replaced), and per vehicle ``n_kept`` (0 without a path), ``length`` / ``length_before``

@@ -69,6 +69,8 @@ atexit.register(clear_native_pool)
 
 
 class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
+    _metric = ("hops", 0, 0)  # (metric, prefer in cells, weight) of the lattice search until set_search_metric says otherwise
+
     def __init__(
         self,
         n_vehicles=5,
@@ -234,6 +236,7 @@ class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
         self.pos_max = np.array(space_dims[self.D:])
         self.trajectories = None
         self._obstacles = self._corridor = self._boxes = None  # (they belong to the scenario that is being replaced)
+        self._metric = SCP._metric  # (so does set_search_metric's setting: a reused solver starts with the default)
 
     # ------------------------------------------------------------------------------------------------
     # a0: states (scp.py:99-129)

@@ -162,8 +162,8 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *   "stg_batch_transposed" (default -1: chosen by the call, from 16 candidates on; 0 never; 1 always): scp_schedule_starts_batch
  *     first writes a transposed copy of the masks (N^2 words in the context's workspace) and reads the masks' columns from
  *     its rows; a developer switch.
- *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths; a
- *     developer switch.
+ *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths,
+ *     scp_reference_paths_weighted and scp_lattice_costs; a developer switch.
  *   "shorten_threads" (default 0: chosen by the call; or 64, 128 or 256): threads per workgroup of scp_shorten_paths (one
  *     wave per vehicle, so 1, 2 or 4 vehicles per workgroup); a developer switch. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
@@ -1127,6 +1127,68 @@ int scp_obstacle_clearance(scp_ctx* ctx, int N, int K, int D, double h, const sc
                            const uint32_t* field /* DEVICE [nz][ny][nx], gap = 1 */, int pieces /* 1 .. 16 */,
                            const double* pos, const double* vel, const double* acc /* DEVICE [N][K][D] */,
                            scp_obstacle_stats* out /* DEVICE [N] */, uint64_t* step_min /* DEVICE [K] */);
+
+/* ---- static obstacles: weighted search ------------------------------------------------------------------------------------------
+ * A further additive part of ABI version 7: three functions; nothing above changes.  scp_reference_paths counts lattice moves,
+ * a diagonal one like a straight one, and cannot tell a node beside a wall from one in open space.  These calls search the
+ * same lattice by LENGTH (move weights) and, optionally, by CLEARANCE (node penalties read from the gap = 1 distance field).
+ * Grid, cell lookup, lattice, node ids, blocks, direction codes, DIRECTION ORDER, edge masks and "passable" are those of
+ * scp_lattice_edges / scp_reference_paths.  Everything new is integer arithmetic.  tests/weighted_path_ref.py restates every
+ * rule in numpy / plain Python.
+ *
+ * Move weights.  W[1] = 70, W[2] = 99, W[3] = 121, indexed by len = |dx| + |dy| + |dz| of the move (99 / 70 and 121 / 70 are
+ *   within 0.3 % of sqrt 2 and sqrt 3).
+ * Node penalties (scp_lattice_penalties).  From `field`, the gap = 1 field of scp_obstacle_distance of the same grid (squared
+ *   cells, UINT32_MAX on an empty map), the stride s, prefer >= 0 (cells) and weight >= 0:
+ *     m[node]   = the minimum of field over the cells of the node's block,
+ *     rho[node] = the largest integer t with t^2 <= m[node] (exact: the rounded square root corrected in integers),
+ *     pen[node] = weight * (prefer - min(rho[node], prefer)),  uint32 [nodes].
+ *   Supported: weight * prefer <= SCP_PENALTY_MAX_PRODUCT; anything else returns SCP_ERR_INVALID with a message.  With that a
+ *   path of 32767 edges costs at most 32767 * (242 + 65536) < 2^32 - 1: costs never wrap and 0xFFFFFFFF is free to mean
+ *   "unreached".  One thread per node while s^D < 64, one wave per node with a wave minimum from there on.
+ * Edge cost.  w(u, v) = 2 W[len(u -> v)] + pen[u] + pen[v]: symmetric and at least 140, so a search from the goal gives the
+ *   costs of a search from the start.  pen = NULL means every penalty is zero.
+ * Cost field of an origin.  cost[origin] = 0; every other node holds the minimum over all walks along set edge bits of the sum
+ *   of w, uint32, 0xFFFFFFFF = unreached.  The field is always COMPLETE: the search runs to its fixed point (a cheaper path
+ *   may have more moves than the first one found).  The field is unique, so nothing depends on how the search is scheduled.
+ *
+ * scp_reference_paths_weighted: the arguments of scp_reference_paths, and pen, path_cost, cost_out.  Status 1 and 2 as there.
+ *   The field is computed from the GOAL node.  STATUS 3 if cost[start] is unreached.  Path: node_0 = start; node_{t+1} = the
+ *   first neighbour nb of node_t, in direction order, whose edge bit is set and for which cost[nb] + w(node_t, nb) ==
+ *   cost[node_t]; costs fall strictly along the path, so the walk ends at the goal.  STATUS 4 if the goal has not been reached
+ *   after max_path nodes.  m, the path row, scp_path_info, the reference points, the treatment of a vehicle with status != 0
+ *   (ref untouched, path row all -1, n_nodes 0) and *n_failed follow the rules of scp_reference_paths exactly, so
+ *   scp_shorten_paths consumes the outputs unchanged.  path_cost[i] = cost[start], 0xFFFFFFFF unless status 0.  cost_out (for
+ *   tests): all 0xFFFFFFFF with status 1 or 2, otherwise the complete field, also when the start node is the goal node.
+ * scp_lattice_costs: the arguments of scp_lattice_distances, and pen.  costs[a][b] = cost_a[dst_node[b]], the field of source
+ *   a; 0xFFFFFFFF if either node is -1 or the destination is unreached; 0 on the same node.  cost_out: every source's field.
+ *
+ * ONE workgroup per vehicle / source and no workgroup waits for another; the field lives in the workgroup's LDS as uint32:
+ * 32 KiB for lattices of at most 8192 nodes, 128 KiB of the CU's 160 KiB beyond (static; one workgroup per CU).  Sweeps in
+ * pull form: a thread owns the nodes it writes, reads their neighbours and stores min(own, cost[nb] + w); every stored value
+ * is the cost of a real walk and values only fall, so a racing read sees an older or a newer upper bound and the sweep that
+ * changes nothing ends the search at the shortest-cost field.  One barrier per sweep, at most `nodes` sweeps, within the
+ * growing box of scp_reference_paths' level sweep.  Both searches call one copy of the sweep.  Edge masks and penalties are
+ * read from global memory.  The workgroup width follows "ref_path_threads".  Supported: what scp_reference_paths /
+ * scp_lattice_distances support; pen made with the same stride.  Argument checks, enqueue on the ctx's stream, no host read,
+ * timing through scp_ctx_last_pair_ms. */
+#define SCP_PENALTY_MAX_PRODUCT 32768
+int scp_lattice_penalties(scp_ctx* ctx, int D, const scp_occupancy_grid* grid,
+                          const uint32_t* field /* DEVICE [nz][ny][nx], gap = 1 */, int stride, int prefer, int weight,
+                          uint32_t* pen /* DEVICE [nodes] */);
+int scp_reference_paths_weighted(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride,
+                                 const uint32_t* edges, const uint32_t* pen /* DEVICE [nodes] or NULL */,
+                                 const double* p0, const double* pf /* DEVICE [N][D] */, int max_path,
+                                 double* ref /* DEVICE [N][K+1][D], in/out */,
+                                 int32_t* path /* DEVICE [N][max_path] or NULL; entries beyond n_nodes are -1 */,
+                                 scp_path_info* info /* DEVICE [N] */,
+                                 uint32_t* path_cost /* DEVICE [N]; 0xFFFFFFFF unless status 0 */,
+                                 uint32_t* cost_out /* DEVICE [N][nodes] or NULL, for tests */, uint64_t* n_failed /* DEVICE */);
+int scp_lattice_costs(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+                      const uint32_t* pen /* DEVICE [nodes] or NULL */, int n_src, const double* src /* DEVICE [n_src][D] */,
+                      int n_dst, const double* dst /* DEVICE [n_dst][D] */, uint32_t* costs /* DEVICE [n_src][n_dst] */,
+                      int32_t* src_node /* DEVICE [n_src] */, int32_t* dst_node /* DEVICE [n_dst] */,
+                      uint32_t* cost_out /* DEVICE [n_src][nodes] or NULL */);
 
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
