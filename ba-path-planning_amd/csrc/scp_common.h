@@ -74,6 +74,12 @@ struct scp_ctx {
                                   // call (from 16 candidates on), 0 never, 1 always
   int ref_path_threads;           // threads per workgroup of scp_reference_paths and the weighted searches: 0 chosen by the call, 256, 512 or 1024
   int shorten_threads;            // threads per workgroup of scp_shorten_paths: 0 chosen by the call, 64, 128 or 256
+  int raster_item_cells;          // cells per work item of scp_rasterize_shapes: 0 chosen by the call (1024), or 64 .. 2^24
+  void* rast_ws;                  // its device copy of shapes, vertices and work items (grown on demand) ...
+  size_t rast_ws_bytes;
+  void* rast_host;                // ... and the pinned host buffer the copy starts from (grown on demand);
+  size_t rast_host_bytes;
+  hipEvent_t rast_copied;         // recorded behind the copy: the next call waits for it before it refills the buffer
   int* h_gen_flag;                // mapped host word "a block was flagged in this sweep" and its device address
   int* d_gen_flag;
   void* asg_ws;                   // device workspace of scp_straight_line_check (per-workgroup partials; grown on demand)

@@ -123,6 +123,12 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
     ctx->shorten_threads = value;
     return SCP_OK;
   }
+  if (strcmp(key, "raster_item_cells") == 0) {  // scp_rasterize_shapes (same grid; tests/test_rasterize_gpu.py compares them)
+    if (value != 0 && (value < 64 || value > (1 << 24)))
+      return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0 or 64 .. 2^24)", key, value);
+    ctx->raster_item_cells = value;
+    return SCP_OK;
+  }
   if (strcmp(key, "assign_wide_min_bidders") == 0) {
     if (value < 0) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d is negative", key, value);
     ctx->asgw_min_bidders = value;
@@ -157,6 +163,9 @@ extern "C" void scp_ctx_destroy(scp_ctx* ctx) {
   if (ctx->sep_ws) (void)hipFree(ctx->sep_ws);
   if (ctx->asg_ws) (void)hipFree(ctx->asg_ws);
   if (ctx->asgw_ws) (void)hipFree(ctx->asgw_ws);
+  if (ctx->rast_ws) (void)hipFree(ctx->rast_ws);
+  if (ctx->rast_host) (void)hipHostFree(ctx->rast_host);
+  if (ctx->rast_copied) (void)hipEventDestroy(ctx->rast_copied);
   if (ctx->h_gen_flag) (void)hipHostFree(ctx->h_gen_flag);
   (void)hipHostFree(ctx->h_scratch);
   (void)hipHostFree(ctx->h_mirror);

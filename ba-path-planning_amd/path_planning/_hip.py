@@ -265,6 +265,19 @@ OBSTACLE_MAX_RANGE = 4096     # SCP_OBSTACLE_MAX_RANGE: cells of a piece's range
 OBSTACLE_MAX_DIM = 32768      # scp_obstacle_distance: the largest grid dimension
 DIST_NONE = 2**32 - 1         # UINT32_MAX: a field without an occupied cell, a record without a judged piece
 
+
+class ObstacleShape(C.Structure):
+    """host: one shape of scp_rasterize_shapes (scenarios.obstacles.pack_shapes writes the array)"""
+    _fields_ = [("kind", C.c_int32), ("first_vertex", C.c_int32), ("n_vertices", C.c_int32), ("reserved", C.c_int32),
+                ("p", C.c_double * 7)]
+
+
+OBSTACLE_SHAPE_DTYPE = np.dtype(ObstacleShape)
+SHAPE_SPHERE, SHAPE_BOX, SHAPE_CAPSULE, SHAPE_POLYGON = 0, 1, 2, 3  # SCP_SHAPE_*
+RASTER_MAX_SHAPES = 65536     # SCP_RASTER_MAX_SHAPES
+RASTER_MAX_VERTICES = 1 << 20  # SCP_RASTER_MAX_VERTICES
+RASTER_MAX_POLYGON = 4096     # SCP_RASTER_MAX_POLYGON: vertices of one polygon
+
 # Every struct of include/scp_hip.h -> its mirror above, the only Python statement of the layout (each *_DTYPE derives from it)
 STRUCTS = {
     "scp_pair_stats": PairStats, "scp_qp_settings": QpSettings, "scp_solve_options": SolveOptions, "scp_qp_record": QpRecord,
@@ -273,6 +286,7 @@ STRUCTS = {
     "scp_delay_margin": DelayMargin, "scp_start_schedule_stats": StartScheduleStats, "scp_assign_stats": AssignStats,
     "scp_line_stats": LineStats, "scp_occupancy_grid": OccupancyGrid, "scp_corridor_stats": CorridorStats,
     "scp_path_info": PathInfo, "scp_shorten_info": ShortenInfo, "scp_obstacle_stats": ObstacleStats,
+    "scp_obstacle_shape": ObstacleShape,
 }
 
 
@@ -388,6 +402,7 @@ PROTOTYPES = {
     "scp_lattice_penalties": (i32, [vp, i32, pg, vp, i32, i32, i32, vp]),
     "scp_reference_paths_weighted": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "scp_lattice_costs": (i32, [vp, i32, pg, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_rasterize_shapes": (i32, [vp, i32, pg, i32, P(ObstacleShape), i32, pd, f64, vp]),
     "scp_gemm_f64": (i32, [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]),
     "scp_qp_peek": (i32, [vp, cstr, vp, i64, P(i64)]),
     "scp_qp_debug_set": (i32, [vp, cstr, i32]),
@@ -507,7 +522,8 @@ class Context:
         "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
         never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths, reference_paths_weighted
         and lattice_costs: 0 chosen by the call, 256, 512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
-        256; likewise)"""
+        256; likewise), "raster_item_cells" (the most cells of one work item of rasterize_shapes: 0 chosen by the call, or
+        64 .. 2^24; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
         if key != "kernel_timing":  # (every SCP object sets that one itself; a context with other switches moved is not pooled)
             self.options_changed = True
@@ -1055,6 +1071,20 @@ class Context:
                                                    int(pieces), pos.data_ptr(), vel.data_ptr(), acc.data_ptr(), out.data_ptr(),
                                                    step_min.data_ptr()))
         return self._read_records(out, N, OBSTACLE_STATS_DTYPE), step_min.cpu().numpy().view(np.uint64)[:K].copy()
+
+    # ---- static obstacles: shapes into an occupancy grid ------------------------------------------------------------------
+    def rasterize_shapes(self, D, grid: OccupancyGrid, packed, margin=0.0):
+        """scp_rasterize_shapes: packed = what scenarios.obstacles.pack_shapes returns ({"shapes": records of
+        OBSTACLE_SHAPE_DTYPE, "vertices": (n, 2) float64}) -> the occupancy grid, a uint8 device tensor [nz][ny][nx] of 0 / 1,
+        as occupancy_prepare and obstacle_distance take it.  The host arrays are copied before the call returns; no host read."""
+        torch = _torch()
+        shapes = np.ascontiguousarray(packed["shapes"], dtype=OBSTACLE_SHAPE_DTYPE).reshape(-1)
+        vertices = np.ascontiguousarray(packed["vertices"], dtype=np.float64).reshape(-1, 2)
+        occ = torch.empty((int(grid.dims[2]), int(grid.dims[1]), int(grid.dims[0])), dtype=torch.uint8, device=self.tdev)
+        self.check(self.lib.scp_rasterize_shapes(self.h, int(D), C.byref(grid), int(shapes.size),
+                                                 shapes.ctypes.data_as(P(ObstacleShape)), int(vertices.shape[0]),
+                                                 vertices.ctypes.data_as(pd), float(margin), occ.data_ptr()))
+        return occ
 
     def gemm(self, A, X, use_mfma=True, alpha=1.0, beta=0.0, Y=None):
         R, M = A.shape

@@ -92,6 +92,16 @@ def build_parser():
                    help="static obstacles: discs (spheres in 3-D) given as centre and radius; before the solve, safe flight "
                         "corridors around the straight lines from start to goal become per-step position boxes of the QP, and "
                         "after it one line says whether every segment stays inside its box")
+    p.add_argument("--obstacle-boxes", nargs="+", default=None, metavar="MIN...,MAX...",
+                   help="static obstacles: axis-aligned boxes given as their lower and upper corner (4 numbers, 6 in 3-D).  With "
+                        "this flag, --obstacle-capsules or --obstacle-polygons all obstacles, --obstacle-discs included, are "
+                        "rasterised on the GPU, and one line says what was rasterised; every flag that needs --obstacle-discs is "
+                        "content with any of the four")
+    p.add_argument("--obstacle-capsules", nargs="+", default=None, metavar="X0,Y0[,Z0],X1,Y1[,Z1],R",
+                   help="static obstacles: capsules, a segment with a radius (an oblique wall, a beam, a pipe)")
+    p.add_argument("--obstacle-polygons", nargs="+", default=None, metavar="X,Y,X,Y,...[:Z0,Z1]",
+                   help="static obstacles: polygons given by their vertices in the xy plane (at least 3, closed by an implied "
+                        "edge, any winding direction, convex or not); in 3-D the prism over the heights Z0 .. Z1")
     p.add_argument("--corridor-cell", type=float, default=None, metavar="METRES",
                    help="with --obstacle-discs: edge length of the occupancy grid's cells (default: a quarter of the minimum "
                         "distance)")
@@ -153,7 +163,8 @@ def obstacle_discs(parser, args):
                             ("--corridor-shorten", args.corridor_shorten or None)):
             if value is not None:
                 parser.error(f"{flag} needs --corridor-search")
-    if args.obstacle_discs is None:
+    shaped = any(getattr(args, "obstacle_" + kind, None) is not None for kind in ("boxes", "capsules", "polygons"))
+    if args.obstacle_discs is None and not shaped:
         if by_path:
             parser.error(f"--assign-cost {args.assign_cost} needs --obstacle-discs")
         for flag, value in (("--corridor-cell", args.corridor_cell), ("--corridor-grow", args.corridor_grow),
@@ -163,6 +174,8 @@ def obstacle_discs(parser, args):
         return None
     if args.obstacle_clearance is not None and not 1 <= args.obstacle_clearance <= 16:
         parser.error(f"--obstacle-clearance {args.obstacle_clearance}: 1 .. 16 pieces per segment")
+    if args.obstacle_discs is None:
+        return None
     discs = []
     for text in args.obstacle_discs:
         try:
@@ -173,6 +186,48 @@ def obstacle_discs(parser, args):
             parser.error(f"--obstacle-discs {text}: {args.dim} centre coordinates and a radius, separated by commas")
         discs.append(disc)
     return discs
+
+
+def obstacle_shapes(parser, args):
+    """the shapes of --obstacle-boxes / --obstacle-capsules / --obstacle-polygons as the keywords of SCP.set_obstacle_shapes,
+    or None when none of the three is given (then --obstacle-discs alone goes the host's way, as before)"""
+    if args.obstacle_boxes is None and args.obstacle_capsules is None and args.obstacle_polygons is None:
+        return None
+    D = args.dim
+
+    def numbers(text):
+        try:
+            return [float(v) for v in text.split(",")]
+        except ValueError:
+            return None
+
+    out = {"boxes": [], "capsules": [], "polygons": []}
+    for text in args.obstacle_boxes or ():
+        v = numbers(text)
+        if v is None or len(v) != 2 * D:
+            parser.error(f"--obstacle-boxes {text}: {D} lower and {D} upper coordinates, separated by commas")
+        out["boxes"].append(tuple(v))
+    for text in args.obstacle_capsules or ():
+        v = numbers(text)
+        if v is None or len(v) != 2 * D + 1:
+            parser.error(f"--obstacle-capsules {text}: two points of {D} coordinates and a radius, separated by commas")
+        out["capsules"].append(tuple(v))
+    for text in args.obstacle_polygons or ():
+        flat, _, heights = text.partition(":")
+        v, z = numbers(flat), numbers(heights) if heights else []
+        if v is None or len(v) < 6 or len(v) % 2 or z is None or len(z) != (2 if D == 3 else 0):
+            parser.error(f"--obstacle-polygons {text}: X,Y pairs of at least 3 vertices" + (", then :Z0,Z1" if D == 3 else
+                                                                                           " (a height range needs --dim 3)"))
+        out["polygons"].append((np.asarray(v).reshape(-1, 2),) + tuple(z))
+    return out
+
+
+def obstacle_shapes_summary(oi):
+    """the line of the device rasteriser from SCP.obstacle_info"""
+    counts = ", ".join(f"{n} {kind}" for kind, n in oi["counts"].items() if n)
+    return (f"Obstacles: {oi['n_shapes']} shapes ({counts}) rasterised on the GPU with margin {oi['margin']:g} m: "
+            f"{oi['n_occupied']} of {oi['n_cells']} cells occupied ({oi['rasterize_ms']:.3f} ms, summed table "
+            f"{oi['prepare_ms']:.3f} ms)")
 
 
 def shortened_summary(fr):
@@ -204,6 +259,7 @@ def main(argv=None):
     args = parser.parse_args([] if argv is None else argv)
     stagger_search = stagger_search_keywords(parser, args)
     discs = obstacle_discs(parser, args)
+    shapes = obstacle_shapes(parser, args)
     print("------ WOW Fleet Collision-Free 2D Trajectory Generation ------")
 
     n_vehicles = args.n_agents
@@ -247,11 +303,18 @@ def main(argv=None):
             solver.assign_goals(method=args.assign_method)
             print(describe(solver.assignment_info))
 
-        if discs is not None:
+        if shapes is not None:  # (the device rasteriser takes every kind, the discs too)
+            cell = args.corridor_cell or min_distance / 4
+            oi = solver.set_obstacle_shapes(cell, discs=discs or (), **shapes)
+            n_obstacles, grid_dims = oi["n_shapes"], tuple(oi["dims"]) + (1,) * (3 - args.dim)
+            print(obstacle_shapes_summary(oi))
+        elif discs is not None:
             from ..scenarios.obstacles import rasterize
 
             occ, origin, cell = rasterize(space_dims, args.corridor_cell or min_distance / 4, discs=discs, margin=min_distance / 2)
             solver.set_obstacles(occ, origin, cell)
+            n_obstacles, grid_dims = len(discs), occ.shape[::-1]
+        if discs is not None or shapes is not None:
             if args.corridor_metric == "length" or args.assign_cost == "length":
                 solver.set_search_metric("length", keep_clear=args.corridor_keep_clear or 0,
                                          clear_weight=1.0 if args.corridor_clear_weight is None else args.corridor_clear_weight)
@@ -285,9 +348,9 @@ def main(argv=None):
         print(f"Total computation time: {end_time - start_time:.3f} seconds")
         print(f"Number of time steps: {solver.K}")
         print(f"Total trajectory duration: {solver.T} seconds")
-        if discs is not None:
+        if discs is not None or shapes is not None:
             cr = solver.validate_corridor()
-            print(f"Corridors: {len(discs)} obstacles on a grid of {occ.shape[2]} x {occ.shape[1]} x {occ.shape[0]} cells of "
+            print(f"Corridors: {n_obstacles} obstacles on a grid of {grid_dims[0]} x {grid_dims[1]} x {grid_dims[2]} cells of "
                   f"{cell:g} m, boxes shrunk by {co['shrink']:.4f} m; " + ("every segment stays inside its box" if cr["inside"] else
                   f"{cr['n_outside']} segments leave their box") + f" (largest excess {cr['max_excess']:.4f} m, vehicle "
                   f"{cr['worst_vehicle']})")

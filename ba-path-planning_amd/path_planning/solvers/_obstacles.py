@@ -1,10 +1,10 @@
 """Static obstacles (not in the reference): the map, safe flight corridors as per-state position boxes,
 reference paths around the obstacles, the distance field and the clearance of a plan.  ObstacleMethods is a state-free base of
-solvers.scp.SCP.  It reads ``N``, ``K``, ``D``, ``h``, ``acc_min`` / ``acc_max``, ``pos_min`` / ``pos_max``, ``initial_positions`` /
-``final_positions``, ``trajectories`` and ``_ctx`` and calls ``_require`` / ``_device_trajectories``; it writes ``_obstacles`` (None
-or an ObstacleMap), ``_corridor`` (None or {"cells"}: the boxes of the segments, on the map's grid), ``_boxes`` (None or (lo, hi)
-device tensors (N, K, D) by state), ``_metric`` ((metric, prefer, weight) of set_search_metric) and ``last_info["corridor"]`` /
-``last_info["reference"]``."""
+solvers.scp.SCP.  It reads ``N``, ``K``, ``D``, ``h``, ``R``, ``space_dims``, ``acc_min`` / ``acc_max``, ``pos_min`` / ``pos_max``,
+``initial_positions`` / ``final_positions``, ``trajectories`` and ``_ctx`` and calls ``_require`` / ``_device_trajectories``; it writes
+``_obstacles`` (None or an ObstacleMap), ``obstacle_info`` (None or what set_obstacle_shapes rasterised), ``_corridor`` (None or
+{"cells"}: the boxes of the segments, on the map's grid), ``_boxes`` (None or (lo, hi) device tensors (N, K, D) by state),
+``_metric`` ((metric, prefer, weight) of set_search_metric) and ``last_info["corridor"]`` / ``last_info["reference"]``."""
 import numpy as np
 
 from .. import _hip
@@ -135,6 +135,37 @@ class ObstacleMethods:
             raise ValueError(f"cell={cell!r}: a finite number > 0")
         self._obstacles = ObstacleMap(self._ctx, self.D, _hip.occupancy_grid(self.D, origin, cell, occ.shape[::-1]), occ)
         self._corridor = self._boxes = None
+        self.obstacle_info = None
+
+    def set_obstacle_shapes(self, cell, *, discs=(), boxes=(), capsules=(), polygons=(), margin=None):
+        """Static obstacles as shapes, rasterised on the device (scp_rasterize_shapes): ``discs`` (x, y[, z], r) (spheres in
+        3-D) and ``boxes`` (min..., max...) as scenarios.obstacles.rasterize takes them, ``capsules`` (a..., b..., r) -- a
+        segment with a radius: an oblique wall, a beam, a pipe -- and ``polygons`` (vertices (n, 2),) in 2-D, (vertices, z0,
+        z1) in 3-D (the prism over a height range; any winding direction, convex or not); scenarios.obstacles.pack_shapes
+        checks them.  The grid is scenarios.obstacles.grid_shape(space_dims, cell); a cell is occupied if it comes closer than
+        ``margin`` (None: min_distance / 2, the body radius) to a shape or touches it.  The grid never visits the host: the
+        device tensor goes straight to scp_occupancy_prepare.  Corridors and boxes set before are dropped, as with
+        set_obstacles.  Returns and stores as ``obstacle_info``: {"n_shapes", "counts" (per kind), "dims", "cell", "margin",
+        "n_cells", "n_occupied", "rasterize_ms", "prepare_ms" (device milliseconds)}."""
+        from ..scenarios.obstacles import grid_shape, pack_shapes
+
+        self._require("set_obstacle_shapes", one_rank=True)
+        packed = pack_shapes(self.D, discs=discs, boxes=boxes, capsules=capsules, polygons=polygons)
+        origin, dims = grid_shape(self.space_dims, cell)
+        margin = float(self.R) / 2.0 if margin is None else float(margin)
+        if not (margin >= 0.0 and np.isfinite(margin)):
+            raise ValueError(f"margin={margin!r}: a finite number >= 0")
+        c = self._ctx
+        grid = _hip.occupancy_grid(self.D, origin, float(cell), dims)
+        occ = c.rasterize_shapes(self.D, grid, packed, margin)
+        rasterize_ms = c.last_pair_ms()
+        self._obstacles = ObstacleMap(c, self.D, grid, occ)
+        self._corridor = self._boxes = None
+        self.obstacle_info = {"n_shapes": int(packed["shapes"].size), "counts": dict(packed["counts"]), "dims": tuple(dims),
+                              "cell": float(cell), "margin": margin, "n_cells": int(occ.numel()),
+                              "n_occupied": int(self._obstacles.sat.reshape(-1)[-1].item()), "rasterize_ms": rasterize_ms,
+                              "prepare_ms": self._obstacles.prepare_ms}
+        return self.obstacle_info
 
     def set_corridors(self, reference=None, max_grow=8, pad=0.02, allow_open=False):
         """Safe flight corridors around a reference path: for every vehicle and segment an axis-aligned box of free cells

@@ -165,7 +165,9 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths,
  *     scp_reference_paths_weighted and scp_lattice_costs; a developer switch.
  *   "shorten_threads" (default 0: chosen by the call; or 64, 128 or 256): threads per workgroup of scp_shorten_paths (one
- *     wave per vehicle, so 1, 2 or 4 vehicles per workgroup); a developer switch. */
+ *     wave per vehicle, so 1, 2 or 4 vehicles per workgroup); a developer switch.
+ *   "raster_item_cells" (default 0: 1024; or 64 .. 2^24): the most cells of one work item (one workgroup) of
+ *     scp_rasterize_shapes; a developer switch. */
 int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value);
 /* The near form of scp_collision_violations_at: only the pairs close enough to be violated are evaluated (a uniform grid
  * per time step), with the exhaustive pass as the fallback when no examined row is close to active or an input is not
@@ -1189,6 +1191,89 @@ int scp_lattice_costs(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int s
                       int n_dst, const double* dst /* DEVICE [n_dst][D] */, uint32_t* costs /* DEVICE [n_src][n_dst] */,
                       int32_t* src_node /* DEVICE [n_src] */, int32_t* dst_node /* DEVICE [n_dst] */,
                       uint32_t* cost_out /* DEVICE [n_src][nodes] or NULL */);
+
+/* ---- static obstacles: shapes into an occupancy grid ---------------------------------------------------------------------------
+ * A further additive part of ABI version 7: one struct and one function; nothing above changes.  scp_rasterize_shapes makes
+ * the occupancy grid that scp_occupancy_prepare and everything after it consume, on the device, from spheres (discs in 2-D),
+ * axis-aligned boxes, capsules (a segment with a radius: oblique walls, beams, pipes) and polygons (in 3-D: prisms over a
+ * height range).  tests/rasterize_ref.py restates every rule below in numpy over all cells of the grid.
+ *
+ * Grid: that of scp_occupancy_prepare.  In coordinate d the closed cell c is [lo_d, hi_d], lo_d = origin_d + cell * (double)c_d,
+ * hi_d = origin_d + cell * ((double)c_d + 1.0): one product and one sum each.  Every product, quotient, sum and difference
+ * below is rounded on its own (no contraction).  margin >= 0 is the body radius of a vehicle.  A cell is OCCUPIED (occ = 1)
+ * if the predicate of at least one shape holds for it, otherwise occ = 0: shapes combine by OR, so the grid depends neither on
+ * their order nor on how the work is split.  "sq(g)" below is ((0 + g_x g_x) + g_y g_y) (+ g_z g_z), summed in that order.
+ *
+ * SPHERE (kind 0): centre c = p[0 .. D), radius r = p[6] >= 0.  g_d = max(max(lo_d - c_d, c_d - hi_d), 0), g2 = sq(g),
+ *   reach = r + margin.  Occupied if g2 < reach * reach.
+ * BOX (kind 1): bmin = p[0 .. D), bmax = p[3 .. 3 + D), bmin_d <= bmax_d.  g_d = max(max(lo_d - bmax_d, bmin_d - hi_d), 0),
+ *   g2 = sq(g).  Occupied if g2 < margin * margin or g2 == 0.
+ *   (These two are the rules of the host rasteriser scenarios.obstacles.rasterize and give its bits.)
+ * CAPSULE (kind 2): the segment a -> b, a = p[0 .. D), b = p[3 .. 3 + D), radius r = p[6] >= 0.  With e = b - a,
+ *   x_d(t) = a_d + t * e_d and f(t) = sq(g(t)), g_d(t) = max(max(lo_d - x_d(t), x_d(t) - hi_d), 0), g2 is the minimum of f
+ *   over a finite SET of t (v replaces the minimum so far if v < it; the minimum starts at +infinity):
+ *     - 0 and 1;
+ *     - every breakpoint (lo_d - a_d) / e_d and (hi_d - a_d) / e_d, d < D with e_d != 0, that lies strictly inside (0, 1);
+ *     - for every pair t0 < t1 of consecutive members of the sorted set so far, the stationary point of the quadratic that
+ *       f is on [t0, t1], clamped: with tm = 0.5 * (t0 + t1), coordinate d is ACTIVE if x_d(tm) < lo_d (then c_d = a_d - lo_d)
+ *       or x_d(tm) > hi_d (then c_d = a_d - hi_d); num = sum of c_d * e_d and den = sum of e_d * e_d over the active
+ *       coordinates in the order x, y, z, from 0; t* = -num / den, replaced by t0 if t* < t0 and then by t1 if t* > t1.  If
+ *       den == 0, f is constant on the interval and the pair adds tm itself: a segment that passes through the cell has
+ *       f(tm) = 0 exactly between its entry and its exit, where the two breakpoints may carry a rounding error of an ulp
+ *       squared -- without this member the touch rule g2 == 0 would miss cells a thin segment runs through.
+ *   A minimum over a set needs no order among its members: only the set is normative, not how it is sorted.  f is convex
+ *   and piecewise quadratic with exactly these breakpoints, so in exact arithmetic g2 is the squared distance between the
+ *   segment and the closed cell.  reach = r + margin.  Occupied if g2 < reach * reach or g2 == 0.  a == b gives the set
+ *   {0, 1} and the SPHERE's g2 bit for bit.
+ * POLYGON (kind 3; a PRISM in 3-D): the vertices v_0 .. v_{n-1} = vertices[first_vertex .. first_vertex + n_vertices) in the
+ *   xy plane, 3 <= n <= SCP_RASTER_MAX_POLYGON, with the closing edge v_{n-1} -> v_0; in 3-D the height range z0 = p[0] <=
+ *   z1 = p[1].  Even-odd rule: the winding direction does not matter, non-convex polygons are allowed.  gz = max(max(lo_z -
+ *   z1, z0 - hi_z), 0) in 3-D, 0 in 2-D.  Occupied if (i) or (ii):
+ *     (i)  some edge v_i -> v_{i+1} has g2 = g2xy + gz * gz with g2 < margin * margin or g2 == 0, g2xy being the CAPSULE's g2
+ *          of that edge in the two coordinates x, y;
+ *     (ii) the cell's centre is inside the polygon and gz * gz < margin * margin or gz == 0.  Centre: cx = origin_x + cell *
+ *          ((double)c_x + 0.5), cy likewise.  An edge p -> q is CROSSED if (p_y <= cy) != (q_y <= cy) and cx < p_x + ((cy -
+ *          p_y) * (q_x - p_x)) / (q_y - p_y); the centre is inside if the integer count of crossed edges is odd.
+ *   Why this is the distance rule of the solid: cell and prism are both products of a planar set and an interval, so dist^2 =
+ *   dist_xy^2 + dist_z^2; the planar distance is 0 if an edge touches the cell's rectangle or the rectangle lies inside the
+ *   polygon -- a rectangle no edge touches lies wholly inside or wholly outside, so its centre decides -- and otherwise it
+ *   is the minimum over the edges.
+ *
+ * Invalid (SCP_ERR_INVALID with a message, nothing enqueued): a kind other than the four, a parameter the kind reads that is
+ * not finite, r < 0, bmax_d < bmin_d, z1 < z0 (3-D), n_vertices outside 3 .. SCP_RASTER_MAX_POLYGON, a vertex range outside
+ * [0, n_vertices of the call), n_shapes outside 0 .. SCP_RASTER_MAX_SHAPES, n_vertices of the call outside 0 ..
+ * SCP_RASTER_MAX_VERTICES, a margin that is negative or not finite, a grid scp_occupancy_prepare rejects.  Fields a kind
+ * does not read (and `reserved`) are ignored.
+ *
+ * How it runs.  The host side computes per shape a conservative inclusive CELL RANGE -- per coordinate floor((min_d - reach -
+ * origin_d) / cell) - 2 .. floor((max_d + reach - origin_d) / cell) + 2 from the shape's extremes (reach = margin for BOX and
+ * POLYGON), clipped to the grid -- and cuts every range into WORK ITEMS of at most "raster_item_cells" cells (scp_ctx_set_option;
+ * default 1024; doubled for a call until there are at most 2^18 items), rows along x first.  The range only prunes: the
+ * predicate decides, and a shape whose range is empty costs nothing.  Shapes, vertices and items travel in one copy; occ is
+ * cleared; then ONE launch, a workgroup per item (the shape is uniform across it: scalar registers), a thread per cell, x
+ * fastest, stores 1 where the predicate holds (byte stores of the same value: no atomics).  A polygon's vertices are staged in
+ * LDS in blocks; every lane reads the same edge.  No workgroup waits for another, every loop is bounded by a count.  The
+ * work of a shape is proportional to its own range, and one large shape spreads over the whole GPU.  n_shapes = 0 gives an
+ * all-free grid.  Enqueued on the ctx's stream, no host read (the host arrays are copied before the call returns), timing
+ * through scp_ctx_last_pair_ms. */
+#define SCP_SHAPE_SPHERE 0
+#define SCP_SHAPE_BOX 1
+#define SCP_SHAPE_CAPSULE 2
+#define SCP_SHAPE_POLYGON 3
+#define SCP_RASTER_MAX_SHAPES 65536
+#define SCP_RASTER_MAX_VERTICES 1048576
+#define SCP_RASTER_MAX_POLYGON 4096
+typedef struct scp_obstacle_shape { /* [host], 72 bytes */
+  int32_t kind;         /* SCP_SHAPE_* */
+  int32_t first_vertex; /* POLYGON: its first vertex in `vertices` */
+  int32_t n_vertices;   /* POLYGON: 3 .. SCP_RASTER_MAX_POLYGON */
+  int32_t reserved;
+  double p[7];          /* SPHERE c, -, r; BOX bmin, bmax, -; CAPSULE a, b, r (three slots per point, D used); POLYGON z0, z1 */
+} scp_obstacle_shape;
+int scp_rasterize_shapes(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int n_shapes,
+                         const scp_obstacle_shape* shapes /* [host] [n_shapes] */, int n_vertices,
+                         const double* vertices /* [host] [n_vertices][2] */, double margin,
+                         uint8_t* occ /* DEVICE out [nz][ny][nx], 0 / 1 */);
 
 /* ---- test hooks (dense K-dimension products used by the QP; exercised by tests/test_kernels_gpu.py::test_gemm_f64) ------
  * Y[R][C] = alpha * A[R][M] X[M][C] + beta * Y, row-major, device pointers. */
