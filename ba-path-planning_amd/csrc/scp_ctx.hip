@@ -265,6 +265,53 @@ void scp_ctx_mirror_rel(scp_ctx* ctx, int64_t n, double* out) {
   out[2] = out[0] / out[1];
 }
 
+// ---- test hooks for the state a context carries from one call to the next ("What a context owns") ----
+// Scratch: every word is written by the call that reads it, so any pattern between two calls must change nothing.  The
+// invariants (cmp_map, the d_ticket block, scp_rel_step's ticket and completion word, the stats mirror) are left alone.
+extern "C" int scp_ctx_debug_fill(scp_ctx* ctx, uint32_t word) {
+  if (!ctx) return SCP_ERR_INVALID;
+  const struct { void* p; size_t bytes; } scratch[] = {
+      {ctx->tm_scratch, ctx->tm_bytes},     {ctx->cmp_tot, ctx->cmp_tot_bytes},
+      {ctx->wg_part, 4 * SCP_SMALL_MAX_WG * sizeof(unsigned long long)},
+      {ctx->wg_rows, ctx->wg_rows_bytes},   {ctx->gen_ws, ctx->gen_ws_bytes},
+      {ctx->sep_ws, ctx->sep_ws_bytes},     {ctx->asg_ws, ctx->asg_ws_bytes},
+      {ctx->asgw_ws, ctx->asgw_ws_bytes},   {ctx->rast_ws, ctx->rast_ws_bytes},
+      {ctx->d_scratch, 64 * sizeof(double)}, {ctx->h_scratch_dev, 64 * sizeof(double)},
+  };
+  for (const auto& s : scratch)
+    if (s.p && s.bytes >= sizeof(uint32_t))
+      SCP_HIP_CHECK(ctx, hipMemsetD32Async((hipDeviceptr_t)s.p, (int)word, s.bytes / sizeof(uint32_t), ctx->stream));
+  return SCP_OK;
+}
+
+extern "C" int scp_ctx_debug_state(scp_ctx* ctx, scp_ctx_state* out) {
+  if (!ctx || !out) return SCP_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  SCP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  SCP_HIP_CHECK(ctx, hipMemcpy(out->ticket, ctx->d_ticket, 64, hipMemcpyDeviceToHost));
+  SCP_HIP_CHECK(ctx, hipMemcpy(&out->rel_ticket, ctx->d_scratch + 64, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const size_t map_words = ctx->cmp_map_bytes / sizeof(uint32_t);
+  if (map_words > 0) {
+    uint32_t* map = (uint32_t*)malloc(map_words * sizeof(uint32_t));
+    if (!map) return scp_fail(ctx, SCP_ERR_INVALID, "ctx_debug_state: no host memory for %zu map words", map_words);
+    const hipError_t e = hipMemcpy(map, ctx->cmp_map, map_words * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    for (size_t w = 0; e == hipSuccess && w < map_words; ++w) out->cmp_map_nonzero += map[w] != 0u;
+    free(map);
+    SCP_HIP_CHECK(ctx, e);
+  }
+  out->tm_bytes = ctx->tm_bytes;
+  out->cmp_map_bytes = ctx->cmp_map_bytes;
+  out->cmp_tot_bytes = ctx->cmp_tot_bytes;
+  out->wg_rows_bytes = ctx->wg_rows_bytes;
+  out->gen_ws_bytes = ctx->gen_ws_bytes;
+  out->sep_ws_bytes = ctx->sep_ws_bytes;
+  out->asg_ws_bytes = ctx->asg_ws_bytes;
+  out->asgw_ws_bytes = ctx->asgw_ws_bytes;
+  out->rast_ws_bytes = ctx->rast_ws_bytes;
+  out->rast_host_bytes = ctx->rast_host_bytes;
+  return SCP_OK;
+}
+
 extern "C" const char* scp_last_error(const scp_ctx* ctx) { return ctx ? ctx->err : "null context"; }
 
 extern "C" int scp_ctx_synchronize(scp_ctx* ctx) {

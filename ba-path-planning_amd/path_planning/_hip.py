@@ -42,6 +42,19 @@ class PairStats(C.Structure):
                 ("max_violation", C.c_double)]
 
 
+class CtxState(C.Structure):
+    """what Context.debug_state reports: the ticket / counter block, scp_rel_step's ticket, the non-zero words of the
+    violations passes' scratch bitmap and the current size of every grown-on-demand buffer"""
+    _fields_ = [("ticket", C.c_uint32 * 16), ("rel_ticket", C.c_uint32), ("reserved", C.c_uint32),
+                ("cmp_map_nonzero", C.c_uint64)] + [(f, C.c_uint64) for f in (
+                    "tm_bytes", "cmp_map_bytes", "cmp_tot_bytes", "wg_rows_bytes", "gen_ws_bytes", "sep_ws_bytes",
+                    "asg_ws_bytes", "asgw_ws_bytes", "rast_ws_bytes", "rast_host_bytes")]
+
+    def as_dict(self):
+        d = {f: int(getattr(self, f)) for f, _ in self._fields_[3:]}
+        return dict(d, ticket=[int(w) for w in self.ticket], rel_ticket=int(self.rel_ticket))
+
+
 class QpSettings(C.Structure):
     _fields_ = [
         ("rho", C.c_double), ("sigma", C.c_double), ("alpha", C.c_double), ("rho_eq_scale", C.c_double),
@@ -286,7 +299,7 @@ STRUCTS = {
     "scp_delay_margin": DelayMargin, "scp_start_schedule_stats": StartScheduleStats, "scp_assign_stats": AssignStats,
     "scp_line_stats": LineStats, "scp_occupancy_grid": OccupancyGrid, "scp_corridor_stats": CorridorStats,
     "scp_path_info": PathInfo, "scp_shorten_info": ShortenInfo, "scp_obstacle_stats": ObstacleStats,
-    "scp_obstacle_shape": ObstacleShape,
+    "scp_obstacle_shape": ObstacleShape, "scp_ctx_state": CtxState,
 }
 
 
@@ -333,6 +346,8 @@ PROTOTYPES = {
     "scp_ctx_set_near_pass": (i32, [vp, i32]),
     "scp_ctx_near_pass_counts": (i32, [vp, pu64, pu64]),
     "scp_ctx_peek_scratch_map": (i32, [vp, vp, i64]),
+    "scp_ctx_debug_fill": (i32, [vp, C.c_uint32]),
+    "scp_ctx_debug_state": (i32, [vp, P(CtxState)]),
     "scp_kinematics": (i32, [vp, i32, i32, i32, f64, vp, vp, vp, vp, vp]),
     "scp_fixed_bounds": (i32, [vp, i32, i32, i32, f64, pd, pd, vp, vp, vp, vp, vp, vp]),
     "scp_linearize_pairs": (i32, [vp, i32, i32, i32, f64, f64, i64, i64, vp, vp, vp, vp, vp, f64, vp, i64, vp, vp]),
@@ -547,6 +562,18 @@ class Context:
             return out
         self.check(self.lib.scp_ctx_peek_scratch_map(self.h, out.ctypes.data_as(C.c_void_p), int(words)))
         return out
+
+    def debug_fill(self, word):
+        """test hook (scp_ctx_debug_fill): every scratch workspace the context owns right now is filled with the 32-bit
+        `word` on its stream; no result may depend on it"""
+        self.check(self.lib.scp_ctx_debug_fill(self.h, int(word) & 0xFFFFFFFF))
+
+    def debug_state(self):
+        """test hook (scp_ctx_debug_state): the words a context relies on between calls and its buffers' sizes, as a dict
+        -- synchronises"""
+        st = CtxState()
+        self.check(self.lib.scp_ctx_debug_state(self.h, C.byref(st)))
+        return st.as_dict()
 
     def set_timing(self, on):
         self.set_option("kernel_timing", 1 if on else 0)

@@ -13,7 +13,7 @@ Differences to the reference that a caller can observe (INTEGRATION.md has the f
     2.6e9-non-zero CSC matrix; ``C_jerk/C_acc/C_vel/C_pos`` are not materialised (they stay None);
   * new keyword-only arguments: ``dim`` (2 or 3), ``device``, ``qp_settings``, ``working_set_margin``,
     ``feasibility_tol``, ``max_rounds``, ``refresh_feasibility``, ``polish``/``polish_eps``, ``native``, ``row_free``, ``carry_rho``, ``kernel_timing``,
-    ``qp_row_capacity``, ``reuse_native``, ``verbose``, ``rank``/``world_size``/``group`` (pair-range-sharded multi-GPU: the SCP iteration natively,
+    ``qp_row_capacity``, ``reuse_native``, ``ctx`` (an open Context of the caller to work on; never pooled or closed here), ``verbose``, ``rank``/``world_size``/``group`` (pair-range-sharded multi-GPU: the SCP iteration natively,
     split at its exchange points -- ``scp_iteration_sharded``).
 
 What is not in the reference lives in three state-free bases of SCP: static obstacles in _obstacles.py, the post-solve reports in
@@ -99,6 +99,7 @@ class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
         world_size=1,
         group=None,
         reuse_native=True,
+        ctx=None,
     ):
         # --- reference attributes (scp.py:40-91) ---
         self.N = n_vehicles
@@ -163,6 +164,11 @@ class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
 
             device = torch.cuda.current_device() if torch.cuda.is_available() else 0
         # the native half of a released object of the same shape on this stream, if there is one (module docstring of _POOL)
+        # ctx: an open _hip.Context of the caller's to work on instead of one of its own (every device object of this SCP is
+        # created on it); it is never pooled and never closed here -- close() destroys what this object created and leaves it open
+        self._borrowed_ctx = ctx is not None
+        if self._borrowed_ctx:
+            device, reuse_native = ctx.device, False
         self.reuse_native = bool(reuse_native)
         self._pool_key = None
         if self.reuse_native:
@@ -185,7 +191,9 @@ class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
                     _POOL_STATS["hits" if entry else "misses"] += 1
                 if entry:
                     self._ctx, self._native = entry
-        if self._native is None:
+        if self._borrowed_ctx:
+            self._ctx = ctx
+        elif self._native is None:
             self._ctx = _hip.Context(device)  # raises without a GPU / without libscp_hip.so
         # False: no HIP events around the kernels (linearize_ms / violations_ms read 0, solve_ms is host wall clock): fewer queue
         # packets per solve, for many concurrent solves on one GPU
@@ -422,6 +430,10 @@ class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
         self._dev = {}
         self._ctx = None
         if ctx is None:
+            return
+        if getattr(self, "_borrowed_ctx", False):  # the caller's context: ours to use, not to pool or close
+            if nat is not None:
+                nat.close()
             return
         keep = (nat is not None and self._pool_key is not None and getattr(ctx, "h", None)
                 and not getattr(ctx, "options_changed", False))

@@ -179,6 +179,30 @@ int scp_ctx_set_near_pass(scp_ctx* ctx, int mode);
 int scp_ctx_near_pass_counts(scp_ctx* ctx, uint64_t* n_near /* [host] */, uint64_t* n_fell_back /* [host] */);
 /* Test hook: the first `words` words of the scratch bitmap of the violations passes (all zero between calls).  Synchronises. */
 int scp_ctx_peek_scratch_map(scp_ctx* ctx, uint32_t* out /* [host] */, int64_t words);
+/* Test hook: fills every device workspace the ctx owns at this moment, to its current size, with `word` -- the time-major
+ * copy, the compaction totals, the per-workgroup partials and row sub-lists of the one-launch passes, the workspaces of the
+ * scenario generator, of the continuous-time / hold / reference-path / distance-field calls, of the line check, of the wide
+ * auction and of the rasteriser, and the 64 partial sums of scp_rel_step on the device and in pinned host memory.  Every
+ * call writes each of these words before it reads it, so no result may change.  NOT touched: the scratch bitmap of the
+ * violations passes, the ticket / counter block, scp_rel_step's ticket and completion word and the stats mirror -- what
+ * they hold between calls is relied upon.  Enqueued on the ctx's stream; allocates nothing. */
+int scp_ctx_debug_fill(scp_ctx* ctx, uint32_t word);
+/* [host] what scp_ctx_debug_state reports */
+typedef struct scp_ctx_state {
+  uint32_t ticket[16];       /* the block of device words that lives as long as the ctx: [0] last-workgroup ticket of the
+                                one-launch pairwise passes, [1] and [2] those of the QP's checks and row build (all three zero
+                                between calls), [3] number of the latest recomputing violations pass that staged a value that
+                                was not finite, [4, 8) the two result words of scp_schedule_starts_batch, [8, 10) / [10, 12) /
+                                [12, 14) / [14, 16) the 64-bit counters behind scp_ctx_last_lag_solved / _delay_solved /
+                                _separation_solved / _clearance_solved */
+  uint32_t rel_ticket;       /* last-workgroup ticket of scp_rel_step (zero between calls) */
+  uint32_t reserved;
+  uint64_t cmp_map_nonzero;  /* words of the violations passes' scratch bitmap that are not zero (none between calls) */
+  uint64_t tm_bytes, cmp_map_bytes, cmp_tot_bytes, wg_rows_bytes, gen_ws_bytes, sep_ws_bytes, asg_ws_bytes, asgw_ws_bytes,
+      rast_ws_bytes, rast_host_bytes; /* current size of each grown-on-demand buffer of the ctx (0: never allocated) */
+} scp_ctx_state;
+/* Test hook: the words above, after the ctx's stream has drained. */
+int scp_ctx_debug_state(scp_ctx* ctx, scp_ctx_state* out /* [host] */);
 
 /* ---- a4 / a7: SCP._compute_positions_velocities (scp.py:371-397),
  *               SCP._accelerations_to_positions_velocities (scp.py:559-595) ---------------------------
