@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void check_corridor_kernel(int N, int K, doubl
 }  // namespace
 
 // ----------------------------------------------------------------------------------------------------
-// host side (the first three are shared with scp_reference.hip: scp_corridor_device.h)
+// host side (the first three are shared with the lattice calls: scp_corridor_device.h)
 // ----------------------------------------------------------------------------------------------------
 int corridor_grid(scp_ctx* ctx, const char* who, int D, const scp_occupancy_grid* grid, CorridorGrid& g) {
   SCP_REQUIRE(ctx, D == 2 || D == 3, "%s: D=%d (2 or 3)", who, D);

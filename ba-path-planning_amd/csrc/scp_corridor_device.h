@@ -1,4 +1,4 @@
-// Arithmetic shared by the kernels of scp_corridor.hip, scp_reference.hip and scp_obstacle_dist.hip (the rules are stated in
+// Arithmetic shared by the kernels of scp_corridor.hip, the lattice files (scp_lattice_device.h) and scp_obstacle_dist.hip (the rules are stated in
 // include/scp_hip.h, "static obstacles").
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
-// The search lattice shared by scp_reference.hip, scp_lattice_dist.hip, scp_lattice_weighted.hip and scp_shorten.hip: its
-// shape, node coordinates, the node of a point, the directions, the level-by-level search, the weighted relaxation, block
-// centres, the vertices of a lattice path and the reference points along it (the rules
-// are stated in include/scp_hip.h, "reference paths by a lattice search").
+// The search lattice shared by scp_lattice_graph.hip, scp_lattice_search.hip and scp_shorten.hip: its shape, node
+// coordinates, the node of a point, the directions, the sweep scaffold of the searches with its hop rule and its cost rule,
+// the field description of either metric, block centres, the vertices of a lattice path and the reference points along it
+// (the rules are stated in include/scp_hip.h, "reference paths by a lattice search"), and the host side every call on a
+// lattice begins with.
 #pragma once
 #include "scp_common.h"
 #include "scp_corridor_device.h"
@@ -13,8 +14,8 @@ struct Lattice {
 };
 
 constexpr int LATTICE_SELF = 13;  // the direction code of the node itself
-constexpr unsigned DIST_UNREACHED = 0xFFFFu;
-constexpr uint32_t COST_UNREACHED = 0xFFFFFFFFu;  // the weighted search (scp_lattice_weighted.hip)
+constexpr uint16_t DIST_UNREACHED = 0xFFFFu;      // an entry of a hop field / of a cost field that the search has not
+constexpr uint32_t COST_UNREACHED = 0xFFFFFFFFu;  // reached
 
 // direction order: the codes other than 13 by |dx| + |dy| + |dz|, then by code
 struct DirectionOrder {
@@ -95,74 +96,33 @@ __device__ inline int path_endpoints(const Lattice& lt, const CorridorGrid& g, c
   return (edges[goal] >> LATTICE_SELF & 1u) ? 0 : 2;
 }
 
-// The breadth-first search of one workgroup (every thread calls it with the same arguments), level by level from `origin`
-// with dist[origin] = 0 and every other entry DIST_UNREACHED on entry, behind a barrier.  In level l a node becomes l + 1 if
-// it is unreached and has a neighbour at l over a set edge bit; a concurrent store turns 0xFFFF into l + 1 and neither equals
-// l, so the reads of a level need no order among themselves.  The two flags of a level live in slot l mod 3 of `changed` /
-// `reached` (3 LDS words each, zero on entry): written in the sweep, read by everybody after the barrier, cleared by thread 0
-// two levels later (after everybody has read them, before anybody writes them again).
-// A move changes every coordinate by at most one, so a node at l + 1 lies within l + 1 of the origin per coordinate: the
-// sweep of level l walks that box only (the same dist as a sweep over every node).
-// The search ends after the level that changes nothing or -- the stop condition -- reaches the node `stop_at` (-1: none, the
-// field is then complete).  One barrier per level, at most `nodes` levels.
-__device__ __forceinline__ void lattice_search(const Lattice& lt, const uint32_t* __restrict__ edges, uint16_t* dist, int* changed_flag,
-                                      int* reached_flag, int origin, int stop_at, bool go) {
-  const int tid = threadIdx.x, T = blockDim.x;
-  const int G[3] = {origin % lt.L[0], (origin / lt.L[0]) % lt.L[1], origin / (lt.L[0] * lt.L[1])};
-  for (int level = 0; level < lt.nodes && go; ++level) {  // (go is the same in every thread: both exits are the workgroup's)
-    const int slot = level % 3;
-    int lo[3], w[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      lo[d] = G[d] - (level + 1) > 0 ? G[d] - (level + 1) : 0;
-      const int hi = G[d] + (level + 1) < lt.L[d] - 1 ? G[d] + (level + 1) : lt.L[d] - 1;
-      w[d] = hi - lo[d] + 1;
-    }
-    const int count = w[0] * w[1] * w[2];
-    const bool whole = count == lt.nodes;
-    bool changed = false, reached = false;
-    for (int idx = tid; idx < count; idx += T) {
-      const int node = whole ? idx : ((lo[2] + idx / (w[0] * w[1])) * lt.L[1] + lo[1] + (idx / w[0]) % w[1]) * lt.L[0] + lo[0] + idx % w[0];
-      if (dist[node] != DIST_UNREACHED) continue;
-      uint32_t m = edges[node];
-      if (!(m >> LATTICE_SELF & 1u)) continue;
-      m &= ~(1u << LATTICE_SELF) & 0x7FFFFFFu;
-      while (m) {
-        const int n = __ffs(m) - 1;
-        m &= m - 1;
-        const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
-        if ((unsigned)nb < (unsigned)lt.nodes && dist[nb] == level) {
-          dist[node] = (uint16_t)(level + 1);
-          changed = true;
-          if (node == stop_at) reached = true;
-          break;
-        }
-      }
-    }
-    if (changed) changed_flag[slot] = 1;
-    if (reached) reached_flag[slot] = 1;
-    __syncthreads();
-    go = changed_flag[slot] != 0 && reached_flag[slot] == 0;
-    if (tid == 0) changed_flag[(level + 2) % 3] = reached_flag[(level + 2) % 3] = 0;
-  }
-}
+// ----------------------------------------------------------------------------------------------------
+// the searches: one sweep scaffold, a rule per metric
+// ----------------------------------------------------------------------------------------------------
+struct SweepVisit {  // what the visit of one node did
+  bool changed, reached;  // its entry of the field changed / it is the rule's stop node and has just been reached
+};
 
-// The weighted search of one workgroup (every thread calls it with the same arguments): sweeps from `origin` with
-// cost[origin] = 0 and every other entry COST_UNREACHED on entry, behind a barrier.  Pull form: a thread owns the nodes it
-// writes; a passable node reads its neighbours over its set edge bits and stores min(own, cost[nb] + w), w = edge_cost.  No two threads write one word and a 32-bit LDS read does not tear, so
-// a racing read sees an older or a newer upper bound: every stored value is the cost of a real walk (a simple one: a walk
-// back through the node costs more than the node holds), values only fall, and a sweep that changes nothing has read final
-// values everywhere -- the fixed point, which is the shortest-cost field whatever the schedule.  With weight * prefer <=
-// 32768 an edge costs at most 65778 and a simple path at most 32767 of them, so no sum (a candidate included) wraps.
-// The growing box of lattice_search holds here too: a node reachable in k moves lies within k of the origin per coordinate,
-// so sweep k walks the box of k + 1; if it changes nothing, the box's outer shell is unreached and nothing beyond it can be
-// reached.  Flags as in lattice_search (slot sweep mod 3 of `changed`, zero on entry); one barrier per sweep, at most
-// `nodes` sweeps (sweep k leaves every node at least as good as k + 1 synchronous Bellman-Ford rounds).
-__device__ __forceinline__ void lattice_relax(const Lattice& lt, const uint32_t* __restrict__ edges, const uint32_t* __restrict__ pen,
-                                              uint32_t* cost, int* changed_flag, int origin, bool go) {
+// The search of one workgroup (every thread calls it with the same arguments): sweeps from `origin`, whose entry of the
+// rule's field is 0 and every other entry the field's UNREACHED on entry, behind a barrier.  A sweep offers every passable
+// node of its box that the rule has not settled to rule.visit, with the node's edge mask less the self bit; what a visit
+// reads and stores, and why the threads of a sweep need no order among themselves, is the rule's.
+// The box: a move changes every coordinate by at most one, so a node reachable in k moves lies within k of the origin per
+// coordinate: sweep k walks the box of k + 1 only.  If it changes nothing, the box's outer shell is unreached and nothing
+// beyond it can be reached: the same field as sweeps over every node.
+// The flags: sweep k's live in slot k mod 3 of `flags` (three "changed" words, then three "reached" words if the rule has a
+// stop node; all zero on entry): written in the sweep, read by everybody after the barrier, cleared by thread 0 two sweeps
+// later (after everybody has read them, before anybody writes them again).
+// The search ends after the sweep that changes nothing or reaches the rule's stop node.  One barrier per sweep (it also
+// stands between the last sweep and the caller's reads), at most `nodes` sweeps.
+template <class Rule>
+__device__ __forceinline__ void lattice_sweeps(const Lattice& lt, const uint32_t* __restrict__ edges, const Rule& rule, int* flags,
+                                               int origin, bool go) {
   const int tid = threadIdx.x, T = blockDim.x;
+  int* changed_flag = flags;
+  int* reached_flag = flags + 3;  // (only where Rule::HAS_STOP)
   const int G[3] = {origin % lt.L[0], (origin / lt.L[0]) % lt.L[1], origin / (lt.L[0] * lt.L[1])};
-  for (int sweep = 0; sweep < lt.nodes && go; ++sweep) {  // (go is the same in every thread)
+  for (int sweep = 0; sweep < lt.nodes && go; ++sweep) {  // (go is the same in every thread: both exits are the workgroup's)
     const int slot = sweep % 3;
     int lo[3], w[3];
 #pragma unroll
@@ -173,35 +133,113 @@ __device__ __forceinline__ void lattice_relax(const Lattice& lt, const uint32_t*
     }
     const int count = w[0] * w[1] * w[2];
     const bool whole = count == lt.nodes;
-    bool changed = false;
+    bool changed = false, reached = false;
     for (int idx = tid; idx < count; idx += T) {
       const int node = whole ? idx : ((lo[2] + idx / (w[0] * w[1])) * lt.L[1] + lo[1] + (idx / w[0]) % w[1]) * lt.L[0] + lo[0] + idx % w[0];
+      if (rule.settled(node)) continue;
       uint32_t m = edges[node];
       if (!(m >> LATTICE_SELF & 1u)) continue;
       m &= ~(1u << LATTICE_SELF) & 0x7FFFFFFu;
-      const uint32_t own = cost[node];
-      uint32_t best = own;
-      while (m) {
-        const int n = __ffs(m) - 1;
-        m &= m - 1;
-        const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
-        if ((unsigned)nb >= (unsigned)lt.nodes) continue;
-        const uint32_t c = cost[nb];
-        if (c == COST_UNREACHED) continue;
-        const uint32_t via = c + edge_cost(pen, node, nb, n);
-        best = via < best ? via : best;
-      }
-      if (best < own) {
-        cost[node] = best;
-        changed = true;
-      }
+      const SweepVisit v = rule.visit(lt, sweep, node, m);
+      if (v.changed) changed = true;
+      if (Rule::HAS_STOP && v.reached) reached = true;
     }
     if (changed) changed_flag[slot] = 1;
+    if (Rule::HAS_STOP && reached) reached_flag[slot] = 1;
     __syncthreads();
-    go = changed_flag[slot] != 0;
-    if (tid == 0) changed_flag[(sweep + 2) % 3] = 0;
+    go = changed_flag[slot] != 0 && !(Rule::HAS_STOP && reached_flag[slot] != 0);
+    if (tid == 0) {
+      changed_flag[(sweep + 2) % 3] = 0;
+      if (Rule::HAS_STOP) reached_flag[(sweep + 2) % 3] = 0;
+    }
   }
 }
+
+// The hop rule: breadth first, sweep l is level l.  A node becomes l + 1 if it is unreached and has a neighbour at l over a
+// set edge bit; a concurrent store turns 0xFFFF into l + 1 and neither equals l, so the reads of a level need no order among
+// themselves.  A reached node is settled.  `stop_at`: the node whose reaching ends the search (-1: none, the field is then
+// complete).
+struct HopRule {
+  static constexpr bool HAS_STOP = true;
+  uint16_t* dist;
+  int stop_at;
+  __device__ __forceinline__ bool settled(int node) const { return dist[node] != DIST_UNREACHED; }
+  __device__ __forceinline__ SweepVisit visit(const Lattice& lt, int level, int node, uint32_t m) const {
+    while (m) {
+      const int n = __ffs(m) - 1;
+      m &= m - 1;
+      const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
+      if ((unsigned)nb < (unsigned)lt.nodes && dist[nb] == level) {
+        dist[node] = (uint16_t)(level + 1);
+        return {true, node == stop_at};
+      }
+    }
+    return {false, false};
+  }
+};
+
+// The cost rule: the weighted search, run to its fixed point (no stop node, no node is ever settled).  Pull form: a thread
+// owns the nodes it writes; a node reads its neighbours over its set edge bits and stores min(own, cost[nb] + w), w =
+// edge_cost.  No two threads write one word and a 32-bit LDS read does not tear, so a racing read sees an older or a newer
+// upper bound: every stored value is the cost of a real walk (a simple one: a walk back through the node costs more than the
+// node holds), values only fall, and a sweep that changes nothing has read final values everywhere -- the fixed point, which
+// is the shortest-cost field whatever the schedule.  With weight * prefer <= 32768 an edge costs at most 65778 and a simple
+// path at most 32767 of them, so no sum (a candidate included) wraps.  Sweep k leaves every node at least as good as k + 1
+// synchronous Bellman-Ford rounds.
+struct CostRule {
+  static constexpr bool HAS_STOP = false;
+  uint32_t* cost;
+  const uint32_t* __restrict__ pen;
+  __device__ __forceinline__ bool settled(int) const { return false; }
+  __device__ __forceinline__ SweepVisit visit(const Lattice& lt, int, int node, uint32_t m) const {
+    const uint32_t own = cost[node];
+    uint32_t best = own;
+    while (m) {
+      const int n = __ffs(m) - 1;
+      m &= m - 1;
+      const int nb = node + direction_offset(lt, n);  // (in the lattice wherever the masks belong to this lattice)
+      if ((unsigned)nb >= (unsigned)lt.nodes) continue;
+      const uint32_t c = cost[nb];
+      if (c == COST_UNREACHED) continue;
+      const uint32_t via = c + edge_cost(pen, node, nb, n);
+      best = via < best ? via : best;
+    }
+    if (best < own) {
+      cost[node] = best;
+      return {true, false};
+    }
+    return {false, false};
+  }
+};
+
+// What the kernels of scp_lattice_search.hip know of a metric: the field's word, its UNREACHED, the rule of its search, the
+// flag words that rule needs, whether a path search stops once it reaches the start and has a cost to report, for the walk
+// from the start to the goal whether the neighbour nb in direction n leads on from a node that holds `here`, and SMALL_CAP:
+// a lattice of at most so many nodes runs an instantiation whose LDS field holds just these (the cost field: 32 KiB and
+// several workgroups per CU instead of the full 128 KiB and one; the hop field is 64 KiB whatever the lattice).
+struct HopField {
+  using Word = uint16_t;
+  using Rule = HopRule;
+  static constexpr Word UNREACHED = DIST_UNREACHED;
+  static constexpr int FLAG_WORDS = 6, SMALL_CAP = SCP_LATTICE_MAX_NODES;
+  static constexpr bool STOPS_AT_START = true, HAS_PATH_COST = false;
+  __device__ static Rule rule(Word* field, const uint32_t*, int stop_at) { return {field, stop_at}; }
+  __device__ static bool leads_on(const Word* field, const uint32_t*, int, unsigned here, int nb, int) {
+    return field[nb] == here - 1u;
+  }
+};
+
+struct CostField {
+  using Word = uint32_t;
+  using Rule = CostRule;
+  static constexpr Word UNREACHED = COST_UNREACHED;
+  static constexpr int FLAG_WORDS = 3, SMALL_CAP = 8192;
+  static constexpr bool STOPS_AT_START = false, HAS_PATH_COST = true;
+  __device__ static Rule rule(Word* field, const uint32_t* pen, int) { return {field, pen}; }
+  __device__ static bool leads_on(const Word* field, const uint32_t* pen, int node, uint32_t here, int nb, int n) {
+    return field[nb] != UNREACHED && field[nb] + edge_cost(pen, node, nb, n) == here;
+  }
+};
 
 // coordinate d of a node
 __device__ inline int lattice_coord(const Lattice& lt, int node, int d) {
@@ -227,7 +265,7 @@ __device__ inline double reference_vertex(const Lattice& lt, const CorridorGrid&
 }
 
 // The K + 1 reference points of vehicle i along p0, the centres of its path's m nodes, pf (the rule "reference points" of
-// include/scp_hip.h), written side by side by the workgroup's threads: the hop search and the weighted search share it.
+// include/scp_hip.h), written side by side by the workgroup's threads.
 template <int D>
 __device__ __forceinline__ void write_reference_points(const Lattice& lt, const CorridorGrid& g, int K, const int32_t* my_path, int m,
                                                        const double* a0, const double* af, double* ref_i) {
@@ -252,6 +290,9 @@ __device__ __forceinline__ void write_reference_points(const Lattice& lt, const 
   }
 }
 
+// ----------------------------------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------------------------------
 // the lattice of a grid; SCP_ERR_INVALID with a message where it is not supported
 inline int lattice_of(scp_ctx* ctx, const char* who, int D, const CorridorGrid& g, int stride, Lattice& lt) {
   SCP_REQUIRE(ctx, stride >= 1, "%s: stride=%d (>= 1 cells)", who, stride);
@@ -265,5 +306,31 @@ inline int lattice_of(scp_ctx* ctx, const char* who, int D, const CorridorGrid& 
   }
   lt.nodes = (int)nodes;
   lt.stride = stride;
+  return SCP_OK;
+}
+
+// what every call on a lattice begins with: the ctx, the grid, the lattice (who: the call's name in messages)
+inline int lattice_begin(scp_ctx* ctx, const char* who, int D, const scp_occupancy_grid* grid, int stride, CorridorGrid& g,
+                         Lattice& lt) {
+  if (!ctx) return SCP_ERR_INVALID;
+  const int rc = corridor_grid(ctx, who, D, grid, g);
+  return rc ? rc : lattice_of(ctx, who, D, g, stride, lt);
+}
+
+// a clearance beyond the widest dimension clipped to it (the grown ranges are clipped to the grid: the same answers, no
+// overflow)
+inline int clipped_clearance(int D, const CorridorGrid& g, int clearance) {
+  int widest = 1;
+  for (int d = 0; d < D; ++d) widest = g.dims[d] > widest ? g.dims[d] : widest;
+  return clearance > widest ? widest : clearance;
+}
+
+// An N x max_path int32 table a kernel keeps for itself where the caller wants none of it (`table` NULL): the workspace of
+// the continuous-time passes.
+inline int path_table(scp_ctx* ctx, int N, int max_path, int32_t*& table) {
+  if (table) return SCP_OK;
+  const int rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes, (size_t)N * max_path * sizeof(int32_t));
+  if (rc) return rc;
+  table = (int32_t*)ctx->sep_ws;
   return SCP_OK;
 }

@@ -203,25 +203,17 @@ __global__ __launch_bounds__(256) void shorten_paths_kernel(int N, int K, Lattic
 extern "C" int scp_shorten_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, const int32_t* sat, int stride,
                                  int clearance, const double* p0, const double* pf, int max_path, const int32_t* path,
                                  const scp_path_info* info, double* ref, int32_t* kept, scp_shorten_info* out) {
-  if (!ctx) return SCP_ERR_INVALID;
   CorridorGrid g;
   Lattice lt;
-  int rc = corridor_grid(ctx, "shorten_paths", D, grid, g);
+  int rc = lattice_begin(ctx, "shorten_paths", D, grid, stride, g, lt);
   if (rc) return rc;
-  if ((rc = lattice_of(ctx, "shorten_paths", D, g, stride, lt))) return rc;
   SCP_REQUIRE(ctx, clearance >= 0, "shorten_paths: clearance=%d (>= 0 cells)", clearance);
   SCP_REQUIRE(ctx, N >= 1 && K >= 1, "shorten_paths: bad shape N=%d K=%d", N, K);
   SCP_REQUIRE(ctx, max_path >= 1 && max_path <= lt.nodes, "shorten_paths: max_path=%d (1 .. %d nodes)", max_path, lt.nodes);
   SCP_REQUIRE(ctx, sat && p0 && pf && path && info && ref && out, "shorten_paths: null pointer");
-  int widest = 1;
-  for (int d = 0; d < D; ++d) widest = g.dims[d] > widest ? g.dims[d] : widest;
-  if (clearance > widest) clearance = widest;  // (the grown range is clipped to the grid: the same answers, no overflow)
+  clearance = clipped_clearance(D, g, clearance);
   const bool kept_wanted = kept != nullptr;
-  if (!kept) {  // the kernel keeps the list somewhere: the workspace of the continuous-time passes
-    rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes, (size_t)N * max_path * sizeof(int32_t));
-    if (rc) return rc;
-    kept = (int32_t*)ctx->sep_ws;
-  }
+  if ((rc = path_table(ctx, N, max_path, kept))) return rc;
   // measured with 64, 128 and 256 threads (1, 2 and 4 vehicles per workgroup) on a 46 x 46 and a 32 x 32 x 32 lattice with
   // 1024 vehicles: within 2 % of each other on both, so the finest grain
   const int threads = ctx->shorten_threads ? ctx->shorten_threads : 64;

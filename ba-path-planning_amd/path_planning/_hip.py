@@ -535,8 +535,8 @@ class Context:
         per workgroup of delay_margins and of lag_conflicts, 0: chosen by the call; results never depend on them),
         "stg_batch_threads" (threads per workgroup of schedule_starts_batch: 0 chosen by the call, 256 or 1024; likewise),
         "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
-        never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths, reference_paths_weighted
-        and lattice_costs: 0 chosen by the call, 256, 512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
+        never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths, reference_paths_weighted,
+        lattice_distances and lattice_costs: 0 chosen by the call, 256, 512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
         256; likewise), "raster_item_cells" (the most cells of one work item of rasterize_shapes: 0 chosen by the call, or
         64 .. 2^24; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))

@@ -163,7 +163,7 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *     first writes a transposed copy of the masks (N^2 words in the context's workspace) and reads the masks' columns from
  *     its rows; a developer switch.
  *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths,
- *     scp_reference_paths_weighted and scp_lattice_costs; a developer switch.
+ *     scp_reference_paths_weighted, scp_lattice_distances and scp_lattice_costs; a developer switch.
  *   "shorten_threads" (default 0: chosen by the call; or 64, 128 or 256): threads per workgroup of scp_shorten_paths (one
  *     wave per vehicle, so 1, 2 or 4 vehicles per workgroup); a developer switch.
  *   "raster_item_cells" (default 0: 1024; or 64 .. 2^24): the most cells of one work item (one workgroup) of
@@ -1008,9 +1008,9 @@ int scp_reference_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_g
  *   dist_out (for tests): the complete field of every source.
  * ONE workgroup per source and no workgroup waits for another; dist lives in the workgroup's LDS (the layout of
  * scp_reference_paths: 64 KiB plus a few control words, static, two workgroups per CU); the level sweep is that call's, one
- * barrier per level, at most `nodes` levels; every workgroup looks the destinations' nodes up for itself.  Supported: n_src,
- * n_dst >= 1, nodes <= SCP_LATTICE_MAX_NODES.  Argument checks, enqueue on the ctx's stream, no host read, timing through
- * scp_ctx_last_pair_ms as scp_reference_paths. */
+ * barrier per level, at most `nodes` levels; every workgroup looks the destinations' nodes up for itself.  The workgroup
+ * width follows "ref_path_threads".  Supported: n_src, n_dst >= 1, nodes <= SCP_LATTICE_MAX_NODES.  Argument checks, enqueue
+ * on the ctx's stream, no host read, timing through scp_ctx_last_pair_ms as scp_reference_paths. */
 int scp_lattice_distances(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
                           int n_src, const double* src /* DEVICE [n_src][D] */, int n_dst,
                           const double* dst /* DEVICE [n_dst][D] */, uint16_t* hops /* DEVICE [n_src][n_dst] */,

@@ -92,6 +92,36 @@ def test_lattice_distances_equal_the_restatement(ctx, name):
         assert ctx.last_pair_ms() > 0.0
 
 
+@pytest.mark.parametrize("name", ["wall-13x11-stride2", "3d-6x5x4"])
+def test_workgroup_size_does_not_matter_to_lattice_distances(ctx, name):
+    """the matrix, both node lists and every field are the restatement's bytes at every width, with and without the fields"""
+    from path_planning import _hip
+
+    D, occ, stride, clearance, calls = MAPS[name]
+    pts = calls[-1][0]
+    src, dst = pts[:3], pts[3:]  # 3 sources; 9 / 7 destinations; both maps have a point without a node among them
+    g = _hip.occupancy_grid(D, ORIGIN[:D], CELL, occ.shape[::-1])
+    _, sat = ctx.occupancy_prepare(D, g, occ)
+    edges = ctx.lattice_edges(D, g, sat, stride, clearance)
+    want_hops, want_src, want_dst, want_dist, _ = P.hop_matrix(D, ORIGIN[:D], CELL, occ, stride, clearance, src, dst)
+    assert len(src) != len(dst) and (want_dst == -1).any() and (want_src >= 0).any() and (want_hops != 0xFFFF).any()
+    try:
+        for threads in (256, 512, 1024):
+            ctx.set_option("ref_path_threads", threads)
+            for want in (True, False):
+                hops, src_node, dst_node, dist = ctx.lattice_distances(D, g, stride, edges, ctx.tensor(src), ctx.tensor(dst),
+                                                                       want_dist=want)
+                np.testing.assert_array_equal(src_node.cpu().numpy(), want_src, err_msg=f"src_node at {threads}")
+                np.testing.assert_array_equal(dst_node.cpu().numpy(), want_dst, err_msg=f"dst_node at {threads}")
+                np.testing.assert_array_equal(hops.cpu().numpy().view(np.uint16), want_hops, err_msg=f"hops at {threads}")
+                if want:
+                    np.testing.assert_array_equal(dist.cpu().numpy().view(np.uint16), want_dist, err_msg=f"dist at {threads}")
+                else:
+                    assert dist is None
+    finally:
+        ctx.set_option("ref_path_threads", 0)
+
+
 def test_lattice_distances_cover_the_listed_inputs():
     """the restatement's own answers on the wall map show every kind of input the rule names (so the comparison above is
     not one of empty against empty)"""

@@ -134,6 +134,33 @@ def test_lattice_costs(ctx, name):
     np.testing.assert_array_equal(without[0].cpu().numpy().view(np.uint32), w_costs)
 
 
+@pytest.mark.parametrize("name", ["rand2d_13x11_s2", "rand3d_7_s1"])
+def test_workgroup_size_does_not_matter_to_lattice_costs(ctx, name):
+    """the matrix, both node lists and every field are the restatement's bytes at every width, with and without the fields"""
+    c = CASES[name]
+    want = c.want()
+    outside = (np.asarray(c.origin, dtype=np.float64) - 10.0 * c.cell)[None, :c.D]
+    src, dst = c.pf, np.concatenate([c.p0, c.pf[:2], outside])  # 5 sources, 8 destinations, the last one off the grid
+    g, _, edges, pen = _map(ctx, c)
+    w_costs, w_src, w_dst, w_cost = wr.cost_matrix(c.D, c.origin, c.cell, c.dims, c.stride, want["edges"], want["pen"], src, dst)
+    assert len(src) != len(dst) and w_dst[-1] == -1 and (w_src >= 0).any() and (w_costs != 0xFFFFFFFF).any()
+    try:
+        for threads in (256, 512, 1024):
+            ctx.set_option("ref_path_threads", threads)
+            for want_cost in (True, False):
+                costs, src_node, dst_node, cost = ctx.lattice_costs(c.D, g, c.stride, edges, ctx.tensor(src), ctx.tensor(dst), pen=pen,
+                                                                    want_cost=want_cost)
+                np.testing.assert_array_equal(src_node.cpu().numpy(), w_src, err_msg=f"src_node at {threads}")
+                np.testing.assert_array_equal(dst_node.cpu().numpy(), w_dst, err_msg=f"dst_node at {threads}")
+                np.testing.assert_array_equal(costs.cpu().numpy().view(np.uint32), w_costs, err_msg=f"costs at {threads}")
+                if want_cost:
+                    np.testing.assert_array_equal(cost.cpu().numpy().view(np.uint32), w_cost, err_msg=f"fields at {threads}")
+                else:
+                    assert cost is None
+    finally:
+        ctx.set_option("ref_path_threads", 0)
+
+
 @pytest.mark.parametrize("name", ["detour", "rand2d_13x11_s2", "limit"])
 def test_shorten_paths_takes_the_weighted_path(ctx, name):
     from path_planning import _hip
