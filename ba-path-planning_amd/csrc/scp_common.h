@@ -72,7 +72,7 @@ struct scp_ctx {
   int stg_batch_threads;          // threads per workgroup of scp_schedule_starts_batch: 0 chosen by the call, 256 or 1024
   int stg_batch_transposed;       // it reads the masks' columns from a transposed copy it makes in sep_ws: -1 chosen by the
                                   // call (from 16 candidates on), 0 never, 1 always
-  int ref_path_threads;           // threads per workgroup of scp_reference_paths, scp_reference_paths_weighted, scp_lattice_distances and scp_lattice_costs: 0 chosen by the call, 256, 512 or 1024
+  int ref_path_threads;           // threads per workgroup of scp_reference_paths, scp_reference_paths_weighted, scp_reference_paths_shared, scp_lattice_distances and scp_lattice_costs: 0 chosen by the call, 64, 256, 512 or 1024
   int shorten_threads;            // threads per workgroup of scp_shorten_paths: 0 chosen by the call, 64, 128 or 256
   int raster_item_cells;          // cells per work item of scp_rasterize_shapes: 0 chosen by the call (1024), or 64 .. 2^24
   void* rast_ws;                  // its device copy of shapes, vertices and work items (grown on demand) ...

@@ -111,9 +111,9 @@ extern "C" int scp_ctx_set_option(scp_ctx* ctx, const char* key, int value) {
     ctx->stg_batch_transposed = value;
     return SCP_OK;
   }
-  if (strcmp(key, "ref_path_threads") == 0) {  // scp_reference_paths, scp_reference_paths_weighted, scp_lattice_distances and scp_lattice_costs (same results; the GPU tests compare them)
-    if (value != 0 && value != 256 && value != 512 && value != 1024)
-      return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0, 256, 512 or 1024)", key, value);
+  if (strcmp(key, "ref_path_threads") == 0) {  // scp_reference_paths, scp_reference_paths_weighted, scp_reference_paths_shared, scp_lattice_distances and scp_lattice_costs (same results; the GPU tests compare them)
+    if (value != 0 && value != 64 && value != 256 && value != 512 && value != 1024)
+      return scp_fail(ctx, SCP_ERR_INVALID, "ctx_set_option: %s=%d (need 0, 64, 256, 512 or 1024)", key, value);
     ctx->ref_path_threads = value;
     return SCP_OK;
   }

@@ -41,9 +41,34 @@ struct MoveCost {
 };
 static __constant__ MoveCost MOVE_COST;
 
-// the cost w of the edge between two neighbours a and b, n the direction code from one to the other (pen NULL: zeros)
-__device__ inline uint32_t edge_cost(const uint32_t* __restrict__ pen, int a, int b, int n) {
-  return MOVE_COST.twice[n] + (pen ? pen[a] + pen[b] : 0u);
+// the penalty of a node under the map's penalties (pen NULL: zeros)
+__device__ inline uint32_t node_penalty(const uint32_t* __restrict__ pen, int u) { return pen ? pen[u] : 0u; }
+
+// The penalty vehicle i pays at a node once the other vehicles' paths count ("shared penalty" of include/scp_hip.h): the
+// map's pen (NULL: zeros), plus share_weight per vehicle by which the node's load without the vehicle itself, and one for
+// it, exceeds capacity; clamped to SCP_PENALTY_MAX_PRODUCT in 64 bits, before anything can wrap.  `own`: the bitmap of the
+// vehicle's own path (the workgroup's LDS), bit u mod 32 of word u div 32.
+struct SharedPenalty {
+  const uint32_t* __restrict__ pen;
+  const uint32_t* __restrict__ load;
+  const uint32_t* own;
+  uint32_t share_weight, capacity;
+  __device__ __forceinline__ uint32_t at(int u) const {
+    const uint32_t mine = own[u >> 5] >> (u & 31) & 1u, all = load[u];
+    const uint64_t with_me = (uint64_t)(all > mine ? all - mine : 0u) + 1u;  // others_i[u] + 1
+    const uint64_t over = with_me > capacity ? with_me - capacity : 0u;
+    const uint64_t sum = (uint64_t)(pen ? pen[u] : 0u) + (uint64_t)share_weight * over;
+    return sum < (uint64_t)SCP_PENALTY_MAX_PRODUCT ? (uint32_t)sum : (uint32_t)SCP_PENALTY_MAX_PRODUCT;
+  }
+};
+
+__device__ inline uint32_t node_penalty(const SharedPenalty& pen, int u) { return pen.at(u); }
+
+// The cost w of the edge between two neighbours a and b, n the direction code from one to the other, under either kind of
+// penalty; pen_a = node_penalty(pen, a), which a caller that looks at several neighbours of a fetches once.
+template <class Pen>
+__device__ __forceinline__ uint32_t edge_cost(const Pen& pen, uint32_t pen_a, int b, int n) {
+  return MOVE_COST.twice[n] + pen_a + node_penalty(pen, b);
 }
 
 // the id offset of the neighbour in direction n
@@ -186,13 +211,14 @@ struct HopRule {
 // is the shortest-cost field whatever the schedule.  With weight * prefer <= 32768 an edge costs at most 65778 and a simple
 // path at most 32767 of them, so no sum (a candidate included) wraps.  Sweep k leaves every node at least as good as k + 1
 // synchronous Bellman-Ford rounds.
-struct CostRule {
+template <class Pen>
+struct CostRuleOf {
   static constexpr bool HAS_STOP = false;
   uint32_t* cost;
-  const uint32_t* __restrict__ pen;
+  Pen pen;  // what edge_cost reads: the map's penalties (const uint32_t*, NULL: zeros) or one vehicle's SharedPenalty
   __device__ __forceinline__ bool settled(int) const { return false; }
   __device__ __forceinline__ SweepVisit visit(const Lattice& lt, int, int node, uint32_t m) const {
-    const uint32_t own = cost[node];
+    const uint32_t own = cost[node], pen_node = node_penalty(pen, node);  // (the node's own term: once, not per neighbour)
     uint32_t best = own;
     while (m) {
       const int n = __ffs(m) - 1;
@@ -201,7 +227,7 @@ struct CostRule {
       if ((unsigned)nb >= (unsigned)lt.nodes) continue;
       const uint32_t c = cost[nb];
       if (c == COST_UNREACHED) continue;
-      const uint32_t via = c + edge_cost(pen, node, nb, n);
+      const uint32_t via = c + edge_cost(pen, pen_node, nb, n);
       best = via < best ? via : best;
     }
     if (best < own) {
@@ -211,33 +237,80 @@ struct CostRule {
     return {false, false};
   }
 };
+using CostRule = CostRuleOf<const uint32_t*>;
 
 // What the kernels of scp_lattice_search.hip know of a metric: the field's word, its UNREACHED, the rule of its search, the
 // flag words that rule needs, whether a path search stops once it reaches the start and has a cost to report, for the walk
-// from the start to the goal whether the neighbour nb in direction n leads on from a node that holds `here`, and SMALL_CAP:
+// from the start to the goal whether the neighbour nb in direction n leads on from a node that holds `here` and pays pen_node
+// = own_penalty (fetched once per node of the walk), and SMALL_CAP:
 // a lattice of at most so many nodes runs an instantiation whose LDS field holds just these (the cost field: 32 KiB and
 // several workgroups per CU instead of the full 128 KiB and one; the hop field is 64 KiB whatever the lattice).
-struct HopField {
+// Args is what the path kernel is launched with for the metric and Pen what its rule and its walk read penalties through,
+// made by penalty() from the Args and the workgroup's bitmap of its own path.  REROUTES: the kernel improves a path set in
+// place (the rules "re-routing" and "groups" of include/scp_hip.h) -- workgroup b is vehicle(b), a vehicle without a path on
+// entry is skipped, the walk goes to walk_row() and replaces the path row only once it has reached the goal, and a vehicle
+// that keeps its path counts in kept().  The two plain metrics route every vehicle b afresh, straight into its row.
+struct PlainRoutes {
+  using Args = const uint32_t*;  // pen (the hop metric reads none)
+  using Pen = const uint32_t*;
+  static constexpr bool REROUTES = false;
+  __device__ static Pen penalty(Args pen, const uint32_t*) { return pen; }
+  __device__ static int64_t vehicle(Args, int b) { return b; }
+  __device__ static int32_t* walk_row(Args, int, int, int32_t* my_path) { return my_path; }
+  __device__ static void kept(Args) {}
+};
+
+struct HopField : PlainRoutes {
   using Word = uint16_t;
   using Rule = HopRule;
   static constexpr Word UNREACHED = DIST_UNREACHED;
   static constexpr int FLAG_WORDS = 6, SMALL_CAP = SCP_LATTICE_MAX_NODES;
   static constexpr bool STOPS_AT_START = true, HAS_PATH_COST = false;
   __device__ static Rule rule(Word* field, const uint32_t*, int stop_at) { return {field, stop_at}; }
-  __device__ static bool leads_on(const Word* field, const uint32_t*, int, unsigned here, int nb, int) {
+  __device__ static uint32_t own_penalty(const uint32_t*, int) { return 0u; }
+  __device__ static bool leads_on(const Word* field, const uint32_t*, uint32_t, unsigned here, int nb, int) {
     return field[nb] == here - 1u;
   }
 };
 
-struct CostField {
+struct CostField : PlainRoutes {
   using Word = uint32_t;
   using Rule = CostRule;
   static constexpr Word UNREACHED = COST_UNREACHED;
   static constexpr int FLAG_WORDS = 3, SMALL_CAP = 8192;
   static constexpr bool STOPS_AT_START = false, HAS_PATH_COST = true;
   __device__ static Rule rule(Word* field, const uint32_t* pen, int) { return {field, pen}; }
-  __device__ static bool leads_on(const Word* field, const uint32_t* pen, int node, uint32_t here, int nb, int n) {
-    return field[nb] != UNREACHED && field[nb] + edge_cost(pen, node, nb, n) == here;
+  __device__ static uint32_t own_penalty(const uint32_t* pen, int node) { return node_penalty(pen, node); }
+  __device__ static bool leads_on(const Word* field, const uint32_t* pen, uint32_t pen_node, uint32_t here, int nb, int n) {
+    return field[nb] != UNREACHED && field[nb] + edge_cost(pen, pen_node, nb, n) == here;
+  }
+};
+
+// the cost field under one vehicle's shared penalty (scp_reference_paths_shared): the CostField's sizes, a bitmap of CAP / 32
+// words beside it
+struct SharedField {
+  using Word = uint32_t;
+  using Pen = SharedPenalty;
+  using Rule = CostRuleOf<SharedPenalty>;
+  struct Args {
+    const uint32_t* pen;   // [nodes] or NULL
+    const uint32_t* load;  // [nodes]: scp_path_load of the set on entry
+    uint32_t share_weight, capacity;
+    int groups, group;
+    int32_t* walk_rows;          // [workgroups][max_path]: where a walk goes until it has reached the goal
+    unsigned long long* n_kept;  // vehicles whose walk did not
+  };
+  static constexpr Word UNREACHED = COST_UNREACHED;
+  static constexpr int FLAG_WORDS = 3, SMALL_CAP = 8192;
+  static constexpr bool STOPS_AT_START = false, HAS_PATH_COST = true, REROUTES = true;
+  __device__ static Pen penalty(const Args& a, const uint32_t* own) { return {a.pen, a.load, own, a.share_weight, a.capacity}; }
+  __device__ static int64_t vehicle(const Args& a, int b) { return a.group + (int64_t)b * a.groups; }
+  __device__ static int32_t* walk_row(const Args& a, int b, int max_path, int32_t*) { return a.walk_rows + (int64_t)b * max_path; }
+  __device__ static void kept(const Args& a) { atomicAdd(a.n_kept, 1ull); }
+  __device__ static Rule rule(Word* field, const Pen& pen, int) { return {field, pen}; }
+  __device__ static uint32_t own_penalty(const Pen& pen, int node) { return node_penalty(pen, node); }
+  __device__ static bool leads_on(const Word* field, const Pen& pen, uint32_t pen_node, uint32_t here, int nb, int n) {
+    return field[nb] != UNREACHED && field[nb] + edge_cost(pen, pen_node, nb, n) == here;
   }
 };
 
@@ -324,6 +397,22 @@ inline int clipped_clearance(int D, const CorridorGrid& g, int clearance) {
   for (int d = 0; d < D; ++d) widest = g.dims[d] > widest ? g.dims[d] : widest;
   return clearance > widest ? widest : clearance;
 }
+
+// ---- shared paths: what scp_path_share.hip launches for the driver in scp_lattice_search.hip (enqueue only: the caller has
+// checked the arguments and holds the timing bracket) ----
+struct PathSet {  // the four per-vehicle outputs of a path search: [N][K+1][D], [N][max_path], [N], [N]
+  double* ref;
+  int32_t* path;
+  scp_path_info* info;
+  uint32_t* path_cost;
+};
+// load and *overuse of a set (written, not accumulated; `clear_overuse` false: the word is zero already)
+int path_load_enqueue(scp_ctx* ctx, int N, int max_path, int nodes, const int32_t* path, const scp_path_info* info, int capacity,
+                      uint32_t* load, uint64_t* overuse, bool clear_overuse);
+// round r of a negotiation is over: `cur` replaces `best` iff r == 0 or overuse[r] is smaller than every earlier entry,
+// decided on the device; *best_round = the earliest smallest of overuse[0 .. r]
+int keep_better_enqueue(scp_ctx* ctx, int N, int K, int D, int max_path, const PathSet& cur, const PathSet& best,
+                        const uint64_t* overuse, int r, int32_t* best_round);
 
 // An N x max_path int32 table a kernel keeps for itself where the caller wants none of it (`table` NULL): the workspace of
 // the continuous-time passes.

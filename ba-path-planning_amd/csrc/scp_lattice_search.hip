@@ -2,10 +2,12 @@
 // by the length- and clearance-weighted cost (run to its fixed point, a uint32 field).  Per vehicle the search from its goal,
 // the path from its start and the K + 1 reference points along it; per source the search and the values at every
 // destination.  ONE workgroup per vehicle / per source, the field in LDS; one kernel of either kind, instantiated per metric
-// (HopField / CostField of scp_lattice_device.h, where the sweep lives).  The rules are stated in include/scp_hip.h
-// ("reference paths by a lattice search", "lattice distances", "weighted search"); tests/reference_path_ref.py,
-// tests/assign_paths_ref.py and tests/weighted_path_ref.py restate them.  Integers only, except the reference points (bit for
-// bit: no contraction).
+// (HopField / CostField / SharedField of scp_lattice_device.h, where the sweep lives).  The third metric is the weighted one
+// under a penalty per vehicle that counts the other vehicles' paths: it re-routes one group of a path set in place
+// (scp_reference_paths_shared), and scp_negotiate_paths drives it over the rounds with the load and keep kernels of
+// scp_path_share.hip.  The rules are stated in include/scp_hip.h ("reference paths by a lattice search", "lattice distances",
+// "weighted search", "shared paths"); tests/reference_path_ref.py, tests/assign_paths_ref.py, tests/weighted_path_ref.py and
+// tests/shared_path_ref.py restate them.  Integers only, except the reference points (bit for bit: no contraction).
 #include "scp_common.h"
 #include "scp_corridor_device.h"
 #include "scp_lattice_device.h"
@@ -19,24 +21,43 @@ namespace {
 // ----------------------------------------------------------------------------------------------------
 enum { CTL_STATUS = 0, CTL_START, CTL_GOAL, CTL_NODES, CTL_FLAGS /* Field::FLAG_WORDS words */ };
 
-// CAP: the nodes the workgroup's LDS field holds (lt.nodes <= CAP: the host chooses the instantiation).  pen and path_cost
-// belong to the weighted metric (pen NULL: zeros); the hop metric reads and writes neither.
+// CAP: the nodes the workgroup's LDS field holds (lt.nodes <= CAP: the host chooses the instantiation).  args: the metric's
+// (Field::Args: pen for the weighted metric, NULL: zeros; the shared metric's load, weights and group besides); path_cost
+// belongs to the weighted metrics, the hop metric reads and writes neither.  n_failed is the plain metrics' (a re-routing
+// changes no status).
 template <int D, class Field, int CAP>
 __global__ __launch_bounds__(1024) void lattice_paths_kernel(int K, Lattice lt, CorridorGrid g, const uint32_t* __restrict__ edges,
-                                                              const uint32_t* __restrict__ pen, const double* __restrict__ p0,
+                                                              typename Field::Args args, const double* __restrict__ p0,
                                                               const double* __restrict__ pf, int max_path, double* __restrict__ ref,
-                                                              int32_t* path, scp_path_info* __restrict__ info,
+                                                              int32_t* path, scp_path_info* info,
                                                               uint32_t* __restrict__ path_cost,
                                                               typename Field::Word* __restrict__ field_out,
                                                               unsigned long long* __restrict__ n_failed) {
   using Word = typename Field::Word;
   __shared__ Word field[CAP];
+  __shared__ uint32_t own[Field::REROUTES ? CAP / 32 : 1];  // the nodes of the vehicle's path on entry, a bit each
   __shared__ int ctl[CTL_FLAGS + Field::FLAG_WORDS];
   const int tid = threadIdx.x, T = blockDim.x;
-  const int64_t i = blockIdx.x;
+  const int64_t i = Field::vehicle(args, blockIdx.x);
   const double* a0 = p0 + i * D;
   const double* af = pf + i * D;
   int32_t* my_path = path + i * max_path;
+  int32_t* walk_row = Field::walk_row(args, blockIdx.x, max_path, my_path);
+  const typename Field::Pen pen = Field::penalty(args, own);
+
+  if (Field::REROUTES) {
+    // a vehicle without a path is skipped, nothing of it is written (the same word in every thread: the workgroup returns);
+    // the others mark their path in the bitmap before anything overwrites the row (the barrier: the one below)
+    const scp_path_info was = info[i];
+    if (was.status != 0) return;
+    for (int w = tid; w < (lt.nodes + 31) / 32; w += T) own[w] = 0u;
+    __syncthreads();
+    const int m0 = was.n_nodes < max_path ? was.n_nodes : max_path;
+    for (int t = tid; t < m0; t += T) {
+      const int node = my_path[t];
+      if ((unsigned)node < (unsigned)lt.nodes) atomicOr(&own[node >> 5], 1u << (node & 31));
+    }
+  }
 
   // start and goal: decided once, by one thread
   if (tid == 0) {
@@ -78,14 +99,14 @@ __global__ __launch_bounds__(1024) void lattice_paths_kernel(int K, Lattice lt, 
           m = 0;
           break;
         }
-        my_path[m++] = node;
+        walk_row[m++] = node;
         if (node == goal) break;
-        const uint32_t mask = edges[node], here = field[node];
+        const uint32_t mask = edges[node], here = field[node], pen_node = Field::own_penalty(pen, node);
         int next = -1;
         for (int k = 0; k < 26 && next < 0; ++k) {
           const int n = DIRECTION_ORDER.code[k];
           const int nb = node + direction_offset(lt, n);
-          if ((mask >> n & 1u) && (unsigned)nb < (unsigned)lt.nodes && Field::leads_on(field, pen, node, here, nb, n)) next = nb;
+          if ((mask >> n & 1u) && (unsigned)nb < (unsigned)lt.nodes && Field::leads_on(field, pen, pen_node, here, nb, n)) next = nb;
         }
         if (next < 0) {  // (cannot happen: a reached node other than the goal has such a neighbour)
           status = 3;
@@ -97,22 +118,30 @@ __global__ __launch_bounds__(1024) void lattice_paths_kernel(int K, Lattice lt, 
     }
     ctl[CTL_STATUS] = status;
     ctl[CTL_NODES] = m;
-    scp_path_info r;
-    r.status = status;
-    r.n_nodes = m;
-    r.start_node = start;
-    r.goal_node = goal;
-    info[i] = r;
-    if (Field::HAS_PATH_COST) path_cost[i] = status == 0 ? (uint32_t)field[start] : COST_UNREACHED;
-    if (status != 0) atomicAdd(n_failed, 1ull);
+    if (Field::REROUTES && status != 0) {
+      Field::kept(args);  // the vehicle keeps its path row, info, reference points and cost entirely
+    } else {
+      scp_path_info r;
+      r.status = status;
+      r.n_nodes = m;
+      r.start_node = start;
+      r.goal_node = goal;
+      info[i] = r;
+      if (Field::HAS_PATH_COST) path_cost[i] = status == 0 ? (uint32_t)field[start] : COST_UNREACHED;
+      if (!Field::REROUTES && status != 0) atomicAdd(n_failed, 1ull);
+    }
   }
-  __syncthreads();  // (the last barrier: nobody has returned before it)
+  __syncthreads();  // (the last barrier: only a skipped vehicle's workgroup has returned before it, as a whole)
   const int m = ctl[CTL_NODES];
+  if (Field::REROUTES) {
+    if (ctl[CTL_STATUS] != 0) return;
+    for (int t = tid; t < m; t += T) my_path[t] = walk_row[t];
+  }
   for (int t = m + tid; t < max_path; t += T) my_path[t] = -1;
   if (ctl[CTL_STATUS] != 0) return;
 
-  // the reference points, side by side
-  write_reference_points<D>(lt, g, K, my_path, m, a0, af, ref + i * (K + 1) * D);
+  // the reference points, side by side (from the walk's row: thread 0 wrote it before the barrier)
+  write_reference_points<D>(lt, g, K, walk_row, m, a0, af, ref + i * (K + 1) * D);
 }
 
 // ----------------------------------------------------------------------------------------------------
@@ -167,26 +196,141 @@ int search_threads(const scp_ctx* ctx, const Lattice& lt) {
   return ctx->ref_path_threads ? ctx->ref_path_threads : lt.nodes > 8192 ? 1024 : 512;
 }
 
+// what the three path searches check alike (n_failed apart) and the lattice they run on
+struct PathCall {
+  CorridorGrid g;
+  Lattice lt;
+};
+template <class Field>
+int path_call(scp_ctx* ctx, const char* who, int N, int K, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+              const double* p0, const double* pf, int max_path, const double* ref, const scp_path_info* info,
+              const uint32_t* path_cost, PathCall& c) {
+  const int rc = lattice_begin(ctx, who, D, grid, stride, c.g, c.lt);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, N >= 1 && K >= 1, "%s: bad shape N=%d K=%d", who, N, K);
+  SCP_REQUIRE(ctx, max_path >= 1 && max_path <= c.lt.nodes, "%s: max_path=%d (1 .. %d nodes)", who, max_path, c.lt.nodes);
+  SCP_REQUIRE(ctx, edges && p0 && pf && ref && info && (path_cost || !Field::HAS_PATH_COST), "%s: null pointer", who);
+  return SCP_OK;
+}
+
+// the one launch of a path search: `blocks` workgroups of the metric's kernel (inside the caller's timing bracket)
+template <class Field>
+void launch_paths(scp_ctx* ctx, int blocks, int K, int D, const PathCall& c, const uint32_t* edges, typename Field::Args args,
+                  const double* p0, const double* pf, int max_path, double* ref, int32_t* path, scp_path_info* info,
+                  uint32_t* path_cost, typename Field::Word* field_out, uint64_t* n_failed) {
+  const bool small = c.lt.nodes <= Field::SMALL_CAP;
+  auto kernel = D == 2 ? (small ? lattice_paths_kernel<2, Field, Field::SMALL_CAP> : lattice_paths_kernel<2, Field, SCP_LATTICE_MAX_NODES>)
+                       : (small ? lattice_paths_kernel<3, Field, Field::SMALL_CAP> : lattice_paths_kernel<3, Field, SCP_LATTICE_MAX_NODES>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(search_threads(ctx, c.lt)), 0, ctx->stream, K, c.lt, c.g, edges, args, p0, pf,
+                     max_path, ref, path, info, path_cost, field_out, (unsigned long long*)n_failed);
+}
+
 // scp_reference_paths (pen, path_cost NULL) and scp_reference_paths_weighted
 template <class Field>
 int reference_paths(scp_ctx* ctx, const char* who, int N, int K, int D, const scp_occupancy_grid* grid, int stride,
                     const uint32_t* edges, const uint32_t* pen, const double* p0, const double* pf, int max_path, double* ref,
                     int32_t* path, scp_path_info* info, uint32_t* path_cost, typename Field::Word* field_out, uint64_t* n_failed) {
-  CorridorGrid g;
-  Lattice lt;
-  int rc = lattice_begin(ctx, who, D, grid, stride, g, lt);
+  if (!ctx) return SCP_ERR_INVALID;
+  PathCall c;
+  int rc = path_call<Field>(ctx, who, N, K, D, grid, stride, edges, p0, pf, max_path, ref, info, path_cost, c);
   if (rc) return rc;
-  SCP_REQUIRE(ctx, N >= 1 && K >= 1, "%s: bad shape N=%d K=%d", who, N, K);
-  SCP_REQUIRE(ctx, max_path >= 1 && max_path <= lt.nodes, "%s: max_path=%d (1 .. %d nodes)", who, max_path, lt.nodes);
-  SCP_REQUIRE(ctx, edges && p0 && pf && ref && info && (path_cost || !Field::HAS_PATH_COST) && n_failed, "%s: null pointer", who);
+  SCP_REQUIRE(ctx, n_failed, "%s: null pointer", who);
   if ((rc = path_table(ctx, N, max_path, path))) return rc;
-  const bool small = lt.nodes <= Field::SMALL_CAP;
-  auto kernel = D == 2 ? (small ? lattice_paths_kernel<2, Field, Field::SMALL_CAP> : lattice_paths_kernel<2, Field, SCP_LATTICE_MAX_NODES>)
-                       : (small ? lattice_paths_kernel<3, Field, Field::SMALL_CAP> : lattice_paths_kernel<3, Field, SCP_LATTICE_MAX_NODES>);
   if ((rc = corridor_begin(ctx))) return rc;
   SCP_HIP_CHECK(ctx, hipMemsetAsync(n_failed, 0, sizeof(uint64_t), ctx->stream));
-  hipLaunchKernelGGL(kernel, dim3(N), dim3(search_threads(ctx, lt)), 0, ctx->stream, K, lt, g, edges, pen, p0, pf, max_path, ref,
-                     path, info, path_cost, field_out, (unsigned long long*)n_failed);
+  launch_paths<Field>(ctx, N, K, D, c, edges, pen, p0, pf, max_path, ref, path, info, path_cost, field_out, n_failed);
+  return corridor_end(ctx);
+}
+
+// ----------------------------------------------------------------------------------------------------
+// shared paths: one group re-routed under the others' load, and the negotiation over the rounds
+// ----------------------------------------------------------------------------------------------------
+int shared_checks(scp_ctx* ctx, const char* who, int N, int share_weight, int capacity, int groups) {
+  SCP_REQUIRE(ctx, share_weight >= 0 && share_weight <= SCP_PENALTY_MAX_PRODUCT, "%s: share_weight=%d (0 .. %d)", who, share_weight,
+              SCP_PENALTY_MAX_PRODUCT);
+  SCP_REQUIRE(ctx, capacity >= 1, "%s: capacity=%d (>= 1 vehicles per node)", who, capacity);
+  SCP_REQUIRE(ctx, groups >= 1 && groups <= N, "%s: groups=%d (1 .. N = %d)", who, groups, N);
+  return SCP_OK;
+}
+
+inline int group_size(int N, int groups, int group) { return (N - group + groups - 1) / groups; }  // vehicles i = group + b groups < N
+
+// the bytes of a workspace part, kept to 16 so that every part begins aligned
+inline size_t part_bytes(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+int reference_paths_shared(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+                           const uint32_t* pen, const double* p0, const double* pf, int max_path, double* ref, int32_t* path,
+                           scp_path_info* info, uint32_t* path_cost, uint32_t* cost_out, const uint32_t* load, int share_weight,
+                           int capacity, int groups, int group, uint64_t* n_kept) {
+  const char* who = "reference_paths_shared";
+  if (!ctx) return SCP_ERR_INVALID;
+  PathCall c;
+  int rc = path_call<SharedField>(ctx, who, N, K, D, grid, stride, edges, p0, pf, max_path, ref, info, path_cost, c);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, path && load && n_kept, "%s: null pointer (path is required: it holds the set the load was made from)", who);
+  if ((rc = shared_checks(ctx, who, N, share_weight, capacity, groups))) return rc;
+  SCP_REQUIRE(ctx, group >= 0 && group < groups, "%s: group=%d (0 .. groups - 1 = %d)", who, group, groups - 1);
+  const int blocks = group_size(N, groups, group);
+  if ((rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes, (size_t)blocks * max_path * sizeof(int32_t)))) return rc;
+  const SharedField::Args args = {pen, load, (uint32_t)share_weight, (uint32_t)capacity, groups, group, (int32_t*)ctx->sep_ws,
+                                  (unsigned long long*)n_kept};
+  if ((rc = corridor_begin(ctx))) return rc;
+  SCP_HIP_CHECK(ctx, hipMemsetAsync(n_kept, 0, sizeof(uint64_t), ctx->stream));
+  launch_paths<SharedField>(ctx, blocks, K, D, c, edges, args, p0, pf, max_path, ref, path, info, path_cost, cost_out, nullptr);
+  return corridor_end(ctx);
+}
+
+// The workspace: the current set (ref, path, info, path_cost), the load, the walks' rows of the largest group and, where the
+// caller wants no path table, the best set's.  Every word is written by this call before it is read.
+int negotiate_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+                    const uint32_t* pen, const double* p0, const double* pf, int max_path, double* ref, int32_t* path,
+                    scp_path_info* info, uint32_t* path_cost, uint64_t* n_failed, int share_weight, int capacity, int groups,
+                    int rounds, uint64_t* overuse_out, int32_t* best_round, uint64_t* n_kept) {
+  const char* who = "negotiate_paths";
+  if (!ctx) return SCP_ERR_INVALID;
+  PathCall c;
+  int rc = path_call<SharedField>(ctx, who, N, K, D, grid, stride, edges, p0, pf, max_path, ref, info, path_cost, c);
+  if (rc) return rc;
+  SCP_REQUIRE(ctx, n_failed && overuse_out && best_round && n_kept, "%s: null pointer", who);
+  if ((rc = shared_checks(ctx, who, N, share_weight, capacity, groups))) return rc;
+  SCP_REQUIRE(ctx, rounds >= 0 && rounds <= SCP_NEGOTIATE_MAX_ROUNDS, "%s: rounds=%d (0 .. %d)", who, rounds, SCP_NEGOTIATE_MAX_ROUNDS);
+
+  const size_t ref_bytes = part_bytes((size_t)N * (K + 1) * D * sizeof(double));
+  const size_t path_bytes = part_bytes((size_t)N * max_path * sizeof(int32_t));
+  const size_t info_bytes = part_bytes((size_t)N * sizeof(scp_path_info)), cost_bytes = part_bytes((size_t)N * sizeof(uint32_t));
+  const size_t load_bytes = part_bytes((size_t)c.lt.nodes * sizeof(uint32_t));
+  const size_t walk_bytes = part_bytes((size_t)group_size(N, groups, 0) * max_path * sizeof(int32_t));
+  const size_t need = ref_bytes + path_bytes + info_bytes + cost_bytes + load_bytes + walk_bytes + (path ? 0 : path_bytes);
+  if ((rc = scp_ctx_ensure_bytes(ctx, &ctx->sep_ws, &ctx->sep_ws_bytes, need))) return rc;
+  char* at = (char*)ctx->sep_ws;
+  PathSet cur;
+  cur.ref = (double*)at, at += ref_bytes;
+  cur.path = (int32_t*)at, at += path_bytes;
+  cur.info = (scp_path_info*)at, at += info_bytes;
+  cur.path_cost = (uint32_t*)at, at += cost_bytes;
+  uint32_t* load = (uint32_t*)at;
+  at += load_bytes;
+  int32_t* walk_rows = (int32_t*)at;
+  at += walk_bytes;
+  const PathSet best = {ref, path ? path : (int32_t*)at, info, path_cost};
+
+  if ((rc = corridor_begin(ctx))) return rc;
+  // round 0: the weighted search into the current set, whose reference points begin as the caller's
+  SCP_HIP_CHECK(ctx, hipMemcpyAsync(cur.ref, ref, (size_t)N * (K + 1) * D * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  SCP_HIP_CHECK(ctx, hipMemsetAsync(n_failed, 0, sizeof(uint64_t), ctx->stream));
+  SCP_HIP_CHECK(ctx, hipMemsetAsync(n_kept, 0, sizeof(uint64_t), ctx->stream));
+  SCP_HIP_CHECK(ctx, hipMemsetAsync(overuse_out, 0, (size_t)(rounds + 1) * sizeof(uint64_t), ctx->stream));
+  launch_paths<CostField>(ctx, N, K, D, c, edges, pen, p0, pf, max_path, cur.ref, cur.path, cur.info, cur.path_cost, nullptr, n_failed);
+  for (int r = 0;; ++r) {
+    if ((rc = path_load_enqueue(ctx, N, max_path, c.lt.nodes, cur.path, cur.info, capacity, load, overuse_out + r, false))) return rc;
+    if ((rc = keep_better_enqueue(ctx, N, K, D, max_path, cur, best, overuse_out, r, best_round))) return rc;
+    if (r == rounds) break;
+    const int group = r % groups;  // round r + 1 re-routes group r mod groups
+    const SharedField::Args args = {pen, load, (uint32_t)share_weight, (uint32_t)capacity, groups, group, walk_rows,
+                                    (unsigned long long*)n_kept};
+    launch_paths<SharedField>(ctx, group_size(N, groups, group), K, D, c, edges, args, p0, pf, max_path, cur.ref, cur.path, cur.info,
+                              cur.path_cost, nullptr, nullptr);
+  }
   return corridor_end(ctx);
 }
 
@@ -225,6 +369,24 @@ extern "C" int scp_reference_paths_weighted(scp_ctx* ctx, int N, int K, int D, c
                                             uint32_t* cost_out, uint64_t* n_failed) {
   return reference_paths<CostField>(ctx, "reference_paths_weighted", N, K, D, grid, stride, edges, pen, p0, pf, max_path, ref, path,
                                     info, path_cost, cost_out, n_failed);
+}
+
+extern "C" int scp_reference_paths_shared(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride,
+                                          const uint32_t* edges, const uint32_t* pen, const double* p0, const double* pf,
+                                          int max_path, double* ref, int32_t* path, scp_path_info* info, uint32_t* path_cost,
+                                          uint32_t* cost_out, const uint32_t* load, int share_weight, int capacity, int groups,
+                                          int group, uint64_t* n_kept) {
+  return reference_paths_shared(ctx, N, K, D, grid, stride, edges, pen, p0, pf, max_path, ref, path, info, path_cost, cost_out, load,
+                                share_weight, capacity, groups, group, n_kept);
+}
+
+extern "C" int scp_negotiate_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride,
+                                   const uint32_t* edges, const uint32_t* pen, const double* p0, const double* pf, int max_path,
+                                   double* ref, int32_t* path, scp_path_info* info, uint32_t* path_cost, uint64_t* n_failed,
+                                   int share_weight, int capacity, int groups, int rounds, uint64_t* overuse_out,
+                                   int32_t* best_round, uint64_t* n_kept) {
+  return negotiate_paths(ctx, N, K, D, grid, stride, edges, pen, p0, pf, max_path, ref, path, info, path_cost, n_failed, share_weight,
+                         capacity, groups, rounds, overuse_out, best_round, n_kept);
 }
 
 extern "C" int scp_lattice_distances(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,

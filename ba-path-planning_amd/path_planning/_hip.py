@@ -253,6 +253,7 @@ HOPS_UNREACHED = 0xFFFF       # scp_lattice_distances: no path, or a point witho
 COST_UNREACHED = 0xFFFFFFFF   # scp_reference_paths_weighted, scp_lattice_costs: no path, or a point without a node
 MOVE_WEIGHTS = (70, 99, 121)  # W[1 .. 3] of the weighted search: a straight move, a diagonal one in a plane, one in space
 PENALTY_MAX_PRODUCT = 32768   # SCP_PENALTY_MAX_PRODUCT: the largest weight * prefer of scp_lattice_penalties
+NEGOTIATE_MAX_ROUNDS = 64     # SCP_NEGOTIATE_MAX_ROUNDS: the most rounds of scp_negotiate_paths
 PATH_STATUS = {0: "found", 1: "the start lies off the lattice or on a block that is not free",
                2: "the goal lies off the lattice or on a block that is not free", 3: "the goal cannot be reached from the start",
                4: "the path has more nodes than max_path"}
@@ -417,6 +418,11 @@ PROTOTYPES = {
     "scp_lattice_penalties": (i32, [vp, i32, pg, vp, i32, i32, i32, vp]),
     "scp_reference_paths_weighted": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
     "scp_lattice_costs": (i32, [vp, i32, pg, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "scp_path_load": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp]),
+    "scp_reference_paths_shared": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
+                                         vp]),
+    "scp_negotiate_paths": (i32, [vp, i32, i32, i32, pg, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp,
+                                  vp]),
     "scp_rasterize_shapes": (i32, [vp, i32, pg, i32, P(ObstacleShape), i32, pd, f64, vp]),
     "scp_gemm_f64": (i32, [vp, i32, i32, i32, i32, f64, vp, vp, f64, vp]),
     "scp_qp_peek": (i32, [vp, cstr, vp, i64, P(i64)]),
@@ -536,7 +542,7 @@ class Context:
         "stg_batch_threads" (threads per workgroup of schedule_starts_batch: 0 chosen by the call, 256 or 1024; likewise),
         "stg_batch_transposed" (it reads the masks' columns from a transposed copy it makes first: -1 chosen by the call, 0
         never, 1 always; likewise), "ref_path_threads" (threads per workgroup of reference_paths, reference_paths_weighted,
-        lattice_distances and lattice_costs: 0 chosen by the call, 256, 512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
+        reference_paths_shared, lattice_distances and lattice_costs: 0 chosen by the call, 64, 256, 512 or 1024; likewise), "shorten_threads" (threads per workgroup of shorten_paths: 0 chosen by the call, 64, 128 or
         256; likewise), "raster_item_cells" (the most cells of one work item of rasterize_shapes: 0 chosen by the call, or
         64 .. 2^24; likewise)"""
         self.check(self.lib.scp_ctx_set_option(self.h, key.encode(), int(value)))
@@ -1063,6 +1069,57 @@ class Context:
                                               src.data_ptr(), n_dst, dst.data_ptr(), costs.data_ptr(), src_node.data_ptr(),
                                               dst_node.data_ptr(), _ptr(cost)))
         return costs, src_node, dst_node, cost
+
+    # ---- static obstacles: shared paths -------------------------------------------------------------------------------------
+    def path_load(self, N, max_path, nodes, path, info, capacity=1, load=None, overuse=None):
+        """scp_path_load: path (N, max_path) int32 and info as a path search returned them -> (load (nodes,) int32 device tensor
+        holding the uint32 words: the vehicles whose path uses each node, overuse int64 device tensor of one word: the sum of
+        max(0, load - capacity)).  Both are written, not accumulated (load / overuse: tensors to write into).  No host read."""
+        torch = _torch()
+        if load is None:
+            load = torch.empty(max(int(nodes), 1), dtype=torch.int32, device=self.tdev)
+        if overuse is None:
+            overuse = torch.empty(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_path_load(self.h, int(N), int(max_path), int(nodes), _ptr(path), _ptr(info), int(capacity),
+                                          _ptr(load), _ptr(overuse)))
+        return load, overuse
+
+    def reference_paths_shared(self, N, K, D, grid: OccupancyGrid, stride, edges, p0, pf, max_path, ref, path, info, path_cost, load,
+                               share_weight, capacity=1, groups=1, group=0, pen=None, cost=None):
+        """scp_reference_paths_shared: the vehicles i with i mod groups == group are re-routed under the load of the others'
+        paths.  ref, path, info, path_cost (as reference_paths_weighted returned them) are updated IN PLACE; load as path_load
+        made it from path / info; cost: an (N, nodes) int32 device tensor for the fields of the re-routed vehicles, or None.
+        Returns n_kept, an int64 device tensor of one word: the vehicles that kept their path because the new walk did not reach
+        the goal within max_path nodes.  No host read."""
+        torch = _torch()
+        n_kept = torch.empty(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_reference_paths_shared(self.h, N, K, D, C.byref(grid), int(stride), _ptr(edges), _ptr(pen),
+                                                       p0.data_ptr(), pf.data_ptr(), int(max_path), _ptr(ref), _ptr(path), _ptr(info),
+                                                       _ptr(path_cost), _ptr(cost), _ptr(load), int(share_weight), int(capacity),
+                                                       int(groups), int(group), n_kept.data_ptr()))
+        return n_kept
+
+    def negotiate_paths(self, N, K, D, grid: OccupancyGrid, stride, edges, p0, pf, max_path, ref, share_weight, capacity=1, groups=1,
+                        rounds=0, pen=None, want_path=True):
+        """scp_negotiate_paths: reference_paths_weighted, then `rounds` rounds in which one group after the other is re-routed
+        under the load of the others' paths; the least crowded set of paths is kept.  ref is updated IN PLACE.  Returns (path,
+        info, path_cost, n_failed as reference_paths_weighted returns them, overuse (rounds + 1,) int64 device tensor: the
+        overuse after every round, best_round int32 device tensor of one word, n_kept int64 device tensor of one word).  The
+        whole negotiation is enqueued at once.  No host read."""
+        torch = _torch()
+        path = torch.empty((N, max(int(max_path), 1)), dtype=torch.int32, device=self.tdev) if want_path else None
+        path_cost = torch.empty(max(N, 1), dtype=torch.int32, device=self.tdev)
+        info = self._record_buffer(N, PATH_INFO_DTYPE)
+        n_failed = torch.zeros(1, dtype=torch.int64, device=self.tdev)
+        overuse = torch.empty(max(int(rounds), 0) + 1, dtype=torch.int64, device=self.tdev)
+        best_round = torch.empty(1, dtype=torch.int32, device=self.tdev)
+        n_kept = torch.empty(1, dtype=torch.int64, device=self.tdev)
+        self.check(self.lib.scp_negotiate_paths(self.h, N, K, D, C.byref(grid), int(stride), _ptr(edges), _ptr(pen), p0.data_ptr(),
+                                                pf.data_ptr(), int(max_path), _ptr(ref), _ptr(path), info.data_ptr(),
+                                                path_cost.data_ptr(), n_failed.data_ptr(), int(share_weight), int(capacity),
+                                                int(groups), int(rounds), overuse.data_ptr(), best_round.data_ptr(),
+                                                n_kept.data_ptr()))
+        return path, info, path_cost, n_failed, overuse, best_round, n_kept
 
     def shorten_paths(self, N, K, D, grid: OccupancyGrid, sat, stride, clearance, p0, pf, max_path, path, info, ref, want_kept=True):
         """scp_shorten_paths: path (N, max_path) int32 and info as reference_paths returned them, p0 / pf (N, D) and ref

@@ -127,6 +127,18 @@ def build_parser():
     p.add_argument("--corridor-clear-weight", type=float, default=None, metavar="W",
                    help="with --corridor-keep-clear: how many straight moves one missing cell of clearance costs per node passed "
                         "(default 1)")
+    p.add_argument("--corridor-share", type=float, default=None, metavar="W",
+                   help="with --corridor-search and --corridor-metric length: the paths avoid each other's routes -- a lattice "
+                        "node that more vehicles' paths use than --corridor-share-capacity costs every further vehicle W straight "
+                        "moves per vehicle over capacity, the fleet re-routes in groups and the least crowded set of paths is "
+                        "kept (negotiated on the GPU, no host read between the rounds); the line then shows the overuse before "
+                        "and after")
+    p.add_argument("--corridor-share-capacity", type=int, default=None, metavar="C",
+                   help="with --corridor-share: the paths one lattice node carries for free (default 1)")
+    p.add_argument("--corridor-share-groups", type=int, default=None, metavar="G",
+                   help="with --corridor-share: the fleet re-routes in G groups, one per round (default 4)")
+    p.add_argument("--corridor-share-rounds", type=int, default=None, metavar="R",
+                   help="with --corridor-share: rounds of re-routing, 0 .. 64 (default: twice the groups)")
     p.add_argument("--corridor-shorten", action="store_true",
                    help="with --corridor-search: every path is cut down to the lattice nodes it cannot skip and its reference "
                         "points are spaced evenly by length (one GPU wave per vehicle)")
@@ -145,7 +157,8 @@ def obstacle_discs(parser, args):
     """the discs of --obstacle-discs as tuples of floats; the corridor flags are errors without it, --corridor-stride and
     --corridor-clearance without --corridor-search or --assign-cost path / length, --corridor-shorten and --corridor-metric
     without --corridor-search, --corridor-keep-clear without one of the two length searches, --corridor-clear-weight without
-    --corridor-keep-clear"""
+    --corridor-keep-clear, --corridor-share without both --corridor-search and --corridor-metric length, the other three
+    --corridor-share-* flags without --corridor-share"""
     by_path = args.assign_cost in ("path", "length")
     if by_path and not args.assign_goals:
         parser.error("--assign-cost needs --assign-goals")
@@ -157,6 +170,11 @@ def obstacle_discs(parser, args):
         parser.error(f"--corridor-keep-clear {args.corridor_keep_clear}: a whole number of cells >= 0")
     if args.corridor_clear_weight is not None and args.corridor_keep_clear is None:
         parser.error("--corridor-clear-weight needs --corridor-keep-clear")
+    if args.corridor_share is not None and not (args.corridor_search and args.corridor_metric == "length"):
+        parser.error("--corridor-share needs --corridor-search and --corridor-metric length")
+    for flag in ("capacity", "groups", "rounds"):
+        if getattr(args, "corridor_share_" + flag) is not None and args.corridor_share is None:
+            parser.error(f"--corridor-share-{flag} needs --corridor-share")
     if not args.corridor_search:
         for flag, value in (("--corridor-stride", None if by_path else args.corridor_stride),
                             ("--corridor-clearance", None if by_path else args.corridor_clearance),
@@ -236,6 +254,14 @@ def shortened_summary(fr):
     return (f"; shortened to {int(fr['n_kept'][found].sum())} of {int(fr['n_nodes'][found].sum())} nodes, total length "
             f"{float(fr['length'][found].sum()):.2f} m (lattice paths {float(fr['length_before'][found].sum()):.2f} m), "
             f"{fr['shorten_ms']:.3f} ms")
+
+
+def shared_summary(fr):
+    """the part of the search's line that --corridor-share adds: the overuse before and after, and the round that was kept"""
+    sh = fr.get("sharing")
+    if sh is None:
+        return ""
+    return f", overuse {sh['overuse'][0]} -> {sh['overuse'][sh['best_round']]} (round {sh['best_round']} of {sh['rounds']})"
 
 
 def obstacle_clearance_summary(oc, time_step):
@@ -326,6 +352,11 @@ def main(argv=None):
                     solver.set_search_metric("hops")
                 print(describe(solver.assignment_info))
             reference = None
+            if args.corridor_share is not None:
+                solver.set_path_sharing(share=args.corridor_share,
+                                        capacity=1 if args.corridor_share_capacity is None else args.corridor_share_capacity,
+                                        groups=4 if args.corridor_share_groups is None else args.corridor_share_groups,
+                                        rounds=args.corridor_share_rounds)
             if args.corridor_search:
                 if args.corridor_shorten:
                     reference, fr = solver.shorten_reference(stride=args.corridor_stride, clearance=args.corridor_clearance)
@@ -335,7 +366,7 @@ def main(argv=None):
                       f"(clearance {fr['clearance']}), {n_vehicles - fr['n_failed']} of {n_vehicles} paths found, longest "
                       f"E = {fr['max_edges']} for K = {solver.K}" + ("" if fr["guaranteed"] else " (no blocked segment is not "
                       "guaranteed)") + (f", by length (keep clear {fr['keep_clear']} cells): total cost {int(fr['cost'][fr['status'] == 0].sum())}"
-                                       if fr["metric"] == "length" else "")
+                                       if fr["metric"] == "length" else "") + shared_summary(fr)
                       + f", {fr['edges_ms'] + fr['penalties_ms'] + fr['search_ms']:.3f} ms" + (shortened_summary(fr) if args.corridor_shorten else ""))
             co = solver.set_corridors(reference=reference, max_grow=8 if args.corridor_grow is None else args.corridor_grow)
 

@@ -37,6 +37,23 @@ def search_metric(metric, keep_clear, clear_weight):
     return int(keep_clear), weight
 
 
+def path_sharing(share, capacity, groups, rounds):
+    """The checks of set_path_sharing -> None (share = 0: off) or (share_weight, capacity, groups, rounds) for
+    scp_negotiate_paths: share_weight = round(70 share); rounds stays None until the search knows N (twice the groups it runs
+    with, at most the supported 64)."""
+    if isinstance(share, bool) or not isinstance(share, (int, float, np.integer, np.floating)) or \
+            not (share >= 0 and np.isfinite(share)):
+        raise ValueError(f"share={share!r}: a finite number >= 0")
+    share_weight = int(round(_hip.MOVE_WEIGHTS[0] * float(share)))
+    if share_weight > _hip.PENALTY_MAX_PRODUCT:
+        raise ValueError(f"share={share!r}: round(70 share) = {share_weight} exceeds {_hip.PENALTY_MAX_PRODUCT} (costs are 32-bit)")
+    whole_number(capacity, 1, None, f"capacity={capacity!r}: a whole number of vehicles per node >= 1")
+    whole_number(groups, 1, None, f"groups={groups!r}: a whole number >= 1")
+    if rounds is not None:
+        whole_number(rounds, 0, _hip.NEGOTIATE_MAX_ROUNDS, f"rounds={rounds!r}: a whole number in [0, {_hip.NEGOTIATE_MAX_ROUNDS}]")
+    return (share_weight, int(capacity), int(groups), rounds if rounds is None else int(rounds)) if share_weight > 0 else None
+
+
 def straight_reference(p0, pf, K):
     """The default reference path of SCP.set_corridors: the straight line from start to goal, sampled uniformly at the states
     j = 0 .. K -- (N, K + 1, D) from p0, pf (N, D)."""
@@ -234,6 +251,20 @@ class ObstacleMethods:
         self._require("set_search_metric", one_rank=True)
         self._metric = (metric,) + search_metric(metric, keep_clear, clear_weight)
 
+    def set_path_sharing(self, share=0.0, capacity=1, groups=4, rounds=None):
+        """Whether the reference paths of find_reference / shorten_reference / set_corridors(reference="search" /
+        "shortened") avoid each other's routes from now on (a planner setting like set_search_metric's: set_space_dims returns
+        it to off).  Alone, every vehicle takes the cheapest doorway; with ``share`` > 0 the search is negotiated
+        (scp_negotiate_paths): a node that more than ``capacity`` vehicles' paths use costs every further vehicle ``share``
+        straight moves per vehicle over capacity on each edge that touches it (share_weight = round(70 share)), the fleet
+        re-routes in ``groups`` groups, one group per round, for ``rounds`` rounds (None: 2 groups), and the set of paths with
+        the smallest overuse -- the sum over the nodes of the vehicles beyond capacity -- is kept.  ``groups`` larger than N is
+        clipped to N.  ``share`` = 0 is off.  It needs set_search_metric("length"): the search by hops has no penalties (the
+        searches raise ValueError otherwise).  ValueError: share negative, not finite or round(70 share) > 32768; capacity < 1;
+        groups < 1; rounds outside 0 .. 64."""
+        self._require("set_path_sharing", one_rank=True)
+        self._sharing = path_sharing(share, capacity, groups, rounds)
+
     def find_reference(self, stride=None, clearance=0, max_path=None, allow_unreachable=False):
         """Reference paths around the obstacles, one per vehicle, for set_corridors(reference=...): a breadth-first search on
         a lattice of blocks of ``stride`` x ``stride`` (x ``stride``) cells whose edges exist only where both blocks -- for a
@@ -250,8 +281,16 @@ class ObstacleMethods:
         cached).  A vehicle without a path keeps the straight line; unless ``allow_unreachable`` that raises ValueError.
 
         After set_search_metric("length", ...) the path is the cheapest by weighted length and clearance instead.  info
-        also holds ``metric``, ``keep_clear``, ``cost`` (int64 per vehicle: the path's weighted cost, with "hops" its number of
-        moves; -1 without a path) and ``penalties_ms`` (0.0 when cached or not needed)."""
+        also holds ``metric``, ``keep_clear``, ``cost`` (int64 per vehicle: the path's weighted cost under the penalties the
+        path was found with, with "hops" its number of moves; -1 without a path) and ``penalties_ms`` (0.0 when cached or not
+        needed).
+
+        After set_path_sharing(share > 0) the search is the negotiation of scp_negotiate_paths (``search_ms``: all its rounds)
+        and info holds ``sharing``: ``share_weight``, ``capacity``, ``groups``, ``rounds`` as they ran, ``overuse`` (a list:
+        after the plain search and after every round), ``best_round`` (the round whose paths are returned), ``n_kept``
+        (re-routings that kept the old path because the new one was longer than max_path) and ``max_load`` (the most paths of
+        the returned set through one node: one further call, scp_path_load on the returned paths, and one further host read
+        of its maximum)."""
         if clearance is None:
             raise ValueError("clearance=None: a whole number of cells >= 0")
         found = self._search_reference("find_reference", stride, clearance, max_path, want_path=False)
@@ -264,6 +303,10 @@ class ObstacleMethods:
         """the checks and the calls of find_reference -> {"ref", "path", "rec" (device tensors), "p0", "pf", "max_path",
         "info": what find_reference reports}"""
         metric, prefer, weight = self._metric
+        sharing = self._sharing
+        if sharing is not None and metric != "length":
+            raise ValueError(f"{who}: set_path_sharing needs set_search_metric(\"length\") (the search by hops has no penalties "
+                             "for the other vehicles' paths to add to)")
         stride, clearance, lattice, edges, edges_ms = self._lattice_edges(who, stride, clearance)
         N, K, D, c = self.N, self.K, self.D, self._ctx
         nodes = lattice[0] * lattice[1] * lattice[2]
@@ -273,12 +316,22 @@ class ObstacleMethods:
         p0, pf = self.initial_positions.reshape(N, D), self.final_positions.reshape(N, D)
         ref = c.tensor(straight_reference(p0, pf, K))
         d_p0, d_pf = c.tensor(p0), c.tensor(pf)
-        pen, penalties_ms, path_cost = None, 0.0, None
+        pen, penalties_ms, path_cost, shared = None, 0.0, None, None
         if metric == "length":
             if prefer > 0 and weight > 0:
                 pen, penalties_ms = self._obstacles.penalties(stride, prefer, weight)
-            path, dev_rec, path_cost, _, n_failed = c.reference_paths_weighted(N, K, D, self._obstacles.grid, stride, edges, d_p0,
-                                                                               d_pf, int(max_path), ref, pen=pen, want_path=want_path)
+            if sharing is not None:
+                share_weight, capacity, groups, rounds = sharing
+                # (`want_path` is not passed on: the path table is always made, path_load below reads it for max_load)
+                groups = min(groups, N)
+                rounds = min(2 * groups, _hip.NEGOTIATE_MAX_ROUNDS) if rounds is None else rounds
+                path, dev_rec, path_cost, n_failed, overuse, best_round, n_kept = c.negotiate_paths(
+                    N, K, D, self._obstacles.grid, stride, edges, d_p0, d_pf, int(max_path), ref, share_weight, capacity, groups,
+                    rounds, pen=pen)
+                shared = {"share_weight": share_weight, "capacity": capacity, "groups": groups, "rounds": rounds}
+            else:
+                path, dev_rec, path_cost, _, n_failed = c.reference_paths_weighted(
+                    N, K, D, self._obstacles.grid, stride, edges, d_p0, d_pf, int(max_path), ref, pen=pen, want_path=want_path)
         else:
             path, dev_rec, _, n_failed = c.reference_paths(N, K, D, self._obstacles.grid, stride, edges, d_p0, d_pf, int(max_path),
                                                            ref, want_path=want_path)
@@ -293,6 +346,11 @@ class ObstacleMethods:
                 "guaranteed": bool(((E <= K) | (2 * clearance >= stride * -(-E // K)))[found].all()),
                 "edges_ms": edges_ms, "search_ms": search_ms, "metric": metric, "keep_clear": prefer,
                 "cost": np.where(found, cost, -1), "penalties_ms": penalties_ms}
+        if shared is not None:
+            load, _ = c.path_load(N, int(max_path), nodes, path, dev_rec, capacity)
+            shared.update(overuse=[int(v) for v in overuse.cpu().numpy().view(np.uint64)], best_round=int(best_round.item()),
+                          n_kept=int(n_kept.item()), max_load=int(load.max().item()))
+            info["sharing"] = shared
         return {"ref": ref, "path": path, "rec": dev_rec, "p0": d_p0, "pf": d_pf, "max_path": int(max_path), "info": info}
 
     def _lattice_edges(self, who, stride, clearance):

@@ -70,6 +70,7 @@ atexit.register(clear_native_pool)
 
 class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
     _metric = ("hops", 0, 0)  # (metric, prefer in cells, weight) of the lattice search until set_search_metric says otherwise
+    _sharing = None  # None (off) or (share_weight, capacity, groups, rounds) of set_path_sharing
     obstacle_info = None  # what set_obstacle_shapes rasterised (None after set_obstacles: that grid came from the caller)
 
     def __init__(
@@ -245,7 +246,8 @@ class SCP(ObstacleMethods, ValidationMethods, FleetMethods):
         self.pos_max = np.array(space_dims[self.D:])
         self.trajectories = None
         self._obstacles = self._corridor = self._boxes = self.obstacle_info = None  # (they belong to the scenario that is being replaced)
-        self._metric = SCP._metric  # (so does set_search_metric's setting: a reused solver starts with the default)
+        self._metric = SCP._metric  # (so do set_search_metric's and set_path_sharing's settings: a reused solver starts with
+        self._sharing = SCP._sharing  # the defaults)
 
     # ------------------------------------------------------------------------------------------------
     # a0: states (scp.py:99-129)

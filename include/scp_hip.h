@@ -162,8 +162,9 @@ int scp_ctx_last_pair_ms(scp_ctx* ctx, float* ms);
  *   "stg_batch_transposed" (default -1: chosen by the call, from 16 candidates on; 0 never; 1 always): scp_schedule_starts_batch
  *     first writes a transposed copy of the masks (N^2 words in the context's workspace) and reads the masks' columns from
  *     its rows; a developer switch.
- *   "ref_path_threads" (default 0: chosen by the call; or 256, 512 or 1024): threads per workgroup of scp_reference_paths,
- *     scp_reference_paths_weighted, scp_lattice_distances and scp_lattice_costs; a developer switch.
+ *   "ref_path_threads" (default 0: chosen by the call; or 64, 256, 512 or 1024): threads per workgroup of scp_reference_paths,
+ *     scp_reference_paths_weighted, scp_reference_paths_shared, scp_lattice_distances and scp_lattice_costs; a developer
+ *     switch.
  *   "shorten_threads" (default 0: chosen by the call; or 64, 128 or 256): threads per workgroup of scp_shorten_paths (one
  *     wave per vehicle, so 1, 2 or 4 vehicles per workgroup); a developer switch.
  *   "raster_item_cells" (default 0: 1024; or 64 .. 2^24): the most cells of one work item (one workgroup) of
@@ -1215,6 +1216,78 @@ int scp_lattice_costs(scp_ctx* ctx, int D, const scp_occupancy_grid* grid, int s
                       int n_dst, const double* dst /* DEVICE [n_dst][D] */, uint32_t* costs /* DEVICE [n_src][n_dst] */,
                       int32_t* src_node /* DEVICE [n_src] */, int32_t* dst_node /* DEVICE [n_dst] */,
                       uint32_t* cost_out /* DEVICE [n_src][nodes] or NULL */);
+
+/* ---- static obstacles: shared paths ---------------------------------------------------------------------------------------------
+ * A further additive part of ABI version 7: three functions; nothing above changes.  scp_reference_paths_weighted finds every
+ * vehicle's path as if it were alone on the map, so all vehicles on one side of a wall take the same cheapest doorway.  These
+ * calls make the nodes that OTHER vehicles' paths use cost extra, re-route the fleet in groups and keep the least crowded set
+ * of paths (negotiated routing).  Lattice, node ids, edge masks, DIRECTION ORDER, move weights, statuses, the walk rule, the
+ * reference points and scp_path_info are those of scp_lattice_edges / scp_reference_paths_weighted.  Integers only, except the
+ * reference points (scp_reference_paths', bit for bit).  tests/shared_path_ref.py restates every rule in numpy / plain Python.
+ *
+ * Path set.  The path / info pair of N vehicles.  nodes_i = the first n_nodes entries of row i if status == 0, otherwise
+ *   empty.  A path never visits a node twice (costs fall strictly along it).
+ * Load and overuse (scp_path_load), capacity >= 1:
+ *     load[u] = the number of vehicles i with u in nodes_i (uint32),  overuse = sum over u of max(0, load[u] - capacity) (uint64).
+ *   Both are written, not accumulated.  The array is zeroed, then one thread per path entry adds 1 with an integer atomic
+ *   (order-independent, so exact); one thread per node then takes its excess, a wave sum, and one 64-bit atomic add per
+ *   workgroup.  An entry that is no node id of the lattice is not counted.
+ * Shared penalty of vehicle i, share_weight in 0 .. SCP_PENALTY_MAX_PRODUCT:
+ *     others_i[u] = load[u] - [u in nodes_i],
+ *     pen_i[u] = min(pen[u] + share_weight * max(0, others_i[u] + 1 - capacity), SCP_PENALTY_MAX_PRODUCT),
+ *   evaluated as if in unbounded integers (the kernel uses 64 bits and clamps before anything can wrap); pen = NULL means
+ *   zeros.  The edge cost is w_i(u, v) = 2 W[len] + pen_i[u] + pen_i[v]: an edge still costs at most 242 + 65536, so the
+ *   no-wrap argument of the weighted search holds unchanged and 0xFFFFFFFF stays "unreached".
+ * Re-routing vehicle i (scp_reference_paths_shared).  The complete cost field from its goal node under w_i; the walk from the
+ *   start by the weighted search's rule with w_i; path_cost[i] = cost_i[start]; path row, info and reference points as there.
+ *   A vehicle whose info[i].status != 0 ON ENTRY is skipped: nothing of it is written (penalties cannot change what can be
+ *   reached).  A vehicle whose new walk has not reached the goal after max_path nodes KEEPS its path row, info, ref rows and
+ *   path_cost entirely and counts in *n_kept (written, not accumulated).  Every active vehicle reads the load of the set on
+ *   entry and nobody updates it during the call, so the result does not depend on scheduling.  Statuses never change, so
+ *   the call has no n_failed.  path is required: on entry it holds the set `load` was made from.  cost_out (for tests): the
+ *   field of every active vehicle that was not skipped (a keeping one included); other rows are untouched.
+ * Groups.  Vehicle i is ACTIVE in a call iff i mod groups == group; the four outputs of an inactive vehicle are not touched.
+ * Negotiation (scp_negotiate_paths).  Round 0 is scp_reference_paths_weighted; overuse_out[0] is its overuse.  Round r = 1 ..
+ *   rounds: the load of the current set; group (r - 1) mod groups is re-routed; overuse_out[r] is the overuse of the new set.
+ *   The outputs are the set of the round with the smallest overuse, the earliest one on ties (*best_round).  *n_failed is
+ *   round 0's; *n_kept is summed over the rounds.  rounds == 0 is the weighted search bit for bit; with share_weight == 0
+ *   every round reproduces round 0, so *best_round == 0.  (Why groups: if every vehicle re-routes at once the fleet swings
+ *   from one doorway to the other and back.  Why the best round: overuse is not monotone over the rounds even so.)
+ *
+ * scp_reference_paths_shared: ONE workgroup per active vehicle (i = group + b * groups) and no workgroup waits for another;
+ * the kernel, the sweep, the walk and the reference points are those of scp_reference_paths_weighted (a third field type
+ * whose penalty lookup is per vehicle).  On entry the workgroup marks its own path row in an LDS bitmap of nodes / 32 words
+ * (at most 4 KiB beside the 32 KiB / 128 KiB field) before anything overwrites the row; pen and load are read from global
+ * memory and pen_i is formed on the fly.  The walk goes to a row of the context's workspace and is copied over the path row
+ * only once it has reached the goal.  The workgroup width follows "ref_path_threads".
+ * scp_negotiate_paths: everything is enqueued on the ctx's stream with NO host read between the rounds.  The current set
+ * lives in the context's workspace, the best one in the outputs; after every round one kernel compares overuse_out[r] with
+ * the smallest earlier entry and its workgroups copy the current set over the outputs or return (a uniform branch).  Per
+ * round: the shared search, the load (a clear and two kernels) and the keep kernel.
+ * Supported: what scp_reference_paths_weighted supports; capacity >= 1; 0 <= share_weight <= SCP_PENALTY_MAX_PRODUCT; 1 <=
+ * groups <= N; 0 <= group < groups; 0 <= rounds <= SCP_NEGOTIATE_MAX_ROUNDS; scp_path_load: N, max_path >= 1, 1 <= nodes <=
+ * SCP_LATTICE_MAX_NODES.  Anything else returns SCP_ERR_INVALID with a message.  Argument checks, enqueue on the ctx's stream,
+ * no host read, timing through scp_ctx_last_pair_ms, which for scp_negotiate_paths covers all its launches. */
+#define SCP_NEGOTIATE_MAX_ROUNDS 64
+int scp_path_load(scp_ctx* ctx, int N, int max_path, int nodes, const int32_t* path /* DEVICE [N][max_path] */,
+                  const scp_path_info* info /* DEVICE [N] */, int capacity, uint32_t* load /* DEVICE [nodes] */,
+                  uint64_t* overuse /* DEVICE */);
+int scp_reference_paths_shared(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride,
+                               const uint32_t* edges, const uint32_t* pen /* DEVICE [nodes] or NULL */,
+                               const double* p0, const double* pf /* DEVICE [N][D] */, int max_path,
+                               double* ref /* DEVICE [N][K+1][D], in/out */,
+                               int32_t* path /* DEVICE [N][max_path], in/out, required */,
+                               scp_path_info* info /* DEVICE [N], in/out */, uint32_t* path_cost /* DEVICE [N], in/out */,
+                               uint32_t* cost_out /* DEVICE [N][nodes] or NULL, for tests */,
+                               const uint32_t* load /* DEVICE [nodes]: scp_path_load of path / info */, int share_weight,
+                               int capacity, int groups, int group, uint64_t* n_kept /* DEVICE */);
+int scp_negotiate_paths(scp_ctx* ctx, int N, int K, int D, const scp_occupancy_grid* grid, int stride, const uint32_t* edges,
+                        const uint32_t* pen /* DEVICE [nodes] or NULL */, const double* p0,
+                        const double* pf /* DEVICE [N][D] */, int max_path, double* ref /* DEVICE [N][K+1][D], in/out */,
+                        int32_t* path /* DEVICE [N][max_path] or NULL */, scp_path_info* info /* DEVICE [N] */,
+                        uint32_t* path_cost /* DEVICE [N] */, uint64_t* n_failed /* DEVICE */, int share_weight, int capacity,
+                        int groups, int rounds, uint64_t* overuse_out /* DEVICE [rounds + 1] */,
+                        int32_t* best_round /* DEVICE */, uint64_t* n_kept /* DEVICE */);
 
 /* ---- static obstacles: shapes into an occupancy grid ---------------------------------------------------------------------------
  * A further additive part of ABI version 7: one struct and one function; nothing above changes.  scp_rasterize_shapes makes
